@@ -25,9 +25,6 @@ import os
 import sys
 import time
 
-# (before anything initialises the HIP runtime: contexts beyond two need hardware queues of their own, mapper_amd/_capi.py)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -67,7 +64,11 @@ def main():
     ap.add_argument("--engine", default="gpu", choices=["gpu", "hostsim"], help="testing only: hostsim = a DRY RUN of this script's flow (ranks, barriers, max-over-ranks timing, the rank-0 line) "
                     "with the kernel sources compiled for the host (tests/hostsim, tests/sim_engine.py) instead of the GPU library; the line it prints is marked as such and is not a measurement")
     ap.add_argument("--wave-steps", type=int, default=2, help="steps of the opt-in wave-per-read form (XM_WAVE=1) measured beside the headline (0 = skip)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the result streams of the last step (rank 0's; context 0's when there are several) "
+                    "as DIR/<name>.npy in float64, at most 64 MB in all (a fixed seeded sample of the queries past that): two builds compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # launched bare: this process starts the N ranks itself (fresh children, one per GPU) before it has touched a GPU, and only waits for them
@@ -297,6 +298,8 @@ def main():
         digests = None
         pinned = [_capi.pinned_host_bytes()[1]]
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(r, args.dump_outputs)
         info = db.info()
         overfull = db.bucket_stats() if args.config in ("1rep", "3rep", "3shape") else None
         c = r.counters
@@ -584,6 +587,36 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return rc
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: 64 MB in all
+
+
+def dump_outputs(r, out_dir, budget=DUMP_BYTES, seed=0xD0C5):
+    """--dump-outputs: the result streams of one step as the caller of the hot path receives them (api.BatchResult: ints, dbls and their per-query offsets),
+    as float64 .npy files (every int32 and int64 offset here is exact in float64).  When they do not fit into `budget` bytes, whole queries are taken in one
+    fixed seeded order until the next would not fit.  query_index names the queries in the files; int_off / dbl_off are offsets into the dumped ints / dbls."""
+    int_off = np.asarray(r.int_off, dtype=np.int64)
+    dbl_off = np.asarray(r.dbl_off, dtype=np.int64)
+    nq = len(int_off) - 1
+    cost = 8 * (np.diff(int_off) + np.diff(dbl_off) + 3)  # a query's ints and dbls + its entries in query_index, int_off and dbl_off
+    room = budget - 2 * 8 - 5 * 128  # the closing offsets and the .npy headers
+    if int(cost.sum()) <= room:
+        take = np.arange(nq, dtype=np.int64)
+    else:
+        order = np.random.default_rng(seed).permutation(nq)
+        take = np.sort(order[:int(np.searchsorted(np.cumsum(cost[order]), room, side="right"))])
+
+    def gather(vals, off):
+        lens = off[take + 1] - off[take]
+        new_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        return np.asarray(vals)[np.arange(new_off[-1]) - np.repeat(new_off[:-1] - off[take], lens)], new_off
+    ints, new_int_off = gather(r.ints, int_off)
+    dbls, new_dbl_off = gather(r.dbls, dbl_off)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("query_index", take), ("int_off", new_int_off), ("ints", ints), ("dbl_off", new_dbl_off), ("dbls", dbls)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return len(take), nq
 
 
 def end_to_end(args, ref, synth):

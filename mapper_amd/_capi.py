@@ -97,8 +97,6 @@ def lib():
             # (and a half-built library must never be picked up silently); __graft_entry__.build() or `make -C mapper_amd/csrc` builds it
             raise ImportError("%s is missing: build it first (python -c 'import __graft_entry__ as g; g.build()' or make -j8 -C mapper_amd/csrc); "
                               "mapper_amd has no CPU fallback" % path)
-        global _hw_queues_at_load
-        _hw_queues_at_load = os.environ.get("GPU_MAX_HW_QUEUES")  # what the HIP runtime will see when the first GPU-touching call initialises it
         L = C.CDLL(path)  # (XM_LIB_PATH: A/B experiments with another build of the same library)
         if not hasattr(L, "xm_abi_version") or L.xm_abi_version() != ABI_VERSION:
             raise ImportError("%s implements another version of include/xmapper_hip.h than this binding (%d): rebuild it (make -j8 -C mapper_amd/csrc)" % (path, ABI_VERSION))
@@ -205,35 +203,6 @@ def view_result(L, res):
     return dict(ints=view(r.ints, C.c_int32, r.num_ints), dbls=view(r.dbls, C.c_double, r.num_dbls), int_off=view(r.int_off, C.c_int64, r.num_queries + 1),
                 dbl_off=view(r.dbl_off, C.c_int64, r.num_queries + 1), counters=list(r.counters), kernel_ms=r.kernel_ms, h2d_ms=r.h2d_ms,
                 d2h_ms=r.d2h_ms, kernel_launches=r.kernel_launches, prof=list(r.prof), extra=list(r.extra))
-
-
-_hw_queues_at_load = None  # GPU_MAX_HW_QUEUES as it stood when the library was loaded (lib()): the value the HIP runtime reads when it initialises
-
-
-def want_hardware_queues(n=8):
-    """The HIP runtime spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues (default 4); every context has a compute and a copy stream, so with
-    more than two contexts of a GPU launches of different contexts would share a queue and run one after the other (repeat-rich reads, four contexts: 1.5 -> 2.2 M
-    reads/s with 8 queues, profiles/r04/NOTES.md 13).  The variable is read when the runtime initialises, so it is the ENTRY POINTS that set it (python -m mapper_amd,
-    bench.py) - importing the package does not touch the process environment.  A program that embeds the library and wants three contexts or more per GPU calls
-    this (or sets the variable) before anything in the process touches the GPU; returns False when the runtime is already up with another setting."""
-    import warnings
-    if _lib is None:
-        cur = os.environ.get("GPU_MAX_HW_QUEUES")
-        if cur is None:
-            os.environ["GPU_MAX_HW_QUEUES"] = str(n)
-            return True
-        if int(cur) >= n:
-            return True
-        warnings.warn("GPU_MAX_HW_QUEUES is set to %s: with fewer than %d hardware queues, three or more contexts of a GPU share queues and their launches run one after the other" % (cur, n))
-        return False
-    # the library is loaded: what counts is what the environment held at that moment (a value set afterwards is never read by the runtime; under rocprofv3 the
-    # profiler's preloaded library initialises the runtime before Python starts, so the variable must be exported in the shell in front of rocprofv3)
-    seen = _hw_queues_at_load
-    if seen is not None and int(seen) >= n:
-        return True
-    warnings.warn("GPU_MAX_HW_QUEUES was %s when the library was loaded and the HIP runtime may already be initialised: more than two contexts per GPU will share hardware queues "
-                  "(set the variable before the first import that touches the GPU)" % (seen or "unset"))
-    return False
 
 
 def pinned_host_bytes():

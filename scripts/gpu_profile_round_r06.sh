@@ -9,8 +9,6 @@ O=$R/gpurun_out/$RN
 mkdir -p $O
 cd $R
 Q="--cpu-sample 0 --seed-probes 0 --wave-steps 0 --single-context-steps 0 --stream-batches 0 --end-to-end-reads 0"
-# (the HIP runtime reads GPU_MAX_HW_QUEUES when it starts - under rocprofv3 that is before Python runs: exported here for every command)
-export GPU_MAX_HW_QUEUES=8
 if [ $WHAT = all ] || [ $WHAT = bench ]; then
 timeout 900 python3 bench.py --steps 20 > $O/bench_full.log 2>&1
 tail -n 1 $O/bench_full.log > $O/bench_line.json
