@@ -19,7 +19,7 @@
 #include <string.h>
 #include "xmapper_hip.h"
 
-#define XMJ_ABI_VERSION 2  /* include/xmapper_hip.h as of round 6 */
+#define XMJ_ABI_VERSION 3  /* include/xmapper_hip.h: xm_context_set_collapse, xm_result.extra[7] */
 
 /* ---------------------------------------------------------------- part 1: marshalling on plain C arrays ---------------------------------------- */
 

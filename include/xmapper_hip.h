@@ -92,16 +92,17 @@ typedef struct xm_result {
    * 12-15 kernel microseconds by pass: 12 wave-per-read light tier (+ lane-per-read light pass of what the wave form left), 13 wave-per-read
    * chain tier, 14 wave-per-read search tier, 15 lane-per-read gapped / rerun passes */
   int64_t counters[16];
-  double kernel_ms;   /* sum of the align (and search) kernels' launch durations (HIP events on the launch stream) */
+  double kernel_ms;   /* sum of the align (and search, and collapse) kernels' launch durations (HIP events on the launch stream) */
   double h2d_ms, d2h_ms;  /* batch upload; prefix sums + query-order gather + copy of the four streams to the host */
-  int32_t kernel_launches;  /* align + search kernel launches of this call */
+  int32_t kernel_launches;  /* align + search (+ collapse) kernel launches of this call */
   int32_t reserved;
   int64_t prof[16];   /* diagnostic builds (-DXM_PROFILE=1: summed over lanes, =2: per wave) only: shader-clock ticks per phase; otherwise 0 */
   /* (appended in ABI version 2; xm_abi_version())  the rejection filter in front of PathAligner (batches of long reads): 0 searches it examined, 1 searches it
    * proved null without running them (PathAligner.java:169: the search would have returned null after exploring every node within the budget; their nodes
    * are not in counters[6]), 2 cells of the bounding recurrence it computed, 3 = 1 when a pass of this call ran with the filter; 4 pieces (BlockAligner.alignPiece,
    * BlockAligner.java:215-249) the filter examined, 5 pieces it proved unalignable within their budget before their chain ran (their PathAligner calls and nodes are in neither counters[5] nor
-   * counters[6]); 6-7 reserved (0) */
+   * counters[6]); 6 reserved (0); 7 (ABI version 3) queries of this call whose results were copied from a byte-identical query of the batch instead of being
+   * aligned (xm_context_set_collapse; 0 when collapsing is off) */
   int64_t extra[8];
 } xm_result;
 
@@ -119,7 +120,8 @@ const char* xm_last_error(void);
 /* First 16 hex digits of the SHA-256 over the library's sources (every .h and .hip file of mapper_amd/csrc in name order, then this header) at build
  * time: lets a caller check that the loaded library was built from the sources it sits beside. */
 const char* xm_build_stamp(void);
-/* Version of this header's structs and entry points: 2 = xm_result.extra[] appended, xm_seed_probe_packed replaces xm_seed_probe.  A binding checks it once
+/* Version of this header's structs and entry points: 2 = xm_result.extra[] appended, xm_seed_probe_packed replaces xm_seed_probe; 3 = xm_context_set_collapse,
+ * xm_result.extra[7].  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -145,6 +147,15 @@ int xm_index_replicate(xm_index* source, int32_t device, xm_index** out);
  * what xm_device_memory reports as free (after the index is resident) between them.  No reference counterpart (the JVM's -Xmx is the analogue). */
 int xm_context_set_scratch(xm_index* context, int64_t bytes);
 int xm_device_memory(int32_t device, int64_t* free_bytes, int64_t* total_bytes);
+/* Identical queries of a batch aligned once (AlignerWorker.checkCacheAndAlign, AlignerWorker.java:264-291: the reference looks every query up in its
+ * run-wide AlignmentCache and binds the cached alignments to the new query).  Per context, off by default.  With enable != 0 every align call of this
+ * context (xm_align_batch, xm_align_resident after xm_batch_upload or xm_batch_commit) aligns one query of each group of byte-identical queries of the batch
+ * - same mate count, same mate lengths and bytes in order, same bit patterns of expected_inner and deviation - namely the one with the lowest index, and
+ * gives every other query of the group a copy of its results: the streams are the same as with collapsing off.  Queries that are identical only across
+ * batches are aligned in each.  What changes is the meaning of the work counters: counters[0..10] and extra[0..5] then count the work done, for the
+ * aligned queries only, and extra[7] the queries served as copies.  That is why it is not on by default: bench.py and the GPU tests compare those
+ * counters with the oracle read by read.  "Failed to align query q" names the lowest index of the group. */
+int xm_context_set_collapse(xm_index* context, int32_t enable);
 /* Binary index cache, in the spirit of --cache-dir (DirCache.java:19-60, HashBlock_Database.java:106-114,477-487, PackedMap.java:249-279:
  * the reference writes one "length-<n>" file per PackedMap under a directory keyed by its property map).  xm_index_save writes the
  * reference, every table hashed so far and the duplication map into ONE file (beside `path`, then renamed: concurrent writers are safe).

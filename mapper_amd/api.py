@@ -139,6 +139,12 @@ class BatchResult:
     def __len__(self):
         return len(self.int_off) - 1
 
+    @property
+    def copies(self):
+        """Queries of the batch whose results were copied from a byte-identical query instead of being aligned (xm_result.extra[7]; 0 unless
+        ReferenceDatabase.set_collapse(True))."""
+        return int(self.extra[7])
+
     def query_alignments(self, q):
         return decode_streams(self.ints, self.dbls, self.int_off, self.dbl_off, q)
 
@@ -254,6 +260,13 @@ class ReferenceDatabase:
     def set_scratch(self, nbytes):
         """xm_context_set_scratch: upper limit of the HBM this context allocates as scratch for its passes (0: the default)."""
         if self._L.xm_context_set_scratch(self._h, int(nbytes)):
+            raise RuntimeError(self._L.xm_last_error().decode())
+
+    def set_collapse(self, enable):
+        """xm_context_set_collapse: this context aligns one query of each group of byte-identical queries of a batch and copies its results to the
+        others (AlignerWorker.checkCacheAndAlign, AlignerWorker.java:264-291, within a batch).  Same results; the work counters then count the queries
+        aligned, and BatchResult.copies the ones served as copies.  Off by default."""
+        if self._L.xm_context_set_collapse(self._h, 1 if enable else 0):
             raise RuntimeError(self._L.xm_last_error().decode())
 
     def close(self):

@@ -10,6 +10,10 @@ derivation of AlignmentParameters from them (:409-453), reference sorting (:1151
 live in the un-vendored QuickVariants module: the header written here is the minimal SAM-spec one and is marked [unpinned]; the
 VCF / ancestry outputs stay with the Java host (`--cache-dir` is
 honoured: the index goes to one file under it, api.index_cache_path) and are refused here with a message saying so.
+
+Flags of this harness that Mapper does not have: --batch-size <n>, --gpus <n>, --contexts <n>, --devices <i,j,...>, --device <i>, --per-object, and
+--collapse-identical-queries (byte-identical queries of a batch are aligned once and share the results, as the reference's alignment cache does; the
+outputs are the same, and one line on stderr says how many queries were served as copies).
 """
 import gzip
 import sys
@@ -167,6 +171,8 @@ def parse_args(argv):
                 raise UsageError("--contexts must be >= 1")
         elif a == "--devices":  # (not a Mapper flag) explicit GPU ordinals, comma-separated; an ordinal may repeat (two contexts on one GPU)
             o["devices"] = [int(x) for x in argv[i + 1].split(",")]; i += 1
+        elif a == "--collapse-identical-queries":  # (not a Mapper flag) identical queries of a batch aligned once (api.ReferenceDatabase.set_collapse; AlignerWorker.java:264-291)
+            o["collapse"] = True
         elif a == "--per-object":  # (not a Mapper flag) the harness's first implementation: one Python object per read and per alignment (the reference for the formats; tests)
             o["per_object"] = True
         elif a == "--device":  # (not a Mapper flag) which GPU
@@ -287,10 +293,13 @@ def run_streaming(o, params, contigs, out):
     # (a job whose later reads are longer than the first batch's grows the index on demand: xm_index_ensure_length)
     if devices and len(devices) > 1:
         from . import multi
-        db = multi.MultiGpuDatabase(ordered, devices, mode="mapper", enable_gapmers=o["enable_gapmers"], max_query_length=max_len, cache_dir=o.get("cache_dir"))
+        db = multi.MultiGpuDatabase(ordered, devices, collapse=o.get("collapse", False), mode="mapper", enable_gapmers=o["enable_gapmers"], max_query_length=max_len,
+                                    cache_dir=o.get("cache_dir"))
     else:
         db = api.ReferenceDatabase(ordered, mode="mapper", enable_gapmers=o["enable_gapmers"], device=devices[0] if devices else o["device"],
                                    max_query_length=max_len, cache_dir=o.get("cache_dir"))
+        db.set_collapse(o.get("collapse", False))
+    copies = 0
     sam_out = un_out = None
     if o["out_sam"]:
         sam_out = sys.stdout if o["out_sam"] == "-" else open(o["out_sam"], "w")
@@ -330,6 +339,7 @@ def run_streaming(o, params, contigs, out):
         for r in db.align_stream(feed(), params):
             if failure:
                 break
+            copies += r.copies
             to_write.put((in_flight.get(), r))
     finally:
         to_write.put(None)
@@ -343,6 +353,8 @@ def run_streaming(o, params, contigs, out):
         un_out.close()
     st = writer.stats
     n = int(st.num_queries)
+    if o.get("collapse"):
+        report_copies(copies, n)
     global last_timing
     last_timing = {"queries": n, "stream_seconds": time.perf_counter() - t_stream, "contexts": len(devices) if devices else 1}  # first read of the query files .. last byte of the outputs (bench.py's end_to_end leg)
     out.write("\nStatistics: \n")
@@ -351,6 +363,11 @@ def run_streaming(o, params, contigs, out):
         out.write(" Average penalty               : %s per base (%d/%d) in aligned queries\n" % (java_float(st.total_penalty / st.total_aligned_length), int(st.total_penalty), st.total_aligned_length))
         out.write(" Num indels                    : %s per base (%d/%d) in aligned queries\n" % (java_float(st.num_indels / st.total_aligned_length), st.num_indels, st.total_aligned_length))
     return 0
+
+
+def report_copies(copies, n):
+    """--collapse-identical-queries: the one statistics line of the flag (stderr: the outputs stay what they are without it)."""
+    sys.stderr.write("Identical queries: %d of %d queries were served as copies of an identical query of their batch\n" % (copies, n))
 
 
 def run(argv, out=sys.stdout):
@@ -392,11 +409,12 @@ def run(argv, out=sys.stdout):
         # (--out-mutations: every context accumulates its own pile-up on its GPU - depth 8 B, four alternative counts 32 B and, with a query-end fraction, the
         # middle depth 8 B per reference base: 149 GB for a 3.1 Gb reference - so the contexts of a GPU are counted with it: api.divide_scratch)
         pile_up = (48 if o.get("query_end_fraction", 0.1) > 0 else 40) * sum(len(t) for _, t in ordered) + (64 << 20) if o.get("out_mutations") else 0
-        db = multi.MultiGpuDatabase(ordered, devices, mode="mapper", enable_gapmers=o["enable_gapmers"], max_query_length=max_query_length, cache_dir=o.get("cache_dir"),
-                                    per_context_extra=pile_up)
+        db = multi.MultiGpuDatabase(ordered, devices, collapse=o.get("collapse", False), mode="mapper", enable_gapmers=o["enable_gapmers"], max_query_length=max_query_length,
+                                    cache_dir=o.get("cache_dir"), per_context_extra=pile_up)
     else:
         db = api.ReferenceDatabase(ordered, mode="mapper", enable_gapmers=o["enable_gapmers"], device=devices[0] if devices else o["device"],
                                    max_query_length=max_query_length, cache_dir=o.get("cache_dir"))
+        db.set_collapse(o.get("collapse", False))
     sam_out = None
     if o["out_sam"]:
         sam_out = sys.stdout if o["out_sam"] == "-" else open(o["out_sam"], "w")
@@ -413,10 +431,12 @@ def run(argv, out=sys.stdout):
         on_aligned = lambda replica, first_query, qs: match_db.add_last(qs, replica=replica)  # noqa: E731
     results = db.align_batches([q for q, _ in queries], params, batch_size, on_aligned=on_aligned)
     first, result, nxt = 0, None, 0
+    copies = 0
     for qi, (q, quals) in enumerate(queries):
         if qi >= nxt:  # the next batch's results (queries are written in input order)
             first, result = next(results)
             nxt = first + len(result)
+            copies += result.copies
         comps = result.query_alignments(qi - first)
         aligned = any(len(c) > 0 for c in comps)
         if aligned:
@@ -453,6 +473,8 @@ def run(argv, out=sys.stdout):
             match_db.write_mutations(f, filt)
         match_db.close()
     n = len(queries)
+    if o.get("collapse"):
+        report_copies(copies, n)
     out.write("\nStatistics: \n")
     out.write(" Alignment rate                : %d%% of queries (%d/%d)\n" % (num_aligned * 100 // n if n else 0, num_aligned, n))
     if total_len:

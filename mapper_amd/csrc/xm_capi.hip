@@ -12,6 +12,7 @@
 #include "xm_index_host.h"
 #include "xm_kernel_args.h"
 #include "xm_kernel_common.h"
+#include "xm_collapse.h"
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
@@ -790,6 +791,7 @@ struct xm_index {
   bool hostOnly = false;
   int device = 0;
   long long scratchBytes = 0;        // xm_context_set_scratch: upper limit of this context's scratch (0: XM_SCRATCH_GIB / the default)
+  bool collapse = false;             // xm_context_set_collapse: identical queries of a batch are aligned once (xm_collapse.h)
   std::mutex mu;                     // calls on one context serialise; contexts run side by side
   HostIndex& host() { return hs->host; }
   const HostIndex& host() const { return hs->host; }
@@ -818,6 +820,10 @@ struct xm_index {
   DevBuf<int32_t> dFinalInts;
   DevBuf<double> dFinalDbls;
   DevBuf<DevCounters> dCounters;
+  // collapsing of identical queries (xm_collapse.h; allocated only when it is on): fingerprint table, query -> representative, the representatives, block counts
+  DevBuf<unsigned long long> dCollapseKeys, dCollapseReps, dCollapseTotal;
+  DevBuf<int64_t> dRepOf, dRepList;
+  DevBuf<long long> dCollapseBlocks;
   // confidence table (IndexView::conf): host copy, device copy, the settings it was computed for, miss list, reads that wait for it
   std::vector<ConfEntry> confHost;
   size_t confCount = 0;
@@ -972,7 +978,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 2; }
+int32_t xm_abi_version(void) { return 3; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();
@@ -1073,6 +1079,14 @@ int xm_context_set_scratch(xm_index* idx, int64_t bytes) {
     (void)hipSetDevice(idx->device);
     idx->dArenas.release();
   }
+  return 0;
+}
+
+int xm_context_set_collapse(xm_index* idx, int32_t enable) {
+  if (!idx) return fail("xm_context_set_collapse: null argument");
+  std::lock_guard<std::mutex> lock(idx->mu);
+  idx->collapse = enable != 0;
+  if (!idx->collapse) { idx->dCollapseKeys.release(); idx->dCollapseReps.release(); idx->dCollapseTotal.release(); idx->dRepOf.release(); idx->dRepList.release(); idx->dCollapseBlocks.release(); }
   return 0;
 }
 
@@ -1450,6 +1464,39 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 #endif
     const int64_t* todo = nullptr;  // device list of the current pass; null on the first pass = all reads
     long long nTodo = nq;
+    double kernelMs = 0;
+    int launches = 0;
+    // identical queries (xm_context_set_collapse): the first pass gets the representatives, the lowest query index of each group of byte-identical queries,
+    // in ascending order (xm_collapse.h).  Every later list is built by the passes from the reads they ran: representatives only.
+    int64_t copies = 0;
+    if (idx->collapse) {
+      size_t cap = 64;
+      while (cap < (size_t)nq * 2) cap <<= 1;
+      const long long nBlocks = (nq + XM_COLLAPSE_PER_BLOCK - 1) / XM_COLLAPSE_PER_BLOCK;
+      idx->dCollapseKeys.ensure(cap); idx->dCollapseReps.ensure(cap); idx->dCollapseTotal.ensure(1);
+      idx->dRepOf.ensure((size_t)nq); idx->dRepList.ensure((size_t)nq); idx->dCollapseBlocks.ensure((size_t)nBlocks);
+      HIP_CHECK(hipMemsetAsync(idx->dCollapseKeys.p, 0, sizeof(unsigned long long) * cap, s));
+      HIP_CHECK(hipMemsetAsync(idx->dCollapseReps.p, 0xFF, sizeof(unsigned long long) * cap, s));
+      const unsigned waveGrid = (unsigned)((nq + 3) / 4);  // one wave per query, four per block
+      HIP_CHECK(hipEventRecord(e0, s));
+      hipLaunchKernelGGL(xm_collapse_fingerprint_kernel, dim3(waveGrid), dim3(256), 0, s, bv, idx->dCollapseKeys.p, idx->dCollapseReps.p, (unsigned long long)(cap - 1), idx->dRepOf.p);
+      hipLaunchKernelGGL(xm_collapse_verify_kernel, dim3(waveGrid), dim3(256), 0, s, bv, (const unsigned long long*)idx->dCollapseReps.p, idx->dRepOf.p);
+      hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, idx->dCollapseBlocks.p);
+      hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->dCollapseBlocks.p, idx->dCollapseTotal.p);
+      hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, (const long long*)idx->dCollapseBlocks.p, idx->dRepList.p);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(e1, s));
+      unsigned long long nReps = 0;
+      HIP_CHECK(hipMemcpyAsync(&nReps, idx->dCollapseTotal.p, sizeof(nReps), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      kernelMs += ms;
+      launches += 5;
+      if (nReps < 1 || (long long)nReps > nq) throw std::runtime_error("internal error: collapsing found " + std::to_string(nReps) + " distinct queries in a batch of " + std::to_string(nq));
+      copies = nq - (int64_t)nReps;
+      todo = idx->dRepList.p;
+      nTodo = (long long)nReps;
+    }
     unsigned long long pendingHeavy = 0, pendingScale = 0;
     int ts = 0, to = 0, tc = 0;  // which of the two scale / out / confidence lists receives new entries
     unsigned long long pendingConf = 0;
@@ -1463,8 +1510,6 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
     idx->dOutInts.ensure((size_t)intCap); idx->dOutDbls.ensure((size_t)dblCap);
     intCap = idx->dOutInts.n; dblCap = idx->dOutDbls.n;
     unsigned long long cursors[4] = {0, 0, 0, 0};
-    double kernelMs = 0;
-    int launches = 0;
     int64_t rerun = 0;
     const size_t arenaUnit = (size_t)envKnob("XM_ARENA_KB", 288, 64, 16384) * 1024;  // scratch of a lane at scale 1 (experiment knob: the capacities do not follow it, a smaller arena only overflows earlier)
     // scratch limit of this context: xm_context_set_scratch, else XM_SCRATCH_GIB (experiment knob), else 200 GiB
@@ -1628,7 +1673,7 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
         if (tracePasses) fprintf(stderr, "[xm] search kernel: %lld searches, %d x %d threads: %.3f ms\n", n, sl.grid, sl.block, ms);
       };
       // light tier
-      launchTier(0, nullptr, nq, lastTier >= 1 ? idx->dListWaveHeavy.p : (int64_t*)nullptr, idx->dWaveSlotOf.p, nullptr);
+      launchTier(0, todo, nTodo, lastTier >= 1 ? idx->dListWaveHeavy.p : (int64_t*)nullptr, idx->dWaveSlotOf.p, nullptr);
       long long nChain = lastTier >= 1 ? (long long)wctl.nNext : 0;
       if (nChain > 0) {
         idx->dWaveMemo.ensure((size_t)nChain * (size_t)memoBytes);
@@ -1844,6 +1889,17 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
       heavy = true;
       if (scale > 4096) throw std::runtime_error("Failed to align: scratch scale limit reached (query needs more than 4096x the default scratch)");
     }
+    if (copies > 0) {  // every copy's slice is its representative's: the scan and gather below then write it in query order
+      HIP_CHECK(hipEventRecord(e0, s));
+      hipLaunchKernelGGL(xm_collapse_fanout_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, idx->dIntOff.p, idx->dDblOff.p,
+                         idx->dIntLen.p, idx->dDblLen.p);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(e1, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      kernelMs += ms;
+      launches++;
+    }
     // ---- canonical streams in query order: offsets by prefix sum, slices gathered on the device, one copy per stream to the host
     HIP_CHECK(hipEventRecord(e0, s));
     const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
@@ -1859,10 +1915,18 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
     }
 #endif
     idx->dFinalIntOff.ensure((size_t)nq + 1); idx->dFinalDblOff.ensure((size_t)nq + 1);
-    const size_t usedI = (size_t)std::min(cursors[0], intCap), usedD = (size_t)std::min(cursors[1], dblCap);  // upper bounds of the totals
-    idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD);
+    size_t usedI = (size_t)std::min(cursors[0], intCap), usedD = (size_t)std::min(cursors[1], dblCap);  // upper bounds of the totals
+    if (copies == 0) { idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD); }
     hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, idx->dIntLen.p, idx->dDblLen.p, idx->dBlockI.p, idx->dBlockD.p);
     hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, idx->dBlockI.p, idx->dBlockD.p, idx->dFinalIntOff.p, idx->dFinalDblOff.p);
+    if (copies > 0) {  // (a copy's slice is in the result arena once and in the streams once per copy: the totals are the scan's)
+      int64_t totals[2] = {0, 0};
+      HIP_CHECK(hipMemcpyAsync(&totals[0], idx->dFinalIntOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(&totals[1], idx->dFinalDblOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      usedI = (size_t)totals[0]; usedD = (size_t)totals[1];
+      idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD);
+    }
     hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, idx->dIntLen.p, idx->dDblLen.p, idx->dBlockI.p, idx->dBlockD.p,
                        idx->dFinalIntOff.p, idx->dFinalDblOff.p);
     hipLaunchKernelGGL(xm_gather_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, idx->dIntOff.p, idx->dDblOff.p, idx->dIntLen.p, idx->dDblLen.p,
@@ -1888,6 +1952,7 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
     res->counters[7] = (int64_t)dc.quickAccepts; res->counters[8] = (int64_t)dc.alignmentsOut; res->counters[9] = (int64_t)dc.refWindowBytes; res->counters[10] = (int64_t)dc.readBytes;
     res->counters[11] = rerun;
     res->extra[0] = (int64_t)dc.boundChecks; res->extra[1] = (int64_t)dc.boundRejects; res->extra[2] = (int64_t)dc.boundCells; res->extra[3] = boundFilterUsed ? 1 : 0; res->extra[4] = (int64_t)dc.boundPieceChecks; res->extra[5] = (int64_t)dc.boundPieceRejects;
+    res->extra[7] = copies;
     for (int i = 0; i < 16; i++) res->prof[i] = (int64_t)dc.t[i];
     res->kernel_ms = kernelMs;
     res->kernel_launches = launches;

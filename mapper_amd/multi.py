@@ -16,8 +16,9 @@ import threading
 
 
 class MultiGpuDatabase:
-    def __init__(self, contigs, devices, **kw):
+    def __init__(self, contigs, devices, collapse=False, **kw):
         """devices: GPU ordinals, e.g. [0, 1, 2, 3]; a repeated ordinal gives that GPU two independent contexts (tests on one-GPU machines).
+        collapse: every context aligns identical queries of a batch once (ReferenceDatabase.set_collapse).
         kw: ReferenceDatabase's build options (mode, enable_gapmers, max_query_length, cache_dir)."""
         from . import api
         if not devices:
@@ -51,6 +52,8 @@ class MultiGpuDatabase:
         self.devices = [dd for r, dd in zip(self.replicas, self.devices) if any(r is k for k in keep)]
         self.replicas = keep
         self.contigs = first.contigs
+        for r in self.replicas:
+            r.set_collapse(collapse)
 
     def info(self):
         return self.replicas[0].info()
