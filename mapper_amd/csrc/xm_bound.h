@@ -63,16 +63,18 @@ XM_INL bool boundPrices(const BoundProblem& b, BoundPrices& c) {
   const double s = (double)XM_BOUND_SCALE;
   const double t = floor((b.budget + 0.000001 + 0.0000001) * s);
   if (!(t >= 0 && t < 60000.0)) return false;
-  c.thr = (int32_t)t;
-  c.mut = (int32_t)floor(b.mutation * s);
-  c.isie = (int32_t)floor((b.insStart + b.insExt) * s);
-  c.ie = (int32_t)floor(b.insExt * s);
-  c.dsde = (int32_t)floor((b.delStart + b.delExt) * s);
-  c.de = (int32_t)floor(b.delExt * s);
-  // AmbiguityPenalty * getMutationFalseNegativeRate(union) (M/AlignmentParameters.java:156-180): a union of 2, 3, 4 bases
-  c.amb1 = (int32_t)floor(b.ambiguity * (1.0 / 3.0) * s); c.amb2 = (int32_t)floor(b.ambiguity * (2.0 / 3.0) * s); c.amb3 = (int32_t)floor(b.ambiguity * (3.0 / 3.0) * s);
+  // every price is range-checked as a double, before it becomes an integer: a NaN, an infinity or a value beyond int32 has no defined conversion (the host
+  // gives INT_MIN, gfx950's v_cvt_i32_f64 saturates or gives 0), and a price above the cap would overflow the recurrence's int32 sums (eL + ie, (k - 1) de)
   // (prices a path can collect without end must be positive, and none may be negative: the recurrence's values only grow along a path)
-  if (c.mut < 0 || c.isie < 1 || c.ie < 1 || c.dsde < 1 || c.de < 1 || c.amb1 < 0 || c.mut > 30000 || c.isie > 30000 || c.dsde > 30000 || c.amb3 > 30000) return false;
+  const double mut = floor(b.mutation * s), isie = floor((b.insStart + b.insExt) * s), ie = floor(b.insExt * s);
+  const double dsde = floor((b.delStart + b.delExt) * s), de = floor(b.delExt * s);
+  // AmbiguityPenalty * getMutationFalseNegativeRate(union) (M/AlignmentParameters.java:156-180): a union of 2, 3, 4 bases
+  const double amb1 = floor(b.ambiguity * (1.0 / 3.0) * s), amb2 = floor(b.ambiguity * (2.0 / 3.0) * s), amb3 = floor(b.ambiguity * (3.0 / 3.0) * s);  // (amb1 <= amb2 <= amb3)
+  if (!(mut >= 0 && mut <= 30000 && isie >= 1 && isie <= 30000 && ie >= 1 && ie <= 30000 && dsde >= 1 && dsde <= 30000 && de >= 1 && de <= 30000 &&
+        amb1 >= 0 && amb3 <= 30000)) return false;
+  c.thr = (int32_t)t;
+  c.mut = (int32_t)mut; c.isie = (int32_t)isie; c.ie = (int32_t)ie; c.dsde = (int32_t)dsde; c.de = (int32_t)de;
+  c.amb1 = (int32_t)amb1; c.amb2 = (int32_t)amb2; c.amb3 = (int32_t)amb3;
   return true;
 }
 

@@ -1812,8 +1812,8 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
       break;  // (experiment build, scripts/gpu_light_only.sh: only the first pass is meaningful)
 #endif
       const bool tracePasses = envInt("XM_TRACE_PASSES", 0) != 0;
-      if (tracePasses) fprintf(stderr, "[xm] pass %d: %s reads %lld scale %d lpw %d waves %lld: %.3f ms -> heavy %llu scale %llu out %llu\n", launches, !heavy ? "light" : "gapped",
-                               nTodo, scale, lpw, nWaves, ms, ctl.nHeavy + ctl.nHeavyLate, ctl.nScale[ts], ctl.nOut[to]);
+      if (tracePasses) fprintf(stderr, "[xm] pass %d: %s reads %lld scale %d lpw %d waves %lld lanes/read %d filter %d: %.3f ms -> heavy %llu scale %llu out %llu\n", launches,
+                               !heavy ? "light" : "gapped", nTodo, scale, lpw, nWaves, 1 << pairLanes, boundFilter, ms, ctl.nHeavy + ctl.nHeavyLate, ctl.nScale[ts], ctl.nOut[to]);
 #ifdef XM_PROFILE
       if (tracePasses && heavy) {  // reads of a wave that stood at a PathAligner call together, this pass
         unsigned long long a[16] = {0}, z[16] = {0};

@@ -464,6 +464,7 @@ XM_INL PNode* palWaveNodes() { static thread_local double buf[XM_PAL_NODES * 4];
 }  // namespace xm
 #include "xm_bound.h"  // the rejection filter in front of the search (uses the wave's slot)
 namespace xm {
+static_assert(XM_BOUND_REGIONS * XM_BOUND_REGION <= XM_PAL_SLOT_BYTES, "the filter's regions of a wave (one per read) must fit the wave's search slot");
 
 // XM_PROFILE builds: where a search step spends its time (hash lookups / node loads / arithmetic / putNode), summed into t[12..15]
 #if defined(XM_PROFILE) && defined(__HIP_DEVICE_COMPILE__)

@@ -350,6 +350,17 @@ int xmo_kat_bound(const void* paramsIn, const uint8_t* queryCodes, int queryLeng
   } catch (std::exception& e) { g_error = e.what(); return 3; }
 }
 
+// The observer's prices and budget on the filter's grid alone (BoundGrid::prices), without the reference's search: for parameters the search itself has no
+// meaning for (NaN, infinities, prices beyond any penalty), where only "does the bound take them" can be compared.  out10: accepted, thr, mut, isie, ie, dsde, de, amb1..3.
+int xmo_kat_bound_prices(const void* paramsIn, double budget, int64_t* out10) {
+  const AlignmentParameters params = toParams((const ParamsIn*)paramsIn);
+  BoundGrid g;
+  const bool ok = g.prices(params, budget);
+  const int64_t v[10] = {ok ? 1 : 0, g.thr, g.mut, g.isie, g.ie, g.dsde, g.de, g.amb[1], g.amb[2], g.amb[3]};
+  for (int i = 0; i < 10; i++) out10[i] = ok ? v[i] : 0;
+  return 0;
+}
+
 // T/BasepairsTest.java:9-45: AlignmentParameters.getPenalty(byte, byte) on IUPAC letters
 double xmo_kat_base_penalty(char a, char b, double mutationPenalty, double ambiguityPenalty) {
   AlignmentParameters p;

@@ -169,12 +169,16 @@ struct BoundGrid {
     const double s = (double)SCALE;
     const double t = std::floor((budget + 0.000001 + 0.0000001) * s);
     if (!(t >= 0 && t < 60000.0)) return false;
+    // (each price range-checked as a double before the conversion: NaN, infinities and values beyond int64 have none; extensions capped like the rest)
+    const double m = std::floor(p.MutationPenalty * s), is = std::floor((p.InsertionStart_Penalty + p.InsertionExtension_Penalty) * s), ix = std::floor(p.InsertionExtension_Penalty * s);
+    const double ds = std::floor((p.DeletionStart_Penalty + p.DeletionExtension_Penalty) * s), dx = std::floor(p.DeletionExtension_Penalty * s);
+    double a[4] = {0, 0, 0, 0};
+    for (int j = 1; j < 4; j++) a[j] = std::floor(p.AmbiguityPenalty * ((double)j / 3.0) * s);
+    if (!(m >= 0 && m <= 30000 && is >= 1 && is <= 30000 && ix >= 1 && ix <= 30000 && ds >= 1 && ds <= 30000 && dx >= 1 && dx <= 30000 && a[1] >= 0 && a[3] <= 30000)) return false;
     thr = (int64_t)t;
-    mut = (int64_t)std::floor(p.MutationPenalty * s);
-    isie = (int64_t)std::floor((p.InsertionStart_Penalty + p.InsertionExtension_Penalty) * s); ie = (int64_t)std::floor(p.InsertionExtension_Penalty * s);
-    dsde = (int64_t)std::floor((p.DeletionStart_Penalty + p.DeletionExtension_Penalty) * s); de = (int64_t)std::floor(p.DeletionExtension_Penalty * s);
-    for (int j = 1; j < 4; j++) amb[j] = (int64_t)std::floor(p.AmbiguityPenalty * ((double)j / 3.0) * s);
-    return !(mut < 0 || isie < 1 || ie < 1 || dsde < 1 || de < 1 || amb[1] < 0 || mut > 30000 || isie > 30000 || dsde > 30000 || amb[3] > 30000);
+    mut = (int64_t)m; isie = (int64_t)is; ie = (int64_t)ix; dsde = (int64_t)ds; de = (int64_t)dx;
+    for (int j = 1; j < 4; j++) amb[j] = (int64_t)a[j];
+    return true;
   }
   // the band the product would need (it decides which problems the filter takes)
   bool bandFits(int n, int m, bool freeStart) const {

@@ -13,7 +13,8 @@ from helpers import streams_equal, first_difference, filter_counters
 from mapper_amd import synth
 
 
-def batch(rng, ref, n):
+def filter_fuzz_reads(rng, ref, n):
+    """A batch of n reads: lengths 330-1500, five error regimes from mild to far beyond the budget, N bases in some reads."""
     qs = []
     for _ in range(n):
         L = int(rng.choice([330, 500, 800, 1000, 1000, 1500]))
@@ -23,6 +24,19 @@ def batch(rng, ref, n):
             r = r.copy(); r[rng.integers(0, L, int(rng.integers(1, 8)))] = 15
         qs.append(([r], 0.0, 1.0))
     return o.QueryBatch(qs)
+
+
+def filter_fuzz_case(rng, n_lo, n_hi):
+    """One case of the fuzz -> (reference codes, params dict, batch): a random reference (60 kb - 700 kb, a third of them with a repeated stretch: more candidates
+    per read), prices off the filter's grid in 40 % of the cases, and filter_fuzz_reads of n_lo .. n_hi - 1 reads.  (tests/helpers.py hands it to the GPU tier.)"""
+    ref = synth.synthetic_reference(int(rng.choice([60_000, 200_000, 700_000])), seed=int(rng.integers(1, 2**31)))
+    if rng.random() < 0.3:   # a repeat: more candidates per read
+        ref = np.concatenate([ref, ref[1000:9000]])
+    prm = {}
+    if rng.random() < 0.4:
+        prm = dict(MutationPenalty=float(rng.choice([1.0, 0.8, 1.5])), InsertionStart_Penalty=float(rng.choice([1.5, 1.0, 2.2])), InsertionExtension_Penalty=float(rng.choice([0.6, 0.35, 0.77])),
+                   DeletionStart_Penalty=float(rng.choice([1.5, 1.1])), DeletionExtension_Penalty=float(rng.choice([0.5, 0.3])), MaxErrorRate=float(rng.choice([0.1, 0.07, 0.15])))
+    return ref, prm, filter_fuzz_reads(rng, ref, int(rng.integers(n_lo, n_hi)))
 
 
 def main():
@@ -35,15 +49,8 @@ def main():
     t0 = time.time()
     tot = dict(calls=0, nodes=0, pieces=0, piece_rejects=0, rejects=0, skipped_nodes=0)
     for k in range(n_batches):
-        ref = synth.synthetic_reference(int(rng.choice([60_000, 200_000, 700_000])), seed=int(rng.integers(1, 2**31)))
-        if rng.random() < 0.3:   # a repeat: more candidates per read
-            ref = np.concatenate([ref, ref[1000:9000]])
-        prm = {}
-        if rng.random() < 0.4:
-            prm = dict(MutationPenalty=float(rng.choice([1.0, 0.8, 1.5])), InsertionStart_Penalty=float(rng.choice([1.5, 1.0, 2.2])), InsertionExtension_Penalty=float(rng.choice([0.6, 0.35, 0.77])),
-                       DeletionStart_Penalty=float(rng.choice([1.5, 1.1])), DeletionExtension_Penalty=float(rng.choice([0.5, 0.3])), MaxErrorRate=float(rng.choice([0.1, 0.07, 0.15])))
+        ref, prm, b = filter_fuzz_case(rng, *((3000, 9000) if on_gpu else (6, 14)))
         p = o.make_params(prm)
-        b = batch(rng, ref, int(rng.integers(3000, 9000)) if on_gpu else int(rng.integers(6, 14)))
         R = o.OracleReference([("r", ref)])
         with o.observe_bound():
             want = R.align(b, p, threads=os.cpu_count())

@@ -98,6 +98,7 @@ def lib():
         L.xmo_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xmo_result_free.argtypes = [C.POINTER(_Result)]
         L.xmo_kat_bound.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        L.xmo_kat_bound_prices.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64)]
         L.xmo_observe_bound.argtypes = [C.c_int]
         L.xmo_observe_bound.restype = None
         L.xmo_kat_multi_contains.argtypes = [C.c_char_p, C.c_char_p]
@@ -320,3 +321,10 @@ def kat_bound(params, query, query_rc, start_a, end_a, reference, start_b, end_b
     if lib().xmo_kat_bound(C.byref(params), q.ctypes.data, len(q), 1 if query_rc else 0, start_a, end_a, r.ctypes.data, len(r), start_b, end_b, predicted_best_offset, out):
         raise RuntimeError(lib().xmo_last_error().decode())
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def kat_bound_prices(params, budget):
+    """The observer's prices and budget on the rejection filter's grid alone (no search): -> None where it declines them, else (thr, mut, isie, ie, dsde, de, amb1, amb2, amb3)."""
+    out = (C.c_int64 * 10)()
+    lib().xmo_kat_bound_prices(C.byref(params), float(budget), out)
+    return tuple(int(x) for x in out[1:]) if out[0] else None

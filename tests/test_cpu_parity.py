@@ -8,7 +8,7 @@ import pytest
 import oracle_lib as o
 import hostsim_lib as hs
 from helpers import (KAT, streams_equal, first_difference, se_batch, pe_batch, ragged_se_batch, check_align_case, sprinkle_ambiguity, ambiguous_reference,
-                     heavy_ambiguity, low_complexity_reads, bound_problems, filter_counters)
+                     heavy_ambiguity, low_complexity_reads, bound_problems, filter_counters, check_bound_edges)
 from mapper_amd import api, synth, _capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -338,6 +338,14 @@ def test_kernel_logic_rejection_filter_decides_like_the_oracle_observer():
         seen[(verdict, found)] = seen.get((verdict, found), 0) + 1
     assert seen.get((2, 0), 0) > 400 and seen.get((1, 1), 0) > 400 and seen.get((0, 0), 0) + seen.get((0, 1), 0) > 200, seen
 
+
+
+def test_kernel_logic_rejection_filter_at_its_edges_decides_like_the_oracle_observer():
+    """The edge table of tests/helpers.py bound_edge_problems (band and window limits, the foot branch, contig ends in both search directions, the budget cap and
+    its rounding, prices at the grid's limits, non-finite and out-of-range prices) through the host-compiled filter: the observer's verdict on every problem
+    (tests/test_gpu_bound.py runs the same table on the device, where a price's conversion to an integer behaves differently)."""
+    seen = check_bound_edges(lambda prm, *a: hs.test_bound(o.make_params(prm), *a))
+    assert sum(1 for v, _ in seen.values() if v == 2) >= 10 and sum(1 for v, _ in seen.values() if v == 0) >= 10
 
 def test_kernel_logic_rejection_filter_fuzz_through_the_whole_chain(monkeypatch):
     """scripts/cpu_filter_fuzz.py (profiles/r06/fuzz_filter_sim.log has 200 batches of it): batches of long reads with random lengths, error rates, ambiguity codes and prices

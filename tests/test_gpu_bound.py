@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as o
-from helpers import streams_equal, first_difference, bound_problems, filter_counters
-from mapper_amd import api, synth, cli, _capi
+from helpers import streams_equal, first_difference, bound_problems, filter_counters, long_read_batch, check_bound_edges, filter_fuzz_reads
+from mapper_amd import api, synth, _capi
 
 
 def device_bound(prm, query, query_rc, start_a, end_a, ref, start_b, end_b, offset, pair):
@@ -43,11 +43,43 @@ def test_filter_rejects_exactly_what_the_oracle_observer_rejects(pair):
     assert taken > 300 and rejected > 100   # (the problem mix exercises both outcomes)
 
 
-def long_read_batch(ref, n_reads, sub, indel, seed=0x5EED0004):
-    starts = (synth.splitmix64(seed, n_reads) % np.uint64(len(ref) - 12_600)).astype(np.int64)
-    strand = (synth.splitmix64(seed ^ 0x57A, n_reads) >> np.uint64(63)).astype(np.uint8)
-    reads = synth.synthetic_long_reads(ref, starts, 10_000, seed=seed, sub_rate=sub, indel_rate=indel, strand=strand)
-    return o.QueryBatch([([r[a_:b_].copy()], 0.0, 1.0) for r in reads for a_, b_ in cli.split_sections(10_000, 1000)])
+@pytest.mark.gpu
+@pytest.mark.parametrize("pair", [0, 1, 3], ids=["one-lane", "pair-of-lanes", "eight-lanes"])
+def test_filter_at_its_band_budget_and_price_edges_decides_like_the_oracle_observer(pair):
+    """The deterministic edge table of tests/helpers.py bound_edge_problems, problem by problem against the oracle's observer: band slots K = 200 / 201 and windows
+    m = 456 / 457 (a region of the wave's LDS slot <-> the wide band in HBM), K = 2048 / 2049 and m = 4096 / 4097 (taken <-> declined), windows shorter than the
+    query by 1, 2 and n - 1 bases (the foot branch), windows at either end of the contig and one base in from it in both search directions and on both strands
+    (mayExtend), budgets at 59 999 / 60 000 units and on or just beside a grid multiple, prices at the grid's limits (extension 1/60 and just below it, start
+    penalties 0, mutation 0, ambiguity at the 30 000 cap), and prices the C ABI takes but no search has a meaning for (NaN, infinities, 1e12, a negative start
+    with a huge extension: the observer declines them, the device must too - their conversion to integers was undefined before it was range-checked)."""
+    seen = check_bound_edges(lambda prm, *a: device_bound(prm, *a, pair))
+    assert sum(1 for v, _ in seen.values() if v == 2) >= 10 and sum(1 for v, _ in seen.values() if v == 0) >= 10
+
+
+@pytest.mark.gpu
+def test_off_grid_prices_near_the_caps_batch_equals_oracle():
+    """A batch of long reads (tests/helpers.py filter_fuzz_reads) aligned with prices off the filter's 1/60 grid and near its caps - an insertion start of 0, an
+    extension between grid points, a deletion and an ambiguity price a few units under the 30 000-unit cap - so that the chain's own use of the prices (the
+    search's keys, the straight aligner, the pieces' budgets) and the filter's rounding of them are compared with the oracle together: streams bit for bit,
+    counters as above.  (An extension near 1/60 itself makes insertions nearly free and the reference's searches explode: the edge table has it, one problem.)"""
+    rng = np.random.default_rng(0x0FF6)
+    ref = synth.synthetic_reference(300_000, seed=0x0FF7)
+    b = filter_fuzz_reads(rng, ref, 1200)
+    prm = dict(MutationPenalty=1.2345, InsertionStart_Penalty=0.0, InsertionExtension_Penalty=0.7 + 1 / 120, DeletionStart_Penalty=499.0, DeletionExtension_Penalty=0.9,
+               MaxErrorRate=0.1, AmbiguityPenalty=499.99)   # (deletion start + extension: 29 994 of the 30 000 units the filter takes; ambiguity: 29 999)
+    R = o.OracleReference([("r", ref)])
+    with o.observe_bound():
+        want = R.align(b, o.make_params(prm), threads=min(16, os.cpu_count()))
+    db = api.ReferenceDatabase([("r", ref)], max_query_length=1500)
+    try:
+        got = db.align_arrays(b.mate_count, b.mate_offset, b.mate_length, b.codes, b.expected_inner, b.deviation, api.AlignmentParameters(**prm))
+    finally:
+        db.close()
+    assert streams_equal(want, got), first_difference(want, got, b.nq)
+    assert got.extra[3] == 1, "a batch of long reads runs its gapped pass with the filter"
+    ok, what = filter_counters(got.counters, got.extra, want.counters)
+    assert ok, what
+    assert what["oracle_observer"]["searches_examined"] > 0, what
 
 
 @pytest.mark.gpu

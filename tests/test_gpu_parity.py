@@ -163,9 +163,11 @@ def test_long_reads_on_gpu():
 @pytest.mark.parametrize("env", [{"XM_FULL_WAVES": "1"}, {"XM_FULL_WAVES": "1", "XM_FULL_LPW": "32"}, {"XM_FULL_WAVES": "1", "XM_FULL_LPW": "16", "XM_PAIR_LANES": "0"}],
                          ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
 def test_long_reads_sharing_waves_on_gpu(env, monkeypatch):
-    """Enough 1,000 bp queries that the gapped pass puts several of them on every wave (its launch shape for long reads: 8 per wave; here 9 000 reads on
-    1 024 waves, and the shapes of the short-read pass beside it): the searches of a wave's reads - HBM mode from the start at this chain scale - and
-    the two lanes of a read must not disturb each other."""
+    """Enough 1,000 bp queries that the gapped pass puts more than one of them on a wave: 9 000 reads with XM_FULL_WAVES=1 get 1 024 wave slots and
+    lpw = min(XM_FULL_LPW, ceil(9 000 / 1 024)), which the launch logic for long reads then cuts to lanes / 4 096 (the GPU's wave slots, one context) - TWO
+    reads per wave on ~4 100 waves in all three settings (and the shapes of the short-read pass beside it).  The searches of a wave's reads - HBM mode from the
+    start at this chain scale - and the lanes of a read must not disturb each other.  Five to eight reads per wave, eight lanes each, with reads that do not
+    align: tests/test_gpu_dense_waves.py."""
     ref = synth.synthetic_reference(400_000, seed=41)
     reads = synth.synthetic_single_end(ref, 9000, read_len=1000, sub_rate=0.02, indel_prob=0.3, seed=42)[0]
     b = se_batch(reads)
