@@ -12,12 +12,16 @@ and tables in HBM - and each has its own resident copy of the batch, host thread
 same time - how the product aligns a stream of batches (`python -m mapper_amd --contexts N`, mapper_amd/multi.py): the wave slots one
 context's gapped pass leaves idle (its tail, the host gaps between its passes, its result copy) are filled by the other's passes,
 +15-18 % reads/s (configs[1]: three and four contexts measure the same or less; a workload whose passes end in a long tail - --config 1rep -
-gains up to five contexts, given hardware queues for them: GPU_MAX_HW_QUEUES, profiles/r04/NOTES.md 13).  At N=1 the line also carries
-`single_context`: the same kernel with one launch on the GPU at a time (--contexts 1 makes that the headline).
+gains up to five contexts, given hardware queues for them: GPU_MAX_HW_QUEUES, profiles/r04/NOTES.md 13).
 
-The line carries `roofline` (algorithmic bytes of SURVEY.md §8(d) per second of align-kernel time, against the 8 TB/s
-HBM peak) and `cpu_baseline` (the CPU oracle, a port of the Java path, timed on this box's host cores on a bounded
-sample).  The oracle is only the checker/baseline here; nothing under oracle/ is on the measured GPU path.
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the steps, writes --dump-outputs and prints the line,
+which carries `roofline` (algorithmic bytes of SURVEY.md §8(d) per second of align-kernel time, against the 8 TB/s HBM peak, from the
+timed steps' own counters).  --full adds the side measurements and checks, each a run of its own: at N=1 `single_context` (the same kernel
+with one launch on the GPU at a time, measured before the headline; --contexts 1 makes that the headline), `pcie_inclusive`, `streamed`,
+`wave_form`, `cpu_baseline` (the CPU oracle, a port of the Java path, timed on the host's cores on a bounded sample) with
+`bit_identical` and the oracle's work counters, `seed_probe` and `end_to_end`; at every N the `golden` digest of configs[1] / configs[2]
+against the committed one and `overfull_buckets` of the repeat-rich and GRCh38-shaped indexes.  A parity failure among them makes the run
+exit 1.  The oracle is only the checker/baseline here; nothing under oracle/ is on the measured GPU path.
 """
 import argparse
 import json
@@ -40,12 +44,14 @@ def main():
     ap.add_argument("--reads", type=int, default=1_000_000, help="reads per GPU per step (configs[1]: 1,000,000)")
     ap.add_argument("--ref-len", type=int, default=5_000_000)
     ap.add_argument("--read-len", type=int, default=150)
-    ap.add_argument("--seed-probes", type=int, default=64_000_000, help="bucket-header probes of the seed-lookup micro-benchmark (0 = skip); the default is the size of the gather-ceiling measurement it is held against (2^26 accesses); a quarter of them are run again with up to four positions each on the workload's index, all of them with up to seven on the HBM-resident index")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements and checks of the line (single_context, pcie_inclusive, streamed, wave_form, golden, cpu_baseline, "
+                    "seed_probe, end_to_end and the options below that size them); without it the run measures the headline alone")
+    ap.add_argument("--seed-probes", type=int, default=64_000_000, help="--full: bucket-header probes of the seed-lookup micro-benchmark (0 = skip); the default is the size of the gather-ceiling measurement it is held against (2^26 accesses); a quarter of them are run again with up to four positions each on the workload's index, all of them with up to seven on the HBM-resident index")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only to exercise the multi-rank path on a one-GPU box)")
     ap.add_argument("--force-device", type=int, default=-1, help="testing: every rank uses this GPU instead of its LOCAL_RANK")
-    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="reads of the same workload timed on the host cores (0 = skip); default: the whole batch (about a second on the GPU box's 256 cores)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="the CPU baseline's timed run is repeated until the oracle has worked this long (best and median run reported)")
-    ap.add_argument("--end-to-end-reads", type=int, default=2_000_000, help="reads of the end_to_end leg (--config 1 / 2, N = 1): `python -m mapper_amd` from a FASTQ file on disk to a SAM file on disk (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="--full: reads of the same workload timed on the host cores (0 = skip); default: the whole batch (about a second on 256 host cores)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: the CPU baseline's timed run is repeated until the oracle has worked this long (best and median run reported)")
+    ap.add_argument("--end-to-end-reads", type=int, default=2_000_000, help="--full: reads of the end_to_end leg (--config 1 / 2, N = 1): `python -m mapper_amd` from a FASTQ file on disk to a SAM file on disk (0 = skip)")
     ap.add_argument("--config", default="1", choices=["1", "1rep", "2", "4shape", "3shape", "3rep", "4", "4mild"],
                     help="1: BASELINE.json configs[1] (single-end 150 bp, the headline); 2: configs[2] shape (2x150 bp pairs, --spacing 100 50); "
                     "4shape: the 1,000 bp queries --split-queries-past-size 1000 makes of configs[4]'s reads, against the same 5 Mb reference; "
@@ -53,17 +59,17 @@ def main():
                     "(pairs; 10 kb reads split at 1000 with the error rates as stated; the same with 2 %% substitutions + 0.2 %% indel events); "
                     "3rep: configs[3]'s pairs against the same shape with the repeat structure of a genome (synth.grch38_repeat_rich_reference: 120 k copies of 300 bp families at 85-95 %% "
                     "identity, 2 000 segmental duplications, 50 000 tandem repeats)")
-    ap.add_argument("--stream-batches", type=int, default=4, help="batches of the PCIe-inclusive streamed measurement (api.align_stream: the upload of batch k+1 overlaps the alignment of batch k; 0 = skip)")
-    ap.add_argument("--seed-index-mb", type=int, default=500, help="size (M bases) of the second, HBM-resident index the seed-probe leg builds so that its probes miss every cache (0 = probes on the workload's own index only)")
+    ap.add_argument("--stream-batches", type=int, default=4, help="--full: batches of the PCIe-inclusive streamed measurement (api.align_stream: the upload of batch k+1 overlaps the alignment of batch k; 0 = skip)")
+    ap.add_argument("--seed-index-mb", type=int, default=500, help="--full: size (M bases) of the second, HBM-resident index the seed-probe leg builds so that its probes miss every cache (0 = probes on the workload's own index only)")
     ap.add_argument("--big-scale", type=float, default=1.0, help="testing: the GRCh38-shaped reference of --config 3shape / 4 / 4mild at this fraction of its size (1.0 = the 3.1 Gb of SURVEY.md section 8(d))")
     ap.add_argument("--share-dir", default=None, help="--gpus N with --config 3shape / 4 / 4mild: where rank 0 leaves the synthetic reference (memory-mapped by the other ranks) and the index "
                     "it built (xm_index_save; the other ranks xm_index_load it): one generation and one hashing per node instead of N (default: a directory under the system's temporary directory named after MASTER_PORT)")
     ap.add_argument("--contexts", type=int, default=None, help="contexts per GPU (default: --config 1 three, --config 1rep four, the others two): the steps are dealt to this many contexts of the GPU (xm_context_new: they share the index) that align their resident batches at the same time (1: one launch at a time)")
     ap.add_argument("--scratch-gib", type=float, default=0.0, help="upper limit of a context's scratch in GiB (0: what is free, divided between the contexts, up to 200 GiB): the headline against the scratch budget (profiles/r06/scratch_budget.log)")
-    ap.add_argument("--single-context-steps", type=int, default=3, help="steps of the one-launch-at-a-time measurement beside the headline at N=1 (0 = skip)")
+    ap.add_argument("--single-context-steps", type=int, default=3, help="--full: steps of the one-launch-at-a-time measurement beside the headline at N=1 (0 = skip)")
     ap.add_argument("--engine", default="gpu", choices=["gpu", "hostsim"], help="testing only: hostsim = a DRY RUN of this script's flow (ranks, barriers, max-over-ranks timing, the rank-0 line) "
                     "with the kernel sources compiled for the host (tests/hostsim, tests/sim_engine.py) instead of the GPU library; the line it prints is marked as such and is not a measurement")
-    ap.add_argument("--wave-steps", type=int, default=2, help="steps of the opt-in wave-per-read form (XM_WAVE=1) measured beside the headline (0 = skip)")
+    ap.add_argument("--wave-steps", type=int, default=2, help="--full: steps of the opt-in wave-per-read form (XM_WAVE=1) measured beside the headline (0 = skip)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the result streams of the last step (rank 0's; context 0's when there are several) "
                     "as DIR/<name>.npy in float64, at most 64 MB in all (a fixed seeded sample of the queries past that): two builds compared output for output")
     args = ap.parse_args()
@@ -103,6 +109,8 @@ def main():
         dist = None
         gpu.set_device(local_rank)
     assert args.gpus == world, "--gpus must equal the number of launched ranks"
+    # the side measurements: --full, N=1 (N > 1: the line carries the headline only; the other ranks must not wait at the barrier for rank 0's side measurements)
+    extras = args.full and world == 1
 
     from mapper_amd import api, synth, _capi
     build = _capi.check_stamp()  # refuses to measure a library that was not built from the sources in the tree
@@ -246,7 +254,7 @@ def main():
     else:
         db = api.ReferenceDatabase(contigs, mode="mapper", max_query_length=args.read_len, device=local_rank)
     index_build_s = time.time() - t0
-    # One context at a time first (at N=1, when the headline uses several): the kernel's own numbers, one launch on the GPU at a time
+    # One context at a time first (--full at N=1, when the headline uses several): the kernel's own numbers, one launch on the GPU at a time
     single = None
     if args.contexts is None:
         # a pass of the repeat-rich workload ends with a long tail of few heavy reads (a quarter of its wave slots busy on average): more contexts fill it
@@ -255,7 +263,7 @@ def main():
         args.contexts = 4 if args.config == "1rep" else (3 if args.config == "1" else 2)
     n_ctx = max(1, args.contexts)
     scratch_each = None
-    if n_ctx > 1 and world == 1 and args.single_context_steps > 0:
+    if n_ctx > 1 and extras and args.single_context_steps > 0:
         db.upload_arrays(mc, mo, ml, codes, exp_in, dev_in)
         run_steps([db], max(1, args.warmup))
         gpu.synchronize()
@@ -301,16 +309,15 @@ def main():
         if args.dump_outputs:
             dump_outputs(r, args.dump_outputs)
         info = db.info()
-        overfull = db.bucket_stats() if args.config in ("1rep", "3rep", "3shape") else None
+        overfull = db.bucket_stats() if args.full and args.config in ("1rep", "3rep", "3shape") else None
         c = r.counters
         # algorithmic bytes of one step: B_in + 8*P + sum_hits(B_pos + 20) + window bytes + B_out
         pos_bytes = info["position_bytes"]
         alg_bytes = c[10] + 8 * c[1] + c[3] * (pos_bytes + 20) + c[9] + 4 * len(r.ints) + 8 * len(r.dbls)
         avg_launch_ms = kernel_ms / max(launches, 1)
         achieved = (alg_bytes * args.steps / max(launches, 1)) / (avg_launch_ms * 1e-3) / 1e9  # GB/s: bytes per launch / avg launch duration
-        aligned = int(sum(1 for q in range(nq) if r.ints[r.int_off[q] + 1] > 0)) if nq <= 2_000_000 else -1
+        aligned = int(np.count_nonzero(np.asarray(r.ints)[np.asarray(r.int_off)[:nq] + 1] > 0)) if nq <= 2_000_000 else -1
 
-        extras = world == 1   # (N > 1: the line carries the headline only; the other ranks must not wait at the barrier for rank 0's side measurements)
         # host buffers in (xm_align_batch: H2D copy + the same passes), every context at the same time: the PCIe-inclusive rate, never the headline value
         import threading
         rps = [None] * len(ctx)
@@ -367,11 +374,11 @@ def main():
             finally:
                 os.environ["XM_WAVE"] = "0"
 
-        # the committed golden digest of this exact batch (tests/golden/synthetic_golden.json, made once by the oracle): checked even with --cpu-sample 0
+        # the committed golden digest of this exact batch (tests/golden/synthetic_golden.json, made once by the oracle): checked by --full even with --cpu-sample 0
         golden = None
         try:
             key = {"1": "configs1_single_end_1000000", "2": "configs2_paired_end_1000000"}.get(args.config)
-            if key and rank == 0 and (args.reads, args.ref_len, args.read_len) == (1_000_000, 5_000_000, 150):
+            if key and args.full and rank == 0 and (args.reads, args.ref_len, args.read_len) == (1_000_000, 5_000_000, 150):
                 import hashlib
                 want_g = json.load(open(os.path.join(ROOT, "tests", "golden", "synthetic_golden.json")))["full_digests"][key]
                 hsh = hashlib.sha256()
@@ -525,7 +532,7 @@ def main():
         value = world * nq * reads_per_query * args.steps / elapsed / 1e6
         line = {
             "metric": "M reads/s aligned (150 bp)", "value": round(value, 4), "unit": "Mreads/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "full": args.full,
             "vs_baseline": None, "dtype": "f64", "data": "synthetic" if not dry else "synthetic; DRY RUN on the host simulation of the kernel sources (--engine hostsim): the multi-rank flow is exercised, nothing is measured",
             "rank_batch_digests": digests if world > 1 else None,
             "pinned_host_bytes_high_water_per_rank": pinned,
@@ -556,9 +563,9 @@ def main():
                          "traffic_rate": None if traffic is None else round(traffic / (avg_launch_ms * 1e-3) / 1e9, 1),
                          "note": "achieved/peak/frac: algorithmic bytes of one launch over that launch's duration, against the 8 TB/s stream peak; with several contexts "
                                  "the launches of the contexts share the GPU, so a launch lasts longer than it would alone (single_context has the kernel's numbers with one "
-                                 "launch at a time; frac_one_launch_at_a_time is this fraction from that leg) and frac_of_all_concurrent_launches is the algorithmic rate of the GPU as a whole.  traffic (PMC) is per-lane scratch in HBM, touched in "
+                                 "launch at a time, --full; frac_one_launch_at_a_time is this fraction from that leg) and frac_of_all_concurrent_launches is the algorithmic rate of the GPU as a whole.  traffic (PMC) is per-lane scratch in HBM, touched in "
                                  "scattered 32-64 B pieces: traffic_rate (GB/s, traffic / average launch duration) is to be read against this GPU's measured "
-                                 "random-64-B-sector ceiling (seed_probe.random_64B_gather_ceiling_sectors_per_s x 64 B), not against the stream peak"},
+                                 "random-64-B-sector ceiling (seed_probe.random_64B_gather_ceiling_sectors_per_s x 64 B, --full), not against the stream peak"},
             "contexts": {"per_gpu": n_ctx, "scratch_gib_each": round(scratch_each / 2**30, 1) if scratch_each else None,
                          "note": "a step is one whole pass of the hot path over one resident batch; the steps are dealt to %d contexts of the GPU (xm_context_new: one index - host "
                                  "tables and tables in HBM - shared by all; a resident copy of the batch, a host thread, a stream and a share of the scratch each) that align at the same time: "
@@ -578,7 +585,7 @@ def main():
             rc = 1  # a parity failure is not a measurement
     for c_ in ctx:
         c_.close()
-    if rank == 0 and line is not None and world == 1 and args.end_to_end_reads > 0 and args.config in ("1", "2") and args.ref_len <= 50_000_000:
+    if rank == 0 and line is not None and extras and args.end_to_end_reads > 0 and args.config in ("1", "2") and args.ref_len <= 50_000_000:
         # (after the contexts of the timed region are closed: the command line builds its own index and contexts)
         line["end_to_end"] = end_to_end(args, ref, synth)
     if rank == 0 and line is not None:

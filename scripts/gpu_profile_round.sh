@@ -8,10 +8,10 @@ mkdir -p $O
 cd $R
 # the library is built before any profiler starts: nothing under rocprofv3 may spawn make/hipcc (mapper_amd/_capi.py lib() never builds)
 make -j8 -C $R/mapper_amd/csrc > /dev/null || exit 1
-timeout 900 python3 bench.py > $O/bench_full.log 2>&1
+timeout 900 python3 bench.py --full > $O/bench_full.log 2>&1
 tail -n 1 $O/bench_full.log > $O/bench_line.json
-timeout 600 python3 bench.py --config 2 --seed-probes 0 --steps 9 --stream-batches 10 2> $O/bench_config2.err | tail -n 1 > $O/bench_config2.json
-timeout 600 python3 bench.py --config 4shape --seed-probes 0 --steps 6 2> $O/bench_config4shape.err | tail -n 1 > $O/bench_config4shape.json
+timeout 600 python3 bench.py --full --config 2 --seed-probes 0 --steps 9 --stream-batches 10 2> $O/bench_config2.err | tail -n 1 > $O/bench_config2.json
+timeout 600 python3 bench.py --full --config 4shape --seed-probes 0 --steps 6 2> $O/bench_config4shape.err | tail -n 1 > $O/bench_config4shape.json
 cd /tmp && export TMPDIR=/tmp
 Q="--cpu-sample 0 --seed-probes 0 --wave-steps 0 --single-context-steps 0 --stream-batches 0"
 # (the profiled command is the headline measurement alone: the default contexts and steps, without the extra measurements of the bench line)

@@ -9,7 +9,7 @@ READS=${3:-400000}
 timeout 900 python3 -m pytest tests/test_gpu_bound.py -x -q 2>&1 | tail -5 > $O/tests.log
 cat $O/tests.log
 for f in 1 0; do
-  XM_BOUND_FILTER=$f timeout 1200 python3 bench.py --config 4 --big-scale $SCALE --reads $READS --contexts 1 --steps 1 --warmup 1 --seed-probes 0 --stream-batches 0 --single-context-steps 0 --cpu-sample 20000 2> $O/bench_config4_filter$f.err | tail -n 1 > $O/bench_config4_filter$f.json
+  XM_BOUND_FILTER=$f timeout 1200 python3 bench.py --full --config 4 --big-scale $SCALE --reads $READS --contexts 1 --steps 1 --warmup 1 --seed-probes 0 --stream-batches 0 --single-context-steps 0 --cpu-sample 20000 2> $O/bench_config4_filter$f.err | tail -n 1 > $O/bench_config4_filter$f.json
   python3 - <<PY
 import json
 d = json.load(open("$O/bench_config4_filter$f.json"))

@@ -94,3 +94,22 @@ def test_bench_dump_outputs_samples_whole_queries_within_the_budget(tmp_path):
     for i, qq in enumerate(q):
         assert np.array_equal(ints[int(io[i]):int(io[i + 1])], r.ints[r.int_off[qq]:r.int_off[qq + 1]])
         assert np.array_equal(dbls[int(do[i]):int(do[i + 1])], r.dbls[r.dbl_off[qq]:r.dbl_off[qq + 1]])
+
+
+def test_bench_plain_run_measures_the_headline_alone():
+    """Without --full a run sets up, warms up, times its steps and prints the line: none of the side measurements or checks runs (their options are left
+    at their defaults here, which start every one of them under --full), and the line says so."""
+    reads = 40
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--engine", "hostsim", "--reads", str(reads), "--ref-len", "60000", "--steps", "2", "--warmup", "1"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - reads / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * max(d["value"], 1e-9) + 1e-4
+    for k in ("single_context", "pcie_inclusive", "streamed", "wave_form", "golden", "cpu_baseline", "bit_identical", "seed_probe"):
+        assert d[k] is None, k
+    assert "end_to_end" not in d and list(d["counters"]) == ["device"] and d["roofline"]["frac_one_launch_at_a_time"] is None
+    assert 0 < d["config"]["aligned_reads"] <= reads and d["roofline"]["algorithmic_bytes_per_step"] > 0   # (from the timed steps' own result)
