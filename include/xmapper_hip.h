@@ -219,7 +219,21 @@ int xm_measure_random_gather(int device, int64_t table_bytes, int64_t accesses, 
  * batch still in HBM): per forward reference position the depth and the counts of differing query bases (A, C, G, T), in integer units of
  * 1 / XM_PILEUP_UNIT read bases (a query with n alignments adds 1/n per alignment; the mates of a pair add 1/2 each where they overlap), and one
  * event per insertion / deletion block: eight int64 = contig, position (startB of the block), type (1 insertion, 2 deletion), length, query
- * ordinal (over all batches added), mate | reversed << 1 | near-query-end << 2, startA, weight.  Several GPUs: one pile-up per replica, summed by the host in rank order. */
+ * ordinal (over all batches added), mate | reversed << 1 | near-query-end << 2, startA, weight.  Several GPUs: one pile-up per replica, summed by the host in rank order.
+ * The rules in full (tests/pileup_model.py recounts them on the host and the GPU tier compares the device with it, unit for unit):
+ *  - weight: a component with n >= 1 alignments gives alignment a (0-based, stream order) UNIT / n, plus one unit when a < UNIT mod n, so the n weights
+ *    sum to UNIT for any n (17, 19, 23 ... do not divide UNIT); a component without alignments adds nothing;
+ *  - depth: every reference base under a block of equal lengths and every base of a deletion block (lengthA == 0) gets the weight; an insertion adds none;
+ *  - alt: under a block of equal lengths the query base is the mate's base at startA + i on the strand that was aligned (the reverse complement of the
+ *    mate as given when referenceReversed); it is counted in plane A, C, G or T only when it and the reference base are both unambiguous and differ;
+ *  - mate: in a query with one component, sequence k of an alignment is mate k; with two components (the pair fell back to unpaired alignments)
+ *    the sequences of component c are mate c;
+ *  - overlap: the two sequences of one pair alignment that lie on the same contig share the depth where their reference intervals
+ *    [first startB, last startB + lengthB) intersect: there the first adds w / 2 and the second w - w / 2 (integer division) - to depth, alt and middle
+ *    alike; an event's weight is that of a base at its startB;
+ *  - near a query end (fraction f > 0): query index k on the aligned strand with (double)k < f * len || (double)k >= len - f * len, len the mate's own
+ *    length, evaluated in doubles as written; the bases of a deletion and every event take k = startA of their block;
+ *  - the events of one xm_pileup_add_last call are ordered by (query ordinal, contig, position, flags, startA). */
 #define XM_PILEUP_UNIT 1441440ull
 typedef struct xm_pileup xm_pileup;
 int xm_pileup_new(xm_index* index, xm_pileup** out);

@@ -208,3 +208,30 @@ class MatchDatabase:
         out.write("CHR\tPOS\tREF\tALT\tALT DEPTH\tTOTAL DEPTH\n")
         for c, pos1, ra, qa, w, total in self.mutations(parameters):
             out.write("%s\t%d\t%s\t%s\t%s\t%s\n" % (self.contigs[c][0], pos1, ra, qa, _number(w), _number(total)))
+
+
+class CountedMatchDatabase(MatchDatabase):
+    """The host half of MatchDatabase (event grouping, thresholds, continuation cut, line order) over counts that are handed in instead of read from
+    a device pile-up: no library is loaded and no GPU is needed.  contigs: [(name, codes)]; depth[c], alt[c] ([4, n]) and middle[c] in units of 1 / UNIT;
+    events: the eight fields of xm_pileup_events per event; batches: the queries of each batch added, in order (for the text of insertions)."""
+
+    def __init__(self, contigs, depth, alt, middle, events, batches=(), query_end_fraction=0.0):
+        self.dbs, self._h, self._L = [], [], None
+        self.query_end_fraction = float(query_end_fraction)
+        self.contigs = contigs
+        self._counts = [(np.asarray(d, np.uint64), np.asarray(a, np.uint64), np.asarray(m, np.uint64)) for d, a, m in zip(depth, alt, middle)]
+        self._event_rows = [(0,) + tuple(int(x) for x in e) for e in events]
+        self._reads = {}
+        self._batches = [list(batches)]
+
+    def add_last(self, queries=None, replica=0):
+        raise RuntimeError("CountedMatchDatabase holds counts that were handed in: there is no device batch to add")
+
+    def _sum(self, contig):
+        return self._counts[contig][0], self._counts[contig][1]
+
+    def _middle(self, contig):
+        return self._counts[contig][2]
+
+    def _events(self):
+        return list(self._event_rows)
