@@ -56,6 +56,20 @@ struct BoundProblem {
   int32_t piece;   // 1: the bound over a piece's whole inner chain (boundPieceProblem below): both ends of the window free, the piece's first and last base left out
 };
 
+// the problem of the filter's test entries (xm_test_bound_kernel, the host simulation's xmsim_test_bound): one search over the given sections at the prices of
+// `p` (Params or xm_params)
+template <class P>
+XM_INL BoundProblem boundTestProblem(const P& p, const uint8_t* query, int queryLength, int queryRc, int startA, int endA, const uint8_t* reference, int referenceLength, int startB, int endB,
+                                     int predictedBestOffset) {
+  BoundProblem bp;
+  bp.qBase = query; bp.qLen = queryLength; bp.qRc = queryRc != 0; bp.rBase = reference; bp.referenceLen = referenceLength;
+  bp.startA = startA; bp.endA = endA; bp.startB = startB; bp.endB = endB; bp.predictedBestOffset = predictedBestOffset;
+  bp.mutation = p.MutationPenalty; bp.insStart = p.InsertionStart_Penalty; bp.insExt = p.InsertionExtension_Penalty; bp.delStart = p.DeletionStart_Penalty;
+  bp.delExt = p.DeletionExtension_Penalty; bp.maxErrorRate = p.MaxErrorRate; bp.ambiguity = p.AmbiguityPenalty;
+  bp.budget = (endA - startA) * p.MaxErrorRate; bp.piece = 0;
+  return bp;
+}
+
 struct BoundPrices { int32_t mut, isie, ie, dsde, de, amb1, amb2, amb3, thr; };
 
 // prices and budget on the grid (the oracle's observer evaluates the same expressions: IEEE double products and floors)

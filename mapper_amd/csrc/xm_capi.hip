@@ -12,6 +12,7 @@
 #include "xm_index_host.h"
 #include "xm_kernel_args.h"
 #include "xm_kernel_common.h"
+#include "xm_pass_plan.h"
 #include "xm_collapse.h"
 #include <hip/hip_runtime.h>
 #include <string>
@@ -41,19 +42,6 @@ int fail(const std::string& msg) { g_error = msg; return 1; }
     hipError_t _e = (expr);                                                                                 \
     if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
   } while (0)
-
-static long long envInt(const char* name, long long dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoll(v) : dflt;
-}
-
-// experiment knobs are validated: a value outside [lo, hi] (or not a power of two where the capacities need one) is an error, not a silent corruption
-static long long envKnob(const char* name, long long dflt, long long lo, long long hi, bool pow2 = false) {
-  const long long v = envInt(name, dflt);
-  if (v < lo || v > hi || (pow2 && (v & (v - 1)) != 0))
-    throw std::runtime_error(std::string(name) + "=" + std::to_string(v) + " is not valid: expected " + (pow2 ? "a power of two in " : "a value in ") + std::to_string(lo) + ".." + std::to_string(hi));
-  return v;
-}
 
 #ifndef XM_WAVES_PER_SIMD
 #define XM_WAVES_PER_SIMD 4  // 128 registers per lane: the path is latency-bound, four waves per SIMD hide more of it than the spills cost
@@ -242,12 +230,7 @@ __global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_test_bound_kernel(P
   xmSetBoundFilter(3);
   xmLoadMergeRule();  // (every thread of the block: it ends with a barrier)
   if (threadIdx.x >= (1u << pair)) return;
-  BoundProblem bp;
-  bp.qBase = query; bp.qLen = queryLength; bp.qRc = queryRc != 0; bp.rBase = reference; bp.referenceLen = referenceLength;
-  bp.startA = startA; bp.endA = endA; bp.startB = startB; bp.endB = endB; bp.predictedBestOffset = predictedBestOffset;
-  bp.mutation = params.MutationPenalty; bp.insStart = params.InsertionStart_Penalty; bp.insExt = params.InsertionExtension_Penalty; bp.delStart = params.DeletionStart_Penalty;
-  bp.delExt = params.DeletionExtension_Penalty; bp.maxErrorRate = params.MaxErrorRate; bp.ambiguity = params.AmbiguityPenalty;
-  bp.budget = (endA - startA) * params.MaxErrorRate; bp.piece = 0;
+  const BoundProblem bp = boundTestProblem(params, query, queryLength, queryRc, startA, endA, reference, referenceLength, startB, endB, predictedBestOffset);
   bool taken = false;
   unsigned long long cells = 0;
   Arena tmp;
@@ -971,6 +954,410 @@ struct xm_pileup {
   std::vector<long long> events;  // (host) 8 per event, in the order of the calls
 };
 
+// ---------------------------------------------------------------- the align call: its state and its steps, in the order alignResidentLocked runs them
+// (what the passes are sized by and how they follow each other is xm_pass_plan.h; here are the buffers, the launches and the copies)
+struct AlignCall {
+  xm_index* idx;
+  ResultBox* box;
+  xm_result* res;
+  int64_t nq;
+  hipStream_t s;
+  int numCUs;
+  IndexView view;
+  Params params;
+  BatchView bv;
+  const int64_t* todo = nullptr;  // device list of the current pass; null on the first pass = all reads
+  long long nTodo = 0;
+  double kernelMs = 0;
+  int launches = 0;
+  int64_t copies = 0, rerun = 0;
+  unsigned long long intCap = 0, dblCap = 0;
+  unsigned long long cursors[4] = {0, 0, 0, 0};
+  bool boundFilterUsed = false;
+#ifdef XM_READ_TIMES
+  DevBuf<unsigned long long> dReadTimes;
+  const char* readTimesFile = nullptr;
+#endif
+  OutView outView() const { return OutView{idx->dOutInts.p, idx->dOutDbls.p, intCap, dblCap, idx->dCursors.p, idx->dStatus.p, idx->dIntOff.p, idx->dDblOff.p, idx->dIntLen.p, idx->dDblLen.p}; }
+};
+
+// One timed step on the call's stream: record, launch(es), hipGetLastError, record, `after` (enqueues the copies of the control words the host reads
+// next), synchronise.  The milliseconds between the events go to kernel_ms and, with a slot, to counters[slot] as microseconds.
+template <class Launch, class After>
+static float timedLaunch(AlignCall& c, int nKernels, int slot, Launch&& launch, After&& after) {
+  float ms = 0;
+  HIP_CHECK(hipEventRecord(c.idx->ev0, c.s));
+  launch();
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(c.idx->ev1, c.s));
+  after();
+  HIP_CHECK(hipStreamSynchronize(c.s));
+  HIP_CHECK(hipEventElapsedTime(&ms, c.idx->ev0, c.idx->ev1));
+  c.kernelMs += ms;
+  if (slot >= 0) c.res->counters[slot] += (int64_t)(ms * 1000.0);
+  c.launches += nKernels;
+  return ms;
+}
+
+// buffers that follow the batch's size, the confidence table of these parameters, cleared counters and control words
+static void prepareCall(AlignCall& c) {
+  xm_index* idx = c.idx;
+  const int64_t nq = c.nq;
+  hipStream_t s = c.s;
+  idx->confPrepare(c.params, s);
+  c.view.conf = idx->dConf.p; c.view.confMask = (uint32_t)(idx->confHost.size() - 1); c.view.confMiss = (ConfMiss*)idx->dConfMiss.p;
+  idx->dListConf[0].ensure((size_t)nq); idx->dListConf[1].ensure((size_t)nq);
+  idx->dStatus.ensure((size_t)nq); idx->dIntOff.ensure((size_t)nq); idx->dDblOff.ensure((size_t)nq); idx->dIntLen.ensure((size_t)nq); idx->dDblLen.ensure((size_t)nq);
+  idx->dCursors.ensure(4); idx->dCounters.ensure(1); idx->dCtl.ensure(1);
+  idx->dListHeavy.ensure((size_t)nq); idx->dListHeavyLate.ensure((size_t)nq);
+  HIP_CHECK(hipMemsetAsync(idx->dCounters.p, 0, sizeof(DevCounters), s));
+  HIP_CHECK(hipMemsetAsync(idx->dCursors.p, 0, sizeof(unsigned long long) * 4, s));
+  PassCtl ctl0;
+  memset(&ctl0, 0, sizeof(ctl0));
+  ctl0.errQuery = ~0ull;
+  HIP_CHECK(hipMemcpyAsync(idx->dCtl.p, &ctl0, sizeof(ctl0), hipMemcpyHostToDevice, s));
+#ifdef XM_READ_TIMES
+  c.readTimesFile = getenv("XM_READ_TIMES_FILE");
+  if (c.readTimesFile && *c.readTimesFile) {
+    c.dReadTimes.ensure((size_t)nq);
+    HIP_CHECK(hipMemset(c.dReadTimes.p, 0, sizeof(unsigned long long) * (size_t)nq));
+    unsigned long long* ptr = c.dReadTimes.p;
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_read_times), &ptr, sizeof(ptr)));
+  }
+#endif
+  c.todo = nullptr;
+  c.nTodo = nq;
+}
+
+// identical queries (xm_context_set_collapse): the first pass gets the representatives, the lowest query index of each group of byte-identical queries,
+// in ascending order (xm_collapse.h).  Every later list is built by the passes from the reads they ran: representatives only.
+static void collapseBuildList(AlignCall& c) {
+  xm_index* idx = c.idx;
+  const int64_t nq = c.nq;
+  hipStream_t s = c.s;
+  size_t cap = 64;
+  while (cap < (size_t)nq * 2) cap <<= 1;
+  const long long nBlocks = (nq + XM_COLLAPSE_PER_BLOCK - 1) / XM_COLLAPSE_PER_BLOCK;
+  idx->dCollapseKeys.ensure(cap); idx->dCollapseReps.ensure(cap); idx->dCollapseTotal.ensure(1);
+  idx->dRepOf.ensure((size_t)nq); idx->dRepList.ensure((size_t)nq); idx->dCollapseBlocks.ensure((size_t)nBlocks);
+  HIP_CHECK(hipMemsetAsync(idx->dCollapseKeys.p, 0, sizeof(unsigned long long) * cap, s));
+  HIP_CHECK(hipMemsetAsync(idx->dCollapseReps.p, 0xFF, sizeof(unsigned long long) * cap, s));
+  const unsigned waveGrid = (unsigned)((nq + 3) / 4);  // one wave per query, four per block
+  unsigned long long nReps = 0;
+  timedLaunch(c, 5, -1, [&] {
+    hipLaunchKernelGGL(xm_collapse_fingerprint_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, idx->dCollapseKeys.p, idx->dCollapseReps.p, (unsigned long long)(cap - 1), idx->dRepOf.p);
+    hipLaunchKernelGGL(xm_collapse_verify_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, (const unsigned long long*)idx->dCollapseReps.p, idx->dRepOf.p);
+    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, idx->dCollapseBlocks.p);
+    hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->dCollapseBlocks.p, idx->dCollapseTotal.p);
+    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, (const long long*)idx->dCollapseBlocks.p, idx->dRepList.p);
+  }, [&] { HIP_CHECK(hipMemcpyAsync(&nReps, idx->dCollapseTotal.p, sizeof(nReps), hipMemcpyDeviceToHost, s)); });
+  if (nReps < 1 || (long long)nReps > nq) throw std::runtime_error("internal error: collapsing found " + std::to_string(nReps) + " distinct queries in a batch of " + std::to_string(nq));
+  c.copies = nq - (int64_t)nReps;
+  c.todo = idx->dRepList.p;
+  c.nTodo = (long long)nReps;
+}
+
+// every copy's slice is its representative's: the scan and gather of finishStreams then write it in query order
+static void collapseFanOut(AlignCall& c) {
+  xm_index* idx = c.idx;
+  timedLaunch(c, 1, -1, [&] {
+    hipLaunchKernelGGL(xm_collapse_fanout_kernel, dim3((unsigned)((c.nq + 255) / 256)), dim3(256), 0, c.s, (long long)c.nq, (const int64_t*)idx->dRepOf.p, idx->dIntOff.p, idx->dDblOff.p,
+                       idx->dIntLen.p, idx->dDblLen.p);
+  }, [] {});
+}
+
+// ---- passes 0 (XM_WAVE=1; off by default: measured slower than the lane-per-read passes on MI355X this round, profiles/r02/NOTES.md):
+// the wave-per-read form (xm_wave_kernel.hip).  Light tier over every read (seed, vote, ungapped alignment, accept); chain
+// tier over the reads that need the gapped chain (or more LDS): a read that meets a PathAligner search leaves the request in its memo, the
+// search kernel runs all waiting searches (one wavefront each), and those reads run again with the results, until none waits; then the
+// same with the largest capacities for the reads that outgrew the chain tier's.  What the wave form does not take (ambiguity codes in the
+// read or its reference window, mates longer than 256 bases, overlapping mates, a structure that outgrows LDS) is left in c.todo for the
+// lane-per-read passes.
+static void runWaveForm(AlignCall& c, const bool tracePasses) {
+  xm_index* idx = c.idx;
+  const int64_t nq = c.nq;
+  hipStream_t s = c.s;
+  idx->dListWaveHeavy.ensure((size_t)nq); idx->dListWaveNext.ensure((size_t)nq); idx->dListFallback.ensure((size_t)nq); idx->dWaveCtl.ensure(1);
+  idx->dWaveSlotOf.ensure((size_t)nq);
+  WaveCtl wctl{0, 0, 0, ~0ull};
+  HIP_CHECK(hipMemcpyAsync(idx->dWaveCtl.p, &wctl, sizeof(wctl), hipMemcpyHostToDevice, s));
+  const OutView ov = c.outView();
+  const int lastTier = (int)envKnob("XM_WAVE_TIERS", 3, 1, 3) - 1;  // (experiment knob: 1 = light tier only, 2 = light + chain tier)
+  int sWaves = 4, sLds = 1, sPerSimd = 4, memoBytes = 1, nodesPerWave = 1;
+  xmSearchGeometry(&sWaves, &sLds, &sPerSimd, &memoBytes, &nodesPerWave);
+  unsigned long long fallbackSoFar = 0;
+  // one launch of a tier over `list` (null = all reads) + classification; returns the counts of the lists it filled
+  auto launchTier = [&](int tier, const int64_t* list, long long n, int64_t* listNext, int32_t* slotOfOut, int64_t* listSearch) {
+    WaveLaunch wl;
+    wl.config = tier == 0 ? (idx->residentAnyPaired ? 1 : 0) : (tier == 1 ? (idx->residentAnyPaired ? 3 : 2) : 4);
+    int wavesPerBlock = 1, ldsPerBlock = 1, wavesPerSimd = 1;
+    xmWaveGeometry(wl.config, &wavesPerBlock, &ldsPerBlock, &wavesPerSimd);
+    long long blocksPerCU = std::min<long long>((160 * 1024) / ldsPerBlock, (long long)(wavesPerSimd * 4) / wavesPerBlock);
+    if (blocksPerCU < 1) blocksPerCU = 1;
+    wl.itemsPerFetch = (int)envKnob(tier == 0 ? "XM_WAVE_FETCH" : "XM_WAVE_CHAIN_FETCH", tier == 0 ? 8 : 1, 1, 1024);
+    long long blocks = std::min<long long>((long long)c.numCUs * blocksPerCU, (n + (long long)wavesPerBlock * wl.itemsPerFetch - 1) / ((long long)wavesPerBlock * wl.itemsPerFetch));
+    if (blocks < 1) blocks = 1;
+    wl.grid = (int)blocks; wl.block = wavesPerBlock * 64;
+    wl.ix = c.view; wl.params = c.params; wl.batch = c.bv; wl.todo = list; wl.nTodo = n; wl.out = ov; wl.nextItem = idx->dCursors.p + 2; wl.counters = idx->dCounters.p;
+    wl.memoBase = (WMemo*)idx->dWaveMemo.p; wl.slotOf = idx->dWaveSlotOf.p;
+    wl.waveNodes = nullptr;
+    if (tier >= 1 && envInt("XM_WAVE_INLINE_SEARCH", 1) != 0) {  // (0: every search through the memo and the search kernel)
+      idx->dWaveNodes2.ensure(((size_t)blocks * wavesPerBlock * (size_t)xmWaveInlineNodeBytes() + sizeof(PNode) - 1) / sizeof(PNode));
+      wl.waveNodes = idx->dWaveNodes2.p;
+    }
+    HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
+    HIP_CHECK(hipMemsetAsync(idx->dWaveCtl.p, 0, 2 * sizeof(unsigned long long), s));  // nNext, nSearch
+    const float ms = timedLaunch(c, 1, tier == 0 ? 12 : 13, [&] {  // kernel microseconds: light tier / chain tiers
+      const int rc = xmWaveLaunch(wl, (void*)s);
+      if (rc != 0) throw std::runtime_error(std::string("wave kernel launch: ") + hipGetErrorString((hipError_t)rc));
+    }, [&] {  // (the classification is not part of the tier's time)
+      hipLaunchKernelGGL(xm_wave_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, list, n, idx->dStatus.p, listNext, slotOfOut, listSearch, idx->dListFallback.p, idx->dWaveCtl.p);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(&wctl, idx->dWaveCtl.p, sizeof(wctl), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, s));
+    });
+    if (tracePasses) fprintf(stderr, "[xm] wave tier %d config %d: reads %lld, %d x %d threads: %.3f ms -> next tier %llu, searches %llu, lane-per-read %llu (so far)\n", tier, wl.config, n, wl.grid,
+                             wl.block, ms, listNext ? wctl.nNext : 0ull, wctl.nSearch, wctl.nFallback);
+    if (wctl.errQuery != ~0ull) {
+      int32_t code = 0;
+      HIP_CHECK(hipMemcpy(&code, idx->dStatus.p + wctl.errQuery, sizeof(code), hipMemcpyDeviceToHost));
+      throw std::runtime_error("Failed to align query " + std::to_string(wctl.errQuery) + ": the reference implementation would have thrown here (status " + std::to_string(code & 0xFF) + ")");
+    }
+    fallbackSoFar = wctl.nFallback;
+  };
+  auto launchSearches = [&](const int64_t* list, long long n) {
+    SearchLaunch sl;
+    long long blocks = std::min<long long>((long long)c.numCUs * std::min<long long>((160 * 1024) / sLds, (long long)(sPerSimd * 4) / sWaves), (n + sWaves - 1) / sWaves);
+    if (blocks < 1) blocks = 1;
+    sl.grid = (int)blocks; sl.block = sWaves * 64;
+    sl.ix = c.view; sl.params = c.params; sl.batch = c.bv; sl.list = list; sl.n = n; sl.memoBase = (WMemo*)idx->dWaveMemo.p; sl.slotOf = idx->dWaveSlotOf.p; sl.nextItem = idx->dCursors.p + 2;
+    idx->dWaveArenas.ensure((size_t)blocks * sWaves * (size_t)nodesPerWave);  // (node payloads: bytes per wave)
+    sl.waveNodes = idx->dWaveArenas.p; sl.counters = idx->dCounters.p;
+    HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
+    const float ms = timedLaunch(c, 1, 14, [&] {  // search kernel microseconds
+      const int rc = xmSearchLaunch(sl, (void*)s);
+      if (rc != 0) throw std::runtime_error(std::string("search kernel launch: ") + hipGetErrorString((hipError_t)rc));
+    }, [] {});
+    if (tracePasses) fprintf(stderr, "[xm] search kernel: %lld searches, %d x %d threads: %.3f ms\n", n, sl.grid, sl.block, ms);
+  };
+  // light tier
+  launchTier(0, c.todo, c.nTodo, lastTier >= 1 ? idx->dListWaveHeavy.p : (int64_t*)nullptr, idx->dWaveSlotOf.p, nullptr);
+  long long nChain = lastTier >= 1 ? (long long)wctl.nNext : 0;
+  if (nChain > 0) {
+    idx->dWaveMemo.ensure((size_t)nChain * (size_t)memoBytes);
+    if (xmMemoInitLaunch((WMemo*)idx->dWaveMemo.p, nChain, (void*)s) != 0) throw std::runtime_error("memo init launch failed");
+    idx->dListWaveSearch[0].ensure((size_t)nChain); idx->dListWaveSearch[1].ensure((size_t)nChain);
+    long long nBig = 0;  // reads for the chain tier with the largest capacities (dListWaveNext, filled behind what is already there)
+    for (int tier = 1; tier <= 2 && tier <= lastTier; tier++) {
+      const int64_t* list = tier == 1 ? idx->dListWaveHeavy.p : idx->dListWaveNext.p;
+      long long n = tier == 1 ? nChain : nBig;
+      int which = 0, rounds = 0;
+      while (n > 0) {
+        // (tier 1 appends its hand-overs to dListWaveNext behind those of its earlier rounds)
+        launchTier(tier, list, n, tier == 1 && lastTier >= 2 ? idx->dListWaveNext.p + nBig : (int64_t*)nullptr, nullptr, idx->dListWaveSearch[which].p);
+        if (tier == 1 && lastTier >= 2) nBig += (long long)wctl.nNext;
+        const long long nSearch = (long long)wctl.nSearch;
+        if (nSearch == 0) break;
+        if (++rounds > 4 * 16) throw std::runtime_error("internal error: search rounds do not end");
+        launchSearches(idx->dListWaveSearch[which].p, nSearch);
+        list = idx->dListWaveSearch[which].p; n = nSearch;
+        which ^= 1;
+      }
+    }
+  }
+  c.todo = idx->dListFallback.p;
+  c.nTodo = (long long)fallbackSoFar;
+  HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
+}
+
+// scratch a context may hold now: up to its limit (halved `shift` times), never more than 3/4 of what is free (+ what this context already holds)
+static unsigned long long scratchBudget(xm_index* idx, const BatchPolicy& pol, int shift) {
+  unsigned long long want = pol.scratchWanted >> shift;
+  size_t freeB = 0, totalB = 0;
+  if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
+    const unsigned long long avail = (unsigned long long)(freeB + idx->dArenas.n) / 4 * 3;
+    if (want > avail) want = avail;
+  }
+  return want < (64ull << 20) ? (64ull << 20) : want;
+}
+
+// one launch of xm_align_kernel as planned, over c.todo; the control words and cursors it left are on the host when it returns
+static float launchAlignPass(AlignCall& c, const BatchPolicy& pol, const PassState& st, const LaunchPlan& pl, PassCtl& ctl) {
+  xm_index* idx = c.idx;
+  hipStream_t s = c.s;
+  uint8_t* laneArenas = idx->dArenas.p + pl.regionsTotal;
+  // light pass -> gapped pass hand-over (HandOver, SavedRead): the reads the light pass stops in front of the gapped chain keep their seeding
+  // state in HBM and the gapped pass continues from it
+  HandOver ho{st.hoMode, pol.seedScale, idx->dArenas.p, (unsigned long long)pol.regionBytes, pl.nRegions, idx->dRegionOf.p, idx->dCursors.p + 3};
+  idx->dWaveNodes.ensure((size_t)pl.grid * (pl.block / 64) * XM_PAL_NODES);
+  SearchPool pool{nullptr, 0, 0, 0};
+  if (pl.poolBuffers > 0) {
+    pool.bufBytes = searchPoolBytes(makeCaps(st.scale));
+    pool.n = (int32_t)pl.poolBuffers;
+    idx->dSearchPool.ensure((size_t)pool.n * pool.bufBytes);
+    pool.base = idx->dSearchPool.p;
+  }
+  idx->dListScale[st.ts].ensure((size_t)c.nq); idx->dListOut[st.to].ensure((size_t)c.nq);
+  HIP_CHECK(hipMemcpyAsync(idx->dCursors.p + 2, &pl.firstItem, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+  const OutView ov = c.outView();
+  // the lanes file the reads they could not finish into the work lists of the passes to come as they publish them (PassLists; no kernel behind the pass)
+  PassLists lists{idx->dListHeavy.p, idx->dListHeavyLate.p, idx->dListScale[st.ts].p, idx->dListOut[st.to].p, idx->dListConf[st.tc].p, (int)pol.k.heavyHint, st.ts, st.to, st.tc, idx->dCtl.p};
+  return timedLaunch(c, 1, !st.heavy ? 12 : 15, [&] {  // kernel microseconds: light pass / gapped pass and reruns
+    hipLaunchKernelGGL(xm_align_kernel, dim3(pl.grid), dim3(pl.block), 0, s, c.view, c.params, c.bv, c.todo, c.nTodo, st.scale, st.heavy ? 2 : (int)pol.k.lightLevel, pl.lpw,
+                       laneArenas, (unsigned long long)pl.arenaBytes, ov, idx->dCursors.p + 2, idx->dCounters.p,
+                       pl.taperUnit, pl.firstStride, idx->dWaveNodes.p, ho, pl.pairLanes, pool, lists, pl.boundFilterArg);
+  }, [&] {
+    HIP_CHECK(hipMemcpyAsync(&ctl, idx->dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, s));
+  });
+}
+
+// the lane-per-read passes over c.todo: plan -> allocate -> launch -> what follows, until no list is left
+static void runLanePasses(AlignCall& c, const BatchPolicy& pol) {
+  xm_index* idx = c.idx;
+  hipStream_t s = c.s;
+  PassState st = firstPass(pol);
+  int scratchShift = 0;  // the budget is halved after an allocation the GPU had no room for (another process, or contexts that were given more than there is)
+  while (c.nTodo > 0) {
+    LaunchPlan pl;
+    {
+      // contexts of one GPU size and allocate their scratch one after the other: they all look at the same free memory
+      std::lock_guard<std::mutex> sizing(idx->dt->allocMu);
+      pl = planLaunch(pol, st, c.nTodo, c.nq, c.numCUs, scratchBudget(idx, pol, scratchShift), idx->dArenas.n);
+      if (pl.scratchBytes > 0 && !idx->dArenas.tryEnsure(pl.scratchBytes)) {  // (sized again with half the budget)
+        if (++scratchShift > 8) throw std::runtime_error("no room in HBM for the scratch of even a few lanes (" + std::to_string(pl.scratchBytes >> 20) + " MiB asked)");
+        continue;
+      }
+      if (st.hoMode == 1) {  // the pool's first regions are the lanes' own
+        const unsigned long long firstFree = (unsigned long long)pl.lanes;
+        HIP_CHECK(hipMemcpyAsync(idx->dCursors.p + 3, &firstFree, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+      }
+    }
+    st.nRegions = pl.nRegions; st.regionsTotal = pl.regionsTotal;
+    if (pl.boundFilter) c.boundFilterUsed = true;
+    PassCtl ctl;
+    const float ms = launchAlignPass(c, pol, st, pl, ctl);
+#ifdef XM_LIGHT_ONLY
+    fprintf(stderr, "[xm] light-only experiment build: pass %d %.3f ms\n", c.launches, ms);
+    break;  // (experiment build, scripts/gpu_light_only.sh: only the first pass is meaningful)
+#endif
+    if (pol.k.tracePasses) fprintf(stderr, "[xm] pass %d: %s reads %lld scale %d lpw %d waves %lld lanes/read %d filter %d: %.3f ms -> heavy %llu scale %llu out %llu\n", c.launches,
+                                   !st.heavy ? "light" : "gapped", c.nTodo, st.scale, pl.lpw, pl.nWaves, 1 << pl.pairLanes, pl.boundFilter, ms, ctl.nHeavy + ctl.nHeavyLate, ctl.nScale[st.ts], ctl.nOut[st.to]);
+#ifdef XM_PROFILE
+    if (pol.k.tracePasses && st.heavy) {  // reads of a wave that stood at a PathAligner call together, this pass
+      unsigned long long a[16] = {0}, z[16] = {0};
+      HIP_CHECK(hipMemcpyFromSymbol(a, HIP_SYMBOL(xm_arrive_prof), sizeof(a)));
+      HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_arrive_prof), z, sizeof(z)));
+      fprintf(stderr, "[xm] pass %d: pair checks (status, result, search problem, search outcome): %llu %llu %llu %llu\n", c.launches, a[4], a[5], a[6], a[7]);
+      fprintf(stderr, "[xm] pass %d: PathAligner arrivals %llu with %llu reads (%.2f per arrival); arrivals of four reads or more: %llu with %llu reads\n", c.launches, a[0], a[1], a[0] ? (double)a[1] / (double)a[0] : 0.0, a[2], a[3]);
+    }
+#endif
+    if (ctl.errQuery != ~0ull) {
+      int32_t code = 0;
+      HIP_CHECK(hipMemcpy(&code, idx->dStatus.p + ctl.errQuery, sizeof(code), hipMemcpyDeviceToHost));
+      code &= 0xFF;
+      std::string q = std::to_string(ctl.errQuery);
+      if (code == XM_ST_NEED_GROW) throw std::runtime_error("Failed to align query " + q + ": gapmer longer than the hashed lengths");
+      throw std::runtime_error("Failed to align query " + q + ": the reference implementation would have thrown here (status " + std::to_string(code) + ")");
+    }
+    const NextPass np = nextPass(pol, st, ctl);
+    c.nTodo = np.nTodo;
+    switch (np.kind) {
+      case PassKind::Done: break;
+      case PassKind::OutRerun: {  // room to spare in the result arenas
+        c.todo = idx->dListOut[np.list].p;
+        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nOut[np.clear], 0, sizeof(unsigned long long), s));
+        unsigned long long keepI = std::min(c.cursors[0], c.intCap), keepD = std::min(c.cursors[1], c.dblCap);
+        unsigned long long newI = std::max(c.intCap * 4 + 65536, c.cursors[0] * 2), newD = std::max(c.dblCap * 4 + 65536, c.cursors[1] * 2);
+        idx->dOutInts.growKeep((size_t)newI, (size_t)keepI, s); idx->dOutDbls.growKeep((size_t)newD, (size_t)keepD, s);
+        c.intCap = idx->dOutInts.n; c.dblCap = idx->dOutDbls.n;
+        c.rerun += c.nTodo;
+        break;
+      }
+      case PassKind::Gapped:
+        if (ctl.nHeavyLate > 0) HIP_CHECK(hipMemcpyAsync(idx->dListHeavy.p + ctl.nHeavy, idx->dListHeavyLate.p, sizeof(int64_t) * (size_t)ctl.nHeavyLate, hipMemcpyDeviceToDevice, s));
+        c.todo = idx->dListHeavy.p;
+        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nHeavy, 0, 2 * sizeof(unsigned long long), s));  // nHeavy, nHeavyLate (a gapped pass never adds to these lists)
+        if (pol.k.profGappedOnly) HIP_CHECK(hipMemsetAsync((char*)idx->dCounters.p + offsetof(DevCounters, t), 0, sizeof(((DevCounters*)nullptr)->t), s));
+        break;
+      case PassKind::ConfRerun:
+        idx->confAbsorbMisses(c.params, s);
+        c.view.conf = idx->dConf.p; c.view.confMask = (uint32_t)(idx->confHost.size() - 1);
+        c.todo = idx->dListConf[np.list].p;
+        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nConf[np.clear], 0, sizeof(unsigned long long), s));
+        c.rerun += c.nTodo;
+        break;
+      case PassKind::ScaleRerun:
+        c.todo = idx->dListScale[np.list].p;
+        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nScale[np.clear], 0, sizeof(unsigned long long), s));
+        c.rerun += c.nTodo;
+        break;
+    }
+  }
+}
+
+// ---- canonical streams in query order: offsets by prefix sum, slices gathered on the device, one copy per stream to the host; the counters
+static void finishStreams(AlignCall& c) {
+  xm_index* idx = c.idx;
+  xm_result* res = c.res;
+  const int64_t nq = c.nq;
+  hipStream_t s = c.s;
+  float ms = 0;
+  HIP_CHECK(hipEventRecord(idx->ev0, s));
+  const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
+  idx->dBlockI.ensure((size_t)nBlocks); idx->dBlockD.ensure((size_t)nBlocks);
+#ifdef XM_READ_TIMES
+  if (c.dReadTimes.p) {
+    std::vector<unsigned long long> t((size_t)nq);
+    HIP_CHECK(hipMemcpy(t.data(), c.dReadTimes.p, sizeof(unsigned long long) * (size_t)nq, hipMemcpyDeviceToHost));
+    unsigned long long* none = nullptr;
+    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_read_times), &none, sizeof(none)));
+    if (FILE* f = fopen(c.readTimesFile, "wb")) { fwrite(t.data(), sizeof(unsigned long long), t.size(), f); fclose(f); }
+    c.dReadTimes.release();
+  }
+#endif
+  idx->dFinalIntOff.ensure((size_t)nq + 1); idx->dFinalDblOff.ensure((size_t)nq + 1);
+  size_t usedI = (size_t)std::min(c.cursors[0], c.intCap), usedD = (size_t)std::min(c.cursors[1], c.dblCap);  // upper bounds of the totals
+  if (c.copies == 0) { idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD); }
+  hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, idx->dIntLen.p, idx->dDblLen.p, idx->dBlockI.p, idx->dBlockD.p);
+  hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, idx->dBlockI.p, idx->dBlockD.p, idx->dFinalIntOff.p, idx->dFinalDblOff.p);
+  if (c.copies > 0) {  // (a copy's slice is in the result arena once and in the streams once per copy: the totals are the scan's)
+    int64_t totals[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(&totals[0], idx->dFinalIntOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&totals[1], idx->dFinalDblOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    usedI = (size_t)totals[0]; usedD = (size_t)totals[1];
+    idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD);
+  }
+  hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, idx->dIntLen.p, idx->dDblLen.p, idx->dBlockI.p, idx->dBlockD.p,
+                     idx->dFinalIntOff.p, idx->dFinalDblOff.p);
+  hipLaunchKernelGGL(xm_gather_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, idx->dIntOff.p, idx->dDblOff.p, idx->dIntLen.p, idx->dDblLen.p,
+                     idx->dFinalIntOff.p, idx->dFinalDblOff.p, idx->dOutInts.p, idx->dOutDbls.p, idx->dFinalInts.p, idx->dFinalDbls.p);
+  HIP_CHECK(hipGetLastError());
+  res->ints = (int32_t*)g_pinned->get(sizeof(int32_t) * (usedI ? usedI : 1), &c.box->bytesInts);
+  res->dbls = (double*)g_pinned->get(sizeof(double) * (usedD ? usedD : 1), &c.box->bytesDbls);
+  idx->lastAlignedNq = nq;
+  idx->lastAlignedGen = idx->residentGen;
+  HIP_CHECK(hipMemcpyAsync(res->int_off, idx->dFinalIntOff.p, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(res->dbl_off, idx->dFinalDblOff.p, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost, s));
+  if (usedI) HIP_CHECK(hipMemcpyAsync(res->ints, idx->dFinalInts.p, sizeof(int32_t) * usedI, hipMemcpyDeviceToHost, s));
+  if (usedD) HIP_CHECK(hipMemcpyAsync(res->dbls, idx->dFinalDbls.p, sizeof(double) * usedD, hipMemcpyDeviceToHost, s));
+  DevCounters dc;
+  HIP_CHECK(hipMemcpyAsync(&dc, idx->dCounters.p, sizeof(dc), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipEventRecord(idx->ev1, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  HIP_CHECK(hipEventElapsedTime(&ms, idx->ev0, idx->ev1));
+  res->d2h_ms = ms;
+  res->num_ints = res->int_off[nq]; res->num_dbls = res->dbl_off[nq];
+  countersToResult(dc, res);
+  res->counters[11] = c.rerun;
+  res->extra[3] = c.boundFilterUsed ? 1 : 0;
+  res->extra[7] = c.copies;
+  for (int i = 0; i < 16; i++) res->prof[i] = (int64_t)dc.t[i];
+  res->kernel_ms = c.kernelMs;
+  res->kernel_launches = c.launches;
+}
+
 extern "C" {
 
 const char* xm_last_error(void) { return g_error.c_str(); }
@@ -1409,11 +1796,8 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
   try {
     const int64_t nq = idx->residentNq;
     HIP_CHECK(hipSetDevice(idx->device));
-    hipStream_t s = idx->stream;
     // the shared tables stay as they are while this call's kernels read them (another context that grows them waits; so does this one's next growth)
     std::shared_lock<std::shared_mutex> tablesInUse(idx->dt->rw);
-    IndexView view = idx->dt->view;
-    const int numCUs = idx->dt->numCUs;
     res->num_queries = nq;
     res->int_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(nq + 1), &box->bytesIntOff);
     res->dbl_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(nq + 1), &box->bytesDblOff);
@@ -1423,539 +1807,25 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
       *out = res;
       return 0;
     }
-    hipEvent_t e0 = idx->ev0, e1 = idx->ev1;
-    float ms = 0;
-
-    BatchView bv{nq, idx->dMateCount.p, idx->dMateOffset.p, idx->dMateLength.p, idx->dCodes.p, idx->dExpected.p, idx->dDeviation.p};
-    Params params;
-    params.MutationPenalty = p->MutationPenalty; params.InsertionStart_Penalty = p->InsertionStart_Penalty; params.InsertionExtension_Penalty = p->InsertionExtension_Penalty;
-    params.DeletionStart_Penalty = p->DeletionStart_Penalty; params.DeletionExtension_Penalty = p->DeletionExtension_Penalty; params.MaxErrorRate = p->MaxErrorRate;
-    params.UnalignedPenalty = p->UnalignedPenalty; params.AmbiguityPenalty = p->AmbiguityPenalty; params.Max_PenaltySpan = p->Max_PenaltySpan;
-    params.MaxNumMatches = p->MaxNumMatches; params.StartingInsertionStartFree = 0;
-
-    idx->confPrepare(params, s);
-    view.conf = idx->dConf.p; view.confMask = (uint32_t)(idx->confHost.size() - 1); view.confMiss = (ConfMiss*)idx->dConfMiss.p;
-    idx->dListConf[0].ensure((size_t)nq); idx->dListConf[1].ensure((size_t)nq);
-    idx->dStatus.ensure((size_t)nq); idx->dIntOff.ensure((size_t)nq); idx->dDblOff.ensure((size_t)nq); idx->dIntLen.ensure((size_t)nq); idx->dDblLen.ensure((size_t)nq);
-    idx->dCursors.ensure(4); idx->dCounters.ensure(1); idx->dCtl.ensure(1);
-    idx->dListHeavy.ensure((size_t)nq); idx->dListHeavyLate.ensure((size_t)nq);
-    HIP_CHECK(hipMemsetAsync(idx->dCounters.p, 0, sizeof(DevCounters), s));
-    HIP_CHECK(hipMemsetAsync(idx->dCursors.p, 0, sizeof(unsigned long long) * 4, s));
-    PassCtl ctl0;
-    memset(&ctl0, 0, sizeof(ctl0));
-    ctl0.errQuery = ~0ull;
-    HIP_CHECK(hipMemcpyAsync(idx->dCtl.p, &ctl0, sizeof(ctl0), hipMemcpyHostToDevice, s));
-
-    // Passes, all on the GPU:
-    //  (1) light pass over every read at scale 1: reads that reach the gapped extension chain stop with XM_ST_NEED_HEAVY
-    //      instead of serialising their wave;
-    //  (2) gapped pass over exactly those reads at scale 4, continued from the state the light pass saved (HandOver);
-    //  (3) reads whose scratch overflowed are rerun with 16x, 64x, ... the scratch.
-    // The work lists are built on the GPU by the lanes themselves (PassLists); every pass appends to the same result arenas.
-#ifdef XM_READ_TIMES
-    DevBuf<unsigned long long> dReadTimes;
-    const char* readTimesFile = getenv("XM_READ_TIMES_FILE");
-    if (readTimesFile && *readTimesFile) {
-      dReadTimes.ensure((size_t)nq);
-      HIP_CHECK(hipMemset(dReadTimes.p, 0, sizeof(unsigned long long) * (size_t)nq));
-      unsigned long long* ptr = dReadTimes.p;
-      HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_read_times), &ptr, sizeof(ptr)));
-    }
-#endif
-    const int64_t* todo = nullptr;  // device list of the current pass; null on the first pass = all reads
-    long long nTodo = nq;
-    double kernelMs = 0;
-    int launches = 0;
-    // identical queries (xm_context_set_collapse): the first pass gets the representatives, the lowest query index of each group of byte-identical queries,
-    // in ascending order (xm_collapse.h).  Every later list is built by the passes from the reads they ran: representatives only.
-    int64_t copies = 0;
-    if (idx->collapse) {
-      size_t cap = 64;
-      while (cap < (size_t)nq * 2) cap <<= 1;
-      const long long nBlocks = (nq + XM_COLLAPSE_PER_BLOCK - 1) / XM_COLLAPSE_PER_BLOCK;
-      idx->dCollapseKeys.ensure(cap); idx->dCollapseReps.ensure(cap); idx->dCollapseTotal.ensure(1);
-      idx->dRepOf.ensure((size_t)nq); idx->dRepList.ensure((size_t)nq); idx->dCollapseBlocks.ensure((size_t)nBlocks);
-      HIP_CHECK(hipMemsetAsync(idx->dCollapseKeys.p, 0, sizeof(unsigned long long) * cap, s));
-      HIP_CHECK(hipMemsetAsync(idx->dCollapseReps.p, 0xFF, sizeof(unsigned long long) * cap, s));
-      const unsigned waveGrid = (unsigned)((nq + 3) / 4);  // one wave per query, four per block
-      HIP_CHECK(hipEventRecord(e0, s));
-      hipLaunchKernelGGL(xm_collapse_fingerprint_kernel, dim3(waveGrid), dim3(256), 0, s, bv, idx->dCollapseKeys.p, idx->dCollapseReps.p, (unsigned long long)(cap - 1), idx->dRepOf.p);
-      hipLaunchKernelGGL(xm_collapse_verify_kernel, dim3(waveGrid), dim3(256), 0, s, bv, (const unsigned long long*)idx->dCollapseReps.p, idx->dRepOf.p);
-      hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, idx->dCollapseBlocks.p);
-      hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->dCollapseBlocks.p, idx->dCollapseTotal.p);
-      hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, (const long long*)idx->dCollapseBlocks.p, idx->dRepList.p);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(e1, s));
-      unsigned long long nReps = 0;
-      HIP_CHECK(hipMemcpyAsync(&nReps, idx->dCollapseTotal.p, sizeof(nReps), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      kernelMs += ms;
-      launches += 5;
-      if (nReps < 1 || (long long)nReps > nq) throw std::runtime_error("internal error: collapsing found " + std::to_string(nReps) + " distinct queries in a batch of " + std::to_string(nq));
-      copies = nq - (int64_t)nReps;
-      todo = idx->dRepList.p;
-      nTodo = (long long)nReps;
-    }
-    unsigned long long pendingHeavy = 0, pendingScale = 0;
-    int ts = 0, to = 0, tc = 0;  // which of the two scale / out / confidence lists receives new entries
-    unsigned long long pendingConf = 0;
-    int confRounds = 0;
-    // the scratch capacities are sized for ~150-300 bp mates at scale 1; batches of longer reads start at a larger scale instead of
-    // sending every read through a pass that can only overflow
-    int scale = idx->residentMaxLen <= 320 ? 1 : (idx->residentMaxLen <= 1280 ? 4 : 16), overflowScale = scale;
-    const int gappedScale = scale < 4 ? (int)envKnob("XM_GAPPED_SCALE", 4, 1, 64, true) : scale * (int)envKnob("XM_GAPPED_FACTOR", 4, 1, 64, true);
-    bool heavy = false;
-    unsigned long long intCap = (unsigned long long)nq * 40 + 4096, dblCap = (unsigned long long)nq * 12 + 4096;
-    idx->dOutInts.ensure((size_t)intCap); idx->dOutDbls.ensure((size_t)dblCap);
-    intCap = idx->dOutInts.n; dblCap = idx->dOutDbls.n;
-    unsigned long long cursors[4] = {0, 0, 0, 0};
-    int64_t rerun = 0;
-    const size_t arenaUnit = (size_t)envKnob("XM_ARENA_KB", 288, 64, 16384) * 1024;  // scratch of a lane at scale 1 (experiment knob: the capacities do not follow it, a smaller arena only overflows earlier)
-    // scratch limit of this context: xm_context_set_scratch, else XM_SCRATCH_GIB (experiment knob), else 200 GiB
-    const unsigned long long scratchWanted = idx->scratchBytes > 0 ? (unsigned long long)idx->scratchBytes : (unsigned long long)envKnob("XM_SCRATCH_GIB", 200, 1, 280) << 30;
-    int scratchShift = 0;  // halved after an allocation the GPU had no room for (another process, or contexts that were given more than there is)
-    // wave slots a launch is sized for (in waves per SIMD): alone on the GPU a context fills it (4 are resident at 128 registers; the light pass asks
-    // for twice that, the second half starts as the first drains).  Contexts that share the GPU (xm_context_new) must leave each other room: a
-    // persistent launch that holds every slot keeps the next context's launch waiting until its own tail, and the contexts then run one after the
-    // other instead of side by side.  Together the contexts of a GPU ask for 12 waves per SIMD worth of light lanes and 6 of gapped lanes: two contexts 6 / 3
-    // each (round 3), three 4 / 2 - 14.1-14.3 M reads/s against 13.1-13.2 with two, once the runtime has hardware queues for three contexts' streams
-    // (GPU_MAX_HW_QUEUES, mapper_amd/_capi.py); with 6 / 3 each three contexts measured 12.3-12.7, four with 3 / 1 13.5 (profiles/r04/NOTES.md 15)
-    // (the contexts that EXIST on the GPU, not the ones aligning at the moment: sizing by activity was tried in round 5 and made the headline bimodal - a context that
-    // finds itself alone launches for the whole GPU, the runtime then gives its queue scratch memory for a whole GPU's waves (5.8 KB per lane), and in about half the
-    // runs the other contexts' launches then ran one after the other for the rest of the process, 4.6 M reads/s instead of 15.  A process that keeps contexts it does
-    // not use should close them.)
-    const int gpuContexts = idx->dt->contexts.load();
-    const bool sharedGpu = gpuContexts > 1;
-    // Batches of long reads (gapped pass beyond scale 4: every read goes through the chain, and its searches - thousands of nodes each, all in HBM mode -
-    // are most of its time): the lanes of a wave run their searches one after the other, so 8 reads per wave on twice as many waves instead of 32
-    // (1 kb queries: 382 ms -> 265-280 ms per 150 k; 4 to 8 reads per wave and 8 to 16 waves per SIMD worth of lanes measure the same, profiles/r03/NOTES.md 13)
-    const bool longReads = gappedScale > 4;
-    // (long reads: every lane of the light pass holds a region of 288 KiB, and every read goes on to the gapped pass, whose lanes are 6.7 MB each:
-    // two waves per SIMD worth of light lanes leave the scratch to those)
-    const long long lightWaves = envKnob("XM_LIGHT_WAVES", longReads ? 2 : (sharedGpu ? std::max(2, 12 / gpuContexts) : 8), 1, 16), fullWaves = envKnob("XM_FULL_WAVES", longReads ? 8 : (sharedGpu ? std::max(1, 6 / gpuContexts) : 4), 1, 16);
-    const long long fullLpw = envKnob("XM_FULL_LPW", longReads ? 8 : 32, 1, 64), lightLpw = envKnob("XM_LIGHT_LPW", 64, 1, 64);
-    const long long lightLevel = envKnob("XM_LIGHT_LEVEL", 0, 0, 2);  // what the light pass still does itself (Caps::heavyAllowed)
-    // straight-alignment penalty x 8 from which a read is put first in the gapped pass and dealt out evenly (0: no order).  Batches of single reads of up to 320
-    // bases: 8 penalty units - the reads with an indel (they mismatch on one whole side of it), whose searches are the long ones of the pass: started first
-    // they do not end it (gapped pass 70.0 / 70.5 -> 65.2 / 64.8 ms per 1 M reads, same box; with 4 units 75 ms; pairs 146 -> 152-154 ms: not for them)
-    const long long heavyHintThreshold = envKnob("XM_HEAVY_HINT", (idx->residentAnyPaired || longReads) ? 0 : 64, 0, 1 << 20);
-    const long long taperWaves = envKnob("XM_TAPER_PCT", 100, 0, 1000);  // lane l of a gapped-pass wave stops taking reads when fewer than l * waves * pct/100 are left
-    auto scratchBudget = [&]() -> unsigned long long {  // scratch: up to the limit, never more than 3/4 of what is free now (+ what this context already holds)
-      unsigned long long want = scratchWanted >> scratchShift;
-      size_t freeB = 0, totalB = 0;
-      if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-        const unsigned long long avail = (unsigned long long)(freeB + idx->dArenas.n) / 4 * 3;
-        if (want > avail) want = avail;
-      }
-      return want < (64ull << 20) ? (64ull << 20) : want;
-    };
-    // contexts of one GPU size and allocate their scratch one after the other: they all look at the same free memory
-    auto allocScratch = [&](size_t bytes) -> bool {
-      if (idx->dArenas.tryEnsure(bytes)) return true;
-      if (++scratchShift > 8) throw std::runtime_error("no room in HBM for the scratch of even a few lanes (" + std::to_string(bytes >> 20) + " MiB asked)");
-      return false;
-    };
-    // light pass -> gapped pass hand-over (HandOver, SavedRead): the reads the light pass stops in front of the gapped chain keep their seeding
-    // state in HBM and the gapped pass continues from it.  Scratch layout while saved regions are alive: [region pool | lane arenas].
-    const bool pairMode = envInt("XM_PAIR_LANES", 1) != 0;
-    const bool groupLanes = envInt("XM_GROUP_LANES", 1) != 0;
-    // (batches of long reads only: where reads align, the filter costs what it saves - 2 % of the search nodes of configs[1], 16 % of a repeat-rich reference's
-    // sit in searches it rejects, and it would look at every search: profiles/r06/NOTES.md 1.  XM_BOUND_FILTER=0: off, for comparison)
-    const bool boundFilterOn = envInt("XM_BOUND_FILTER", 1) != 0 && longReads;
-    bool boundFilterUsed = false;
-    // temporaries of a gapped-pass lane (reads that resume from a saved region): 7/12 of the arena of that scale by default (experiment knob: percent of it)
-    // HBM-mode searches take their arrays from a pool of the launch (SearchPool) in batches of short reads (gapped pass at scale <= 4): a lane's
-    // temporaries then hold the chain's structures only (matchers 148 KB + piece lists 23 KB + small change at scale 4; default 30 % of 7/12 of
-    // the arena = 201 KB).  Batches of long reads run every search in HBM mode: no pool, whole temporaries.
-    const bool searchPoolOn = envInt("XM_SEARCH_POOL", 1) != 0 && gappedScale <= 4;
-    const long long gappedTmpPct = envKnob("XM_GAPPED_TMP_PCT", searchPoolOn ? 20 : 100, 5, 100);  // (134 KB: matchers 74 KB, piece lists 23 KB, the rest small change)
-    // (+ the node arrays of a long-read chain: applyChainCaps)
-    auto gappedTmpBytes = [&](size_t arena) -> size_t { return ((size_t)((arena - arenaPersistBytes(arena)) * (size_t)gappedTmpPct / 100) & ~(size_t)15) + chainExtraTmpBytes(gappedScale); };
-    // light pass: a lane's temporaries hold the three matchers alignMatch sets aside (37 KB at scale 1; the chain that would fill them does not
-    // run there) and the joined text of overlapping mates; a read's region holds its seeding state: 49 KB single-end, 99 KB paired at scale 1
-    // (ambiguity codes add up to 18 KB per mate: a pair with them in both mates overflows its region - and the region of the same size a gapped-pass lane seeds reads
-    // without saved state in - so it is filed for the pass behind the gapped pass and run from its start at four times the gapped pass's scale, one read per wave.
-    // Correct (the ambiguity fuzz equals the oracle) and late: FASTQ pairs with N tails in both mates pay a latency-bound extra pass.  Known, not fixed: knowing it
-    // at upload would mean reading every base of the batch on the host.)
-    const size_t lightTmpUnit = (size_t)envKnob("XM_LIGHT_TMP_KB", 48, 16, 16384) * 1024;
-    const size_t regionPersistUnit = (size_t)envKnob("XM_REGION_KB", idx->residentAnyPaired ? 120 : 72, 32, 16384) * 1024;
-    const bool handOver = envInt("XM_HANDOVER", 1) != 0;
-    bool orderedList = false;   // the next launch's list is the gapped pass's ordered one (expensive-looking reads first): only that list is dealt out lane-major
-    int hoMode = handOver ? 1 : 0;   // mode of the next launch
-    const int seedScale = scale;
-    const size_t regionBytes = ((regionPersistUnit * (size_t)seedScale) & ~(size_t)15) + ((sizeof(SavedRead) + 15) & ~(size_t)15);
-    long long nRegions = 0;
-    size_t regionsTotal = 0;         // bytes at the start of the scratch that hold saved reads (0: none alive)
-    if (handOver) {
+    AlignCall c;
+    c.idx = idx; c.box = box; c.res = res; c.nq = nq; c.s = idx->stream; c.numCUs = idx->dt->numCUs;
+    c.view = idx->dt->view;
+    c.params = paramsFromC(*p);
+    c.bv = BatchView{nq, idx->dMateCount.p, idx->dMateOffset.p, idx->dMateLength.p, idx->dCodes.p, idx->dExpected.p, idx->dDeviation.p};
+    prepareCall(c);
+    if (idx->collapse) collapseBuildList(c);
+    const BatchFacts facts{idx->residentMaxLen, idx->residentAnyPaired, idx->dt->contexts.load(), idx->scratchBytes};
+    const BatchPolicy pol = makePolicy(facts, readPassKnobs(facts));
+    idx->dOutInts.ensure((size_t)nq * 40 + 4096); idx->dOutDbls.ensure((size_t)nq * 12 + 4096);
+    c.intCap = idx->dOutInts.n; c.dblCap = idx->dOutDbls.n;
+    if (pol.k.handOver) {
       idx->dRegionOf.ensure((size_t)nq);
-      HIP_CHECK(hipMemsetAsync(idx->dRegionOf.p, 0xFF, sizeof(int32_t) * (size_t)nq, s));
+      HIP_CHECK(hipMemsetAsync(idx->dRegionOf.p, 0xFF, sizeof(int32_t) * (size_t)nq, c.s));
     }
-    // ---- passes 0 (XM_WAVE=1; off by default: measured slower than the lane-per-read passes on MI355X this round, profiles/r02/NOTES.md):
-    // the wave-per-read form (xm_wave_kernel.hip).  Light tier over every read (seed, vote, ungapped alignment, accept); chain
-    // tier over the reads that need the gapped chain (or more LDS): a read that meets a PathAligner search leaves the request in its memo, the
-    // search kernel runs all waiting searches (one wavefront each), and those reads run again with the results, until none waits; then the
-    // same with the largest capacities for the reads that outgrew the chain tier's.  What the wave form does not take (ambiguity codes in the
-    // read or its reference window, mates longer than 256 bases, overlapping mates, a structure that outgrows LDS) goes through the
-    // lane-per-read passes below.
-    if (envInt("XM_WAVE", 0) != 0 && idx->residentMaxLen <= 256) {
-      const bool tracePasses = envInt("XM_TRACE_PASSES", 0) != 0;
-      idx->dListWaveHeavy.ensure((size_t)nq); idx->dListWaveNext.ensure((size_t)nq); idx->dListFallback.ensure((size_t)nq); idx->dWaveCtl.ensure(1);
-      idx->dWaveSlotOf.ensure((size_t)nq);
-      WaveCtl wctl{0, 0, 0, ~0ull};
-      HIP_CHECK(hipMemcpyAsync(idx->dWaveCtl.p, &wctl, sizeof(wctl), hipMemcpyHostToDevice, s));
-      OutView ov{idx->dOutInts.p, idx->dOutDbls.p, intCap, dblCap, idx->dCursors.p, idx->dStatus.p, idx->dIntOff.p, idx->dDblOff.p, idx->dIntLen.p, idx->dDblLen.p};
-      const int lastTier = (int)envKnob("XM_WAVE_TIERS", 3, 1, 3) - 1;  // (experiment knob: 1 = light tier only, 2 = light + chain tier)
-      int sWaves = 4, sLds = 1, sPerSimd = 4, memoBytes = 1, nodesPerWave = 1;
-      xmSearchGeometry(&sWaves, &sLds, &sPerSimd, &memoBytes, &nodesPerWave);
-      unsigned long long fallbackSoFar = 0;
-      // one launch of a tier over `list` (null = all reads) + classification; returns the counts of the lists it filled
-      auto launchTier = [&](int tier, const int64_t* list, long long n, int64_t* listNext, int32_t* slotOfOut, int64_t* listSearch) {
-        WaveLaunch wl;
-        wl.config = tier == 0 ? (idx->residentAnyPaired ? 1 : 0) : (tier == 1 ? (idx->residentAnyPaired ? 3 : 2) : 4);
-        int wavesPerBlock = 1, ldsPerBlock = 1, wavesPerSimd = 1;
-        xmWaveGeometry(wl.config, &wavesPerBlock, &ldsPerBlock, &wavesPerSimd);
-        long long blocksPerCU = std::min<long long>((160 * 1024) / ldsPerBlock, (long long)(wavesPerSimd * 4) / wavesPerBlock);
-        if (blocksPerCU < 1) blocksPerCU = 1;
-        wl.itemsPerFetch = (int)envKnob(tier == 0 ? "XM_WAVE_FETCH" : "XM_WAVE_CHAIN_FETCH", tier == 0 ? 8 : 1, 1, 1024);
-        long long blocks = std::min<long long>((long long)numCUs * blocksPerCU, (n + (long long)wavesPerBlock * wl.itemsPerFetch - 1) / ((long long)wavesPerBlock * wl.itemsPerFetch));
-        if (blocks < 1) blocks = 1;
-        wl.grid = (int)blocks; wl.block = wavesPerBlock * 64;
-        wl.ix = view; wl.params = params; wl.batch = bv; wl.todo = list; wl.nTodo = n; wl.out = ov; wl.nextItem = idx->dCursors.p + 2; wl.counters = idx->dCounters.p;
-        wl.memoBase = (WMemo*)idx->dWaveMemo.p; wl.slotOf = idx->dWaveSlotOf.p;
-        wl.waveNodes = nullptr;
-        if (tier >= 1 && envInt("XM_WAVE_INLINE_SEARCH", 1) != 0) {  // (0: every search through the memo and the search kernel)
-          idx->dWaveNodes2.ensure(((size_t)blocks * wavesPerBlock * (size_t)xmWaveInlineNodeBytes() + sizeof(PNode) - 1) / sizeof(PNode));
-          wl.waveNodes = idx->dWaveNodes2.p;
-        }
-        HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
-        HIP_CHECK(hipMemsetAsync(idx->dWaveCtl.p, 0, 2 * sizeof(unsigned long long), s));  // nNext, nSearch
-        HIP_CHECK(hipEventRecord(e0, s));
-        const int rc = xmWaveLaunch(wl, (void*)s);
-        if (rc != 0) throw std::runtime_error(std::string("wave kernel launch: ") + hipGetErrorString((hipError_t)rc));
-        HIP_CHECK(hipEventRecord(e1, s));
-        hipLaunchKernelGGL(xm_wave_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, list, n, idx->dStatus.p, listNext, slotOfOut, listSearch, idx->dListFallback.p, idx->dWaveCtl.p);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(&wctl, idx->dWaveCtl.p, sizeof(wctl), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(cursors, idx->dCursors.p, sizeof(cursors), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        kernelMs += ms;
-        res->counters[tier == 0 ? 12 : 13] += (int64_t)(ms * 1000.0);  // kernel microseconds: light tier / chain tiers
-        launches++;
-        if (tracePasses) fprintf(stderr, "[xm] wave tier %d config %d: reads %lld, %d x %d threads: %.3f ms -> next tier %llu, searches %llu, lane-per-read %llu (so far)\n", tier, wl.config, n, wl.grid,
-                                 wl.block, ms, listNext ? wctl.nNext : 0ull, wctl.nSearch, wctl.nFallback);
-        if (wctl.errQuery != ~0ull) {
-          int32_t code = 0;
-          HIP_CHECK(hipMemcpy(&code, idx->dStatus.p + wctl.errQuery, sizeof(code), hipMemcpyDeviceToHost));
-          throw std::runtime_error("Failed to align query " + std::to_string(wctl.errQuery) + ": the reference implementation would have thrown here (status " + std::to_string(code & 0xFF) + ")");
-        }
-        fallbackSoFar = wctl.nFallback;
-      };
-      auto launchSearches = [&](const int64_t* list, long long n) {
-        SearchLaunch sl;
-        long long blocks = std::min<long long>((long long)numCUs * std::min<long long>((160 * 1024) / sLds, (long long)(sPerSimd * 4) / sWaves), (n + sWaves - 1) / sWaves);
-        if (blocks < 1) blocks = 1;
-        sl.grid = (int)blocks; sl.block = sWaves * 64;
-        sl.ix = view; sl.params = params; sl.batch = bv; sl.list = list; sl.n = n; sl.memoBase = (WMemo*)idx->dWaveMemo.p; sl.slotOf = idx->dWaveSlotOf.p; sl.nextItem = idx->dCursors.p + 2;
-        idx->dWaveArenas.ensure((size_t)blocks * sWaves * (size_t)nodesPerWave);  // (node payloads: bytes per wave)
-        sl.waveNodes = idx->dWaveArenas.p; sl.counters = idx->dCounters.p;
-        HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
-        HIP_CHECK(hipEventRecord(e0, s));
-        const int rc = xmSearchLaunch(sl, (void*)s);
-        if (rc != 0) throw std::runtime_error(std::string("search kernel launch: ") + hipGetErrorString((hipError_t)rc));
-        HIP_CHECK(hipEventRecord(e1, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-        kernelMs += ms;
-        res->counters[14] += (int64_t)(ms * 1000.0);  // search kernel microseconds
-        launches++;
-        if (tracePasses) fprintf(stderr, "[xm] search kernel: %lld searches, %d x %d threads: %.3f ms\n", n, sl.grid, sl.block, ms);
-      };
-      // light tier
-      launchTier(0, todo, nTodo, lastTier >= 1 ? idx->dListWaveHeavy.p : (int64_t*)nullptr, idx->dWaveSlotOf.p, nullptr);
-      long long nChain = lastTier >= 1 ? (long long)wctl.nNext : 0;
-      if (nChain > 0) {
-        idx->dWaveMemo.ensure((size_t)nChain * (size_t)memoBytes);
-        if (xmMemoInitLaunch((WMemo*)idx->dWaveMemo.p, nChain, (void*)s) != 0) throw std::runtime_error("memo init launch failed");
-        idx->dListWaveSearch[0].ensure((size_t)nChain); idx->dListWaveSearch[1].ensure((size_t)nChain);
-        long long nBig = 0;  // reads for the chain tier with the largest capacities (dListWaveNext, filled behind what is already there)
-        for (int tier = 1; tier <= 2 && tier <= lastTier; tier++) {
-          const int64_t* list = tier == 1 ? idx->dListWaveHeavy.p : idx->dListWaveNext.p;
-          long long n = tier == 1 ? nChain : nBig;
-          int which = 0, rounds = 0;
-          while (n > 0) {
-            // (tier 1 appends its hand-overs to dListWaveNext behind those of its earlier rounds)
-            launchTier(tier, list, n, tier == 1 && lastTier >= 2 ? idx->dListWaveNext.p + nBig : (int64_t*)nullptr, nullptr, idx->dListWaveSearch[which].p);
-            if (tier == 1 && lastTier >= 2) nBig += (long long)wctl.nNext;
-            const long long nSearch = (long long)wctl.nSearch;
-            if (nSearch == 0) break;
-            if (++rounds > 4 * 16) throw std::runtime_error("internal error: search rounds do not end");
-            launchSearches(idx->dListWaveSearch[which].p, nSearch);
-            list = idx->dListWaveSearch[which].p; n = nSearch;
-            which ^= 1;
-          }
-        }
-      }
-      todo = idx->dListFallback.p;
-      nTodo = (long long)fallbackSoFar;
-      HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
-    }
-    while (nTodo > 0) {
-      std::unique_lock<std::mutex> sizing(idx->dt->allocMu);
-      size_t arenaBytes = arenaUnit * (size_t)scale;  // bytes of scratch a lane owns in this launch
-      if (hoMode == 1) arenaBytes = lightTmpUnit * (size_t)scale;                   // temporaries only (+ one region of the pool per lane / the read's own region)
-      if (hoMode == 2) arenaBytes = regionBytes + gappedTmpBytes(arenaBytes);       // a region for reads without saved state + temporaries
-      // launch shape (measured on MI355X, profiles/r01/NOTES.md): 8 waves per SIMD worth of lanes in the light pass; the gapped chain
-      // diverges inside each wave, so it runs 32 reads per wave on 4 waves per SIMD.  The XM_* variables are experiment knobs.
-      // a pass over few reads spreads them over all the wave slots of the GPU (the time of a launch is its longest wave)
-      const long long waveSlots = (long long)numCUs * 4 * (heavy ? fullWaves : lightWaves);
-      int lpw = (int)(heavy ? fullLpw : lightLpw);  // active lanes per wave
-      if (heavy) lpw = (int)std::max(1ll, std::min((long long)lpw, (nTodo + waveSlots - 1) / waveSlots));
-      long long lanes = waveSlots * lpw;
-      const unsigned long long budget = scratchBudget();
-      if (hoMode == 1) lanes = std::min(lanes, (long long)(budget / (arenaBytes + regionBytes)));
-      else if (regionsTotal > 0) lanes = std::min(lanes, (long long)((idx->dArenas.n - regionsTotal) / arenaBytes));  // (sized below, before the pool was filled)
-      else lanes = std::min(lanes, (long long)(budget / arenaBytes));
-      if (lanes > nTodo) lanes = nTodo;
-      // long reads, scratch for fewer lanes than asked for: fewer reads per wave before fewer waves than the GPU holds at a time (4 per SIMD) - a wave's
-      // reads wait for each other's searches, an empty wave slot does nothing
-      // (contexts that share the GPU share its wave slots)
-      const long long slotsHeld = (long long)numCUs * 16 / std::max(1, gpuContexts);
-      if (heavy && longReads && lpw > 1 && lanes / lpw < slotsHeld) lpw = (int)std::max(1ll, lanes / slotsHeld);
-      long long nWaves = (lanes + lpw - 1) / lpw;
-      if (nWaves < 1) nWaves = 1;
-      if (hoMode != 1 && regionsTotal > 0) {  // the scratch cannot grow now: whole waves (and whole blocks of four) that fit behind the pool
-        const long long cap = (long long)((idx->dArenas.n - regionsTotal) / arenaBytes);
-        if (cap < 1) throw std::runtime_error("the scratch behind the saved reads is smaller than one lane's arena (XM_SCRATCH_GIB / XM_ARENA_KB too small for this batch)");
-        if (lpw > cap) lpw = (int)cap;
-        long long w = cap / lpw;
-        if (w >= 4) w &= ~3ll;
-        if ((nWaves >= 4 ? ((nWaves + 3) & ~3ll) : nWaves) > w) nWaves = w;
-      }
-      int block = nWaves < 4 ? (int)nWaves * 64 : 256;
-      int grid = (int)((nWaves * 64 + block - 1) / block);
-      lanes = (long long)grid * (block / 64) * lpw;
-      if (hoMode == 1) {
-        // pool: one region per lane + one per read that may stop (at most 40 % of the scratch; reads beyond that are seeded again by the
-        // gapped pass).  The scratch is sized here for the gapped pass as well: it must not move while saved regions are alive.
-        // (a lane takes a fresh region only before it fetches another read, and only nTodo - lanes reads are fetched by lanes that already had one)
-        // (+ some slack: lanes that see a few reads left all take a region, but only some of them get a read)
-        long long extra = nTodo > lanes ? (long long)nTodo - lanes + std::min(lanes, 4096ll) : 0;
-        // (long reads: a fifth - their seeding is 4 % of their time, and a gapped-pass lane of theirs is 6.7 MB: the scratch is worth more as lanes)
-        extra = std::min(extra, (long long)(budget * (longReads ? 1 : 2) / 5 / regionBytes) - lanes);
-        extra = std::min(extra, ((long long)budget - lanes * (long long)(arenaBytes + regionBytes)) / (long long)regionBytes);
-        if (extra < 0) extra = 0;
-        nRegions = lanes + extra;
-        regionsTotal = (size_t)nRegions * regionBytes;
-        const size_t gappedArena = arenaUnit * (size_t)gappedScale, gappedLane = regionBytes + gappedTmpBytes(gappedArena);
-        long long gappedLanes = std::min((long long)nq, (long long)numCUs * 4 * fullWaves * fullLpw);
-        gappedLanes = std::min(gappedLanes, std::max(1ll, ((long long)budget - (long long)regionsTotal) / (long long)gappedLane));
-        size_t behind = std::max((size_t)lanes * arenaBytes, (size_t)gappedLanes * gappedLane);
-        behind = std::max(behind, gappedArena);  // (a rerun after a full result arena runs plain, at least one lane of it)
-        if (!allocScratch(regionsTotal + behind + 1024)) { regionsTotal = 0; nRegions = 0; continue; }  // (sized again with half the budget)
-        const unsigned long long firstFree = (unsigned long long)lanes;
-        HIP_CHECK(hipMemcpyAsync(idx->dCursors.p + 3, &firstFree, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-      } else if (regionsTotal > 0) {
-        if (regionsTotal + (size_t)lanes * arenaBytes > idx->dArenas.n) throw std::runtime_error("internal error: scratch layout (hand-over)");
-      } else {
-        if (!allocScratch((size_t)lanes * arenaBytes)) continue;
-      }
-      sizing.unlock();
-      // two lanes per read (xm_extend.h, xmSetPairMode); eight in the passes that run the rejection filter (8 reads per wave at most): its recurrence
-      // spreads a column's cells over them (XM_GROUP_LANES=0: two there as well)
-      int pairLanes = (heavy && lpw <= 32 && pairMode) ? 1 : 0;
-      // the rejection filter in front of PathAligner's searches (xm_bound.h): the gapped passes of batches of long reads - their searches do not use the wave's
-      // LDS slot, which the filter cuts into one region per read of the wave (8); reads that do not align spend 83 % of their search nodes in searches it proves null
-      const int boundFilter = (heavy && boundFilterOn && lpw <= XM_BOUND_REGIONS && scale >= XM_HBM_ONLY_FROM) ? 1 : 0;
-      if (boundFilter) boundFilterUsed = true;
-      if (boundFilter && pairLanes && groupLanes) pairLanes = 3;
-      const int boundFilterArg = boundFilter ? (1 | (envInt("XM_GROUP_SWEEP", 1) != 0 ? 2 : 0)) : 0;
-      uint8_t* laneArenas = idx->dArenas.p + regionsTotal;
-      HandOver ho{hoMode, seedScale, idx->dArenas.p, (unsigned long long)regionBytes, nRegions, idx->dRegionOf.p, idx->dCursors.p + 3};
-      const int launchedMode = hoMode;
-      idx->dWaveNodes.ensure((size_t)grid * (block / 64) * XM_PAL_NODES);
-      SearchPool pool{nullptr, 0, 0, 0};
-      if (searchPoolOn && heavy && scale == gappedScale) {
-        pool.bufBytes = searchPoolBytes(makeCaps(scale));
-        pool.n = (int32_t)((long long)grid * (block / 64));  // one per wave of the launch
-        idx->dSearchPool.ensure((size_t)pool.n * pool.bufBytes);
-        pool.base = idx->dSearchPool.p;
-      }
-      idx->dListScale[ts].ensure((size_t)nq); idx->dListOut[to].ensure((size_t)nq);
-      // gapped pass with an ordered list: the first read of every lane is dealt out (kernel), the counter starts behind those items
-      const long long firstStride = (heavy && orderedList && heavyHintThreshold > 0 && scale == gappedScale) ? (long long)grid * (block / 64) : 0;
-      const unsigned long long firstItem = (unsigned long long)std::min((long long)nTodo, firstStride * lpw);
-      HIP_CHECK(hipMemcpyAsync(idx->dCursors.p + 2, &firstItem, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-      OutView ov{idx->dOutInts.p, idx->dOutDbls.p, intCap, dblCap, idx->dCursors.p, idx->dStatus.p, idx->dIntOff.p, idx->dDblOff.p, idx->dIntLen.p, idx->dDblLen.p};
-      // the lanes file the reads they could not finish into the work lists of the passes to come as they publish them (PassLists; no kernel behind the pass)
-      PassLists lists{idx->dListHeavy.p, idx->dListHeavyLate.p, idx->dListScale[ts].p, idx->dListOut[to].p, idx->dListConf[tc].p, (int)heavyHintThreshold, ts, to, tc, idx->dCtl.p};
-      HIP_CHECK(hipEventRecord(e0, s));
-      hipLaunchKernelGGL(xm_align_kernel, dim3(grid), dim3(block), 0, s, view, params, bv, todo, nTodo, scale, heavy ? 2 : (int)lightLevel, lpw,
-                         laneArenas, (unsigned long long)arenaBytes, ov, idx->dCursors.p + 2, idx->dCounters.p,
-                         heavy ? (long long)((double)nWaves * taperWaves / 100.0) : 0ll, firstStride, idx->dWaveNodes.p, ho, pairLanes, pool, lists, boundFilterArg);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(e1, s));
-      PassCtl ctl;
-      HIP_CHECK(hipMemcpyAsync(&ctl, idx->dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(cursors, idx->dCursors.p, sizeof(cursors), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      kernelMs += ms;
-      res->counters[!heavy ? 12 : 15] += (int64_t)(ms * 1000.0);  // kernel microseconds: light pass / gapped pass and reruns
-      launches++;
-      orderedList = false;
-      hoMode = 0;                                // (the gapped pass below switches to 2; reruns run plain)
-      if (launchedMode == 2) regionsTotal = 0;   // the saved reads have all been consumed
-#ifdef XM_LIGHT_ONLY
-      fprintf(stderr, "[xm] light-only experiment build: pass %d %.3f ms\n", launches, ms);
-      break;  // (experiment build, scripts/gpu_light_only.sh: only the first pass is meaningful)
-#endif
-      const bool tracePasses = envInt("XM_TRACE_PASSES", 0) != 0;
-      if (tracePasses) fprintf(stderr, "[xm] pass %d: %s reads %lld scale %d lpw %d waves %lld lanes/read %d filter %d: %.3f ms -> heavy %llu scale %llu out %llu\n", launches,
-                               !heavy ? "light" : "gapped", nTodo, scale, lpw, nWaves, 1 << pairLanes, boundFilter, ms, ctl.nHeavy + ctl.nHeavyLate, ctl.nScale[ts], ctl.nOut[to]);
-#ifdef XM_PROFILE
-      if (tracePasses && heavy) {  // reads of a wave that stood at a PathAligner call together, this pass
-        unsigned long long a[16] = {0}, z[16] = {0};
-        HIP_CHECK(hipMemcpyFromSymbol(a, HIP_SYMBOL(xm_arrive_prof), sizeof(a)));
-        HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_arrive_prof), z, sizeof(z)));
-        fprintf(stderr, "[xm] pass %d: pair checks (status, result, search problem, search outcome): %llu %llu %llu %llu\n", launches, a[4], a[5], a[6], a[7]);
-        fprintf(stderr, "[xm] pass %d: PathAligner arrivals %llu with %llu reads (%.2f per arrival); arrivals of four reads or more: %llu with %llu reads\n", launches, a[0], a[1], a[0] ? (double)a[1] / (double)a[0] : 0.0, a[2], a[3]);
-      }
-#endif
-      if (ctl.errQuery != ~0ull) {
-        int32_t code = 0;
-        HIP_CHECK(hipMemcpy(&code, idx->dStatus.p + ctl.errQuery, sizeof(code), hipMemcpyDeviceToHost));
-        code &= 0xFF;
-        std::string q = std::to_string(ctl.errQuery);
-        if (code == XM_ST_NEED_GROW) throw std::runtime_error("Failed to align query " + q + ": gapmer longer than the hashed lengths");
-        throw std::runtime_error("Failed to align query " + q + ": the reference implementation would have thrown here (status " + std::to_string(code) + ")");
-      }
-      pendingHeavy = ctl.nHeavy + ctl.nHeavyLate;
-      pendingScale = ctl.nScale[ts];
-      pendingConf = ctl.nConf[tc];   // (accumulates over the passes until the list is run)
-      if (ctl.nOut[to] > 0) {  // result arena too small: rerun those reads with the same settings and room to spare
-        todo = idx->dListOut[to].p; nTodo = (long long)ctl.nOut[to];
-        to ^= 1;
-        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nOut[to], 0, sizeof(unsigned long long), s));
-        unsigned long long keepI = std::min(cursors[0], intCap), keepD = std::min(cursors[1], dblCap);
-        unsigned long long newI = std::max(intCap * 4 + 65536, cursors[0] * 2), newD = std::max(dblCap * 4 + 65536, cursors[1] * 2);
-        idx->dOutInts.growKeep((size_t)newI, (size_t)keepI, s); idx->dOutDbls.growKeep((size_t)newD, (size_t)keepD, s);
-        intCap = idx->dOutInts.n; dblCap = idx->dOutDbls.n;
-        rerun += nTodo;
-        continue;
-      }
-      if (pendingHeavy > 0) {
-        // the gapped pass runs at scale 4 straight away: far fewer lanes are needed than in the light pass, and most reads whose
-        // gapped search outgrows the scale-1 scratch then finish here instead of costing one more (latency-bound) pass
-        if (ctl.nHeavyLate > 0) {  // one list: the expensive-looking reads first, the others behind them
-          HIP_CHECK(hipMemcpyAsync(idx->dListHeavy.p + ctl.nHeavy, idx->dListHeavyLate.p, sizeof(int64_t) * (size_t)ctl.nHeavyLate, hipMemcpyDeviceToDevice, s));
-        }
-        todo = idx->dListHeavy.p; nTodo = (long long)pendingHeavy;
-        orderedList = true;
-        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nHeavy, 0, 2 * sizeof(unsigned long long), s));  // nHeavy, nHeavyLate (a gapped pass never adds to these lists)
-        scale = gappedScale;
-        if (overflowScale < gappedScale) overflowScale = gappedScale;
-        heavy = true;
-        if (regionsTotal > 0) hoMode = 2;
-        if (envInt("XM_PROF_GAPPED_ONLY", 0) != 0)  // XM_PROFILE builds: the in-kernel timers of the gapped pass alone
-          HIP_CHECK(hipMemsetAsync((char*)idx->dCounters.p + offsetof(DevCounters, t), 0, sizeof(((DevCounters*)nullptr)->t), s));
-        continue;
-      }
-      if (pendingScale == 0 && pendingConf > 0) {
-        // reads that met a (penalty, length) the confidence table did not hold: the host evaluates the keys they left (its libm, the oracle's)
-        // and they run again, start to finish, in a pass of their own
-        if (++confRounds > 1024) throw std::runtime_error("internal error: the confidence table does not converge");
-        idx->confAbsorbMisses(params, s);
-        view.conf = idx->dConf.p; view.confMask = (uint32_t)(idx->confHost.size() - 1);
-        todo = idx->dListConf[tc].p; nTodo = (long long)pendingConf;
-        tc ^= 1;
-        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nConf[tc], 0, sizeof(unsigned long long), s));
-        rerun += nTodo;
-        regionsTotal = 0;
-        if (scale < gappedScale) scale = gappedScale;
-        if (overflowScale < scale) overflowScale = scale;
-        heavy = true;
-        continue;
-      }
-      if (pendingScale == 0) break;
-      todo = idx->dListScale[ts].p; nTodo = (long long)pendingScale;
-      ts ^= 1;
-      HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nScale[ts], 0, sizeof(unsigned long long), s));
-      rerun += nTodo;
-      regionsTotal = 0;  // (no gapped pass ran: whatever the light pass saved is not wanted any more)
-      overflowScale *= 4;
-      scale = overflowScale;
-      heavy = true;
-      if (scale > 4096) throw std::runtime_error("Failed to align: scratch scale limit reached (query needs more than 4096x the default scratch)");
-    }
-    if (copies > 0) {  // every copy's slice is its representative's: the scan and gather below then write it in query order
-      HIP_CHECK(hipEventRecord(e0, s));
-      hipLaunchKernelGGL(xm_collapse_fanout_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, idx->dIntOff.p, idx->dDblOff.p,
-                         idx->dIntLen.p, idx->dDblLen.p);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(e1, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      kernelMs += ms;
-      launches++;
-    }
-    // ---- canonical streams in query order: offsets by prefix sum, slices gathered on the device, one copy per stream to the host
-    HIP_CHECK(hipEventRecord(e0, s));
-    const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
-    idx->dBlockI.ensure((size_t)nBlocks); idx->dBlockD.ensure((size_t)nBlocks);
-#ifdef XM_READ_TIMES
-    if (dReadTimes.p) {
-      std::vector<unsigned long long> t((size_t)nq);
-      HIP_CHECK(hipMemcpy(t.data(), dReadTimes.p, sizeof(unsigned long long) * (size_t)nq, hipMemcpyDeviceToHost));
-      unsigned long long* none = nullptr;
-      HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_read_times), &none, sizeof(none)));
-      if (FILE* f = fopen(readTimesFile, "wb")) { fwrite(t.data(), sizeof(unsigned long long), t.size(), f); fclose(f); }
-      dReadTimes.release();
-    }
-#endif
-    idx->dFinalIntOff.ensure((size_t)nq + 1); idx->dFinalDblOff.ensure((size_t)nq + 1);
-    size_t usedI = (size_t)std::min(cursors[0], intCap), usedD = (size_t)std::min(cursors[1], dblCap);  // upper bounds of the totals
-    if (copies == 0) { idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD); }
-    hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, idx->dIntLen.p, idx->dDblLen.p, idx->dBlockI.p, idx->dBlockD.p);
-    hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, idx->dBlockI.p, idx->dBlockD.p, idx->dFinalIntOff.p, idx->dFinalDblOff.p);
-    if (copies > 0) {  // (a copy's slice is in the result arena once and in the streams once per copy: the totals are the scan's)
-      int64_t totals[2] = {0, 0};
-      HIP_CHECK(hipMemcpyAsync(&totals[0], idx->dFinalIntOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(&totals[1], idx->dFinalDblOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      usedI = (size_t)totals[0]; usedD = (size_t)totals[1];
-      idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD);
-    }
-    hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, idx->dIntLen.p, idx->dDblLen.p, idx->dBlockI.p, idx->dBlockD.p,
-                       idx->dFinalIntOff.p, idx->dFinalDblOff.p);
-    hipLaunchKernelGGL(xm_gather_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, idx->dIntOff.p, idx->dDblOff.p, idx->dIntLen.p, idx->dDblLen.p,
-                       idx->dFinalIntOff.p, idx->dFinalDblOff.p, idx->dOutInts.p, idx->dOutDbls.p, idx->dFinalInts.p, idx->dFinalDbls.p);
-    HIP_CHECK(hipGetLastError());
-    res->ints = (int32_t*)g_pinned->get(sizeof(int32_t) * (usedI ? usedI : 1), &box->bytesInts);
-    res->dbls = (double*)g_pinned->get(sizeof(double) * (usedD ? usedD : 1), &box->bytesDbls);
-    idx->lastAlignedNq = nq;
-    idx->lastAlignedGen = idx->residentGen;
-    HIP_CHECK(hipMemcpyAsync(res->int_off, idx->dFinalIntOff.p, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(res->dbl_off, idx->dFinalDblOff.p, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost, s));
-    if (usedI) HIP_CHECK(hipMemcpyAsync(res->ints, idx->dFinalInts.p, sizeof(int32_t) * usedI, hipMemcpyDeviceToHost, s));
-    if (usedD) HIP_CHECK(hipMemcpyAsync(res->dbls, idx->dFinalDbls.p, sizeof(double) * usedD, hipMemcpyDeviceToHost, s));
-    DevCounters dc;
-    HIP_CHECK(hipMemcpyAsync(&dc, idx->dCounters.p, sizeof(dc), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    res->d2h_ms = ms;
-    res->num_ints = res->int_off[nq]; res->num_dbls = res->dbl_off[nq];
-    res->counters[0] = (int64_t)dc.reads; res->counters[1] = (int64_t)dc.headerProbes; res->counters[2] = (int64_t)dc.bucketFetches; res->counters[3] = (int64_t)dc.hitsFetched;
-    res->counters[4] = (int64_t)dc.candidatesExtended; res->counters[5] = (int64_t)dc.pathAlignerCalls; res->counters[6] = (int64_t)dc.pathAlignerNodes;
-    res->counters[7] = (int64_t)dc.quickAccepts; res->counters[8] = (int64_t)dc.alignmentsOut; res->counters[9] = (int64_t)dc.refWindowBytes; res->counters[10] = (int64_t)dc.readBytes;
-    res->counters[11] = rerun;
-    res->extra[0] = (int64_t)dc.boundChecks; res->extra[1] = (int64_t)dc.boundRejects; res->extra[2] = (int64_t)dc.boundCells; res->extra[3] = boundFilterUsed ? 1 : 0; res->extra[4] = (int64_t)dc.boundPieceChecks; res->extra[5] = (int64_t)dc.boundPieceRejects;
-    res->extra[7] = copies;
-    for (int i = 0; i < 16; i++) res->prof[i] = (int64_t)dc.t[i];
-    res->kernel_ms = kernelMs;
-    res->kernel_launches = launches;
+    if (pol.k.waveForm && idx->residentMaxLen <= 256) runWaveForm(c, pol.k.tracePasses);
+    runLanePasses(c, pol);
+    if (c.copies > 0) collapseFanOut(c);
+    finishStreams(c);
     *out = res;
     return 0;
   } catch (...) {
@@ -2171,12 +2041,7 @@ int xm_test_bound(int32_t device, const xm_params* p, const uint8_t* query, int3
   if (query_length < 1 || reference_length < 1 || start_a < 0 || end_a > query_length || start_a > end_a || start_b < 0 || end_b > reference_length || start_b > end_b) return fail("xm_test_bound: bad sections");
   try {
     if (device >= 0) HIP_CHECK(hipSetDevice(device));
-    Params params;
-    memset(&params, 0, sizeof(params));
-    params.MutationPenalty = p->MutationPenalty; params.InsertionStart_Penalty = p->InsertionStart_Penalty; params.InsertionExtension_Penalty = p->InsertionExtension_Penalty;
-    params.DeletionStart_Penalty = p->DeletionStart_Penalty; params.DeletionExtension_Penalty = p->DeletionExtension_Penalty; params.MaxErrorRate = p->MaxErrorRate;
-    params.UnalignedPenalty = p->UnalignedPenalty; params.AmbiguityPenalty = p->AmbiguityPenalty; params.Max_PenaltySpan = p->Max_PenaltySpan;
-    params.MaxNumMatches = p->MaxNumMatches; params.StartingInsertionStartFree = 0;
+    const Params params = paramsFromC(*p);
     DevBuf<uint8_t> dq, dr, dArena;
     DevBuf<int64_t> dOut;
     struct Release { DevBuf<uint8_t>&a, &b, &d; DevBuf<int64_t>& c; ~Release() { a.release(); b.release(); c.release(); d.release(); } } releaseAll{dq, dr, dArena, dOut};
@@ -2203,12 +2068,7 @@ int xm_test_local_align(int32_t device, int32_t chain, int32_t mode, const xm_pa
   { fail("xm_test_local_align: bad arguments (chain 0: modes 0 LDS slot, 1 HBM, 2 wave search with the search kernel's capacities, 3 with the inline capacities, 4 lane-private form; chain 1: modes 0, 1, 4)"); return -1; }
   try {
     if (device >= 0) HIP_CHECK(hipSetDevice(device));
-    Params params;
-    memset(&params, 0, sizeof(params));
-    params.MutationPenalty = p->MutationPenalty; params.InsertionStart_Penalty = p->InsertionStart_Penalty; params.InsertionExtension_Penalty = p->InsertionExtension_Penalty;
-    params.DeletionStart_Penalty = p->DeletionStart_Penalty; params.DeletionExtension_Penalty = p->DeletionExtension_Penalty; params.MaxErrorRate = p->MaxErrorRate;
-    params.UnalignedPenalty = p->UnalignedPenalty; params.AmbiguityPenalty = p->AmbiguityPenalty; params.Max_PenaltySpan = p->Max_PenaltySpan;
-    params.MaxNumMatches = p->MaxNumMatches; params.StartingInsertionStartFree = 0;
+    const Params params = paramsFromC(*p);
     const int cap = block_cap < 256 ? block_cap : 256;
     DevBuf<uint8_t> dq, dr, arena, nodes;
     DevBuf<int32_t> dInts;
@@ -2242,7 +2102,7 @@ int xm_test_local_align(int32_t device, int32_t chain, int32_t mode, const xm_pa
       if (rc != 0) throw std::runtime_error(std::string("test search launch: ") + hipGetErrorString((hipError_t)rc));
     } else {
       const int scale = 4;
-      const size_t arenaBytes = (size_t)288 * 1024 * scale;
+      const size_t arenaBytes = (size_t)XM_ARENA_KB_DEFAULT * 1024 * scale;
       arena.ensure(arenaBytes);
       nodes.ensure((size_t)XM_PAL_NODES * 4 * sizeof(PNode));
       hipLaunchKernelGGL(xm_test_local_kernel, dim3(1), dim3(256), 0, 0, (int)chain, (int)mode + (withBound ? 8 : 0), params, (const uint8_t*)dq.p, (int)query_length, (const uint8_t*)dr.p, (int)reference_length,

@@ -9,6 +9,7 @@
 #include "../../mapper_amd/csrc/xm_wsearch.h"
 #include "../../mapper_amd/csrc/xm_wave.h"
 #include "../../mapper_amd/csrc/xm_index_host.h"
+#include "../../mapper_amd/csrc/xm_pass_plan.h"
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -90,11 +91,7 @@ int xmsim_align_batch(void* idxp, const xm_params* p, const xm_query_batch* b, x
     int maxLen = 1;
     for (int64_t q = 0; q < b->num_queries; q++) for (int m = 0; m < b->mate_count[q]; m++) if (b->mate_length[q * 2 + m] > maxLen) maxLen = b->mate_length[q * 2 + m];
     if (maxLen > idx->host.maxHashedLength) { idx->host.ensureLength(maxLen); idx->refresh(); }
-    Params params;
-    params.MutationPenalty = p->MutationPenalty; params.InsertionStart_Penalty = p->InsertionStart_Penalty; params.InsertionExtension_Penalty = p->InsertionExtension_Penalty;
-    params.DeletionStart_Penalty = p->DeletionStart_Penalty; params.DeletionExtension_Penalty = p->DeletionExtension_Penalty; params.MaxErrorRate = p->MaxErrorRate;
-    params.UnalignedPenalty = p->UnalignedPenalty; params.AmbiguityPenalty = p->AmbiguityPenalty; params.Max_PenaltySpan = p->Max_PenaltySpan;
-    params.MaxNumMatches = p->MaxNumMatches; params.StartingInsertionStartFree = 0;
+    const Params params = paramsFromC(*p);
     const int64_t nq = b->num_queries;
     std::vector<int32_t> ints;
     std::vector<double> dbls;
@@ -124,7 +121,7 @@ int xmsim_align_batch(void* idxp, const xm_params* p, const xm_query_batch* b, x
         static LightLds ldsLight;
         static MidLds ldsMid;
         static HeavyLds ldsHeavy;
-        static std::vector<uint8_t> waveArena((size_t)(288 * 1024 * 4 * 7 / 12 + 4096));
+        static std::vector<uint8_t> waveArena((size_t)(XM_ARENA_KB_DEFAULT * 1024 * 4 * 7 / 12 + 4096));
         static WMemo memo;
         memo.count = 0; memo.pending = 0;
         bool finished = false;
@@ -184,75 +181,75 @@ int xmsim_align_batch(void* idxp, const xm_params* p, const xm_query_batch* b, x
         }
         if (finished) continue;
       }
-      // the product's pass sequence for one read: light pass at scale 1; a read that needs the gapped chain goes on at scale 4 from the state it
-      // saved (hand-over), on another context object and other temporaries; scratch overflow -> reruns from the start at 16x, 64x...
-      // XMSIM_INLINE=1: plain run at scale 1, 4, 16... (the first implementation's sequence)
+      // the product's pass sequence for one read (xm_pass_plan.h, PassState / nextPass, with a work list of this one read): light pass at the seed scale; a read
+      // that needs the gapped chain goes on at the gapped scale from the state it saved (hand-over), on another context object and other temporaries; scratch
+      // overflow -> reruns from the start at four times the scale.  XMSIM_INLINE=1: plain runs with the chain from the seed scale on (the first implementation's sequence)
       static const bool inlineOnly = getenv("XMSIM_INLINE") && atoi(getenv("XMSIM_INLINE")) != 0;
-      // (the product sizes a batch by its longest mate: scratch scale 1 up to 320 bases, 4 up to 1280, 16 beyond, the gapped pass at four times that;
-      // here every read by its own longest mate)
+      // (the product sizes a batch by its longest mate and by whether any read is paired - xm_pass_plan.h, seedScaleOf and BatchPolicy; here every read by its
+      // own longest mate and its own mates, with the product's default knobs)
       int longestMate = 0;
       for (int m = 0; m < in.nMates; m++) longestMate = std::max(longestMate, (int)in.mateLen[m]);
-      const int seedScale = longestMate <= 320 ? 1 : (longestMate <= 1280 ? 4 : 16);
-      int scale = seedScale;
-      int stage = inlineOnly ? 2 : 0;  // 0 light, 1 gapped, 2 rerun
+      const BatchFacts facts{longestMate, in.nMates > 1, 1, 0};
+      const BatchPolicy pol = makePolicy(facts, readPassKnobs(facts, knobDefault));
       static const int lightLevel = getenv("XMSIM_LIGHT_LEVEL") ? atoi(getenv("XMSIM_LIGHT_LEVEL")) : 0;
       // light pass -> gapped pass hand-over (runReadRetaining / runReadResumed): the read's region outlives the light "lane"; the gapped pass
       // runs on another context object and another temporaries buffer, as it does on another lane of the GPU
       static const bool handOver = !(getenv("XMSIM_NO_HANDOVER") && atoi(getenv("XMSIM_NO_HANDOVER")) != 0);
-      // the product's sizes: light-pass temporaries 48 KB, a read's region 72 KB (single-end) or 120 KB (paired) + its saved context
-      const size_t lightTmpBytes = (size_t)48 * 1024 * (size_t)seedScale, regionBytes = ((size_t)(in.nMates > 1 ? 120 : 72) * 1024 * (size_t)seedScale) + ((sizeof(SavedRead) + 15) & ~(size_t)15);
-      // temporaries of a gapped-pass lane: a fifth of 7/12 of the arena for short reads (their HBM-mode searches use the wave's buffer), all of it + the
-      // node arrays of a long-read chain for long ones (xm_capi.hip, gappedTmpBytes)
-      auto gappedTmp = [&](size_t bytes, int chainScale) -> size_t {
-        const size_t whole = bytes - arenaPersistBytes(bytes);
-        return ((seedScale == 1 ? whole / 5 : whole) & ~(size_t)15) + chainExtraTmpBytes(chainScale);
-      };
+      PassState st = firstPass(pol);
+      if (!handOver || inlineOnly) st.hoMode = 0;  // (XM_HANDOVER=0)
+      if (inlineOnly) st.heavy = true;
+      const size_t regionBytes = pol.regionBytes;
       std::vector<double> regionBuf(regionBytes / 8 + 2);
       uint8_t* region = (uint8_t*)(((uintptr_t)regionBuf.data() + 15) & ~(uintptr_t)15);
       SavedRead* saved = nullptr;
       static ReadCtx cx2;
       std::vector<uint8_t> arena2;
       while (true) {
-        size_t bytes = (size_t)288 * 1024 * (size_t)scale;
+        const int scale = st.scale;
+        size_t bytes = pol.arenaUnit * (size_t)scale;
         ReadResult rr;
         DevCounters before = dc;
-        // the rejection filter in front of PathAligner (xm_bound.h): the product turns it on for the gapped passes of batches of long reads (xm_capi.hip, boundFilter)
+        // the rejection filter in front of PathAligner (xm_bound.h): the product turns it on for the gapped passes of batches of long reads (planLaunch, boundFilter)
         static const bool boundFilterOn = !(getenv("XMSIM_BOUND_FILTER") && atoi(getenv("XMSIM_BOUND_FILTER")) == 0);
-        xmSetBoundFilter(boundFilterOn && stage != 0 && seedScale >= 4 && scale >= 16 ? 1 : 0);
-        if (stage == 1 && saved) {
+        xmSetBoundFilter(boundFilterOn && pol.filterAllowed(st.heavy, scale) ? 1 : 0);  // (one read per "wave": never more than XM_BOUND_REGIONS)
+        if (st.hoMode == 2 && saved) {
           arena2.assign(bytes + chainExtraTmpBytes(scale) + 64, 0xAB);
           uint8_t* a2 = (uint8_t*)(((uintptr_t)arena2.data() + 15) & ~(uintptr_t)15);
-          runReadResumed(cx2, saved, &idx->view, scale, a2, gappedTmp(bytes, scale), &dc, rr);
+          runReadResumed(cx2, saved, &idx->view, scale, a2, pol.gappedTmpBytes(bytes), &dc, rr);
           cx.status = cx2.status;
           cx.persist = cx2.persist; cx.tmp = cx2.tmp;  // (for the overflow trace)
-          saved = nullptr;
         } else {
           arena.resize(bytes + chainExtraTmpBytes(scale) + 64);
           uint8_t* a = (uint8_t*)(((uintptr_t)arena.data() + 15) & ~(uintptr_t)15);
-          if (stage == 0 && handOver) {
-            runReadRetaining(cx, &idx->view, params, in, scale, region, regionBytes, a, lightTmpBytes, &dc, rr, lightLevel);
+          if (st.hoMode == 1) {
+            runReadRetaining(cx, &idx->view, params, in, scale, region, regionBytes, a, pol.lightTmpUnit * (size_t)scale, &dc, rr, lightLevel);
+            st.nRegions = 1; st.regionsTotal = regionBytes;  // (the pool of the light pass: this read's region)
             if (cx.status == XM_ST_NEED_HEAVY) {
               SavedRead* sv = savedReadOf(region, regionBytes);
               saved = sv->valid ? sv : nullptr;
               std::vector<uint8_t>().swap(arena);  // the light lane's temporaries are gone (a stale pointer into them would be caught by the sanitizer run)
             }
-          } else if (stage == 1 && handOver) {
+          } else if (st.hoMode == 2) {
             // gapped pass, read without saved state (stopped where it cannot be resumed): seeded again in a region of light-pass size
-            runReadRetaining(cx, &idx->view, params, in, seedScale, region, regionBytes, a, ((bytes - arenaPersistBytes(bytes)) & ~(size_t)15) + chainExtraTmpBytes(scale), &dc, rr, 2, scale);
+            runReadRetaining(cx, &idx->view, params, in, pol.seedScale, region, regionBytes, a, pol.gappedTmpBytes(bytes), &dc, rr, 2, scale);
           } else {
-            runRead(cx, &idx->view, params, in, scale, a, bytes, &dc, rr, stage != 0 ? 2 : lightLevel);
+            runRead(cx, &idx->view, params, in, scale, a, bytes, &dc, rr, st.heavy ? 2 : lightLevel);
           }
-          if (cx.status == XM_ST_NEED_HEAVY && stage == 0) { dc = before; stage = 1; scale = seedScale * 4; continue; }
         }
-        if (cx.status == XM_ST_OVERFLOW) {
-          if (getenv("XMSIM_TRACE_OVERFLOW")) fprintf(stderr, "[xmsim] query %lld overflow at stage %d scale %d: persist %zu of %zu%s, tmp %zu of %zu%s\n", (long long)q, stage, scale, cx.persist.used, cx.persist.size, cx.persist.overflow ? " (overflow)" : "", cx.tmp.used, cx.tmp.size, cx.tmp.overflow ? " (overflow)" : "");
-          dc = before; rerun++;
-          saved = nullptr;
-          if (stage == 0) { stage = 2; scale = seedScale * 4; } else { stage = 2; scale *= 4; }
-          if (scale > 4096) throw std::runtime_error("scratch scale limit");
+        saved = st.hoMode == 1 ? saved : nullptr;  // (consumed, or not wanted any more)
+        // what the read's lane files it as (publishRead): the list of the gapped pass, or of the rerun at a larger scale
+        PassCtl ctl;
+        memset(&ctl, 0, sizeof(ctl));
+        if (cx.status == XM_ST_NEED_HEAVY && !st.heavy) ctl.nHeavy = 1;
+        else if (cx.status == XM_ST_OVERFLOW) ctl.nScale[st.ts] = 1;
+        else if (cx.status != XM_OK) throw std::runtime_error("Failed to align query " + std::to_string(q) + " (status " + std::to_string(cx.status) + ")");
+        if (cx.status == XM_ST_OVERFLOW && getenv("XMSIM_TRACE_OVERFLOW")) fprintf(stderr, "[xmsim] query %lld overflow at %s scale %d: persist %zu of %zu%s, tmp %zu of %zu%s\n", (long long)q, st.heavy ? "gapped / rerun" : "light", scale, cx.persist.used, cx.persist.size, cx.persist.overflow ? " (overflow)" : "", cx.tmp.used, cx.tmp.size, cx.tmp.overflow ? " (overflow)" : "");
+        const NextPass np = nextPass(pol, st, ctl);
+        if (np.kind != PassKind::Done) {
+          dc = before;  // work of a read that is rerun by a later pass is counted there
+          if (np.kind == PassKind::ScaleRerun) { rerun++; saved = nullptr; }
           continue;
         }
-        if (cx.status != XM_OK) throw std::runtime_error("Failed to align query " + std::to_string(q) + " (status " + std::to_string(cx.status) + ")");
         int64_t ni, nd;
         resultSize(rr, ni, nd);
         res->int_off[q] = (int64_t)ints.size(); res->dbl_off[q] = (int64_t)dbls.size();
@@ -269,11 +266,9 @@ int xmsim_align_batch(void* idxp, const xm_params* p, const xm_query_batch* b, x
     res->dbls = (double*)malloc(sizeof(double) * (dbls.size() + 1));
     if (!ints.empty()) memcpy(res->ints, ints.data(), ints.size() * sizeof(int32_t));
     if (!dbls.empty()) memcpy(res->dbls, dbls.data(), dbls.size() * sizeof(double));
-    res->counters[0] = (int64_t)dc.reads; res->counters[1] = (int64_t)dc.headerProbes; res->counters[2] = (int64_t)dc.bucketFetches; res->counters[3] = (int64_t)dc.hitsFetched;
-    res->counters[4] = (int64_t)dc.candidatesExtended; res->counters[5] = (int64_t)dc.pathAlignerCalls; res->counters[6] = (int64_t)dc.pathAlignerNodes;
-    res->counters[7] = (int64_t)dc.quickAccepts; res->counters[8] = (int64_t)dc.alignmentsOut; res->counters[9] = (int64_t)dc.refWindowBytes; res->counters[10] = (int64_t)dc.readBytes;
+    countersToResult(dc, res);
     res->counters[11] = rerun;
-    res->extra[0] = (int64_t)dc.boundChecks; res->extra[1] = (int64_t)dc.boundRejects; res->extra[2] = (int64_t)dc.boundCells; res->extra[3] = (dc.boundChecks | dc.boundPieceChecks) > 0 ? 1 : 0; res->extra[4] = (int64_t)dc.boundPieceChecks; res->extra[5] = (int64_t)dc.boundPieceRejects;
+    res->extra[3] = (dc.boundChecks | dc.boundPieceChecks) > 0 ? 1 : 0;
     *out = res;
     return 0;
   } catch (std::exception& e) { g_err = e.what(); return 1; }
@@ -282,12 +277,7 @@ int xmsim_align_batch(void* idxp, const xm_params* p, const xm_query_batch* b, x
 // the rejection filter of xm_bound.h alone on one problem (what xm_test_bound runs on the GPU); out3: taken, rejected, cells
 int xmsim_test_bound(const xm_params* p, const uint8_t* query, int queryLength, int queryRc, int startA, int endA, const uint8_t* reference, int referenceLength, int startB, int endB,
                      int predictedBestOffset, int64_t* out3) {
-  BoundProblem bp;
-  bp.qBase = query; bp.qLen = queryLength; bp.qRc = queryRc != 0; bp.rBase = reference; bp.referenceLen = referenceLength;
-  bp.startA = startA; bp.endA = endA; bp.startB = startB; bp.endB = endB; bp.predictedBestOffset = predictedBestOffset;
-  bp.mutation = p->MutationPenalty; bp.insStart = p->InsertionStart_Penalty; bp.insExt = p->InsertionExtension_Penalty; bp.delStart = p->DeletionStart_Penalty;
-  bp.delExt = p->DeletionExtension_Penalty; bp.maxErrorRate = p->MaxErrorRate; bp.ambiguity = p->AmbiguityPenalty;
-  bp.budget = (endA - startA) * p->MaxErrorRate; bp.piece = 0;
+  const BoundProblem bp = boundTestProblem(*p, query, queryLength, queryRc, startA, endA, reference, referenceLength, startB, endB, predictedBestOffset);
   bool taken = false;
   unsigned long long cells = 0;
   static thread_local std::vector<uint8_t> arena(64 * 1024 + 64);
@@ -311,17 +301,15 @@ void xmsim_wave_why_counts(long long* out) { for (int i = 0; i < 64; i++) out[i]
 // out[3 * i + 0] = arena (0 region, 1 temporaries), [1] = capacity in bytes, [2] = bytes written, summed over the reads; returns the number of rows.
 int64_t xmsim_light_footprint(void* idxp, const xm_params* p, const xm_query_batch* b, int64_t* out, int64_t capRows, int64_t* readsDone) {
   SimIndex* idx = (SimIndex*)idxp;
-  Params params;
-  params.MutationPenalty = p->MutationPenalty; params.InsertionStart_Penalty = p->InsertionStart_Penalty; params.InsertionExtension_Penalty = p->InsertionExtension_Penalty;
-  params.DeletionStart_Penalty = p->DeletionStart_Penalty; params.DeletionExtension_Penalty = p->DeletionExtension_Penalty; params.MaxErrorRate = p->MaxErrorRate;
-  params.UnalignedPenalty = p->UnalignedPenalty; params.AmbiguityPenalty = p->AmbiguityPenalty; params.Max_PenaltySpan = p->Max_PenaltySpan;
-  params.MaxNumMatches = p->MaxNumMatches; params.StartingInsertionStartFree = 0;
+  const Params params = paramsFromC(*p);
   {
     int maxLen = 1;
     for (int64_t q = 0; q < b->num_queries; q++) for (int m = 0; m < b->mate_count[q]; m++) if (b->mate_length[q * 2 + m] > maxLen) maxLen = b->mate_length[q * 2 + m];
     if (maxLen > idx->host.maxHashedLength) { idx->host.ensureLength(maxLen); idx->refresh(); }
   }
-  const size_t regionBytes = (size_t)72 * 1024 + ((sizeof(SavedRead) + 15) & ~(size_t)15), tmpBytes = (size_t)48 * 1024;
+  const BatchFacts facts{1, false, 1, 0};  // (single reads of up to 320 bases)
+  const BatchPolicy pol = makePolicy(facts, readPassKnobs(facts, knobDefault));
+  const size_t regionBytes = pol.regionBytes, tmpBytes = pol.lightTmpUnit;
   std::vector<uint8_t> region(regionBytes + 64), tmp(tmpBytes + 64);
   uint8_t* rg = (uint8_t*)(((uintptr_t)region.data() + 15) & ~(uintptr_t)15);
   uint8_t* tp = (uint8_t*)(((uintptr_t)tmp.data() + 15) & ~(uintptr_t)15);
@@ -553,6 +541,54 @@ int64_t xmsim_pyramid_dump_multi(const uint8_t* codes, int len, int scale, int32
     }
   }
   return n;
+}
+
+// ---- the product's pass planner (mapper_amd/csrc/xm_pass_plan.h) for tests/test_pass_plan.py.  facts: longest mate, any paired, contexts on the GPU, scratch limit
+// of the context in bytes (0: none).  The knobs are read from the environment as an align call reads them.  state (11): heavy, hoMode, scale, overflowScale,
+// orderedList, ts, to, tc, confRounds, nRegions, regionsTotal.  Non-zero: failed, xmsim_last_error() says why.
+static BatchPolicy simPolicy(const int64_t* f) {
+  const BatchFacts facts{(int)f[0], f[1] != 0, (int)f[2], (long long)f[3]};
+  return makePolicy(facts, readPassKnobs(facts));
+}
+static PassState simState(const int64_t* s) { return PassState{s[0] != 0, (int)s[1], (int)s[2], (int)s[3], s[4] != 0, (int)s[5], (int)s[6], (int)s[7], (int)s[8], (long long)s[9], (size_t)s[10]}; }
+static void simStateOut(const PassState& st, int64_t* s) {
+  s[0] = st.heavy; s[1] = st.hoMode; s[2] = st.scale; s[3] = st.overflowScale; s[4] = st.orderedList; s[5] = st.ts; s[6] = st.to; s[7] = st.tc; s[8] = st.confRounds;
+  s[9] = st.nRegions; s[10] = (int64_t)st.regionsTotal;
+}
+// policy (16): seedScale, gappedScale, longReads, arenaUnit, lightTmpUnit, regionBytes, scratchWanted, boundFilterOn, searchPoolOn, heavyHint, lightWaves, fullWaves,
+// lightLpw, fullLpw, gappedTmpBytes(arena of the gapped scale), handOver; state: the first pass's
+int xmsim_pass_policy(const int64_t* facts, int64_t* policy, int64_t* state) {
+  try {
+    const BatchPolicy pol = simPolicy(facts);
+    const int64_t v[16] = {pol.seedScale, pol.gappedScale, pol.longReads, (int64_t)pol.arenaUnit, (int64_t)pol.lightTmpUnit, (int64_t)pol.regionBytes, (int64_t)pol.scratchWanted, pol.boundFilterOn,
+                           pol.searchPoolOn, pol.k.heavyHint, pol.k.lightWaves, pol.k.fullWaves, pol.k.lightLpw, pol.k.fullLpw, (int64_t)pol.gappedTmpBytes(pol.arenaUnit * (size_t)pol.gappedScale), pol.k.handOver};
+    for (int i = 0; i < 16; i++) policy[i] = v[i];
+    simStateOut(firstPass(pol), state);
+    return 0;
+  } catch (std::exception& e) { g_err = e.what(); return 1; }
+}
+// plan (16): arenaBytes, lpw, nWaves, grid, block, lanes, nRegions, regionsTotal, scratchBytes, gappedReserve, pairLanes, boundFilter, boundFilterArg, firstStride, firstItem, poolBuffers;
+// plan[16] = taperUnit
+int xmsim_plan_launch(const int64_t* facts, const int64_t* state, int64_t nTodo, int64_t nq, int numCUs, uint64_t budget, uint64_t scratchHeld, int64_t* plan) {
+  try {
+    const LaunchPlan pl = planLaunch(simPolicy(facts), simState(state), nTodo, nq, numCUs, budget, (size_t)scratchHeld);
+    const int64_t v[17] = {(int64_t)pl.arenaBytes, pl.lpw, pl.nWaves, pl.grid, pl.block, pl.lanes, pl.nRegions, (int64_t)pl.regionsTotal, (int64_t)pl.scratchBytes, (int64_t)pl.gappedReserve, pl.pairLanes,
+                           pl.boundFilter, pl.boundFilterArg, pl.firstStride, (int64_t)pl.firstItem, pl.poolBuffers, pl.taperUnit};
+    for (int i = 0; i < 17; i++) plan[i] = v[i];
+    return 0;
+  } catch (std::exception& e) { g_err = e.what(); return 1; }
+}
+// ctl (9): nHeavy, nHeavyLate, nScale[2], nOut[2], errQuery, nConf[2]; state is updated; next (4): kind (0 done, 1 result-arena rerun, 2 gapped, 3 confidence rerun,
+// 4 scale rerun), nTodo, list, clear
+int xmsim_next_pass(const int64_t* facts, int64_t* state, const uint64_t* ctl, int64_t* next) {
+  try {
+    PassState st = simState(state);
+    const PassCtl c{ctl[0], ctl[1], {ctl[2], ctl[3]}, {ctl[4], ctl[5]}, ctl[6], {ctl[7], ctl[8]}};
+    const NextPass np = nextPass(simPolicy(facts), st, c);
+    simStateOut(st, state);
+    next[0] = (int64_t)np.kind; next[1] = np.nTodo; next[2] = np.list; next[3] = np.clear;
+    return 0;
+  } catch (std::exception& e) { g_err = e.what(); return 1; }
 }
 
 }  // extern "C"

@@ -57,6 +57,9 @@ def lib():
         L.xmsim_test_bound.argtypes = [C.POINTER(_capi.XmParams), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]
         L.xmsim_set_wave_mode.argtypes = [C.c_int]
         L.xmsim_wave_status_counts.argtypes = [C.c_void_p, C.c_int]
+        L.xmsim_pass_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xmsim_plan_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.xmsim_next_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -183,3 +186,44 @@ def test_bound(params, query, query_rc, start_a, end_a, reference, start_b, end_
     out = (C.c_int64 * 3)()
     lib().xmsim_test_bound(C.byref(p), q.ctypes.data, len(q), 1 if query_rc else 0, start_a, end_a, r.ctypes.data, len(r), start_b, end_b, predicted_best_offset, out)
     return int(out[0]), int(out[1]), int(out[2])
+
+
+# ---- the product's pass planner (mapper_amd/csrc/xm_pass_plan.h); the knobs are read from the environment as an align call reads them
+POLICY_FIELDS = ("seedScale", "gappedScale", "longReads", "arenaUnit", "lightTmpUnit", "regionBytes", "scratchWanted", "boundFilterOn", "searchPoolOn", "heavyHint", "lightWaves",
+                 "fullWaves", "lightLpw", "fullLpw", "gappedTmpBytes", "handOver")
+STATE_FIELDS = ("heavy", "hoMode", "scale", "overflowScale", "orderedList", "ts", "to", "tc", "confRounds", "nRegions", "regionsTotal")
+PLAN_FIELDS = ("arenaBytes", "lpw", "nWaves", "grid", "block", "lanes", "nRegions", "regionsTotal", "scratchBytes", "gappedReserve", "pairLanes", "boundFilter", "boundFilterArg",
+               "firstStride", "firstItem", "poolBuffers", "taperUnit")
+PASS_KINDS = ("done", "out_rerun", "gapped", "conf_rerun", "scale_rerun")
+
+
+def _facts(longest_mate, paired=False, contexts=1, context_scratch=0):
+    return np.array([longest_mate, 1 if paired else 0, contexts, context_scratch], dtype=np.int64)
+
+
+def _check(rc):
+    if rc:
+        raise RuntimeError(lib().xmsim_last_error().decode())
+
+
+def pass_policy(longest_mate, paired=False, contexts=1, context_scratch=0):
+    """-> (policy dict, state dict of the first pass) of a batch"""
+    f, pol, st = _facts(longest_mate, paired, contexts, context_scratch), np.zeros(16, dtype=np.int64), np.zeros(11, dtype=np.int64)
+    _check(lib().xmsim_pass_policy(f.ctypes.data, pol.ctypes.data, st.ctypes.data))
+    return dict(zip(POLICY_FIELDS, map(int, pol))), dict(zip(STATE_FIELDS, map(int, st)))
+
+
+def plan_launch(state, n_todo, nq, num_cus, budget, scratch_held, longest_mate, paired=False, contexts=1, context_scratch=0):
+    f, plan = _facts(longest_mate, paired, contexts, context_scratch), np.zeros(17, dtype=np.int64)
+    st = np.array([state[k] for k in STATE_FIELDS], dtype=np.int64)
+    _check(lib().xmsim_plan_launch(f.ctypes.data, st.ctypes.data, n_todo, nq, num_cus, budget, scratch_held, plan.ctypes.data))
+    return dict(zip(PLAN_FIELDS, map(int, plan)))
+
+
+def next_pass(state, ctl, longest_mate, paired=False, contexts=1):
+    """ctl: dict with nHeavy, nHeavyLate, nScale (2), nOut (2), nConf (2) (missing = 0) -> (kind, nTodo, list, clear, new state)"""
+    f, nxt = _facts(longest_mate, paired, contexts), np.zeros(4, dtype=np.int64)
+    st = np.array([state[k] for k in STATE_FIELDS], dtype=np.int64)
+    c = np.array([ctl.get("nHeavy", 0), ctl.get("nHeavyLate", 0)] + list(ctl.get("nScale", (0, 0))) + list(ctl.get("nOut", (0, 0))) + [2 ** 64 - 1] + list(ctl.get("nConf", (0, 0))), dtype=np.uint64)
+    _check(lib().xmsim_next_pass(f.ctypes.data, st.ctypes.data, c.ctypes.data, nxt.ctypes.data))
+    return PASS_KINDS[int(nxt[0])], int(nxt[1]), int(nxt[2]), int(nxt[3]), dict(zip(STATE_FIELDS, map(int, st)))

@@ -3,13 +3,14 @@
 was built (profiles/r06/NOTES.md 2, 12, 15a), and the one in which each read of a wave works in its own region of the wave's LDS slot.  The other tests of the
 tier reach it with one or two reads per wave only.
 
-Shape.  The launch logic (xm_capi.hip, the gapped pass) gives a batch of long reads waveSlots = numCUs x 4 x XM_FULL_WAVES wave slots and
+Shape.  The launch logic (xm_pass_plan.h, planLaunch, the gapped pass) gives a batch of long reads waveSlots = numCUs x 4 x XM_FULL_WAVES wave slots and
 lpw = min(XM_FULL_LPW = 8, ceil(reads / waveSlots)) reads per wave, then - when the lanes would fill fewer waves than the GPU holds at a time - cuts lpw to
 lanes / slotsHeld with slotsHeld = numCUs x 16 / contexts.  On an MI355X (256 CUs) with XM_FULL_WAVES=1 and FOUR contexts of the database open:
 waveSlots = 1 024, lanes = 1 024 x 8 = 8 192 for a pass of >= 8 192 reads, slotsHeld = 4 096 / 4 = 1 024, and 8 192 / 8 = 1 024 waves is not fewer than that:
 lpw stays 8.  A pass of R reads between 5 200 and 8 192 gets lanes = R and lpw = floor(R / 1 024) >= 5.  (One context: slotsHeld = 4 096 and lpw = 2.)
 The shape is not assumed: every run reads the pass trace (XM_TRACE_PASSES=1, "[xm] pass N: gapped reads R ... lpw L waves W lanes/read G filter F" on fd 2)
 and asserts, for the pass that ran the filter, L >= 5, R / W >= 5 and G = 8.  A change of the launch logic that loses the shape fails here.
+(The arithmetic itself - xm_pass_plan.h, planLaunch - is pinned without a GPU for these cases in tests/test_pass_plan.py.)
 
 What is compared: the oracle's streams bit for bit (with its observer of the filter's bound on: it raises when a search the bound rejects aligns), the
 filter's counters against the observer's (tests/helpers.py filter_counters), and the work counters against the reference's minus what the filter skipped -

@@ -167,7 +167,7 @@ def test_long_reads_sharing_waves_on_gpu(env, monkeypatch):
     lpw = min(XM_FULL_LPW, ceil(9 000 / 1 024)), which the launch logic for long reads then cuts to lanes / 4 096 (the GPU's wave slots, one context) - TWO
     reads per wave on ~4 100 waves in all three settings (and the shapes of the short-read pass beside it).  The searches of a wave's reads - HBM mode from the
     start at this chain scale - and the lanes of a read must not disturb each other.  Five to eight reads per wave, eight lanes each, with reads that do not
-    align: tests/test_gpu_dense_waves.py."""
+    align: tests/test_gpu_dense_waves.py.  (The shape as arithmetic, without a GPU: tests/test_pass_plan.py.)"""
     ref = synth.synthetic_reference(400_000, seed=41)
     reads = synth.synthetic_single_end(ref, 9000, read_len=1000, sub_rate=0.02, indel_prob=0.3, seed=42)[0]
     b = se_batch(reads)
