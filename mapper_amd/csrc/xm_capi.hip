@@ -1,11 +1,14 @@
-// libxmapper_hip.so: kernels, HBM residency and the C ABI of include/xmapper_hip.h.
+// libxmapper_hip.so: the align call and the C ABI of include/xmapper_hip.h, one translation unit.
 //
-// Kernel design (round 1): one read per lane, persistent lanes.  The per-read algorithm is a long, data-dependent
-// state machine (adaptive pyramid walk -> bucket probes -> votes -> ungapped check -> best-first gapped search), so a
-// lane pulls reads from a global counter until the batch is drained; each lane owns a scratch arena in HBM (sized by
-// `scale`), the index is read-only in HBM (bucket header = 2 adjacent u32, positions contiguous per bucket, reference
-// one 4-bit code per byte).  Results go to a bump-allocated result arena and are put into query order on the host.
-// Reads whose fixed-capacity scratch overflowed are rerun by a second launch with a 4x larger scale (never on the CPU).
+// In this file, in this order: the lane-per-read align kernel (one read per lane, persistent lanes that draw reads from a counter; the per-read
+// state machine is xm_worker.h) and the small kernels of the pass bookkeeping (work lists, prefix sums, the gather of the result streams into
+// query order on the device); the tables of a reference on the host and in HBM (HostShare, DeviceTables); a context (xm_index): its stream, its
+// resident and its staged batch (DeviceBatch), its scratch, the device copy of its confidence table; the steps of an align call (AlignCall ...
+// finishStreams), which launch what xm_pass_plan.h plans - reads a pass could not finish are run again by a later pass on the GPU, never on the
+// CPU; the C entries for indexes, contexts, batches and alignment.
+// Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_conf_table.h (the host's confidence table),
+// xm_capi_probe.h (seed-probe and random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries).  The
+// wave-per-read kernels are xm_wave_kernel.hip, the index build on the device is xm_index_device.hip.
 #include "../../include/xmapper_hip.h"
 #include "xm_worker.h"
 #include "xm_wsearch.h"
@@ -14,10 +17,11 @@
 #include "xm_kernel_common.h"
 #include "xm_pass_plan.h"
 #include "xm_collapse.h"
+#include "xm_conf_table.h"
+#include "xm_device_rt.h"
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
-#include <unordered_set>
 #include <mutex>
 #include <shared_mutex>
 #include <memory>
@@ -33,15 +37,6 @@ namespace xm { bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int 
 using namespace xm;
 
 namespace {
-
-thread_local std::string g_error;
-int fail(const std::string& msg) { g_error = msg; return 1; }
-
-#define HIP_CHECK(expr)                                                                                     \
-  do {                                                                                                      \
-    hipError_t _e = (expr);                                                                                 \
-    if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-  } while (0)
 
 #ifndef XM_WAVES_PER_SIMD
 #define XM_WAVES_PER_SIMD 4  // 128 registers per lane: the path is latency-bound, four waves per SIMD hide more of it than the spills cost
@@ -160,174 +155,11 @@ __global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_align_kernel(IndexV
   if (!second) addCounters(counters, local);
 }
 
-// Test entry (xm_test_local_align): the reference's component-level known-answer tests (PathAligner_Test.java:10-39: PathAligner alone;
-// HashBlockAligner_Test.java:10-48: HashBlock_Aligner -> StraightAligner -> PathAligner_Runner) over two given texts, run by the code the align
-// kernel runs.  chain 0: one search, in the wave's LDS slot (mode 0), in HBM mode (mode 1) or in the lane-private form (mode 4); chain 1: hashBlockAlign with the searches
-// slot-first as in the kernel (mode 0), all in HBM mode (mode 1) or all in the lane-private form of xm_wsearch.h (mode 4).  One lane works; out: found, nb, status, nodes, blocks; penalties.
-__global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_test_local_kernel(int chain, int mode, Params params, const uint8_t* query, int queryLength, const uint8_t* reference, int referenceLength,
-                                                            double maxIns, double maxDel, int scale, uint8_t* arena, unsigned long long arenaBytes, PNode* waveNodes, int blockCap,
-                                                            int32_t* outInts, double* outDbls) {
-  xmSetWaveNodes(waveNodes);
-  xmSetPairMode(0);
-  xmSetSearchPool(SearchPool{nullptr, 0, 0, 0});
-  xmSetBoundFilter(mode >= 8 ? 1 : 0);  // (mode + 8: the search behind the rejection filter of xm_bound.h)
-  mode &= 7;
-  xmLoadMergeRule();  // (every thread of the block: it ends with a barrier)
-  if (threadIdx.x != 0) return;
-  DevCounters local;
-  memset(&local, 0, sizeof(local));
-  Caps caps = makeCaps(scale);
-  caps.searchInHbmOnly = mode == 1 ? 1 : (mode == 4 ? 2 : 0);
-  Arena tmp;
-  tmp.init(arena, (size_t)arenaBytes);
-  int32_t status = XM_OK;
-  float hint = 0;
-  ExtEnv e;
-  e.caps = &caps; e.dc = &local; e.status = &status; e.tmp = &tmp;
-  e.query.base = query; e.query.len = queryLength; e.query.rc = 0; e.query.id = 0;
-  e.reference.base = reference; e.reference.len = referenceLength; e.reference.rc = 0; e.reference.id = 0;
-  e.contig = 0;
-  e.heavyHint = &hint;
-  Matcher* slots = arenaArray<Matcher>(tmp, 3);
-  for (int i = 0; i < 3; i++) {
-    slots[i].present = arenaArray<uint8_t>(tmp, caps.maxSections);
-    slots[i].tables = arenaArray<int16_t>(tmp, caps.matcherEntries);
-    slots[i].tableCap = caps.matcherEntries;
-    slots[i].maxSections = caps.maxSections;
-    slots[i].nSections = 0;
-    slots[i].presentMask = 0;
-    slots[i].sectionLength = 0;
-  }
-  e.slotA = &slots[0]; e.slotB = &slots[1]; e.slotT = &slots[2];
-  SeqAl out;
-  out.blocks = arenaArray<ABlock>(tmp, caps.maxBlocks);
-  out.nb = 0; out.contig = 0; out.referenceReversed = 0; out.seqAId = 0; out.totalPenalty = 0; out.alignedPenalty = 0;
-  bool found = false;
-  if (tmp.overflow) status = XM_ST_OVERFLOW;
-  else {
-    const Section qs{0, queryLength}, rs{0, referenceLength};
-    Analysis an;  // AlignmentAnalysis as the tests construct it: nothing known about the offset, the two extension limits given
-    an.matcher = nullptr; an.predictedBestOffset = 0; an.lastCheckedOffset = 0; an.confidentAboutBestOffset = false;
-    an.maxInsertionExtensionPenalty = maxIns; an.maxDeletionExtensionPenalty = maxDel;
-    if (chain == 0) found = pathAlign(e, qs, rs, params, an, out);
-    else found = hashBlockAlign(e, qs, rs, params, an, out, e.slotB, NextStraight3());
-  }
-  outInts[0] = found && status == XM_OK ? 1 : 0; outInts[1] = found ? out.nb : 0; outInts[2] = status; outInts[3] = (int32_t)local.pathAlignerNodes;
-  outInts[4 + 4 * blockCap] = (int32_t)local.boundChecks; outInts[5 + 4 * blockCap] = (int32_t)local.boundRejects; outInts[6 + 4 * blockCap] = (int32_t)local.boundCells;  // (behind the blocks)
-  if (found) {
-    for (int i = 0; i < out.nb && i < blockCap; i++) { outInts[4 + 4 * i] = out.blocks[i].startA; outInts[5 + 4 * i] = out.blocks[i].startB; outInts[6 + 4 * i] = out.blocks[i].lenA; outInts[7 + 4 * i] = out.blocks[i].lenB; }
-    outDbls[0] = out.totalPenalty; outDbls[1] = out.alignedPenalty;
-  }
-}
+}  // namespace
 
-// Test entry (xm_test_bound): the rejection filter of xm_bound.h alone, on one problem - a section of a query against a window of a reference - as a lane of a
-// long-read chain runs it (lane 0 of a wave, its region of the wave's slot; pair = 1: lanes 0 and 1 together, 3: lanes 0 .. 7).  out: taken, rejected, cells.
-__global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_test_bound_kernel(Params params, const uint8_t* query, int queryLength, int queryRc, int startA, int endA, const uint8_t* reference, int referenceLength,
-                                                            int startB, int endB, int predictedBestOffset, int pair, uint8_t* arena, unsigned long long arenaBytes, int64_t* out) {
-  xmSetWaveNodes(nullptr);
-  xmSetPairMode(pair);
-  xmSetSearchPool(SearchPool{nullptr, 0, 0, 0});
-  xmSetBoundFilter(3);
-  xmLoadMergeRule();  // (every thread of the block: it ends with a barrier)
-  if (threadIdx.x >= (1u << pair)) return;
-  const BoundProblem bp = boundTestProblem(params, query, queryLength, queryRc, startA, endA, reference, referenceLength, startB, endB, predictedBestOffset);
-  bool taken = false;
-  unsigned long long cells = 0;
-  Arena tmp;
-  tmp.init(arena, (size_t)arenaBytes);  // (the two lanes of a pair keep the same band in the same memory, as they do in the passes: same values twice)
-  const bool rejected = boundRejects(bp, pair, tmp, taken, cells);
-  if (threadIdx.x == 0) { out[0] = taken ? 1 : 0; out[1] = rejected ? 1 : 0; out[2] = (int64_t)cells; }
-}
+#include "xm_capi_test.h"  // (the test-only entries run parts of the align kernel alone: their kernels stand behind it)
 
-// ---------------------------------------------------------------- pile-up of the alignments on the reference
-// What MatchDatabase.addAlignments / groupByPosition feed the mutation and VCF writers with (M/Mapper.java:700-708,758-785; the classes are
-// un-vendored, the behaviour is pinned by T/MatchDatabase_Test.java and T/MutationsWriter_Test.java): per forward reference position the depth
-// and the counts of differing query bases, plus one event per insertion / deletion block.  One lane per query walks its result stream in HBM.
-// Counts are integers in units of 1 / XM_PILEUP_UNIT of a read base (a query with n alignments adds 1/n per alignment, the two mates of a pair
-// add 1/2 each where they overlap: T/MatchDatabase_Test.java:38-69), so sums do not depend on the order of the atomic adds.
-struct PileupView {
-  unsigned long long* depth;     // [totalForwardSize]
-  unsigned long long* alt;       // [4][totalForwardSize]: query base A, C, G, T where it differs from an unambiguous reference base
-  long long total;
-  long long* events;             // 7 per event: contig, position, type (1 insertion, 2 deletion), length, query, mate | reversed << 1, startA; weight in [7]
-  unsigned long long eventCap;
-  unsigned long long* eventCount;
-  long long queryBase;           // index of the batch's first query among all queries added so far
-  unsigned long long* mid;       // [totalForwardSize] depth from query bases that are not near a query end (null: no query-end fraction set)
-  double endFraction;            // MatchDatabase(queryEndFraction), --distinguish-query-ends (Mapper.java:76,351-353,700)
-};
-// a query base "near the end of the query": within endFraction of the query's length of either end  [inferred: the rule lives in the un-vendored
-// MatchDatabase; pinned by MutationsWriter_Test.java:114-134 only for fraction 0.5 = every base]
-__device__ __forceinline__ bool xmNearQueryEnd(int k, int readLen, double f) { return (double)k < f * readLen || (double)k >= readLen - f * readLen; }
-__global__ void __launch_bounds__(256) xm_pileup_kernel(IndexView ix, BatchView batch, const int32_t* ints, const int64_t* intOff, PileupView pv) {
-  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= batch.nq) return;
-  const int32_t* p = ints + intOff[q];
-  const int numComponents = *p++;
-  for (int c = 0; c < numComponents; c++) {
-    const int numAlignments = *p++;
-    if (numAlignments < 1) continue;
-    for (int a = 0; a < numAlignments; a++) {
-      // a query's alignments share one read's worth of weight exactly: UNIT / n each, the first UNIT mod n of them one unit more (n above 16 need not
-      // divide UNIT; the sums over a query then still come out whole)
-      const unsigned long long w = XM_PILEUP_UNIT / (unsigned long long)numAlignments + ((unsigned long long)a < XM_PILEUP_UNIT % (unsigned long long)numAlignments ? 1ull : 0ull);
-      p++;  // innerDistance
-      const int numSequences = *p++;
-      // the reference interval of each sequence alignment first (mates of a pair share the depth where they overlap)
-      int contigOf[2] = {-1, -1};
-      long long lo[2] = {0, 0}, hi[2] = {0, 0};
-      {
-        const int32_t* t = p;
-        for (int sq = 0; sq < numSequences && sq < 2; sq++) {
-          contigOf[sq] = t[0];
-          const int nb = t[2];
-          t += 3;
-          if (nb > 0) { lo[sq] = t[1]; hi[sq] = t[4 * (nb - 1) + 1] + t[4 * (nb - 1) + 3]; }
-          t += 4 * nb;
-        }
-      }
-      long long ovLo = 0, ovHi = 0;
-      if (numSequences == 2 && contigOf[0] == contigOf[1]) { ovLo = lo[0] > lo[1] ? lo[0] : lo[1]; ovHi = hi[0] < hi[1] ? hi[0] : hi[1]; }
-      for (int sq = 0; sq < numSequences; sq++) {
-        const int contig = *p++;
-        const int reversed = *p++;
-        const int nb = *p++;
-        const int mate = numComponents > 1 ? c : sq;
-        const uint8_t* read = batch.codes + batch.mateOffset[q * 2 + mate];
-        const int readLen = batch.mateLength[q * 2 + mate];
-        const long long base = ix.contigStart[contig];
-        for (int b = 0; b < nb; b++, p += 4) {
-          const int startA = p[0], startB = p[1], lenA = p[2], lenB = p[3];
-          if (lenA == lenB) {
-            for (int i = 0; i < lenA; i++) {
-              const long long pos = startB + i;
-              const unsigned long long wi = (pos >= ovLo && pos < ovHi) ? (sq == 0 ? w / 2 : w - w / 2) : w;
-              const uint8_t r = ix.refCodes[base + pos];
-              const int k = startA + i;
-              if (pv.mid && !xmNearQueryEnd(k, readLen, pv.endFraction)) atomicAdd(&pv.mid[base + pos], wi);
-              const uint8_t qb = reversed ? bpComplement(read[readLen - 1 - k]) : read[k];
-              atomicAdd(&pv.depth[base + pos], wi);
-              if (!bpIsAmbiguous(r) && !bpIsAmbiguous(qb) && qb != r) atomicAdd(&pv.alt[(long long)encodedCharToInt(qb) * pv.total + base + pos], wi);
-            }
-          } else {
-            if (lenA == 0) for (int i = 0; i < lenB; i++) {  // a deletion: the read spans these reference bases
-              const long long pos = startB + i;
-              const unsigned long long wi = (pos >= ovLo && pos < ovHi) ? (sq == 0 ? w / 2 : w - w / 2) : w;
-              atomicAdd(&pv.depth[base + pos], wi);
-              if (pv.mid && !xmNearQueryEnd(startA, readLen, pv.endFraction)) atomicAdd(&pv.mid[base + pos], wi);  // (the gap sits in front of query base startA)
-            }
-            const unsigned long long at = atomicAdd(pv.eventCount, 1ull);
-            if (at < pv.eventCap) {
-              long long* e = pv.events + at * 8;
-              e[0] = contig; e[1] = startB; e[2] = lenA > 0 ? 1 : 2; e[3] = lenA > 0 ? lenA : lenB; e[4] = pv.queryBase + q; e[5] = mate | (reversed << 1) | ((pv.mid && xmNearQueryEnd(startA, readLen, pv.endFraction)) ? 4 : 0); e[6] = startA;
-              e[7] = (long long)((startB >= ovLo && startB < ovHi) ? (sq == 0 ? w / 2 : w - w / 2) : w);
-            }
-          }
-        }
-      }
-    }
-  }
-}
+namespace {
 
 // ---------------------------------------------------------------- pass bookkeeping on the device (PassCtl, PassLists: xm_kernel_common.h)
 // after a pass of the wave-per-read form (xm_wave_kernel.hip): reads for the next tier, reads with a waiting search request, reads left
@@ -426,238 +258,6 @@ __global__ void __launch_bounds__(256) xm_lines_kernel(Table t, const uint32_t* 
   W* dst = lines + (t.offBase + k) * 8;
   for (int j = 0; j < 8; j++) dst[j] = line[j];
 }
-
-// Where a probe's positions go: the 64 probes i = 64 c ... 64 c + 63 (the lanes of one wavefront) write theirs one behind the other, in probe order, from
-// out_positions[64 c max_per_probe] on - whole lines leave for HBM, and only as many bytes as there are positions (rows of max_per_probe slots cost the
-// memory 56 bytes a probe at 7 slots, of which a genome's buckets fill 12; a row per position index, written only where a bucket has that many, is holes
-// in every line, and a partly written line costs a read besides the write).  The reader finds probe i's positions behind those of the probes before it
-// in its chunk: offsets are the running sum of min(max(counts, 0), max_per_probe) over the chunk.  Returns this lane's first slot.
-__device__ __forceinline__ long long xmProbeSlot(long long i, int m, int maxPerProbe) {
-  // exclusive prefix sum of m (0 ... 7: three bits) over the lanes of the wave
-  const unsigned long long b0 = __ballot(m & 1), b1 = __ballot(m & 2), b2 = __ballot(m & 4), b3 = __ballot(m & 8);
-  const unsigned long long below = (1ull << (threadIdx.x & 63u)) - 1ull;
-  const int before = __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below) + 8 * __popcll(b3 & below);
-  return (i & ~63ll) * (long long)maxPerProbe + before;
-}
-
-// PackedMap.getNumMatchesLowerBound + PackedMap.get for a batch of (used length, key): one lane per probe.
-__global__ void __launch_bounds__(256) xm_seed_probe_kernel(IndexView ix, long long n, const int32_t* usedLength, const int32_t* keys, int maxPerProbe,
-                                                            int32_t* counts, int64_t* outPositions) {
-  // (the probe through the CSR arrays - two adjacent offsets, then the positions: what an index without bucket lines offers)
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = i < n;
-  const int used = live ? usedLength[i] : -1;
-  const bool ok = live && used >= 0 && used <= ix.maxHashedLength;
-  int count = -2;
-  int64_t first = 0;
-  if (ok) {
-    const Table* t = &ix.tables[used];
-    const uint32_t k = packedKey(t, keys[i]);
-    const uint32_t* off = ix.bucketOff + t->offBase + k;
-    const uint32_t o0 = off[0], o1 = off[1];
-    count = (o0 & XM_OVERFULL) ? -1 : (int)((o1 & ~XM_OVERFULL) - (o0 & ~XM_OVERFULL));
-    if (count > t->maxCount) count = -1;
-    first = t->posBase + (int64_t)(o0 & ~XM_OVERFULL);
-  }
-  const int m = (count > 0 && maxPerProbe > 0) ? (count < maxPerProbe ? count : maxPerProbe) : 0;
-  const long long slot = xmProbeSlot(i, m, maxPerProbe);
-  if (!live) return;
-  counts[i] = count;
-  for (int j = 0; j < m; j++) outPositions[slot + j] = ix.posIs64 ? (int64_t)ix.positions64[first + j] : (int64_t)ix.positions32[first + j];
-}
-
-// The same bulk probe over bucket lines with several probes in flight per lane (round 5; it replaces the group-of-lanes form of round 2, which ran at half of this
-// GPU's random-sector rate): a probe's chain - (length, key) -> table descriptor -> key mod capacity -> line - is short but dependent, so what the rate
-// needs is many chains at a time.  A lane takes XM_PROBES_PER_LANE probes a whole launch apart (coalesced reads of the inputs and writes of the counts), takes
-// the table descriptors from LDS (the block copies them there once: no trip to memory between the inputs and the line), and has asked for all its lines
-// before it looks at the first.  64-bit lines: the whole 64-byte line as four 16-byte loads; 32-bit lines: two.  Header only (maxPerProbe == 0): the first
-// 16 bytes.  Buckets with more than XM_LINE_SLOTS positions (1.4 % of a genome-like index) read the CSR arrays behind that.
-constexpr int XM_PROBES_PER_LANE = 4;
-constexpr int XM_PROBE_LDS_TABLES = 512;
-template <bool W64>
-__global__ void __launch_bounds__(256) xm_seed_probe_lines_kernel(IndexView ix, long long n, const int32_t* usedLength, const int32_t* keys, int maxPerProbe,
-                                                                  int32_t* counts, int64_t* outPositions) {
-  __shared__ Table sTables[XM_PROBE_LDS_TABLES];
-  const int nTables = ix.maxHashedLength + 1;
-  const bool inLds = nTables <= XM_PROBE_LDS_TABLES;
-  if (inLds) {
-    for (int t = (int)threadIdx.x; t < nTables; t += (int)blockDim.x) sTables[t] = ix.tables[t];
-    __syncthreads();
-  }
-  const long long lanes = (long long)gridDim.x * blockDim.x;
-  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  int used[XM_PROBES_PER_LANE], key[XM_PROBES_PER_LANE];
-#pragma unroll
-  for (int p = 0; p < XM_PROBES_PER_LANE; p++) {
-    const long long i = tid + (long long)p * lanes;
-    used[p] = i < n ? usedLength[i] : -1;
-    key[p] = i < n ? keys[i] : 0;
-  }
-  Table tb[XM_PROBES_PER_LANE];
-  uint32_t k[XM_PROBES_PER_LANE];
-  typedef typename std::conditional<W64, ulonglong2, uint4>::type Vec;   // 16 bytes of a line
-  constexpr int NV = W64 ? 4 : 2;
-  Vec v[XM_PROBES_PER_LANE][NV];
-#pragma unroll
-  for (int p = 0; p < XM_PROBES_PER_LANE; p++) {
-    const bool ok = used[p] >= 0 && used[p] <= ix.maxHashedLength;
-    tb[p] = inLds ? sTables[ok ? used[p] : 0] : ix.tables[ok ? used[p] : 0];
-    k[p] = packedKey(&tb[p], key[p]);
-    const Vec* lp = W64 ? (const Vec*)(ix.lines64 + (tb[p].offBase + k[p]) * 8) : (const Vec*)(ix.lines32 + (tb[p].offBase + k[p]) * 8);
-    if (ok) v[p][0] = lp[0];
-  }
-  // the rest of a line only where its positions are wanted: the first 16 bytes hold the count and three positions (one with 64-bit positions), and a
-  // request costs the memory pipeline the same whether it brings 16 bytes of a new sector or the next 16 of the one before
-  int cnt[XM_PROBES_PER_LANE];
-#pragma unroll
-  for (int p = 0; p < XM_PROBES_PER_LANE; p++) {
-    const bool ok = used[p] >= 0 && used[p] <= ix.maxHashedLength;
-    const uint32_t h = W64 ? (uint32_t)((const unsigned long long*)&v[p][0])[0] : ((const uint32_t*)&v[p][0])[0];
-    int count = (h & XM_OVERFULL) ? -1 : (int)h;
-    if (ok && count > tb[p].maxCount) count = -1;
-    cnt[p] = ok ? count : -2;
-    const int want = (maxPerProbe > 0 && count > 0 && count <= XM_LINE_SLOTS) ? (count < maxPerProbe ? count : maxPerProbe) : 0;   // positions to take from the line
-    const Vec* lp = W64 ? (const Vec*)(ix.lines64 + (tb[p].offBase + k[p]) * 8) : (const Vec*)(ix.lines32 + (tb[p].offBase + k[p]) * 8);
-#pragma unroll
-    for (int q = 1; q < NV; q++) if (ok && 1 + want > q * (W64 ? 2 : 4)) v[p][q] = lp[q];
-  }
-#pragma unroll
-  for (int p = 0; p < XM_PROBES_PER_LANE; p++) {
-    const long long i = tid + (long long)p * lanes;
-    const int count = cnt[p];
-    const int m = (i < n && count > 0 && maxPerProbe > 0) ? (count < maxPerProbe ? count : maxPerProbe) : 0;
-    const long long slot = xmProbeSlot(i, m, maxPerProbe);  // (every lane of the wave: the lanes' probes of one p are 64 consecutive ones)
-    if (i >= n) continue;
-    counts[i] = count;
-    if (m == 0) continue;
-    if (count <= XM_LINE_SLOTS) {
-#pragma unroll
-      for (int j = 0; j < XM_LINE_SLOTS; j++) {
-        if (j < m) outPositions[slot + j] = W64 ? (int64_t)((const unsigned long long*)&v[p][0])[1 + j] : (int64_t)((const uint32_t*)&v[p][0])[1 + j];
-      }
-      continue;
-    }
-    const int64_t first = tb[p].posBase + (int64_t)(ix.bucketOff[tb[p].offBase + k[p]] & ~XM_OVERFULL);
-    for (int j = 0; j < m; j++) outPositions[slot + j] = ix.posIs64 ? (int64_t)ix.positions64[first + j] : (int64_t)ix.positions32[first + j];
-  }
-}
-
-// Measurement helper: one random 64-byte sector per access out of a table far larger than the caches, 16 bytes of it read.
-// The sectors/s this reaches is the ceiling a hash-probe kernel (one 8-byte bucket header per probe) can be held against.
-__global__ void __launch_bounds__(256) xm_random_gather_kernel(const uint4* table, unsigned long long nSectors, long long nAccesses, int perThread, unsigned long long seed,
-                                                               unsigned int* sink) {
-  long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  uint4 acc = make_uint4(0, 0, 0, 0);
-  for (int k = 0; k < perThread; k++) {
-    long long a = t * perThread + k;
-    if (a >= nAccesses) break;
-    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(a + 1);  // SplitMix64
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    uint4 v = table[(z % nSectors) * 4];
-    acc.x ^= v.x; acc.y ^= v.y; acc.z ^= v.z; acc.w ^= v.w;
-  }
-  if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) sink[0] = acc.x;  // keeps the loads alive
-}
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  void ensure(size_t count) {
-    if (count <= n && p) return;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = count ? count : 1;
-    HIP_CHECK(hipMalloc((void**)&p, n * sizeof(T)));
-  }
-  // like ensure, but an allocation the GPU has no room for returns false (the buffer is then empty) instead of throwing
-  bool tryEnsure(size_t count) {
-    if (count <= n && p) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    const size_t want = count ? count : 1;
-    n = 0;
-    hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) { (void)hipGetLastError(); p = nullptr; return false; }
-    HIP_CHECK(e);
-    n = want;
-    return true;
-  }
-  // grow to `count`, keeping the first `keep` elements
-  void growKeep(size_t count, size_t keep, hipStream_t s) {
-    if (count <= n && p) return;
-    T* np = nullptr;
-    HIP_CHECK(hipMalloc((void**)&np, count * sizeof(T)));
-    if (p && keep) HIP_CHECK(hipMemcpyAsync(np, p, (keep < n ? keep : n) * sizeof(T), hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (p) (void)hipFree(p);
-    p = np; n = count;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-  void swapWith(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
-  ~DevBuf() { release(); }
-};
-
-// Result streams live in pinned host memory (the final device-to-host copy is then one DMA per stream); the buffers are recycled
-// through a process-wide pool because pinning is far more expensive than the copy itself.
-struct PinnedPool {
-  struct Buf { void* p; size_t bytes; };
-  std::mutex mu;
-  std::vector<Buf> idle;
-  size_t idleBytes = 0;
-  std::atomic<size_t> allocatedBytes{0}, highWater{0};  // pinned host memory this process holds through the pool (in use + idle), and the most it ever held
-  void account(long long delta) {
-    const size_t now = (size_t)((long long)allocatedBytes.fetch_add((size_t)delta) + delta);
-    size_t hw = highWater.load();
-    while (now > hw && !highWater.compare_exchange_weak(hw, now)) {}
-  }
-  void* get(size_t bytes, size_t* got) {
-    if (bytes < 64) bytes = 64;
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      int best = -1;
-      for (int i = 0; i < (int)idle.size(); i++)
-        if (idle[i].bytes >= bytes && idle[i].bytes <= bytes * 2 + 4096 && (best < 0 || idle[i].bytes < idle[best].bytes)) best = i;
-      if (best >= 0) {
-        Buf b = idle[best];
-        idle.erase(idle.begin() + best);
-        idleBytes -= b.bytes;
-        *got = b.bytes;
-        return b.p;
-      }
-    }
-    void* p = nullptr;
-    size_t want = bytes + bytes / 8;  // headroom so that the next, slightly larger batch reuses it
-    HIP_CHECK(hipHostMalloc(&p, want, hipHostMallocPortable));
-    account((long long)want);
-    *got = want;
-    return p;
-  }
-  void put(void* p, size_t bytes) {
-    if (!p) return;
-    std::vector<Buf> drop;
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      idle.push_back(Buf{p, bytes});
-      idleBytes += bytes;
-      while (idleBytes > (4ull << 30) && !idle.empty()) {  // oldest first
-        drop.push_back(idle.front());
-        idleBytes -= idle.front().bytes;
-        idle.erase(idle.begin());
-      }
-    }
-    for (auto& b : drop) { (void)hipHostFree(b.p); account(-(long long)b.bytes); }
-  }
-};
-static PinnedPool* g_pinned = new PinnedPool();  // never destroyed: the HIP runtime may be gone before static destructors run
-
-// xm_result plus what xm_result_free needs to know about its buffers
-struct ResultBox {
-  xm_result pub;
-  size_t bytesInts, bytesDbls, bytesIntOff, bytesDblOff;
-};
 
 }  // namespace
 
@@ -765,6 +365,59 @@ struct DeviceTables {
   }
 };
 
+// One batch of queries in HBM: what the kernels read through BatchView, and what the host knows about it.
+struct DeviceBatch {
+  DevBuf<int32_t> mateCount, mateLength;
+  DevBuf<int64_t> mateOffset;
+  DevBuf<uint8_t> codes;
+  DevBuf<double> expected, deviation;
+  int64_t nq = -1;            // -1: no batch
+  int maxLen = 0;             // longest mate
+  bool anyPaired = false;
+  double h2dMs = 0;
+  std::vector<int32_t> lens;  // distinct total query lengths, ascending (the confidence table is seeded for them)
+  // host -> HBM on stream s, timed between the two events (the caller has validated b); a copy that throws leaves "no batch"
+  void copyIn(const xm_query_batch* b, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+    const int64_t n = b->num_queries;
+    nq = -1;
+    h2dMs = 0;
+    if (n > 0) {
+      HIP_CHECK(hipEventRecord(e0, s));
+      mateCount.ensure((size_t)n); mateOffset.ensure((size_t)n * 2); mateLength.ensure((size_t)n * 2);
+      codes.ensure((size_t)b->codes_length); expected.ensure((size_t)n); deviation.ensure((size_t)n);
+      HIP_CHECK(hipMemcpyAsync(mateCount.p, b->mate_count, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(mateOffset.p, b->mate_offset, sizeof(int64_t) * (size_t)n * 2, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(mateLength.p, b->mate_length, sizeof(int32_t) * (size_t)n * 2, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(codes.p, b->codes, (size_t)b->codes_length, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(expected.p, b->expected_inner, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(deviation.p, b->deviation, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipEventRecord(e1, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      float ms = 0;
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+      h2dMs = ms;
+    }
+    nq = n;
+  }
+  BatchView view() const { return BatchView{nq, mateCount.p, mateOffset.p, mateLength.p, codes.p, expected.p, deviation.p}; }
+};
+
+// what only the wave-per-read passes use (runWaveForm)
+struct WaveFormBuffers {
+  DevBuf<int64_t> dListWaveHeavy, dListWaveNext, dListWaveSearch[2], dListFallback;
+  DevBuf<uint8_t> dWaveMemo;
+  DevBuf<int32_t> dWaveSlotOf;
+  DevBuf<WaveCtl> dWaveCtl;
+  DevBuf<uint8_t> dWaveArenas;
+  DevBuf<PNode> dWaveNodes2;
+};
+// collapsing of identical queries (xm_collapse.h; allocated only when it is on): fingerprint table, query -> representative, the representatives, block counts
+struct CollapseBuffers {
+  DevBuf<unsigned long long> dCollapseKeys, dCollapseReps, dCollapseTotal;
+  DevBuf<int64_t> dRepOf, dRepList;
+  DevBuf<long long> dCollapseBlocks;
+};
+
 // An xm_index handle is a CONTEXT of an index: what one host thread needs to align batches on one GPU - a stream, batch buffers, scratch and a
 // result pool of its own - over tables it shares with every other context of the same index (HostShare: all of them; DeviceTables: those on
 // its GPU).  xm_index_build / xm_index_load make the first context; xm_context_new and xm_index_replicate add contexts.
@@ -781,136 +434,35 @@ struct xm_index {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // per-call scratch kept across calls
-  DevBuf<uint8_t> dArenas, dCodes;
-  DevBuf<int32_t> dMateCount, dMateLength, dStatus, dIntLen, dDblLen, dOutInts;
-  DevBuf<int64_t> dMateOffset, dIntOff, dDblOff, dTodo;
-  DevBuf<double> dExpected, dDeviation, dOutDbls;
+  DevBuf<uint8_t> dArenas;
+  DevBuf<int32_t> dStatus, dIntLen, dDblLen, dOutInts;
+  DevBuf<int64_t> dIntOff, dDblOff;
+  DevBuf<double> dOutDbls;
   DevBuf<unsigned long long> dCursors;  // [0],[1] result cursors, [2] next item
   DevBuf<int64_t> dListHeavy, dListHeavyLate, dListScale[2], dListOut[2], dFinalIntOff, dFinalDblOff;
   DevBuf<int32_t> dRegionOf;
   DevBuf<PNode> dWaveNodes;  // per wave: node payloads of its LDS-mode search
   DevBuf<uint8_t> dSearchPool;  // one buffer per wave for the arrays of HBM-mode searches (SearchPool, xm_extend.h)
-  // wave-per-read passes
-  DevBuf<int64_t> dListWaveHeavy, dListWaveNext, dListWaveSearch[2], dListFallback;
-  DevBuf<uint8_t> dWaveMemo;
-  DevBuf<int32_t> dWaveSlotOf;
-  DevBuf<WaveCtl> dWaveCtl;
-  DevBuf<uint8_t> dWaveArenas;
-  DevBuf<PNode> dWaveNodes2;
-  bool residentAnyPaired = false, stagedAnyPaired = false;
+  WaveFormBuffers wave;
   DevBuf<PassCtl> dCtl;
   DevBuf<long long> dBlockI, dBlockD;
   DevBuf<int32_t> dFinalInts;
   DevBuf<double> dFinalDbls;
   DevBuf<DevCounters> dCounters;
-  // collapsing of identical queries (xm_collapse.h; allocated only when it is on): fingerprint table, query -> representative, the representatives, block counts
-  DevBuf<unsigned long long> dCollapseKeys, dCollapseReps, dCollapseTotal;
-  DevBuf<int64_t> dRepOf, dRepList;
-  DevBuf<long long> dCollapseBlocks;
-  // confidence table (IndexView::conf): host copy, device copy, the settings it was computed for, miss list, reads that wait for it
-  std::vector<ConfEntry> confHost;
-  size_t confCount = 0;
-  double confSig[4] = {0, 0, 0, 0};   // Max_PenaltySpan, MutationPenalty, granularity, total size
-  bool confDirty = true;
+  CollapseBuffers collapseBufs;
+  // confidence table (IndexView::conf): the host's table, its copy in HBM, the miss list the kernels write, the reads that wait for a value
+  ConfTable conf;
+  static constexpr size_t kConfMissCap = 1 << 16;
   DevBuf<ConfEntry> dConf;
   DevBuf<uint8_t> dConfMiss;
   DevBuf<int64_t> dListConf[2];
-  std::vector<int32_t> residentLens, stagedLens;  // distinct total query lengths of the batch (the table is seeded for them)
-  int64_t residentNq = -1;   // batch kept in HBM by xm_batch_upload
+  // the batch the align calls work on (xm_batch_upload, xm_batch_commit), and the one xm_batch_stage copies in on its own stream meanwhile
+  DeviceBatch resident, staged;
   int64_t residentGen = 0, lastAlignedGen = -1;  // which resident batch the streams of the last align call belong to
   int64_t lastAlignedNq = -1;  // queries whose result streams (dFinalInts / dFinalDbls / dFinalIntOff) are still in HBM from the last align call (xm_pileup_add_last)
-  int residentMaxLen = 0;    // longest mate of that batch
-  double residentH2dMs = 0;
-  // second set of batch buffers: xm_batch_stage copies the next batch on its own stream while xm_align_resident works on the resident one
   std::mutex stageMu;
   hipStream_t copyStream = nullptr;
   hipEvent_t cev0 = nullptr, cev1 = nullptr;
-  DevBuf<uint8_t> sCodes;
-  DevBuf<int32_t> sMateCount, sMateLength;
-  DevBuf<int64_t> sMateOffset;
-  DevBuf<double> sExpected, sDeviation;
-  int64_t stagedNq = -1;
-  int stagedMaxLen = 0;
-  double stagedH2dMs = 0;
-
-  static constexpr size_t kConfMissCap = 1 << 16;
-  std::unordered_set<int32_t> confSeeded;  // query lengths whose whole-substitution sums are in the table
-  double confSeedRate = -1;               // (... for this MaxErrorRate)
-  bool confInsert(double penalty, int32_t qlen, const Params& p) {  // -> false: already there
-    uint64_t bits;
-    memcpy(&bits, &penalty, 8);
-    if ((confCount + 1) * 2 > confHost.size()) {  // grow (and rehash) at half load
-      std::vector<ConfEntry> old;
-      old.swap(confHost);
-      confHost.assign(old.empty() ? (size_t)1 << 14 : old.size() * 2, ConfEntry{0, 0, 0, 0.0});
-      for (const ConfEntry& e : old) if (e.used) { uint32_t h = confHash(e.penaltyBits, e.queryLength) & (uint32_t)(confHost.size() - 1); while (confHost[h].used) h = (h + 1) & (uint32_t)(confHost.size() - 1); confHost[h] = e; }
-    }
-    const uint32_t mask = (uint32_t)(confHost.size() - 1);
-    uint32_t h = confHash(bits, qlen) & mask;
-    while (confHost[h].used) {
-      if (confHost[h].penaltyBits == bits && confHost[h].queryLength == qlen) return false;
-      h = (h + 1) & mask;
-    }
-    const HostIndex& hst = hs->host;
-    confHost[h] = ConfEntry{bits, qlen, 1, confidenceLengthOnHost(penalty, qlen, p.Max_PenaltySpan, p.MutationPenalty, hst.dupGranularity(), hst.totalForwardSize * 2)};
-    confCount++;
-    confDirty = true;
-    return true;
-  }
-  // the table for this call: reset when the settings it depends on changed; seeded with what the batch's reads will ask for in the common case
-  // (an alignment without indels costs a whole number of substitutions: the sums 0, m, m + m, ... up to the allowed penalty), whatever else
-  // comes up (ambiguity and unaligned penalties, spacing penalties of pairs, other sums) is added after the pass that missed it
-  void confPrepare(const Params& p, hipStream_t s) {
-    const HostIndex& hst = hs->host;
-    const double sig[4] = {p.Max_PenaltySpan, p.MutationPenalty, hst.dupGranularity(), (double)(hst.totalForwardSize * 2)};
-    if (memcmp(sig, confSig, sizeof(sig)) != 0) { memcpy(confSig, sig, sizeof(sig)); confHost.clear(); confCount = 0; confDirty = true; confSeeded.clear(); }
-    if (confSeedRate != p.MaxErrorRate) { confSeedRate = p.MaxErrorRate; confSeeded.clear(); }
-    // a length is seeded once; a call seeds a bounded number of entries (fixed-length batches: a few dozen; a batch of unsplit long reads has thousands
-    // of distinct lengths with thousands of sums each, of which the reads ask for a few: what is not seeded comes in through the miss path)
-    long long budget = envKnob("XM_CONF_SEED", 1 << 18, 0, 1 << 26);  // (0: nothing seeded, every key through the miss path - the tests run that)
-    for (int32_t len : residentLens) {
-      if (confSeeded.count(len)) continue;
-      const double limit = (double)len * p.MaxErrorRate + p.Max_PenaltySpan + p.MutationPenalty;
-      const double steps = p.MutationPenalty > 0 ? std::min(4096.0, std::floor(limit / p.MutationPenalty) + 2) : 1;
-      if (steps > (double)budget) continue;
-      budget -= (long long)steps;
-      double pen = 0;
-      for (int j = 0; j < (int)steps && pen <= limit; j++) { confInsert(pen, len, p); pen += p.MutationPenalty; }
-      confSeeded.insert(len);
-    }
-    confUpload(s);
-    if (!dConfMiss.p) {
-      dConfMiss.ensure(sizeof(ConfMiss) + kConfMissCap * sizeof(ConfMissKey));
-      ConfMiss hdr;
-      memset(&hdr, 0, sizeof(hdr));
-      hdr.cap = kConfMissCap;
-      HIP_CHECK(hipMemcpyAsync(dConfMiss.p, &hdr, offsetof(ConfMiss, keys), hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-    }
-  }
-  void confUpload(hipStream_t s) {
-    if (!confDirty) return;
-    if (confHost.empty()) confHost.assign((size_t)1 << 14, ConfEntry{0, 0, 0, 0.0});
-    HIP_CHECK(hipStreamSynchronize(s));   // (no kernel of this context reads the old copy any more)
-    dConf.ensure(confHost.size());
-    HIP_CHECK(hipMemcpy(dConf.p, confHost.data(), confHost.size() * sizeof(ConfEntry), hipMemcpyHostToDevice));
-    confDirty = false;
-  }
-  // after a pass with XM_ST_NEED_CONF reads: the keys they left, evaluated and added; -> number of new entries
-  size_t confAbsorbMisses(const Params& p, hipStream_t s) {
-    ConfMiss hdr;
-    HIP_CHECK(hipMemcpyAsync(&hdr, dConfMiss.p, offsetof(ConfMiss, keys), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    const size_t n = (size_t)std::min<unsigned long long>(hdr.n, hdr.cap);
-    std::vector<ConfMissKey> keys(n);
-    if (n) HIP_CHECK(hipMemcpy(keys.data(), dConfMiss.p + offsetof(ConfMiss, keys), n * sizeof(ConfMissKey), hipMemcpyDeviceToHost));
-    const unsigned long long zero = 0;
-    HIP_CHECK(hipMemcpy(dConfMiss.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
-    size_t added = 0;
-    for (const ConfMissKey& k : keys) { double pen; memcpy(&pen, &k.penaltyBits, 8); if (confInsert(pen, k.queryLength, p)) added++; }
-    confUpload(s);
-    return added;
-  }
 
   void initContext() {  // stream and events of this context (the device tables exist)
     dt->contexts.fetch_add(1);
@@ -941,17 +493,6 @@ struct xm_index {
     if (stream) (void)hipStreamDestroy(stream);
     if (copyStream) (void)hipStreamDestroy(copyStream);
   }  // (every DevBuf member releases its memory itself; the shared tables go with their last context)
-};
-
-struct xm_pileup {
-  xm_index* index = nullptr;            // the context whose batches are added (xm_pileup_add_last needs it alive; read / events / free do not)
-  std::shared_ptr<HostShare> hs;
-  int device = 0;
-  DevBuf<unsigned long long> dDepth, dAlt, dEventCount, dMid;
-  double endFraction = 0;
-  DevBuf<long long> dEvents;
-  long long total = 0, queriesAdded = 0;
-  std::vector<long long> events;  // (host) 8 per event, in the order of the calls
 };
 
 // ---------------------------------------------------------------- the align call: its state and its steps, in the order alignResidentLocked runs them
@@ -999,13 +540,45 @@ static float timedLaunch(AlignCall& c, int nKernels, int slot, Launch&& launch, 
   return ms;
 }
 
+// the confidence table's copy in HBM brought up to the host's
+static void uploadConfTable(xm_index* idx, hipStream_t s) {
+  if (!idx->conf.dirty()) return;
+  HIP_CHECK(hipStreamSynchronize(s));   // (no kernel of this context reads the old copy any more)
+  idx->dConf.ensure(idx->conf.size());
+  HIP_CHECK(hipMemcpy(idx->dConf.p, idx->conf.data(), idx->conf.size() * sizeof(ConfEntry), hipMemcpyHostToDevice));
+  idx->conf.markUploaded();
+}
+// after a pass with XM_ST_NEED_CONF reads: the keys they left in the miss list, evaluated and added
+static void absorbConfMisses(xm_index* idx, hipStream_t s) {
+  ConfMiss hdr;
+  HIP_CHECK(hipMemcpyAsync(&hdr, idx->dConfMiss.p, offsetof(ConfMiss, keys), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  const size_t n = (size_t)std::min<unsigned long long>(hdr.n, hdr.cap);
+  std::vector<ConfMissKey> keys(n);
+  if (n) HIP_CHECK(hipMemcpy(keys.data(), idx->dConfMiss.p + offsetof(ConfMiss, keys), n * sizeof(ConfMissKey), hipMemcpyDeviceToHost));
+  const unsigned long long zero = 0;
+  HIP_CHECK(hipMemcpy(idx->dConfMiss.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
+  for (const ConfMissKey& k : keys) { double pen; memcpy(&pen, &k.penaltyBits, 8); idx->conf.insert(pen, k.queryLength); }
+  uploadConfTable(idx, s);
+}
+
 // buffers that follow the batch's size, the confidence table of these parameters, cleared counters and control words
 static void prepareCall(AlignCall& c) {
   xm_index* idx = c.idx;
   const int64_t nq = c.nq;
   hipStream_t s = c.s;
-  idx->confPrepare(c.params, s);
-  c.view.conf = idx->dConf.p; c.view.confMask = (uint32_t)(idx->confHost.size() - 1); c.view.confMiss = (ConfMiss*)idx->dConfMiss.p;
+  // (XM_CONF_SEED = 0: nothing seeded, every key through the miss path - the tests run that)
+  idx->conf.prepare(c.params, idx->resident.lens, idx->host().dupGranularity(), idx->host().totalForwardSize * 2, envKnob("XM_CONF_SEED", 1 << 18, 0, 1 << 26));
+  uploadConfTable(idx, s);
+  if (!idx->dConfMiss.p) {
+    idx->dConfMiss.ensure(sizeof(ConfMiss) + xm_index::kConfMissCap * sizeof(ConfMissKey));
+    ConfMiss hdr;
+    memset(&hdr, 0, sizeof(hdr));
+    hdr.cap = xm_index::kConfMissCap;
+    HIP_CHECK(hipMemcpyAsync(idx->dConfMiss.p, &hdr, offsetof(ConfMiss, keys), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  c.view.conf = idx->dConf.p; c.view.confMask = idx->conf.mask(); c.view.confMiss = (ConfMiss*)idx->dConfMiss.p;
   idx->dListConf[0].ensure((size_t)nq); idx->dListConf[1].ensure((size_t)nq);
   idx->dStatus.ensure((size_t)nq); idx->dIntOff.ensure((size_t)nq); idx->dDblOff.ensure((size_t)nq); idx->dIntLen.ensure((size_t)nq); idx->dDblLen.ensure((size_t)nq);
   idx->dCursors.ensure(4); idx->dCounters.ensure(1); idx->dCtl.ensure(1);
@@ -1038,22 +611,22 @@ static void collapseBuildList(AlignCall& c) {
   size_t cap = 64;
   while (cap < (size_t)nq * 2) cap <<= 1;
   const long long nBlocks = (nq + XM_COLLAPSE_PER_BLOCK - 1) / XM_COLLAPSE_PER_BLOCK;
-  idx->dCollapseKeys.ensure(cap); idx->dCollapseReps.ensure(cap); idx->dCollapseTotal.ensure(1);
-  idx->dRepOf.ensure((size_t)nq); idx->dRepList.ensure((size_t)nq); idx->dCollapseBlocks.ensure((size_t)nBlocks);
-  HIP_CHECK(hipMemsetAsync(idx->dCollapseKeys.p, 0, sizeof(unsigned long long) * cap, s));
-  HIP_CHECK(hipMemsetAsync(idx->dCollapseReps.p, 0xFF, sizeof(unsigned long long) * cap, s));
+  idx->collapseBufs.dCollapseKeys.ensure(cap); idx->collapseBufs.dCollapseReps.ensure(cap); idx->collapseBufs.dCollapseTotal.ensure(1);
+  idx->collapseBufs.dRepOf.ensure((size_t)nq); idx->collapseBufs.dRepList.ensure((size_t)nq); idx->collapseBufs.dCollapseBlocks.ensure((size_t)nBlocks);
+  HIP_CHECK(hipMemsetAsync(idx->collapseBufs.dCollapseKeys.p, 0, sizeof(unsigned long long) * cap, s));
+  HIP_CHECK(hipMemsetAsync(idx->collapseBufs.dCollapseReps.p, 0xFF, sizeof(unsigned long long) * cap, s));
   const unsigned waveGrid = (unsigned)((nq + 3) / 4);  // one wave per query, four per block
   unsigned long long nReps = 0;
   timedLaunch(c, 5, -1, [&] {
-    hipLaunchKernelGGL(xm_collapse_fingerprint_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, idx->dCollapseKeys.p, idx->dCollapseReps.p, (unsigned long long)(cap - 1), idx->dRepOf.p);
-    hipLaunchKernelGGL(xm_collapse_verify_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, (const unsigned long long*)idx->dCollapseReps.p, idx->dRepOf.p);
-    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, idx->dCollapseBlocks.p);
-    hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->dCollapseBlocks.p, idx->dCollapseTotal.p);
-    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->dRepOf.p, (const long long*)idx->dCollapseBlocks.p, idx->dRepList.p);
-  }, [&] { HIP_CHECK(hipMemcpyAsync(&nReps, idx->dCollapseTotal.p, sizeof(nReps), hipMemcpyDeviceToHost, s)); });
+    hipLaunchKernelGGL(xm_collapse_fingerprint_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, idx->collapseBufs.dCollapseKeys.p, idx->collapseBufs.dCollapseReps.p, (unsigned long long)(cap - 1), idx->collapseBufs.dRepOf.p);
+    hipLaunchKernelGGL(xm_collapse_verify_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, (const unsigned long long*)idx->collapseBufs.dCollapseReps.p, idx->collapseBufs.dRepOf.p);
+    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, idx->collapseBufs.dCollapseBlocks.p);
+    hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dCollapseTotal.p);
+    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const long long*)idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dRepList.p);
+  }, [&] { HIP_CHECK(hipMemcpyAsync(&nReps, idx->collapseBufs.dCollapseTotal.p, sizeof(nReps), hipMemcpyDeviceToHost, s)); });
   if (nReps < 1 || (long long)nReps > nq) throw std::runtime_error("internal error: collapsing found " + std::to_string(nReps) + " distinct queries in a batch of " + std::to_string(nq));
   c.copies = nq - (int64_t)nReps;
-  c.todo = idx->dRepList.p;
+  c.todo = idx->collapseBufs.dRepList.p;
   c.nTodo = (long long)nReps;
 }
 
@@ -1061,7 +634,7 @@ static void collapseBuildList(AlignCall& c) {
 static void collapseFanOut(AlignCall& c) {
   xm_index* idx = c.idx;
   timedLaunch(c, 1, -1, [&] {
-    hipLaunchKernelGGL(xm_collapse_fanout_kernel, dim3((unsigned)((c.nq + 255) / 256)), dim3(256), 0, c.s, (long long)c.nq, (const int64_t*)idx->dRepOf.p, idx->dIntOff.p, idx->dDblOff.p,
+    hipLaunchKernelGGL(xm_collapse_fanout_kernel, dim3((unsigned)((c.nq + 255) / 256)), dim3(256), 0, c.s, (long long)c.nq, (const int64_t*)idx->collapseBufs.dRepOf.p, idx->dIntOff.p, idx->dDblOff.p,
                        idx->dIntLen.p, idx->dDblLen.p);
   }, [] {});
 }
@@ -1077,10 +650,10 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
   xm_index* idx = c.idx;
   const int64_t nq = c.nq;
   hipStream_t s = c.s;
-  idx->dListWaveHeavy.ensure((size_t)nq); idx->dListWaveNext.ensure((size_t)nq); idx->dListFallback.ensure((size_t)nq); idx->dWaveCtl.ensure(1);
-  idx->dWaveSlotOf.ensure((size_t)nq);
+  idx->wave.dListWaveHeavy.ensure((size_t)nq); idx->wave.dListWaveNext.ensure((size_t)nq); idx->wave.dListFallback.ensure((size_t)nq); idx->wave.dWaveCtl.ensure(1);
+  idx->wave.dWaveSlotOf.ensure((size_t)nq);
   WaveCtl wctl{0, 0, 0, ~0ull};
-  HIP_CHECK(hipMemcpyAsync(idx->dWaveCtl.p, &wctl, sizeof(wctl), hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(idx->wave.dWaveCtl.p, &wctl, sizeof(wctl), hipMemcpyHostToDevice, s));
   const OutView ov = c.outView();
   const int lastTier = (int)envKnob("XM_WAVE_TIERS", 3, 1, 3) - 1;  // (experiment knob: 1 = light tier only, 2 = light + chain tier)
   int sWaves = 4, sLds = 1, sPerSimd = 4, memoBytes = 1, nodesPerWave = 1;
@@ -1089,7 +662,7 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
   // one launch of a tier over `list` (null = all reads) + classification; returns the counts of the lists it filled
   auto launchTier = [&](int tier, const int64_t* list, long long n, int64_t* listNext, int32_t* slotOfOut, int64_t* listSearch) {
     WaveLaunch wl;
-    wl.config = tier == 0 ? (idx->residentAnyPaired ? 1 : 0) : (tier == 1 ? (idx->residentAnyPaired ? 3 : 2) : 4);
+    wl.config = tier == 0 ? (idx->resident.anyPaired ? 1 : 0) : (tier == 1 ? (idx->resident.anyPaired ? 3 : 2) : 4);
     int wavesPerBlock = 1, ldsPerBlock = 1, wavesPerSimd = 1;
     xmWaveGeometry(wl.config, &wavesPerBlock, &ldsPerBlock, &wavesPerSimd);
     long long blocksPerCU = std::min<long long>((160 * 1024) / ldsPerBlock, (long long)(wavesPerSimd * 4) / wavesPerBlock);
@@ -1099,21 +672,21 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
     if (blocks < 1) blocks = 1;
     wl.grid = (int)blocks; wl.block = wavesPerBlock * 64;
     wl.ix = c.view; wl.params = c.params; wl.batch = c.bv; wl.todo = list; wl.nTodo = n; wl.out = ov; wl.nextItem = idx->dCursors.p + 2; wl.counters = idx->dCounters.p;
-    wl.memoBase = (WMemo*)idx->dWaveMemo.p; wl.slotOf = idx->dWaveSlotOf.p;
+    wl.memoBase = (WMemo*)idx->wave.dWaveMemo.p; wl.slotOf = idx->wave.dWaveSlotOf.p;
     wl.waveNodes = nullptr;
     if (tier >= 1 && envInt("XM_WAVE_INLINE_SEARCH", 1) != 0) {  // (0: every search through the memo and the search kernel)
-      idx->dWaveNodes2.ensure(((size_t)blocks * wavesPerBlock * (size_t)xmWaveInlineNodeBytes() + sizeof(PNode) - 1) / sizeof(PNode));
-      wl.waveNodes = idx->dWaveNodes2.p;
+      idx->wave.dWaveNodes2.ensure(((size_t)blocks * wavesPerBlock * (size_t)xmWaveInlineNodeBytes() + sizeof(PNode) - 1) / sizeof(PNode));
+      wl.waveNodes = idx->wave.dWaveNodes2.p;
     }
     HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
-    HIP_CHECK(hipMemsetAsync(idx->dWaveCtl.p, 0, 2 * sizeof(unsigned long long), s));  // nNext, nSearch
+    HIP_CHECK(hipMemsetAsync(idx->wave.dWaveCtl.p, 0, 2 * sizeof(unsigned long long), s));  // nNext, nSearch
     const float ms = timedLaunch(c, 1, tier == 0 ? 12 : 13, [&] {  // kernel microseconds: light tier / chain tiers
       const int rc = xmWaveLaunch(wl, (void*)s);
       if (rc != 0) throw std::runtime_error(std::string("wave kernel launch: ") + hipGetErrorString((hipError_t)rc));
     }, [&] {  // (the classification is not part of the tier's time)
-      hipLaunchKernelGGL(xm_wave_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, list, n, idx->dStatus.p, listNext, slotOfOut, listSearch, idx->dListFallback.p, idx->dWaveCtl.p);
+      hipLaunchKernelGGL(xm_wave_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, list, n, idx->dStatus.p, listNext, slotOfOut, listSearch, idx->wave.dListFallback.p, idx->wave.dWaveCtl.p);
       HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipMemcpyAsync(&wctl, idx->dWaveCtl.p, sizeof(wctl), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(&wctl, idx->wave.dWaveCtl.p, sizeof(wctl), hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, s));
     });
     if (tracePasses) fprintf(stderr, "[xm] wave tier %d config %d: reads %lld, %d x %d threads: %.3f ms -> next tier %llu, searches %llu, lane-per-read %llu (so far)\n", tier, wl.config, n, wl.grid,
@@ -1130,9 +703,9 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
     long long blocks = std::min<long long>((long long)c.numCUs * std::min<long long>((160 * 1024) / sLds, (long long)(sPerSimd * 4) / sWaves), (n + sWaves - 1) / sWaves);
     if (blocks < 1) blocks = 1;
     sl.grid = (int)blocks; sl.block = sWaves * 64;
-    sl.ix = c.view; sl.params = c.params; sl.batch = c.bv; sl.list = list; sl.n = n; sl.memoBase = (WMemo*)idx->dWaveMemo.p; sl.slotOf = idx->dWaveSlotOf.p; sl.nextItem = idx->dCursors.p + 2;
-    idx->dWaveArenas.ensure((size_t)blocks * sWaves * (size_t)nodesPerWave);  // (node payloads: bytes per wave)
-    sl.waveNodes = idx->dWaveArenas.p; sl.counters = idx->dCounters.p;
+    sl.ix = c.view; sl.params = c.params; sl.batch = c.bv; sl.list = list; sl.n = n; sl.memoBase = (WMemo*)idx->wave.dWaveMemo.p; sl.slotOf = idx->wave.dWaveSlotOf.p; sl.nextItem = idx->dCursors.p + 2;
+    idx->wave.dWaveArenas.ensure((size_t)blocks * sWaves * (size_t)nodesPerWave);  // (node payloads: bytes per wave)
+    sl.waveNodes = idx->wave.dWaveArenas.p; sl.counters = idx->dCounters.p;
     HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
     const float ms = timedLaunch(c, 1, 14, [&] {  // search kernel microseconds
       const int rc = xmSearchLaunch(sl, (void*)s);
@@ -1141,31 +714,31 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
     if (tracePasses) fprintf(stderr, "[xm] search kernel: %lld searches, %d x %d threads: %.3f ms\n", n, sl.grid, sl.block, ms);
   };
   // light tier
-  launchTier(0, c.todo, c.nTodo, lastTier >= 1 ? idx->dListWaveHeavy.p : (int64_t*)nullptr, idx->dWaveSlotOf.p, nullptr);
+  launchTier(0, c.todo, c.nTodo, lastTier >= 1 ? idx->wave.dListWaveHeavy.p : (int64_t*)nullptr, idx->wave.dWaveSlotOf.p, nullptr);
   long long nChain = lastTier >= 1 ? (long long)wctl.nNext : 0;
   if (nChain > 0) {
-    idx->dWaveMemo.ensure((size_t)nChain * (size_t)memoBytes);
-    if (xmMemoInitLaunch((WMemo*)idx->dWaveMemo.p, nChain, (void*)s) != 0) throw std::runtime_error("memo init launch failed");
-    idx->dListWaveSearch[0].ensure((size_t)nChain); idx->dListWaveSearch[1].ensure((size_t)nChain);
+    idx->wave.dWaveMemo.ensure((size_t)nChain * (size_t)memoBytes);
+    if (xmMemoInitLaunch((WMemo*)idx->wave.dWaveMemo.p, nChain, (void*)s) != 0) throw std::runtime_error("memo init launch failed");
+    idx->wave.dListWaveSearch[0].ensure((size_t)nChain); idx->wave.dListWaveSearch[1].ensure((size_t)nChain);
     long long nBig = 0;  // reads for the chain tier with the largest capacities (dListWaveNext, filled behind what is already there)
     for (int tier = 1; tier <= 2 && tier <= lastTier; tier++) {
-      const int64_t* list = tier == 1 ? idx->dListWaveHeavy.p : idx->dListWaveNext.p;
+      const int64_t* list = tier == 1 ? idx->wave.dListWaveHeavy.p : idx->wave.dListWaveNext.p;
       long long n = tier == 1 ? nChain : nBig;
       int which = 0, rounds = 0;
       while (n > 0) {
         // (tier 1 appends its hand-overs to dListWaveNext behind those of its earlier rounds)
-        launchTier(tier, list, n, tier == 1 && lastTier >= 2 ? idx->dListWaveNext.p + nBig : (int64_t*)nullptr, nullptr, idx->dListWaveSearch[which].p);
+        launchTier(tier, list, n, tier == 1 && lastTier >= 2 ? idx->wave.dListWaveNext.p + nBig : (int64_t*)nullptr, nullptr, idx->wave.dListWaveSearch[which].p);
         if (tier == 1 && lastTier >= 2) nBig += (long long)wctl.nNext;
         const long long nSearch = (long long)wctl.nSearch;
         if (nSearch == 0) break;
         if (++rounds > 4 * 16) throw std::runtime_error("internal error: search rounds do not end");
-        launchSearches(idx->dListWaveSearch[which].p, nSearch);
-        list = idx->dListWaveSearch[which].p; n = nSearch;
+        launchSearches(idx->wave.dListWaveSearch[which].p, nSearch);
+        list = idx->wave.dListWaveSearch[which].p; n = nSearch;
         which ^= 1;
       }
     }
   }
-  c.todo = idx->dListFallback.p;
+  c.todo = idx->wave.dListFallback.p;
   c.nTodo = (long long)fallbackSoFar;
   HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
 }
@@ -1281,8 +854,8 @@ static void runLanePasses(AlignCall& c, const BatchPolicy& pol) {
         if (pol.k.profGappedOnly) HIP_CHECK(hipMemsetAsync((char*)idx->dCounters.p + offsetof(DevCounters, t), 0, sizeof(((DevCounters*)nullptr)->t), s));
         break;
       case PassKind::ConfRerun:
-        idx->confAbsorbMisses(c.params, s);
-        c.view.conf = idx->dConf.p; c.view.confMask = (uint32_t)(idx->confHost.size() - 1);
+        absorbConfMisses(idx, s);
+        c.view.conf = idx->dConf.p; c.view.confMask = idx->conf.mask();
         c.todo = idx->dListConf[np.list].p;
         HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nConf[np.clear], 0, sizeof(unsigned long long), s));
         c.rerun += c.nTodo;
@@ -1473,7 +1046,7 @@ int xm_context_set_collapse(xm_index* idx, int32_t enable) {
   if (!idx) return fail("xm_context_set_collapse: null argument");
   std::lock_guard<std::mutex> lock(idx->mu);
   idx->collapse = enable != 0;
-  if (!idx->collapse) { idx->dCollapseKeys.release(); idx->dCollapseReps.release(); idx->dCollapseTotal.release(); idx->dRepOf.release(); idx->dRepList.release(); idx->dCollapseBlocks.release(); }
+  if (!idx->collapse) idx->collapseBufs = CollapseBuffers();
   return 0;
 }
 
@@ -1672,34 +1245,15 @@ static int validateBatch(const xm_query_batch* b, bool* anyPaired = nullptr, std
 }
 
 static void uploadBatchLocked(xm_index* idx, const xm_query_batch* b) {
-  const int64_t nq = b->num_queries;
+  DeviceBatch& d = idx->resident;
   bool anyPaired = false;
-  const int maxLen = validateBatch(b, &anyPaired, &idx->residentLens);
-  idx->residentAnyPaired = anyPaired;
+  const int maxLen = validateBatch(b, &anyPaired, &d.lens);
+  d.anyPaired = anyPaired;
   idx->ensureTablesFor(maxLen);  // Readable_HashBlock_Database.getContainingMap growth, done before the launch
   HIP_CHECK(hipSetDevice(idx->device));
-  hipStream_t s = idx->stream;
-  idx->residentNq = -1;
-  if (nq > 0) {
-    hipEvent_t e0 = idx->ev0, e1 = idx->ev1;
-    HIP_CHECK(hipEventRecord(e0, s));
-    idx->dMateCount.ensure((size_t)nq); idx->dMateOffset.ensure((size_t)nq * 2); idx->dMateLength.ensure((size_t)nq * 2);
-    idx->dCodes.ensure((size_t)b->codes_length); idx->dExpected.ensure((size_t)nq); idx->dDeviation.ensure((size_t)nq);
-    HIP_CHECK(hipMemcpyAsync(idx->dMateCount.p, b->mate_count, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(idx->dMateOffset.p, b->mate_offset, sizeof(int64_t) * (size_t)nq * 2, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(idx->dMateLength.p, b->mate_length, sizeof(int32_t) * (size_t)nq * 2, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(idx->dCodes.p, b->codes, (size_t)b->codes_length, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(idx->dExpected.p, b->expected_inner, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(idx->dDeviation.p, b->deviation, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipEventRecord(e1, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    idx->residentH2dMs = ms;
-  }
-  idx->residentNq = nq;
+  d.copyIn(b, idx->stream, idx->ev0, idx->ev1);
   idx->residentGen++;
-  idx->residentMaxLen = maxLen;
+  d.maxLen = maxLen;
 }
 
 static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** out);
@@ -1719,34 +1273,15 @@ int xm_batch_stage(xm_index* idx, const xm_query_batch* b) {
   if (idx->hostOnly) return fail("xm_batch_stage: index was built with host_only=1");
   try {
     std::lock_guard<std::mutex> stageLock(idx->stageMu);
-    const int64_t nq = b->num_queries;
+    DeviceBatch& d = idx->staged;
     bool anyPaired = false;
-    const int maxLen = validateBatch(b, &anyPaired, &idx->stagedLens);
-    idx->stagedAnyPaired = anyPaired;
+    const int maxLen = validateBatch(b, &anyPaired, &d.lens);
+    d.anyPaired = anyPaired;
     idx->ensureTablesFor(maxLen);  // (tables that grow wait for the launches that read them: DeviceTables::rw)
     HIP_CHECK(hipSetDevice(idx->device));
     if (!idx->copyStream) { HIP_CHECK(hipStreamCreateWithFlags(&idx->copyStream, hipStreamNonBlocking)); HIP_CHECK(hipEventCreate(&idx->cev0)); HIP_CHECK(hipEventCreate(&idx->cev1)); }
-    hipStream_t s = idx->copyStream;
-    idx->stagedNq = -1;
-    idx->stagedH2dMs = 0;
-    if (nq > 0) {
-      HIP_CHECK(hipEventRecord(idx->cev0, s));
-      idx->sMateCount.ensure((size_t)nq); idx->sMateOffset.ensure((size_t)nq * 2); idx->sMateLength.ensure((size_t)nq * 2);
-      idx->sCodes.ensure((size_t)b->codes_length); idx->sExpected.ensure((size_t)nq); idx->sDeviation.ensure((size_t)nq);
-      HIP_CHECK(hipMemcpyAsync(idx->sMateCount.p, b->mate_count, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(idx->sMateOffset.p, b->mate_offset, sizeof(int64_t) * (size_t)nq * 2, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(idx->sMateLength.p, b->mate_length, sizeof(int32_t) * (size_t)nq * 2, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(idx->sCodes.p, b->codes, (size_t)b->codes_length, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(idx->sExpected.p, b->expected_inner, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(idx->sDeviation.p, b->deviation, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipEventRecord(idx->cev1, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, idx->cev0, idx->cev1));
-      idx->stagedH2dMs = ms;
-    }
-    idx->stagedNq = nq;
-    idx->stagedMaxLen = maxLen;
+    d.copyIn(b, idx->copyStream, idx->cev0, idx->cev1);
+    d.maxLen = maxLen;
     return 0;
   } catch (std::exception& e) { return fail(std::string("xm_batch_stage: ") + e.what()); }
 }
@@ -1755,14 +1290,11 @@ int xm_batch_commit(xm_index* idx) {
   if (!idx) return fail("xm_batch_commit: null argument");
   try {
     std::lock_guard<std::mutex> stageLock(idx->stageMu);
-    if (idx->stagedNq < 0) return fail("xm_batch_commit: no staged batch (call xm_batch_stage first)");
+    if (idx->staged.nq < 0) return fail("xm_batch_commit: no staged batch (call xm_batch_stage first)");
     std::lock_guard<std::mutex> lock(idx->mu);  // (waits for a running xm_align_resident)
-    idx->dMateCount.swapWith(idx->sMateCount); idx->dMateOffset.swapWith(idx->sMateOffset); idx->dMateLength.swapWith(idx->sMateLength);
-    idx->dCodes.swapWith(idx->sCodes); idx->dExpected.swapWith(idx->sExpected); idx->dDeviation.swapWith(idx->sDeviation);
+    std::swap(idx->resident, idx->staged);      // (the buffers of the batch before go on as the staging set)
+    idx->staged.nq = -1;
     idx->residentGen++;
-    idx->residentNq = idx->stagedNq; idx->residentMaxLen = idx->stagedMaxLen; idx->residentH2dMs = idx->stagedH2dMs; idx->residentAnyPaired = idx->stagedAnyPaired;
-    idx->residentLens.swap(idx->stagedLens);
-    idx->stagedNq = -1;
     return 0;
   } catch (std::exception& e) { return fail(std::string("xm_batch_commit: ") + e.what()); }
 }
@@ -1771,7 +1303,7 @@ int xm_align_resident(xm_index* idx, const xm_params* p, xm_result** out) {
   if (!idx || !p || !out) return fail("xm_align_resident: null argument");
   try {
     std::lock_guard<std::mutex> lock(idx->mu);
-    if (idx->residentNq < 0) throw std::runtime_error("no batch is resident (call xm_batch_upload first)");
+    if (idx->resident.nq < 0) throw std::runtime_error("no batch is resident (call xm_batch_upload first)");
     return alignResidentLocked(idx, p, out);
   } catch (std::exception& e) { return fail(std::string("xm_align_resident: ") + e.what()); }
 }
@@ -1783,7 +1315,7 @@ int xm_align_batch(xm_index* idx, const xm_params* p, const xm_query_batch* b, x
     std::lock_guard<std::mutex> lock(idx->mu);
     uploadBatchLocked(idx, b);
     int rc = alignResidentLocked(idx, p, out);
-    if (rc == 0) (*out)->h2d_ms = idx->residentH2dMs;
+    if (rc == 0) (*out)->h2d_ms = idx->resident.h2dMs;
     return rc;
   } catch (std::exception& e) {
     return fail(std::string("xm_align_batch: ") + e.what());
@@ -1794,7 +1326,7 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
   ResultBox* box = (ResultBox*)calloc(1, sizeof(ResultBox));
   xm_result* res = &box->pub;
   try {
-    const int64_t nq = idx->residentNq;
+    const int64_t nq = idx->resident.nq;
     HIP_CHECK(hipSetDevice(idx->device));
     // the shared tables stay as they are while this call's kernels read them (another context that grows them waits; so does this one's next growth)
     std::shared_lock<std::shared_mutex> tablesInUse(idx->dt->rw);
@@ -1811,10 +1343,10 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
     c.idx = idx; c.box = box; c.res = res; c.nq = nq; c.s = idx->stream; c.numCUs = idx->dt->numCUs;
     c.view = idx->dt->view;
     c.params = paramsFromC(*p);
-    c.bv = BatchView{nq, idx->dMateCount.p, idx->dMateOffset.p, idx->dMateLength.p, idx->dCodes.p, idx->dExpected.p, idx->dDeviation.p};
+    c.bv = idx->resident.view();
     prepareCall(c);
     if (idx->collapse) collapseBuildList(c);
-    const BatchFacts facts{idx->residentMaxLen, idx->residentAnyPaired, idx->dt->contexts.load(), idx->scratchBytes};
+    const BatchFacts facts{idx->resident.maxLen, idx->resident.anyPaired, idx->dt->contexts.load(), idx->scratchBytes};
     const BatchPolicy pol = makePolicy(facts, readPassKnobs(facts));
     idx->dOutInts.ensure((size_t)nq * 40 + 4096); idx->dOutDbls.ensure((size_t)nq * 12 + 4096);
     c.intCap = idx->dOutInts.n; c.dblCap = idx->dOutDbls.n;
@@ -1822,7 +1354,7 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
       idx->dRegionOf.ensure((size_t)nq);
       HIP_CHECK(hipMemsetAsync(idx->dRegionOf.p, 0xFF, sizeof(int32_t) * (size_t)nq, c.s));
     }
-    if (pol.k.waveForm && idx->residentMaxLen <= 256) runWaveForm(c, pol.k.tracePasses);
+    if (pol.k.waveForm && idx->resident.maxLen <= 256) runWaveForm(c, pol.k.tracePasses);
     runLanePasses(c, pol);
     if (c.copies > 0) collapseFanOut(c);
     finishStreams(c);
@@ -1834,297 +1366,7 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
   }
 }
 
-int xm_seed_probe_packed(xm_index* idx, int64_t n, const int32_t* usedLength, const int32_t* keys, int32_t maxPerProbe, int32_t* counts, int64_t* outPositions, double* kernelMs) {
-  if (!idx || idx->hostOnly) return fail("xm_seed_probe_packed: needs a device-resident index");
-  if (maxPerProbe < 0 || maxPerProbe > 15) return fail("xm_seed_probe_packed: max_per_probe must be 0 ... 15");
-  try {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    HIP_CHECK(hipSetDevice(idx->device));
-    hipStream_t s = idx->stream;
-    DevBuf<int32_t> dUsed, dKeys, dCounts;
-    DevBuf<int64_t> dPos;
-    struct Release { DevBuf<int32_t>&a, &b, &c; DevBuf<int64_t>& d; ~Release() { a.release(); b.release(); c.release(); d.release(); } } releaseAll{dUsed, dKeys, dCounts, dPos};
-    dUsed.ensure((size_t)n); dKeys.ensure((size_t)n); dCounts.ensure((size_t)n); dPos.ensure((size_t)n * (size_t)(maxPerProbe > 0 ? maxPerProbe : 1));
-    HIP_CHECK(hipMemcpyAsync(dUsed.p, usedLength, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(dKeys.p, keys, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-    int block = 256;
-    int grid = (int)((n + block - 1) / block);
-    HIP_CHECK(hipEventRecord(idx->ev0, s));
-    std::shared_lock<std::shared_mutex> tablesInUse(idx->dt->rw);
-    IndexView view = idx->dt->view;
-    if (envInt("XM_PROBE_NO_LINES", 0) != 0) { view.lines32 = nullptr; view.lines64 = nullptr; }  // measurement: the CSR probe (two dependent accesses) on the same index
-    const unsigned batched = (unsigned)((n + (long long)block * XM_PROBES_PER_LANE - 1) / ((long long)block * XM_PROBES_PER_LANE));
-    if (n > 0 && view.lines64) hipLaunchKernelGGL((xm_seed_probe_lines_kernel<true>), dim3(batched), dim3(block), 0, s, view, (long long)n, dUsed.p, dKeys.p, (int)maxPerProbe, dCounts.p, dPos.p);
-    else if (n > 0 && view.lines32) hipLaunchKernelGGL((xm_seed_probe_lines_kernel<false>), dim3(batched), dim3(block), 0, s, view, (long long)n, dUsed.p, dKeys.p, (int)maxPerProbe, dCounts.p, dPos.p);
-    else if (n > 0) hipLaunchKernelGGL(xm_seed_probe_kernel, dim3(grid), dim3(block), 0, s, view, (long long)n, dUsed.p, dKeys.p, (int)maxPerProbe, dCounts.p, dPos.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(idx->ev1, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, idx->ev0, idx->ev1));
-    if (kernelMs) *kernelMs = ms;
-    HIP_CHECK(hipMemcpy(counts, dCounts.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
-    if (outPositions && maxPerProbe > 0) HIP_CHECK(hipMemcpy(outPositions, dPos.p, sizeof(int64_t) * (size_t)n * (size_t)maxPerProbe, hipMemcpyDeviceToHost));
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_seed_probe_packed: ") + e.what()); }
-}
-
-int xm_measure_random_gather(int device, int64_t table_bytes, int64_t accesses, double* kernel_ms) {
-  try {
-    HIP_CHECK(hipSetDevice(device));
-    if (table_bytes < 4096 || accesses < 1) return fail("xm_measure_random_gather: bad arguments");
-    DevBuf<uint4> table;
-    DevBuf<unsigned int> sink;
-    struct Release { DevBuf<uint4>& a; DevBuf<unsigned int>& b; ~Release() { a.release(); b.release(); } } releaseAll{table, sink};
-    const size_t nSectors = (size_t)table_bytes / 64;
-    table.ensure(nSectors * 4);
-    sink.ensure(1);
-    HIP_CHECK(hipMemset(table.p, 0, nSectors * 64));
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
-    const int perThread = 4;
-    const long long threads = (accesses + perThread - 1) / perThread;
-    float best = 0;
-    for (int rep = 0; rep < 3; rep++) {  // first repetition warms up
-      HIP_CHECK(hipEventRecord(e0, 0));
-      hipLaunchKernelGGL(xm_random_gather_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, 0, table.p, (unsigned long long)nSectors, (long long)accesses, perThread,
-                         0x5EED0000ull + rep, sink.p);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(e1, 0));
-      HIP_CHECK(hipEventSynchronize(e1));
-      float ms = 0;
-      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-      if (rep > 0 && (best == 0 || ms < best)) best = ms;
-    }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (kernel_ms) *kernel_ms = best;
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_measure_random_gather: ") + e.what()); }
-}
-
-int xm_pileup_new(xm_index* idx, xm_pileup** out) {
-  if (!idx || !out) return fail("xm_pileup_new: null argument");
-  if (idx->hostOnly) return fail("xm_pileup_new: index was built with host_only=1");
-  xm_pileup* p = nullptr;
-  try {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    HIP_CHECK(hipSetDevice(idx->device));
-    p = new xm_pileup();
-    p->index = idx;
-    p->hs = idx->hs;
-    p->device = idx->device;
-    p->total = idx->host().totalForwardSize;
-    p->dDepth.ensure((size_t)p->total); p->dAlt.ensure((size_t)p->total * 4); p->dEventCount.ensure(1);
-    HIP_CHECK(hipMemset(p->dDepth.p, 0, sizeof(unsigned long long) * (size_t)p->total));
-    HIP_CHECK(hipMemset(p->dAlt.p, 0, sizeof(unsigned long long) * (size_t)p->total * 4));
-    *out = p;
-    return 0;
-  } catch (std::exception& e) {
-    if (p) { p->dDepth.release(); p->dAlt.release(); p->dEventCount.release(); delete p; }
-    return fail(std::string("xm_pileup_new: ") + e.what());
-  }
-}
-
-int xm_pileup_set_query_ends(xm_pileup* p, double fraction) {
-  if (!p) return fail("xm_pileup_set_query_ends: null argument");
-  if (!(fraction >= 0 && fraction < 1)) return fail("--distinguish-query-ends must be >= 0 and < 1");  // Mapper.java:424-425
-  if (p->queriesAdded > 0) return fail("xm_pileup_set_query_ends: alignments were already added");
-  try {
-    HIP_CHECK(hipSetDevice(p->device));
-    p->endFraction = fraction;
-    if (fraction > 0) {
-      p->dMid.ensure((size_t)p->total);
-      HIP_CHECK(hipMemset(p->dMid.p, 0, sizeof(unsigned long long) * (size_t)p->total));
-    }
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_pileup_set_query_ends: ") + e.what()); }
-}
-
-int xm_pileup_read_middle(xm_pileup* p, int32_t contig, int64_t first, int64_t n, uint64_t* depth) {
-  if (!p || !p->hs || !depth) return fail("xm_pileup_read_middle: null argument");
-  try {
-    const HostIndex& host = p->hs->host;
-    if (contig < 0 || contig >= host.numContigs() || first < 0 || n < 0 || first + n > host.contigLen[(size_t)contig]) throw std::runtime_error("range outside of the contig");
-    HIP_CHECK(hipSetDevice(p->device));
-    HIP_CHECK(hipDeviceSynchronize());
-    const size_t at = (size_t)host.contigStart[(size_t)contig] + (size_t)first;
-    // (no query-end fraction: every base is a middle base)
-    if (n) HIP_CHECK(hipMemcpy(depth, (p->endFraction > 0 ? p->dMid.p : p->dDepth.p) + at, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_pileup_read_middle: ") + e.what()); }
-}
-
-int xm_pileup_add_last(xm_pileup* p, int64_t* num_events) {
-  if (!p || !p->index) return fail("xm_pileup_add_last: null argument");
-  xm_index* idx = p->index;
-  try {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    if (idx->lastAlignedNq < 0 || idx->lastAlignedNq != idx->residentNq || idx->lastAlignedGen != idx->residentGen)
-      throw std::runtime_error("the batch of the last align call is no longer resident (call xm_pileup_add_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
-    HIP_CHECK(hipSetDevice(idx->device));
-    hipStream_t s = idx->stream;
-    const int64_t nq = idx->lastAlignedNq;
-    if (nq > 0) {
-      const unsigned long long cap = (unsigned long long)idx->dFinalInts.n / 4 + 1;  // (an event is a block: at least four ints of the stream)
-      p->dEvents.ensure((size_t)cap * 8);
-      HIP_CHECK(hipMemsetAsync(p->dEventCount.p, 0, sizeof(unsigned long long), s));
-      BatchView bv{nq, idx->dMateCount.p, idx->dMateOffset.p, idx->dMateLength.p, idx->dCodes.p, idx->dExpected.p, idx->dDeviation.p};
-      PileupView pv{p->dDepth.p, p->dAlt.p, p->total, p->dEvents.p, cap, p->dEventCount.p, p->queriesAdded, p->endFraction > 0 ? p->dMid.p : nullptr, p->endFraction};
-      std::shared_lock<std::shared_mutex> tablesInUse(idx->dt->rw);
-      hipLaunchKernelGGL(xm_pileup_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, idx->dt->view, bv, (const int32_t*)idx->dFinalInts.p, (const int64_t*)idx->dFinalIntOff.p, pv);
-      HIP_CHECK(hipGetLastError());
-      unsigned long long n = 0;
-      HIP_CHECK(hipMemcpyAsync(&n, p->dEventCount.p, sizeof(n), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      if (n > cap) throw std::runtime_error("internal error: more indel events than blocks");
-      const size_t at = p->events.size();
-      p->events.resize(at + (size_t)n * 8);
-      if (n) HIP_CHECK(hipMemcpy(p->events.data() + at, p->dEvents.p, sizeof(long long) * (size_t)n * 8, hipMemcpyDeviceToHost));
-      // the order of the atomic appends is not fixed: events of a call are put in (query, position) order
-      std::vector<std::array<long long, 8>> ev((size_t)n);
-      for (size_t i = 0; i < (size_t)n; i++) for (int k = 0; k < 8; k++) ev[i][(size_t)k] = p->events[at + i * 8 + (size_t)k];
-      std::sort(ev.begin(), ev.end(), [](const std::array<long long, 8>& a, const std::array<long long, 8>& b) {
-        if (a[4] != b[4]) return a[4] < b[4];
-        if (a[0] != b[0]) return a[0] < b[0];
-        if (a[1] != b[1]) return a[1] < b[1];
-        if (a[5] != b[5]) return a[5] < b[5];
-        return a[6] < b[6];
-      });
-      for (size_t i = 0; i < (size_t)n; i++) for (int k = 0; k < 8; k++) p->events[at + i * 8 + (size_t)k] = ev[i][(size_t)k];
-    }
-    p->queriesAdded += nq;
-    if (num_events) *num_events = (int64_t)(p->events.size() / 8);
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_pileup_add_last: ") + e.what()); }
-}
-
-int xm_pileup_read(xm_pileup* p, int32_t contig, int64_t first, int64_t n, uint64_t* depth, uint64_t* alt) {
-  if (!p || !p->hs || !depth || !alt) return fail("xm_pileup_read: null argument");
-  try {
-    const HostIndex& host = p->hs->host;  // (the pile-up shares the reference with its index: it outlives the context it was made from)
-    if (contig < 0 || contig >= host.numContigs() || first < 0 || n < 0 || first + n > host.contigLen[(size_t)contig]) throw std::runtime_error("range outside of the contig");
-    HIP_CHECK(hipSetDevice(p->device));
-    HIP_CHECK(hipDeviceSynchronize());  // (adds of a context's stream that may still be running)
-    const size_t at = (size_t)host.contigStart[(size_t)contig] + (size_t)first;
-    if (n) {
-      HIP_CHECK(hipMemcpy(depth, p->dDepth.p + at, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
-      for (int b = 0; b < 4; b++) HIP_CHECK(hipMemcpy(alt + (size_t)b * (size_t)n, p->dAlt.p + (size_t)b * (size_t)p->total + at, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
-    }
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_pileup_read: ") + e.what()); }
-}
-
-int64_t xm_pileup_events(xm_pileup* p, int64_t first, int64_t n, int64_t* out) {
-  if (!p || (n > 0 && !out)) return -1;
-  const int64_t have = (int64_t)(p->events.size() / 8);
-  if (first < 0 || first > have) return -1;
-  const int64_t m = std::min<int64_t>(n, have - first);
-  if (m > 0) memcpy(out, p->events.data() + (size_t)first * 8, sizeof(int64_t) * (size_t)m * 8);
-  return m;
-}
-
-void xm_pileup_free(xm_pileup* p) {
-  if (!p) return;
-  (void)hipSetDevice(p->device);
-  p->dDepth.release(); p->dAlt.release(); p->dEventCount.release(); p->dEvents.release(); p->dMid.release();
-  delete p;
-}
-
-// Test-only: what the rejection filter did in this thread's last xm_test_local_align call (searches taken, searches rejected, cells computed).
-static thread_local int64_t g_testBound[3] = {0, 0, 0};
-void xm_test_bound_counters(int64_t* out3) { for (int i = 0; i < 3; i++) out3[i] = g_testBound[i]; }
-
-// Test-only entry (tests/test_gpu_bound.py): the rejection filter alone on one problem (xm_test_bound_kernel).  out3: taken, rejected, cells computed.
-int xm_test_bound(int32_t device, const xm_params* p, const uint8_t* query, int32_t query_length, int32_t query_rc, int32_t start_a, int32_t end_a, const uint8_t* reference, int32_t reference_length,
-                  int32_t start_b, int32_t end_b, int32_t predicted_best_offset, int32_t pair, int64_t* out3) {
-  if (!p || !query || !reference || !out3) return fail("xm_test_bound: null argument");
-  if (query_length < 1 || reference_length < 1 || start_a < 0 || end_a > query_length || start_a > end_a || start_b < 0 || end_b > reference_length || start_b > end_b) return fail("xm_test_bound: bad sections");
-  try {
-    if (device >= 0) HIP_CHECK(hipSetDevice(device));
-    const Params params = paramsFromC(*p);
-    DevBuf<uint8_t> dq, dr, dArena;
-    DevBuf<int64_t> dOut;
-    struct Release { DevBuf<uint8_t>&a, &b, &d; DevBuf<int64_t>& c; ~Release() { a.release(); b.release(); c.release(); d.release(); } } releaseAll{dq, dr, dArena, dOut};
-    dq.ensure((size_t)query_length); dr.ensure((size_t)reference_length); dOut.ensure(4); dArena.ensure(64 * 1024);
-    HIP_CHECK(hipMemcpy(dq.p, query, (size_t)query_length, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dr.p, reference, (size_t)reference_length, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(dOut.p, 0, sizeof(int64_t) * 4));
-    hipLaunchKernelGGL(xm_test_bound_kernel, dim3(1), dim3(256), 0, 0, params, (const uint8_t*)dq.p, (int)query_length, (int)query_rc, (int)start_a, (int)end_a, (const uint8_t*)dr.p, (int)reference_length,
-                       (int)start_b, (int)end_b, (int)predicted_best_offset, (int)(pair == 3 ? 3 : (pair ? 1 : 0)), dArena.p, (unsigned long long)(64 * 1024), dOut.p);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy(out3, dOut.p, sizeof(int64_t) * 3, hipMemcpyDeviceToHost));
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_test_bound: ") + e.what()); }
-}
-
-// Test-only entry (tests/test_gpu_kat.py): see xm_test_local_kernel above and xm_test_wave_search_kernel (xm_wave_kernel.hip).
-int xm_test_local_align(int32_t device, int32_t chain, int32_t mode, const xm_params* p, const uint8_t* query, int32_t query_length, const uint8_t* reference, int32_t reference_length,
-                        double max_ins_ext, double max_del_ext, int32_t block_cap, int32_t* blocks, int32_t* num_blocks, double* penalties, int64_t* nodes_put) {
-  if (!p || !query || !reference || !blocks || !num_blocks || !penalties) { fail("xm_test_local_align: null argument"); return -1; }
-  const bool withBound = mode >= 8;  // mode + 8 (modes 0, 1, 4): the search behind the rejection filter of xm_bound.h; xm_test_bound_counters() says what it did
-  if (withBound) mode -= 8;
-  if (chain < 0 || chain > 1 || mode < 0 || mode > 4 || (withBound && (mode == 2 || mode == 3)) || (chain == 1 && (mode == 2 || mode == 3)) || query_length < 1 || reference_length < 1 || query_length > 30000 || reference_length > 100000 || block_cap < 1)
-  { fail("xm_test_local_align: bad arguments (chain 0: modes 0 LDS slot, 1 HBM, 2 wave search with the search kernel's capacities, 3 with the inline capacities, 4 lane-private form; chain 1: modes 0, 1, 4)"); return -1; }
-  try {
-    if (device >= 0) HIP_CHECK(hipSetDevice(device));
-    const Params params = paramsFromC(*p);
-    const int cap = block_cap < 256 ? block_cap : 256;
-    DevBuf<uint8_t> dq, dr, arena, nodes;
-    DevBuf<int32_t> dInts;
-    DevBuf<double> dDbls;
-    DevBuf<int64_t> dStart;
-    DevBuf<int32_t> dLen;
-    struct Release {  // (the buffers of this call are released on every way out)
-      DevBuf<uint8_t>&a, &b, &c, &d; DevBuf<int32_t>&e; DevBuf<double>& f; DevBuf<int64_t>& g; DevBuf<int32_t>& h;
-      ~Release() { a.release(); b.release(); c.release(); d.release(); e.release(); f.release(); g.release(); h.release(); }
-    } releaseAll{dq, dr, arena, nodes, dInts, dDbls, dStart, dLen};
-    dq.ensure((size_t)query_length); dr.ensure((size_t)reference_length); dInts.ensure((size_t)8 + 4 * (size_t)cap); dDbls.ensure(2);
-    HIP_CHECK(hipMemcpy(dq.p, query, (size_t)query_length, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dr.p, reference, (size_t)reference_length, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemset(dInts.p, 0, sizeof(int32_t) * (8 + 4 * (size_t)cap)));
-    HIP_CHECK(hipMemset(dDbls.p, 0, sizeof(double) * 2));
-    if (mode == 2 || mode == 3) {
-      TestSearch t;
-      memset(&t, 0, sizeof(t));
-      t.big = mode == 2 ? 1 : 0;
-      const int64_t start0 = 0;
-      const int32_t len0 = reference_length;
-      dStart.ensure(1); dLen.ensure(1);
-      HIP_CHECK(hipMemcpy(dStart.p, &start0, 8, hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(dLen.p, &len0, 4, hipMemcpyHostToDevice));
-      t.ix.numContigs = 1; t.ix.refCodes = dr.p; t.ix.contigStart = dStart.p; t.ix.contigLen = dLen.p;
-      t.params = params; t.query = dq.p; t.queryLength = query_length; t.referenceLength = reference_length; t.predictedBestOffset = 0; t.confident = 0; t.blockCap = cap;
-      t.maxIns = max_ins_ext; t.maxDel = max_del_ext;
-      nodes.ensure((size_t)xmTestWaveSearchNodeBytes(t.big));
-      t.nodes = nodes.p; t.outInts = dInts.p; t.outDbls = dDbls.p;
-      const int rc = xmTestWaveSearchLaunch(t, 0);
-      if (rc != 0) throw std::runtime_error(std::string("test search launch: ") + hipGetErrorString((hipError_t)rc));
-    } else {
-      const int scale = 4;
-      const size_t arenaBytes = (size_t)XM_ARENA_KB_DEFAULT * 1024 * scale;
-      arena.ensure(arenaBytes);
-      nodes.ensure((size_t)XM_PAL_NODES * 4 * sizeof(PNode));
-      hipLaunchKernelGGL(xm_test_local_kernel, dim3(1), dim3(256), 0, 0, (int)chain, (int)mode + (withBound ? 8 : 0), params, (const uint8_t*)dq.p, (int)query_length, (const uint8_t*)dr.p, (int)reference_length,
-                         max_ins_ext, max_del_ext, scale, arena.p, (unsigned long long)arenaBytes, (PNode*)nodes.p, cap, dInts.p, dDbls.p);
-      HIP_CHECK(hipGetLastError());
-    }
-    HIP_CHECK(hipDeviceSynchronize());
-    std::vector<int32_t> ints((size_t)8 + 4 * (size_t)cap);
-    double dbls[2];
-    HIP_CHECK(hipMemcpy(ints.data(), dInts.p, sizeof(int32_t) * ints.size(), hipMemcpyDeviceToHost));
-    for (int i = 0; i < 3; i++) g_testBound[i] = ints[(size_t)4 + 4 * (size_t)cap + (size_t)i];
-    HIP_CHECK(hipMemcpy(dbls, dDbls.p, sizeof(dbls), hipMemcpyDeviceToHost));
-    if (nodes_put) *nodes_put = ints[3];
-    const int ok = (mode == 2 || mode == 3) ? ints[0] : (ints[2] != XM_OK ? -1 : ints[0]);
-    if (ok < 0) { fail("xm_test_local_align: the search failed with status " + std::to_string(ints[2])); return -1; }
-    if (ok == 0) { *num_blocks = 0; return 1; }
-    if (ints[1] > cap) { fail("xm_test_local_align: more blocks than block_cap"); return -1; }
-    *num_blocks = ints[1];
-    memcpy(blocks, ints.data() + 4, sizeof(int32_t) * 4 * (size_t)ints[1]);
-    penalties[0] = dbls[0]; penalties[1] = dbls[1];
-    return 0;
-  } catch (std::exception& e) { fail(std::string("xm_test_local_align: ") + e.what()); return -1; }
-}
-
 }  // extern "C"
+
+#include "xm_capi_probe.h"
+#include "xm_capi_pileup.h"

@@ -10,6 +10,7 @@
 #include "../../mapper_amd/csrc/xm_wave.h"
 #include "../../mapper_amd/csrc/xm_index_host.h"
 #include "../../mapper_amd/csrc/xm_pass_plan.h"
+#include "../../mapper_amd/csrc/xm_conf_table.h"
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -589,6 +590,45 @@ int xmsim_next_pass(const int64_t* facts, int64_t* state, const uint64_t* ctl, i
     next[0] = (int64_t)np.kind; next[1] = np.nTodo; next[2] = np.list; next[3] = np.clear;
     return 0;
   } catch (std::exception& e) { g_err = e.what(); return 1; }
+}
+
+// ---- the host's confidence table (mapper_amd/csrc/xm_conf_table.h) for tests/test_conf_table.py: a ConfTable driven as a context drives it, and read with the
+// kernels' own lookup (confLookup, xm_defs.h)
+void* xmsim_conf_new(void) { return new ConfTable(); }
+void xmsim_conf_free(void* t) { delete (ConfTable*)t; }
+void xmsim_conf_prepare(void* t, const xm_params* p, const int32_t* lens, int64_t nLens, double granularity, int64_t totalSize, int64_t seedBudget) {
+  ((ConfTable*)t)->prepare(paramsFromC(*p), std::vector<int32_t>(lens, lens + nLens), granularity, totalSize, seedBudget);
+}
+// added[i] = what insert returned for key i; -> how many were added
+int64_t xmsim_conf_insert(void* t, int64_t n, const double* penalties, const int32_t* lens, uint8_t* added) {
+  int64_t k = 0;
+  for (int64_t i = 0; i < n; i++) { added[i] = ((ConfTable*)t)->insert(penalties[i], lens[i]) ? 1 : 0; k += added[i]; }
+  return k;
+}
+// found[i], values[i] = confLookup over the table's slots; -> how many were found
+int64_t xmsim_conf_lookup(void* t, int64_t n, const double* penalties, const int32_t* lens, uint8_t* found, double* values) {
+  const ConfTable& c = *(ConfTable*)t;
+  int64_t k = 0;
+  for (int64_t i = 0; i < n; i++) { values[i] = 0; found[i] = confLookup(c.data(), c.mask(), penalties[i], lens[i], values[i]) ? 1 : 0; k += found[i]; }
+  return k;
+}
+// out (3): slots, entries, dirty
+void xmsim_conf_state(void* t, int64_t* out) { const ConfTable& c = *(ConfTable*)t; out[0] = (int64_t)c.size(); out[1] = (int64_t)c.used(); out[2] = c.dirty() ? 1 : 0; }
+void xmsim_conf_mark_uploaded(void* t) { ((ConfTable*)t)->markUploaded(); }
+// every entry, in slot order -> their number (cap: room in the arrays)
+int64_t xmsim_conf_dump(void* t, int64_t cap, double* penalties, int32_t* lens, double* values) {
+  const ConfTable& c = *(ConfTable*)t;
+  int64_t k = 0;
+  for (size_t i = 0; i < c.size(); i++) {
+    const ConfEntry& e = c.data()[i];
+    if (!e.used) continue;
+    if (k < cap) { memcpy(&penalties[k], &e.penaltyBits, 8); lens[k] = e.queryLength; values[k] = e.totalLengthForHighConfidence; }
+    k++;
+  }
+  return k;
+}
+void xmsim_conf_values(int64_t n, const double* penalties, const int32_t* lens, double maxPenaltySpan, double mutationPenalty, double granularity, int64_t totalSize, double* values) {
+  for (int64_t i = 0; i < n; i++) values[i] = confidenceLengthOnHost(penalties[i], lens[i], maxPenaltySpan, mutationPenalty, granularity, totalSize);
 }
 
 }  // extern "C"

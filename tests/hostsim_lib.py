@@ -60,6 +60,20 @@ def lib():
         L.xmsim_pass_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.xmsim_plan_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
         L.xmsim_next_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xmsim_conf_new.restype = C.c_void_p
+        L.xmsim_conf_free.argtypes = [C.c_void_p]
+        L.xmsim_conf_prepare.argtypes = [C.c_void_p, C.POINTER(_capi.XmParams), C.c_void_p, C.c_int64, C.c_double, C.c_int64, C.c_int64]
+        L.xmsim_conf_prepare.restype = None
+        L.xmsim_conf_insert.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xmsim_conf_insert.restype = C.c_int64
+        L.xmsim_conf_lookup.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xmsim_conf_lookup.restype = C.c_int64
+        L.xmsim_conf_state.argtypes = [C.c_void_p, C.c_void_p]
+        L.xmsim_conf_mark_uploaded.argtypes = [C.c_void_p]
+        L.xmsim_conf_dump.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xmsim_conf_dump.restype = C.c_int64
+        L.xmsim_conf_values.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_void_p]
+        L.xmsim_conf_values.restype = None
         _lib = L
     return _lib
 
@@ -77,6 +91,14 @@ def build_opts(mode="mapper", enable_gapmers=True, custom_dup=None, max_hashed_l
     o.device = -1
     o.host_only = host_only
     return o
+
+
+def _xm_params(params):
+    p = _capi.XmParams()
+    for f, _ in _capi.XmParams._fields_:
+        if f != "reserved":
+            setattr(p, f, getattr(params, f))
+    return p
 
 
 class SimReference:
@@ -100,10 +122,7 @@ class SimReference:
         if not isinstance(batch, oracle_lib.QueryBatch):
             batch = oracle_lib.QueryBatch(batch)
         b, keep = _capi.make_batch(batch.mate_count, batch.mate_offset, batch.mate_length, batch.codes, batch.expected_inner, batch.deviation)
-        p = _capi.XmParams()
-        for f, _ in _capi.XmParams._fields_:
-            if f != "reserved":
-                setattr(p, f, getattr(params, f))
+        p = _xm_params(params)
         res = C.POINTER(_capi.XmResult)()
         if self.L.xmsim_align_batch(self.h, C.byref(p), C.byref(b), C.byref(res)):
             raise RuntimeError(self.L.xmsim_last_error().decode())
@@ -179,10 +198,7 @@ def test_bound(params, query, query_rc, start_a, end_a, reference, start_b, end_
     """the rejection filter of xm_bound.h alone (host-compiled) -> (taken, rejected, cells)"""
     q = np.ascontiguousarray(query, dtype=np.uint8)
     r = np.ascontiguousarray(reference, dtype=np.uint8)
-    p = _capi.XmParams()
-    for f, _ in _capi.XmParams._fields_:
-        if f != "reserved":
-            setattr(p, f, getattr(params, f))
+    p = _xm_params(params)
     out = (C.c_int64 * 3)()
     lib().xmsim_test_bound(C.byref(p), q.ctypes.data, len(q), 1 if query_rc else 0, start_a, end_a, r.ctypes.data, len(r), start_b, end_b, predicted_best_offset, out)
     return int(out[0]), int(out[1]), int(out[2])
@@ -227,3 +243,64 @@ def next_pass(state, ctl, longest_mate, paired=False, contexts=1):
     c = np.array([ctl.get("nHeavy", 0), ctl.get("nHeavyLate", 0)] + list(ctl.get("nScale", (0, 0))) + list(ctl.get("nOut", (0, 0))) + [2 ** 64 - 1] + list(ctl.get("nConf", (0, 0))), dtype=np.uint64)
     _check(lib().xmsim_next_pass(f.ctypes.data, st.ctypes.data, c.ctypes.data, nxt.ctypes.data))
     return PASS_KINDS[int(nxt[0])], int(nxt[1]), int(nxt[2]), int(nxt[3]), dict(zip(STATE_FIELDS, map(int, st)))
+
+
+# ---- the host's confidence table (mapper_amd/csrc/xm_conf_table.h)
+def _keys(penalties, lens):
+    return np.ascontiguousarray(penalties, dtype=np.float64), np.ascontiguousarray(lens, dtype=np.int32)
+
+
+def conf_values(penalties, lens, params, granularity, total_size):
+    """confidenceLengthOnHost (xm_confidence.h) of every key"""
+    pen, ln = _keys(penalties, lens)
+    out = np.zeros(len(pen), dtype=np.float64)
+    lib().xmsim_conf_values(len(pen), pen.ctypes.data, ln.ctypes.data, params.Max_PenaltySpan, params.MutationPenalty, granularity, total_size, out.ctypes.data)
+    return out
+
+
+class SimConfTable:
+    """A ConfTable as a context holds it; lookups go through the kernels' confLookup."""
+
+    def __init__(self):
+        self.L = lib()
+        self.h = C.c_void_p(self.L.xmsim_conf_new())
+
+    def __del__(self):
+        try:
+            self.L.xmsim_conf_free(self.h)
+        except Exception:
+            pass
+
+    def prepare(self, params, lens, granularity, total_size, seed_budget):
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        self.L.xmsim_conf_prepare(self.h, C.byref(_xm_params(params)), ln.ctypes.data, len(ln), granularity, total_size, seed_budget)
+
+    def insert(self, penalties, lens):
+        """-> per key: was it added"""
+        pen, ln = _keys(penalties, lens)
+        added = np.zeros(len(pen), dtype=np.uint8)
+        self.L.xmsim_conf_insert(self.h, len(pen), pen.ctypes.data, ln.ctypes.data, added.ctypes.data)
+        return added.astype(bool)
+
+    def lookup(self, penalties, lens):
+        """-> (per key: found, values)"""
+        pen, ln = _keys(penalties, lens)
+        found, values = np.zeros(len(pen), dtype=np.uint8), np.zeros(len(pen), dtype=np.float64)
+        self.L.xmsim_conf_lookup(self.h, len(pen), pen.ctypes.data, ln.ctypes.data, found.ctypes.data, values.ctypes.data)
+        return found.astype(bool), values
+
+    def state(self):
+        """-> (slots, entries, dirty)"""
+        out = np.zeros(3, dtype=np.int64)
+        self.L.xmsim_conf_state(self.h, out.ctypes.data)
+        return int(out[0]), int(out[1]), bool(out[2])
+
+    def mark_uploaded(self):
+        self.L.xmsim_conf_mark_uploaded(self.h)
+
+    def entries(self):
+        """-> (penalties, lengths, values) of every entry"""
+        n = self.state()[1]
+        pen, ln, val = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64)
+        assert self.L.xmsim_conf_dump(self.h, n, pen.ctypes.data, ln.ctypes.data, val.ctypes.data) == n
+        return pen, ln, val

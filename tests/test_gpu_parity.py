@@ -183,7 +183,7 @@ def test_long_reads_sharing_waves_on_gpu(env, monkeypatch):
 @pytest.mark.parametrize("env", [{}, {"XM_CONF_SEED": "0"}, {"XM_CONF_SEED": "300"}], ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()) or "default")
 def test_many_read_lengths_one_batch_on_gpu(env, monkeypatch):
     """A batch in which every read has its own length (36 ... 700: several hundred distinct (penalty, length) families for the confidence-length table the
-    host keeps for the kernels, xm_capi.hip confPrepare) - with the table seeded as in the product, not seeded at all (every key comes in through the reads that
+    host keeps for the kernels, xm_conf_table.h ConfTable::prepare) - with the table seeded as in the product, not seeded at all (every key comes in through the reads that
     missed it and run again), and seeded for a few lengths only; then the same lengths again in a second batch (nothing left to seed).  The oracle's streams."""
     ref = synth.synthetic_reference(300_000, seed=51)
     rng = np.random.default_rng(52)
@@ -487,6 +487,48 @@ def test_streamed_batches_overlap_upload_and_alignment():
     assert np.array_equal(first.ints, want[0].ints)
     again, _ = gpu_align(db, batches[1])
     assert streams_equal(again, want[1])
+    db.close()
+
+
+def test_batch_lifecycle_upload_stage_commit_and_failed_stage():
+    """The resident and the staged batch of a context (DeviceBatch): a commit makes the staged batch the resident one with everything that describes it (B has
+    pairs, A has none); a batch that fails validation is not staged and leaves the resident batch alone; an empty batch is a batch.  xm_align_batch reports
+    the copy time of its own batch: 0 for an empty one, whatever the batch before took."""
+    ref = synth.synthetic_reference(50_000, seed=77)
+    db = api.ReferenceDatabase([("r", ref)])
+    p = api.AlignmentParameters()
+    a = se_batch(synth.synthetic_single_end(ref, 64, read_len=100, seed=301)[0])
+    m1, m2 = synth.synthetic_paired_end(ref, 64, read_len=100, seed=302)[:2]
+    b = pe_batch(m1, m2, 100.0, 50.0)
+    arrays = lambda t: (t.mate_count, t.mate_offset, t.mate_length, t.codes, t.expected_inner, t.deviation)
+    empty = api.ReferenceDatabase.batch_arrays([])
+    want_b, plain = gpu_align(db, b)
+    assert plain.h2d_ms > 0
+    r = db.align_arrays(*empty, p)   # (not the time the batch before took)
+    assert len(r) == 0 and r.h2d_ms == 0
+
+    def resident_streams():
+        r = db.align_resident(p)
+        return o.Streams(r.ints, r.dbls, r.int_off, r.dbl_off, r.counters), r
+
+    db.upload_arrays(*arrays(a))
+    db.stage_arrays(*arrays(b))
+    db.commit_staged()
+    got, _ = resident_streams()
+    assert streams_equal(got, want_b), first_difference(got, want_b, 1)
+    bad = list(arrays(b))
+    bad[2] = b.mate_length.copy()
+    bad[2][5] = 0
+    with pytest.raises(RuntimeError, match="mate length out of range"):
+        db.stage_arrays(*bad)
+    with pytest.raises(RuntimeError, match="no staged batch"):
+        db.commit_staged()
+    got, _ = resident_streams()
+    assert streams_equal(got, want_b), first_difference(got, want_b, 1)
+    db.stage_arrays(*empty)
+    db.commit_staged()
+    _, r = resident_streams()
+    assert len(r) == 0 and len(r.ints) == 0 and r.h2d_ms == 0
     db.close()
 
 
