@@ -289,14 +289,24 @@ struct DeviceTables {
   bool posIs64 = false;
   IndexView view;
   int numCUs = 0;
-  hipStream_t stream = nullptr;
+  // The one staging stream of this GPU (xm_batch_stage): made by the first batch staged, shared by every context - a batch's copy is a few per cent of its
+  // alignment, so the contexts' copies can queue behind each other - and kept until the tables go, whichever context made it.  The tables keep no other
+  // stream: the runtime spreads a process's live streams over a few hardware queues, and launches of streams that share one run one after the other.
+  std::mutex copyMu;         // creation of copyStream, and one batch's copies at a time on it
+  hipStream_t copyStream = nullptr;
+  // queue(stream) under the lock: the copies of one batch, queued together (the caller has allocated; nothing here waits for the device)
+  template <class Queue>
+  void onStagingStream(Queue&& queue) {
+    std::lock_guard<std::mutex> lock(copyMu);
+    if (!copyStream) HIP_CHECK(hipStreamCreateWithFlags(&copyStream, hipStreamNonBlocking));
+    queue(copyStream);
+  }
 
   // Host tables -> HBM (caller holds hs->mu and rw exclusively).  With `peer` (a replica on another GPU): the tables are copied from the peer's HBM
   // instead (hipMemcpyPeer: over xGMI), not sent over PCIe a second time.
   void upload(const DeviceTables* peer = nullptr) {
     const HostIndex& host = hs->host;
     HIP_CHECK(hipSetDevice(device));
-    if (!stream) HIP_CHECK(hipStreamCreate(&stream));
     hipDeviceProp_t prop;
     HIP_CHECK(hipGetDeviceProperties(&prop, device));
     numCUs = prop.multiProcessorCount;
@@ -331,6 +341,13 @@ struct DeviceTables {
       const size_t need = words * (posIs64 ? 8 : 4);
       if (hipMemGetInfo(&freeB, &totalB) == hipSuccess && need < freeB / 2) {
         if (posIs64) dLines64.ensure(words); else dLines32.ensure(words);
+        // a stream for the life of this upload (a blocking one: its kernels run behind the copies above, which went through the null stream)
+        struct UploadStream {
+          hipStream_t s = nullptr;
+          ~UploadStream() { if (s) (void)hipStreamDestroy(s); }
+        } us;
+        HIP_CHECK(hipStreamCreate(&us.s));
+        hipStream_t stream = us.s;
         for (const Table& t : host.tables) {
           if (t.capacity < 1) continue;
           const unsigned grid = (unsigned)(((long long)t.capacity + 255) / 256);
@@ -361,7 +378,7 @@ struct DeviceTables {
   }
   ~DeviceTables() {
     (void)hipSetDevice(device);
-    if (stream) (void)hipStreamDestroy(stream);
+    if (copyStream) (void)hipStreamDestroy(copyStream);
   }
 };
 
@@ -376,23 +393,28 @@ struct DeviceBatch {
   bool anyPaired = false;
   double h2dMs = 0;
   std::vector<int32_t> lens;  // distinct total query lengths, ascending (the confidence table is seeded for them)
-  // host -> HBM on stream s, timed between the two events (the caller has validated b); a copy that throws leaves "no batch"
-  void copyIn(const xm_query_batch* b, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
+  // host -> HBM, timed between the two events (the caller has validated b); a copy that throws leaves "no batch".  withStream(queue) calls queue(stream) with the
+  // stream the copies go to - the context's own, or the GPU's staging stream under its lock (DeviceTables::onStagingStream).  The buffers are allocated before
+  // that (a buffer that grows frees the old one, which waits for the device), and the wait is for this batch's last copy, not for the stream.
+  template <class WithStream>
+  void copyIn(const xm_query_batch* b, hipEvent_t e0, hipEvent_t e1, WithStream&& withStream) {
     const int64_t n = b->num_queries;
     nq = -1;
     h2dMs = 0;
     if (n > 0) {
-      HIP_CHECK(hipEventRecord(e0, s));
       mateCount.ensure((size_t)n); mateOffset.ensure((size_t)n * 2); mateLength.ensure((size_t)n * 2);
       codes.ensure((size_t)b->codes_length); expected.ensure((size_t)n); deviation.ensure((size_t)n);
-      HIP_CHECK(hipMemcpyAsync(mateCount.p, b->mate_count, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(mateOffset.p, b->mate_offset, sizeof(int64_t) * (size_t)n * 2, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(mateLength.p, b->mate_length, sizeof(int32_t) * (size_t)n * 2, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(codes.p, b->codes, (size_t)b->codes_length, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(expected.p, b->expected_inner, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipMemcpyAsync(deviation.p, b->deviation, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipEventRecord(e1, s));
-      HIP_CHECK(hipStreamSynchronize(s));
+      withStream([&](hipStream_t s) {
+        HIP_CHECK(hipEventRecord(e0, s));
+        HIP_CHECK(hipMemcpyAsync(mateCount.p, b->mate_count, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(mateOffset.p, b->mate_offset, sizeof(int64_t) * (size_t)n * 2, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(mateLength.p, b->mate_length, sizeof(int32_t) * (size_t)n * 2, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(codes.p, b->codes, (size_t)b->codes_length, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(expected.p, b->expected_inner, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(deviation.p, b->deviation, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipEventRecord(e1, s));
+      });
+      HIP_CHECK(hipEventSynchronize(e1));
       float ms = 0;
       HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
       h2dMs = ms;
@@ -461,8 +483,7 @@ struct xm_index {
   int64_t residentGen = 0, lastAlignedGen = -1;  // which resident batch the streams of the last align call belong to
   int64_t lastAlignedNq = -1;  // queries whose result streams (dFinalInts / dFinalDbls / dFinalIntOff) are still in HBM from the last align call (xm_pileup_add_last)
   std::mutex stageMu;
-  hipStream_t copyStream = nullptr;
-  hipEvent_t cev0 = nullptr, cev1 = nullptr;
+  hipEvent_t cev0 = nullptr, cev1 = nullptr;  // this context's events on the GPU's staging stream (DeviceTables::copyStream)
 
   void initContext() {  // stream and events of this context (the device tables exist)
     dt->contexts.fetch_add(1);
@@ -491,7 +512,6 @@ struct xm_index {
     if (cev0) (void)hipEventDestroy(cev0);
     if (cev1) (void)hipEventDestroy(cev1);
     if (stream) (void)hipStreamDestroy(stream);
-    if (copyStream) (void)hipStreamDestroy(copyStream);
   }  // (every DevBuf member releases its memory itself; the shared tables go with their last context)
 };
 
@@ -1251,7 +1271,7 @@ static void uploadBatchLocked(xm_index* idx, const xm_query_batch* b) {
   d.anyPaired = anyPaired;
   idx->ensureTablesFor(maxLen);  // Readable_HashBlock_Database.getContainingMap growth, done before the launch
   HIP_CHECK(hipSetDevice(idx->device));
-  d.copyIn(b, idx->stream, idx->ev0, idx->ev1);
+  d.copyIn(b, idx->ev0, idx->ev1, [&](auto&& queue) { queue(idx->stream); });
   idx->residentGen++;
   d.maxLen = maxLen;
 }
@@ -1279,8 +1299,8 @@ int xm_batch_stage(xm_index* idx, const xm_query_batch* b) {
     d.anyPaired = anyPaired;
     idx->ensureTablesFor(maxLen);  // (tables that grow wait for the launches that read them: DeviceTables::rw)
     HIP_CHECK(hipSetDevice(idx->device));
-    if (!idx->copyStream) { HIP_CHECK(hipStreamCreateWithFlags(&idx->copyStream, hipStreamNonBlocking)); HIP_CHECK(hipEventCreate(&idx->cev0)); HIP_CHECK(hipEventCreate(&idx->cev1)); }
-    d.copyIn(b, idx->copyStream, idx->cev0, idx->cev1);
+    if (!idx->cev0) { HIP_CHECK(hipEventCreate(&idx->cev0)); HIP_CHECK(hipEventCreate(&idx->cev1)); }
+    d.copyIn(b, idx->cev0, idx->cev1, [&](auto&& queue) { idx->dt->onStagingStream(queue); });
     d.maxLen = maxLen;
     return 0;
   } catch (std::exception& e) { return fail(std::string("xm_batch_stage: ") + e.what()); }
