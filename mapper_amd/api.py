@@ -149,6 +149,12 @@ class BatchResult:
         return decode_streams(self.ints, self.dbls, self.int_off, self.dbl_off, q)
 
 
+def _check(rc, prefix=""):
+    """A C entry that returns non-zero has left its message in xm_last_error."""
+    if rc:
+        raise RuntimeError(prefix + _capi.lib().xm_last_error().decode())
+
+
 def index_cache_path(cache_dir, contigs, opts):
     """<cache_dir>/cache/<digest>/index.xmidx, the digest over the property text DirCache would hash (DirCache.java:19-60): the
     sequence database's keys (here: names, lengths and a digest of the bases) + enableGapmers, minInterestingSize, maxNumShortMatches,
@@ -204,8 +210,7 @@ class ReferenceDatabase:
                 self.cache_hit = True
                 return
             # (a file that does not load - other settings behind the same name, truncated, older format - is rebuilt and replaced)
-        if self._L.xm_index_build(C.byref(ref), C.byref(o), C.byref(h)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_index_build(C.byref(ref), C.byref(o), C.byref(h)))
         self._h = h
         if self.cache_file is not None:
             self.save(self.cache_file)
@@ -213,8 +218,7 @@ class ReferenceDatabase:
     def save(self, path):
         """xm_index_save: the reference, every table hashed so far and the duplication map into one file."""
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        if self._L.xm_index_save(self._h, os.fspath(path).encode()):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_index_save(self._h, os.fspath(path).encode()))
 
     @classmethod
     def load(cls, path, device=-1, host_only=False, max_query_length=0):
@@ -228,46 +232,39 @@ class ReferenceDatabase:
         o.device = device
         o.host_only = 1 if host_only else 0
         h = C.c_void_p()
-        if self._L.xm_index_load(os.fspath(path).encode(), None, C.byref(o), C.byref(h)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_index_load(os.fspath(path).encode(), None, C.byref(o), C.byref(h)))
         self._h = h
         return self
+
+    def _sibling(self, create):
+        """A further handle over this index: create(address of the new handle) is the C entry that makes it."""
+        other = ReferenceDatabase.__new__(ReferenceDatabase)
+        other._L = self._L
+        other.contigs, other._keep, other.cache_file, other.cache_hit = self.contigs, self._keep, self.cache_file, self.cache_hit
+        h = C.c_void_p()
+        _check(create(C.byref(h)))
+        other._h = h
+        return other
 
     def replicate(self, device):
         """xm_index_replicate: a further context of this index on GPU `device`.  The host tables are shared; on another GPU the tables are copied
         HBM to HBM (nothing built or uploaded twice), on this index's own GPU the context reads the very same tables (= new_context)."""
-        other = ReferenceDatabase.__new__(ReferenceDatabase)
-        other._L = self._L
-        other.contigs, other._keep, other.cache_file, other.cache_hit = self.contigs, self._keep, self.cache_file, self.cache_hit
-        h = C.c_void_p()
-        if self._L.xm_index_replicate(self._h, int(device), C.byref(h)):
-            raise RuntimeError(self._L.xm_last_error().decode())
-        other._h = h
-        return other
+        return self._sibling(lambda h: self._L.xm_index_replicate(self._h, int(device), h))
 
     def new_context(self):
         """xm_context_new: a further context on the same GPU - own stream, batch buffers, scratch and results over the same tables, as the reference's
         AlignerWorker threads share one HashBlock_Database through per-thread views (HashBlock_Database.java:129-133)."""
-        other = ReferenceDatabase.__new__(ReferenceDatabase)
-        other._L = self._L
-        other.contigs, other._keep, other.cache_file, other.cache_hit = self.contigs, self._keep, self.cache_file, self.cache_hit
-        h = C.c_void_p()
-        if self._L.xm_context_new(self._h, C.byref(h)):
-            raise RuntimeError(self._L.xm_last_error().decode())
-        other._h = h
-        return other
+        return self._sibling(lambda h: self._L.xm_context_new(self._h, h))
 
     def set_scratch(self, nbytes):
         """xm_context_set_scratch: upper limit of the HBM this context allocates as scratch for its passes (0: the default)."""
-        if self._L.xm_context_set_scratch(self._h, int(nbytes)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_context_set_scratch(self._h, int(nbytes)))
 
     def set_collapse(self, enable):
         """xm_context_set_collapse: this context aligns one query of each group of byte-identical queries of a batch and copies its results to the
         others (AlignerWorker.checkCacheAndAlign, AlignerWorker.java:264-291, within a batch).  Same results; the work counters then count the queries
         aligned, and BatchResult.copies the ones served as copies.  Off by default."""
-        if self._L.xm_context_set_collapse(self._h, 1 if enable else 0):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_context_set_collapse(self._h, 1 if enable else 0))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -282,19 +279,16 @@ class ReferenceDatabase:
 
     def info(self):
         i = _capi.XmIndexInfo()
-        if self._L.xm_index_get_info(self._h, C.byref(i)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_index_get_info(self._h, C.byref(i)))
         return {f: getattr(i, f) for f, _ in _capi.XmIndexInfo._fields_}
 
     def ensure_length(self, n):
-        if self._L.xm_index_ensure_length(self._h, int(n)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_index_ensure_length(self._h, int(n)))
 
     def table_shape(self, used_length):
         """(capacity, per-key limit) of the table of one gapmer length."""
         cap, mx = C.c_int32(), C.c_int32()
-        if self._L.xm_index_table_shape(self._h, int(used_length), C.byref(cap), C.byref(mx)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_index_table_shape(self._h, int(used_length), C.byref(cap), C.byref(mx)))
         return cap.value, mx.value
 
     def table(self, used_length):
@@ -309,8 +303,7 @@ class ReferenceDatabase:
     def bucket_stats(self):
         """{buckets, occupied, overfull} over all hashed tables (overfull: more than max(L^2, 5) entries, HashBlock_Database.java:569-577)."""
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
-        if self._L.xm_index_bucket_stats(self._h, C.byref(a), C.byref(b), C.byref(c)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_index_bucket_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {"buckets": a.value, "occupied": b.value, "overfull": c.value, "overfull_share_of_occupied": round(c.value / max(1, b.value + c.value), 6)}
 
     def dup_keys(self, contig):
@@ -322,29 +315,28 @@ class ReferenceDatabase:
     def align_arrays(self, mate_count, mate_offset, mate_length, codes, expected_inner, deviation, parameters):
         """One AlignerWorker.process() batch (AlignerWorker.java:177-231) from flat arrays -> BatchResult."""
         b, keep = _capi.make_batch(mate_count, mate_offset, mate_length, codes, expected_inner, deviation)
+        return self._align(lambda p, res: self._L.xm_align_batch(self._h, p, C.byref(b), res), parameters)
+
+    def _align(self, call, parameters):
+        """call(address of the xm_params, address of the result pointer) is the C entry that aligns -> BatchResult over its streams."""
         p = parameters._c() if isinstance(parameters, AlignmentParameters) else parameters
         res = C.POINTER(_capi.XmResult)()
-        if self._L.xm_align_batch(self._h, C.byref(p), C.byref(b), C.byref(res)):
-            raise RuntimeError("Failed to align: " + self._L.xm_last_error().decode())
-        d = _capi.view_result(self._L, res)
-        return BatchResult(d)
+        _check(call(C.byref(p), C.byref(res)), "Failed to align: ")
+        return BatchResult(_capi.view_result(self._L, res))
 
     def upload_arrays(self, mate_count, mate_offset, mate_length, codes, expected_inner, deviation):
         """xm_batch_upload: validate + copy one batch to HBM; it stays resident for align_resident()."""
         b, keep = _capi.make_batch(mate_count, mate_offset, mate_length, codes, expected_inner, deviation)
-        if self._L.xm_batch_upload(self._h, C.byref(b)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_batch_upload(self._h, C.byref(b)))
 
     def stage_arrays(self, mate_count, mate_offset, mate_length, codes, expected_inner, deviation):
         """xm_batch_stage: copy the NEXT batch to HBM on its own stream (may run while align_resident() works on the resident batch)."""
         b, keep = _capi.make_batch(mate_count, mate_offset, mate_length, codes, expected_inner, deviation)
-        if self._L.xm_batch_stage(self._h, C.byref(b)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_batch_stage(self._h, C.byref(b)))
 
     def commit_staged(self):
         """xm_batch_commit: the staged batch becomes the resident one."""
-        if self._L.xm_batch_commit(self._h):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_batch_commit(self._h))
 
     def align_stream(self, batches, parameters, on_aligned=None):
         """Aligns a sequence of batches (each a tuple of upload_arrays' six arrays) and yields their BatchResults in order.  The copy of
@@ -396,12 +388,7 @@ class ReferenceDatabase:
             t.join(timeout=60)
 
     def align_resident(self, parameters):
-        p = parameters._c() if isinstance(parameters, AlignmentParameters) else parameters
-        res = C.POINTER(_capi.XmResult)()
-        if self._L.xm_align_resident(self._h, C.byref(p), C.byref(res)):
-            raise RuntimeError("Failed to align: " + self._L.xm_last_error().decode())
-        d = _capi.view_result(self._L, res)
-        return BatchResult(d)
+        return self._align(lambda p, res: self._L.xm_align_resident(self._h, p, res), parameters)
 
     @staticmethod
     def batch_arrays(queries):
@@ -431,19 +418,7 @@ class ReferenceDatabase:
             yield s, r
 
     def align_batch(self, queries, parameters):
-        nq = len(queries)
-        mc = np.zeros(nq, np.int32); mo = np.zeros(2 * nq, np.int64); ml = np.zeros(2 * nq, np.int32)
-        ei = np.zeros(nq); dv = np.ones(nq)
-        chunks, off = [], 0
-        for i, q in enumerate(queries):
-            mc[i] = len(q.sequences)
-            ei[i], dv[i] = q.expected_inner_distance, q.spacing_deviation_per_unit_penalty
-            for m, s in enumerate(q.sequences):
-                mo[2 * i + m], ml[2 * i + m] = off, len(s)
-                chunks.append(s)
-                off += len(s)
-        codes = np.concatenate(chunks) if chunks else np.zeros(1, np.uint8)
-        return self.align_arrays(mc, mo, ml, codes, ei, dv, parameters)
+        return self.align_arrays(*self.batch_arrays(queries), parameters)
 
     def seed_probe(self, used_length, keys, max_per_probe=8, unpack=True):
         """Bulk PackedMap.get (PackedMap.java:160-172) on the device -> (counts, positions[n, max_per_probe] with -1 behind a probe's positions, kernel_ms).
@@ -456,8 +431,7 @@ class ReferenceDatabase:
         counts = np.zeros(n, np.int32)
         packed = np.zeros(max(max_per_probe, 1) * max(n, 1), np.int64) if unpack else None
         ms = C.c_double()
-        if self._L.xm_seed_probe_packed(self._h, n, used.ctypes.data, keys.ctypes.data, max_per_probe, counts.ctypes.data, packed.ctypes.data if unpack else None, C.byref(ms)):
-            raise RuntimeError(self._L.xm_last_error().decode())
+        _check(self._L.xm_seed_probe_packed(self._h, n, used.ctypes.data, keys.ctypes.data, max_per_probe, counts.ctypes.data, packed.ctypes.data if unpack else None, C.byref(ms)))
         if not unpack:
             return counts, packed, ms.value
         pos = np.full((n, max(max_per_probe, 1)), -1, np.int64)
@@ -476,8 +450,7 @@ def measure_random_gather(table_bytes=4 << 30, accesses=1 << 26, device=0):
     """Random 64-byte-sector reads per second the GPU sustains (xm_measure_random_gather) -> (sectors/s, kernel ms)."""
     L = _capi.lib()
     ms = C.c_double()
-    if L.xm_measure_random_gather(device, table_bytes, accesses, C.byref(ms)):
-        raise RuntimeError(L.xm_last_error().decode())
+    _check(L.xm_measure_random_gather(device, table_bytes, accesses, C.byref(ms)))
     return accesses / (ms.value * 1e-3), ms.value
 
 
@@ -485,8 +458,7 @@ def device_memory(device=0):
     """xm_device_memory: (free, total) bytes of HBM on GPU `device` right now."""
     L = _capi.lib()
     f, t = C.c_int64(), C.c_int64()
-    if L.xm_device_memory(int(device), C.byref(f), C.byref(t)):
-        raise RuntimeError(L.xm_last_error().decode())
+    _check(L.xm_device_memory(int(device), C.byref(f), C.byref(t)))
     return f.value, t.value
 
 

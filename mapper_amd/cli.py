@@ -15,12 +15,17 @@ Flags of this harness that Mapper does not have: --batch-size <n>, --gpus <n>, -
 --collapse-identical-queries (byte-identical queries of a batch are aligned once and share the results, as the reference's alignment cache does; the
 outputs are the same, and one line on stderr says how many queries were served as copies).
 """
+import contextlib
 import gzip
+import itertools
+import queue
 import sys
+import threading
+import time
 
 import numpy as np
 
-from . import api, sam
+from . import api, hostio, sam
 
 JAVA_HOST_ONLY = {"--out-vcf": 1, "--out-ancestor": 1, "--infer-ancestors": 0, "--verify-consistent-db": 0,
                   "--vcf-exclude-non-mutations": 0, "--vcf-omit-support-reads": 0}
@@ -32,7 +37,7 @@ class UsageError(Exception):
     pass
 
 
-last_timing = None  # run_streaming: queries and seconds of the last job's streaming phase (bench.py's end_to_end leg)
+last_timing = None  # run: queries, seconds and contexts of the last job's streaming phase (bench.py's end_to_end leg)
 
 
 def _open(path):
@@ -257,86 +262,155 @@ def sam_header(contigs):
     return lines
 
 
-def run_streaming(o, params, contigs, out):
-    """The harness without an object per read (round 6): the query files are parsed by libxm_hostio.so straight into batch arrays (mapper_amd/hostio.py), the
-    batches stream through the GPU contexts (align_stream: the copy of batch k + 1 overlaps the alignment of batch k; several contexts align side by side),
-    and a writer thread turns each batch's result streams into SAM text in native code while the next batches are being aligned.  Memory is O(batches in
-    flight), not O(job).  Same records, same statistics lines as the per-object path below, which stays for the outputs that need objects
-    (--out-mutations, --out-refs-map-count)."""
-    import queue
-    import threading
-    from . import hostio
-    ordered = api.sort_reference(contigs)  # Mapper.sortAndComplementReference: alignment results refer to this order
-    names = [n for n, _ in ordered]
-    batch_size = o.get("batch_size") or 1_000_000
+def default_contexts(explicit_devices, batches, single_short):
+    """Contexts per GPU for a job that does not say (--contexts): one where the GPUs are named (--devices, --gpus) and for a job of one batch.  A job of
+    several batches gets two, which align their batches at the same time (+15-18 % reads per second on MI355X; on reads from i.i.d. references more contexts
+    add nothing, profiles/r03/NOTES.md; on a repeat-rich reference, whose passes end with a long tail of few heavy reads, `--contexts 4` gives 1.45x over
+    two, profiles/r04/NOTES.md 13).  single_short - every query a single read of up to 320 bases - in three batches or more: three contexts, each sized for
+    a third of the GPU's wave slots, overlap best (+7 % over two, profiles/r04/NOTES.md 15; pairs and long reads are within 2 % from two to four contexts).
+    Contexts share the index (xm_context_new), so a genome-sized one is no obstacle; they divide the HBM that is free once it is resident, and a GPU with
+    room for fewer contexts uses fewer (api.divide_scratch)."""
+    if explicit_devices or batches < 2:
+        return 1
+    return 3 if batches >= 3 and single_short else 2
+
+
+def context_devices(o, batches, single_short):
+    """-> the GPU ordinal of every context of the job: each GPU of --devices / --gpus (else --device) as often as it gets contexts."""
+    explicit = o.get("devices") or (list(range(o["gpus"])) if o.get("gpus", 1) > 1 else None)
+    contexts = o.get("contexts") or default_contexts(explicit is not None, batches, single_short)
+    return [d for d in (explicit or [o["device"]]) for _ in range(contexts)]
+
+
+def open_gpu_database(contigs, devices, max_query_length, enable_gapmers=True, collapse=False, cache_dir=None, per_context_extra=0):
+    """The index of `contigs` (in api.sort_reference order) with one context per entry of `devices`.  per_context_extra: what every context will allocate
+    beside its scratch (api.divide_scratch).  (A job whose later reads are longer than max_query_length grows the index on demand: xm_index_ensure_length.)"""
+    if len(devices) > 1:
+        from . import multi
+        return multi.MultiGpuDatabase(contigs, devices, collapse=collapse, mode="mapper", enable_gapmers=enable_gapmers, max_query_length=max_query_length,
+                                      cache_dir=cache_dir, per_context_extra=per_context_extra)
+    db = api.ReferenceDatabase(contigs, mode="mapper", enable_gapmers=enable_gapmers, device=devices[0], max_query_length=max_query_length, cache_dir=cache_dir)
+    db.set_collapse(collapse)
+    return db
+
+
+def native_source(o, batch_size, job):
+    """The query files parsed by libxm_hostio.so straight into batch arrays (hostio.Batch): no object per read, memory is O(batches in flight).  The reader
+    cannot know the job's size, so the first batch speaks for the job: a full one counts as three batches or more, a short one as the only one.
+    -> (batches, batch count for default_contexts, single_short, longest mate)"""
     keep_qual = bool(o["out_unaligned"])
 
-    def batches():
+    def read():
         for path, split in o["queries"]:
             yield from hostio.read_batches(path, None, batch_size, split=split, keep_qualities=keep_qual)
         for left, right, expected, deviation in o["paired"]:
             yield from hostio.read_batches(left, right, batch_size, keep_qualities=keep_qual, expected_inner=expected, deviation=deviation)
 
-    # the first batch decides the launch shapes (longest mate) and the number of contexts
-    it = batches()
-    first = next(it, None)
+    rest = read()
+    job.callback(rest.close)  # (closes the query file the reader stands in)
+    first = next(rest, None)
     if first is None:
         raise UsageError("no queries found")
+    job.callback(first.close)
     max_len = int(first.mate_length.max())
-    devices = o.get("devices") or (list(range(o["gpus"])) if o.get("gpus", 1) > 1 else None)
-    contexts = o.get("contexts")
-    if contexts is None:  # (as the per-object path chooses them: three contexts for single reads of up to 320 bases, else two; one for a job of one batch)
-        full = len(first) >= batch_size
-        contexts = 1 if not full or devices is not None else (3 if int(first.mate_count.max()) == 1 and max_len <= 320 else 2)
-    if contexts > 1:
-        devices = [d for d in (devices or [o["device"]]) for _ in range(contexts)]
-    # (a job whose later reads are longer than the first batch's grows the index on demand: xm_index_ensure_length)
-    if devices and len(devices) > 1:
-        from . import multi
-        db = multi.MultiGpuDatabase(ordered, devices, collapse=o.get("collapse", False), mode="mapper", enable_gapmers=o["enable_gapmers"], max_query_length=max_len,
-                                    cache_dir=o.get("cache_dir"))
-    else:
-        db = api.ReferenceDatabase(ordered, mode="mapper", enable_gapmers=o["enable_gapmers"], device=devices[0] if devices else o["device"],
-                                   max_query_length=max_len, cache_dir=o.get("cache_dir"))
-        db.set_collapse(o.get("collapse", False))
-    copies = 0
-    sam_out = un_out = None
-    if o["out_sam"]:
-        sam_out = sys.stdout if o["out_sam"] == "-" else open(o["out_sam"], "w")
-        sam_out.write("\n".join(sam_header(contigs)) + "\n")
-    if o["out_unaligned"]:
-        un_out = open(o["out_unaligned"], "w")
-    writer = hostio.Writer(names, sam_out, un_out)
-    in_flight = queue.Queue()     # batches in the order they were dealt to the GPUs
-    to_write = queue.Queue(maxsize=2 * max(1, len(devices or [0])))
+    return itertools.chain([first], rest), 3 if len(first) >= batch_size else 1, int(first.mate_count.max()) == 1 and max_len <= 320, max_len
+
+
+class ObjectBatch:
+    """A slice of load_queries() in the shape of hostio.Batch."""
+
+    def __init__(self, pairs):
+        self.pairs = pairs
+        self.queries = [q for q, _ in pairs]
+
+    def arrays(self):
+        return api.ReferenceDatabase.batch_arrays(self.queries)
+
+    def __len__(self):
+        return len(self.pairs)
+
+    def close(self):
+        pass
+
+
+def object_source(o, batch_size):
+    """--per-object, the harness's first implementation and the reference for the formats: one api.Query per read, all of them loaded before the first is
+    aligned.  -> as native_source, from the real batch count and all queries."""
+    pairs = load_queries(o)
+    max_len = max([len(s) for q, _ in pairs for s in q.sequences] + [1])
+    batches = [ObjectBatch(pairs[s:s + batch_size]) for s in range(0, len(pairs), batch_size)]
+    return batches, len(batches), all(len(q.sequences) == 1 for q, _ in pairs) and max_len <= 320, max_len
+
+
+class ObjectSink:
+    """hostio.Writer's job with one Python object per alignment (sam.records), plus the count behind --out-refs-map-count."""
+
+    def __init__(self, contig_names, sam_file=None, unaligned_file=None, count_refs=False):
+        self._names, self._sam, self._un = contig_names, sam_file, unaligned_file
+        self.stats = hostio.XmioStats()
+        self.refs_map = {} if count_refs else None
+
+    def write(self, batch, result):
+        st = self.stats
+        for k, (q, quals) in enumerate(batch.pairs):
+            comps = result.query_alignments(k)
+            st.num_queries += 1
+            if any(len(c) > 0 for c in comps):
+                st.num_aligned += 1
+                if self.refs_map is not None:  # ReferenceAlignmentCounter [QuickVariants, inferred]: the set of contigs a query's alignments lie on
+                    key = tuple(sorted({self._names[sa.contig] for comp in comps for al in comp for sa in al.components}))
+                    self.refs_map[key] = self.refs_map.get(key, 0) + 1
+                for comp in comps:  # AlignmentCounter [QuickVariants, inferred]: every reported alignment's aligned length, penalty and indels
+                    for al in comp:
+                        for sa in al.components:
+                            st.total_aligned_length += sum(b.lengthA for b in sa.sections)
+                            st.num_indels += sum(1 for b in sa.sections if b.lengthA != b.lengthB)
+                        st.total_penalty += al.penalty
+                if self._sam:
+                    for line in sam.records(q, comps, self._names):
+                        self._sam.write(line + "\n")
+            elif self._un:  # [unpinned format] the query as it came in: FASTQ when it had qualities, else FASTA
+                for name, seq, qual in zip(q.names, q.sequences, quals):
+                    text = api.decode(seq)
+                    self._un.write("@%s\n%s\n+\n%s\n" % (name, text, qual) if qual is not None else ">%s\n%s\n" % (name, text))
+
+    def write_refs_map(self, path):
+        """Mapper.java:747-756 (referenceAlignmentCounter.sumAlignments); [unpinned format]: one line per combination, most frequent first."""
+        with open(path, "w") as f:
+            for key, count in sorted(self.refs_map.items(), key=lambda kv: (-kv[1], kv[0])):
+                f.write("%s\t%d\n" % (",".join(key), count))
+
+
+def stream(db, batches, params, sink, depth, on_aligned=None):
+    """The job: the batches stream through the GPU contexts (align_stream: the copy of batch k + 1 overlaps the alignment of batch k; several contexts align
+    side by side) and a writer thread hands each batch and its result streams to the sink while the next batches are being aligned; at most `depth` results
+    wait for it.  Every batch taken from `batches` is closed, and the first exception - the reader's, the GPU's or the sink's - reaches the caller.
+    -> the queries that were served as copies (BatchResult.copies)."""
+    in_flight = queue.Queue()  # batches in the order they were dealt to the GPUs
+    to_write = queue.Queue(maxsize=depth)
     failure = []
 
     def feed():
-        for b in [first]:
-            in_flight.put(b)
-            yield b.arrays()
-        for b in it:
+        for b in batches:
             in_flight.put(b)
             yield b.arrays()
 
-    def write_loop():
-        try:
-            while True:
-                item = to_write.get()
-                if item is None:
-                    return
-                b, r = item
-                writer.write(b, r)
+    def write_loop():  # (after a failure it keeps taking what comes, unwritten, up to the end mark: the main thread never waits on a full queue for good)
+        for b, r in iter(to_write.get, None):
+            try:
+                if not failure:
+                    sink.write(b, r)
+            except BaseException as e:  # noqa: BLE001  (handed to the main thread)
+                failure.append(e)
+            finally:
                 b.close()
-        except BaseException as e:  # noqa: BLE001  (handed to the main thread)
-            failure.append(e)
 
     wt = threading.Thread(target=write_loop, daemon=True)
     wt.start()
-    import time
-    t_stream = time.perf_counter()
+    copies = 0
+    results = db.align_stream(feed(), params, on_aligned=on_aligned)
     try:
-        for r in db.align_stream(feed(), params):
+        for r in results:
             if failure:
                 break
             copies += r.copies
@@ -344,25 +418,22 @@ def run_streaming(o, params, contigs, out):
     finally:
         to_write.put(None)
         wt.join()
-        db.close()
+        results.close()  # (ends the threads that deal and upload: nothing takes from `batches` after this)
+        while not in_flight.empty():
+            in_flight.get().close()
     if failure:
         raise failure[0]
-    if sam_out is not None and sam_out is not sys.stdout:
-        sam_out.close()
-    if un_out is not None:
-        un_out.close()
-    st = writer.stats
-    n = int(st.num_queries)
-    if o.get("collapse"):
-        report_copies(copies, n)
-    global last_timing
-    last_timing = {"queries": n, "stream_seconds": time.perf_counter() - t_stream, "contexts": len(devices) if devices else 1}  # first read of the query files .. last byte of the outputs (bench.py's end_to_end leg)
+    return copies
+
+
+def write_statistics(out, st):
+    """Mapper.run's statistics lines (Mapper.java:786-796) from the five numbers of hostio.XmioStats."""
+    n = st.num_queries
     out.write("\nStatistics: \n")
     out.write(" Alignment rate                : %d%% of queries (%d/%d)\n" % (st.num_aligned * 100 // n if n else 0, st.num_aligned, n))
     if st.total_aligned_length:
         out.write(" Average penalty               : %s per base (%d/%d) in aligned queries\n" % (java_float(st.total_penalty / st.total_aligned_length), int(st.total_penalty), st.total_aligned_length))
         out.write(" Num indels                    : %s per base (%d/%d) in aligned queries\n" % (java_float(st.num_indels / st.total_aligned_length), st.num_indels, st.total_aligned_length))
-    return 0
 
 
 def report_copies(copies, n):
@@ -370,7 +441,8 @@ def report_copies(copies, n):
     sys.stderr.write("Identical queries: %d of %d queries were served as copies of an identical query of their batch\n" % (copies, n))
 
 
-def run(argv, out=sys.stdout):
+def run(argv, out=sys.stdout, open_database=None):
+    """open_database: called as open_gpu_database is, in its place (tests hand in a database that needs no GPU)."""
     o = parse_args(argv)
     if o["help"] or not argv:
         out.write(__doc__ + "\n")
@@ -382,105 +454,50 @@ def run(argv, out=sys.stdout):
     out.write("%d reference files:\n" % len(o["references"]))
     for path in o["references"]:
         out.write("Reference path = %s\n" % path)
-    if not o.get("out_mutations") and not o.get("out_refs_map_count") and not o.get("per_object"):
-        return run_streaming(o, params, contigs, out)
-    queries = load_queries(o)
     ordered = api.sort_reference(contigs)  # Mapper.sortAndComplementReference: alignment results refer to this order
     names = [n for n, _ in ordered]
-    devices = o.get("devices") or (list(range(o["gpus"])) if o.get("gpus", 1) > 1 else None)
     batch_size = o.get("batch_size") or 1_000_000
-    contexts = o.get("contexts")
-    if contexts is None:
-        # a job of several batches: two contexts per GPU align their batches at the same time (+15-18 % reads per second on MI355X; on reads
-        # from i.i.d. references more contexts add nothing, profiles/r03/NOTES.md; on a repeat-rich reference, whose passes end with a long tail of
-        # few heavy reads, `--contexts 4` gives 1.45x over two, profiles/r04/NOTES.md 13).  Contexts share the index (xm_context_new), so a genome-sized one is no obstacle; they
-        # divide the HBM that is free once it is resident, and a GPU with room for fewer contexts uses fewer (api.divide_scratch)
-        n_batches = (len(queries) + batch_size - 1) // batch_size
-        contexts = 2 if devices is None and n_batches >= 2 else 1
-        # single reads of up to 320 bases in three batches or more: three contexts, each sized for a third of the GPU's wave slots, overlap best (+7 % over
-        # two, profiles/r04/NOTES.md 15; pairs and long reads are within 2 % from two to four contexts)
-        if contexts == 2 and n_batches >= 3 and all(len(q.sequences) == 1 for q, _ in queries) and max(len(s) for q, _ in queries for s in q.sequences) <= 320:
-            contexts = 3
-    if contexts > 1:
-        devices = [d for d in (devices or [o["device"]]) for _ in range(contexts)]
-    max_query_length = max([len(s) for q, _ in queries for s in q.sequences] + [1])
-    if devices and len(devices) > 1:
-        from . import multi
+    per_object = bool(o.get("out_mutations") or o.get("out_refs_map_count") or o.get("per_object"))  # (the outputs that need objects)
+    with contextlib.ExitStack() as job:  # what the job opens is closed here, last opened first, also when a step raises
+        batches, count, single_short, max_len = object_source(o, batch_size) if per_object else native_source(o, batch_size, job)
+        devices = context_devices(o, count, single_short)
         # (--out-mutations: every context accumulates its own pile-up on its GPU - depth 8 B, four alternative counts 32 B and, with a query-end fraction, the
-        # middle depth 8 B per reference base: 149 GB for a 3.1 Gb reference - so the contexts of a GPU are counted with it: api.divide_scratch)
+        # middle depth 8 B per reference base: 149 GB for a 3.1 Gb reference - so the contexts of a GPU are counted with it)
         pile_up = (48 if o.get("query_end_fraction", 0.1) > 0 else 40) * sum(len(t) for _, t in ordered) + (64 << 20) if o.get("out_mutations") else 0
-        db = multi.MultiGpuDatabase(ordered, devices, collapse=o.get("collapse", False), mode="mapper", enable_gapmers=o["enable_gapmers"], max_query_length=max_query_length,
-                                    cache_dir=o.get("cache_dir"), per_context_extra=pile_up)
-    else:
-        db = api.ReferenceDatabase(ordered, mode="mapper", enable_gapmers=o["enable_gapmers"], device=devices[0] if devices else o["device"],
-                                   max_query_length=max_query_length, cache_dir=o.get("cache_dir"))
-        db.set_collapse(o.get("collapse", False))
-    sam_out = None
-    if o["out_sam"]:
-        sam_out = sys.stdout if o["out_sam"] == "-" else open(o["out_sam"], "w")
-        sam_out.write("\n".join(sam_header(contigs)) + "\n")
-    un_out = open(o["out_unaligned"], "w") if o["out_unaligned"] else None
-    num_aligned = total_len = num_indels = 0
-    total_penalty = 0.0
-    refs_map = {} if o.get("out_refs_map_count") else None
-    match_db = None
-    on_aligned = None
-    if o.get("out_mutations"):  # Mapper.java:700-708: the MatchDatabase listens to every batch; here it accumulates on the GPU while the batch is resident
-        from . import pileup
-        match_db = pileup.MatchDatabase(db.replicas if hasattr(db, "replicas") else db, o.get("query_end_fraction", 0.1))  # (default 0.1: Mapper.java:76)
-        on_aligned = lambda replica, first_query, qs: match_db.add_last(qs, replica=replica)  # noqa: E731
-    results = db.align_batches([q for q, _ in queries], params, batch_size, on_aligned=on_aligned)
-    first, result, nxt = 0, None, 0
-    copies = 0
-    for qi, (q, quals) in enumerate(queries):
-        if qi >= nxt:  # the next batch's results (queries are written in input order)
-            first, result = next(results)
-            nxt = first + len(result)
-            copies += result.copies
-        comps = result.query_alignments(qi - first)
-        aligned = any(len(c) > 0 for c in comps)
-        if aligned:
-            num_aligned += 1
-            if refs_map is not None:  # ReferenceAlignmentCounter [QuickVariants, inferred]: the set of contigs a query's alignments lie on
-                key = tuple(sorted({names[sa.contig] for comp in comps for al in comp for sa in al.components}))
-                refs_map[key] = refs_map.get(key, 0) + 1
-            for comp in comps:  # AlignmentCounter [QuickVariants, inferred]: every reported alignment's aligned length, penalty and indels
-                for al in comp:
-                    for k, sa in enumerate(al.components):
-                        total_len += sum(b.lengthA for b in sa.sections)
-                        num_indels += sum(1 for b in sa.sections if b.lengthA != b.lengthB)
-                    total_penalty += al.penalty
-            if sam_out:
-                for line in sam.records(q, comps, names):
-                    sam_out.write(line + "\n")
-        elif un_out:  # [unpinned format] the query as it came in: FASTQ when it had qualities, else FASTA
-            for name, seq, qual in zip(q.names, q.sequences, quals):
-                text = api.decode(seq)
-                un_out.write("@%s\n%s\n+\n%s\n" % (name, text, qual) if qual is not None else ">%s\n%s\n" % (name, text))
-    if sam_out and sam_out is not sys.stdout:
-        sam_out.close()
-    if un_out:
-        un_out.close()
-    if refs_map is not None:  # Mapper.java:747-756 (referenceAlignmentCounter.sumAlignments); [unpinned format]: one line per combination, most frequent first
-        with open(o["out_refs_map_count"], "w") as f:
-            for key, count in sorted(refs_map.items(), key=lambda kv: (-kv[1], kv[0])):
-                f.write("%s\t%d\n" % (",".join(key), count))
-    if match_db is not None:  # Mapper.java:758-785
-        with open(o["out_mutations"], "w") as f:
-            filt = pileup.MutationDetectionParameters.defaultFilter()  # Mapper.java:56; --snp-threshold etc. override it
-            for k, v in o.get("mutation_filter", {}).items():
-                setattr(filt, k, v)
-            match_db.write_mutations(f, filt)
-        match_db.close()
-    n = len(queries)
+        db = (open_database or open_gpu_database)(ordered, devices, max_len, enable_gapmers=o["enable_gapmers"], collapse=o.get("collapse", False),
+                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up)
+        job.callback(db.close)
+        sam_out = un_out = None
+        if o["out_sam"]:
+            sam_out = sys.stdout if o["out_sam"] == "-" else job.enter_context(open(o["out_sam"], "w"))
+            sam_out.write("\n".join(sam_header(contigs)) + "\n")
+        if o["out_unaligned"]:
+            un_out = job.enter_context(open(o["out_unaligned"], "w"))
+        sink = ObjectSink(names, sam_out, un_out, bool(o.get("out_refs_map_count"))) if per_object else hostio.Writer(names, sam_out, un_out)
+        match_db = on_aligned = None
+        if o.get("out_mutations"):  # Mapper.java:700-708: the MatchDatabase listens to every batch; here it accumulates on the GPU while the batch is resident
+            from . import pileup
+            match_db = pileup.MatchDatabase(db.replicas if hasattr(db, "replicas") else db, o.get("query_end_fraction", 0.1))  # (default 0.1: Mapper.java:76)
+            job.callback(match_db.close)
+
+            def on_aligned(*at):  # ReferenceDatabase.align_stream calls it with (batch), MultiGpuDatabase's with (replica, batch), on the replica's thread
+                match_db.add_last(batches[at[-1]].queries, replica=at[0] if len(at) > 1 else 0)
+        t_stream = time.perf_counter()
+        copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned)
+        if o.get("out_refs_map_count"):
+            sink.write_refs_map(o["out_refs_map_count"])
+        if match_db is not None:  # Mapper.java:758-785
+            with open(o["out_mutations"], "w") as f:
+                filt = pileup.MutationDetectionParameters.defaultFilter()  # Mapper.java:56; --snp-threshold etc. override it
+                for k, v in o.get("mutation_filter", {}).items():
+                    setattr(filt, k, v)
+                match_db.write_mutations(f, filt)
+    n = int(sink.stats.num_queries)
+    global last_timing
+    last_timing = {"queries": n, "stream_seconds": time.perf_counter() - t_stream, "contexts": len(devices)}  # first batch to the GPUs .. last byte of the outputs (bench.py's end_to_end leg)
     if o.get("collapse"):
         report_copies(copies, n)
-    out.write("\nStatistics: \n")
-    out.write(" Alignment rate                : %d%% of queries (%d/%d)\n" % (num_aligned * 100 // n if n else 0, num_aligned, n))
-    if total_len:
-        out.write(" Average penalty               : %s per base (%d/%d) in aligned queries\n" % (java_float(total_penalty / total_len), int(total_penalty), total_len))
-        out.write(" Num indels                    : %s per base (%d/%d) in aligned queries\n" % (java_float(num_indels / total_len), num_indels, total_len))
-    db.close()
+    write_statistics(out, sink.stats)
     return 0
 
 

@@ -14,6 +14,8 @@ histograms are summed on the host in fixed rank order as BASELINE.json's north_s
 import queue
 import threading
 
+import numpy as np
+
 
 class MultiGpuDatabase:
     def __init__(self, contigs, devices, collapse=False, **kw):
@@ -144,9 +146,6 @@ class MultiGpuDatabase:
         hook = (lambda g, k: on_aligned(g, starts[k], queries[starts[k]:starts[k] + batch_size])) if on_aligned else None
         for s, r in zip(starts, self.align_stream(arrays, parameters, on_aligned=hook)):
             yield s, r
-
-
-import numpy as np  # noqa: E402
 
 
 def shard_range(nq, rank, world):

@@ -112,7 +112,7 @@ def test_examples_through_the_command_line(tmp_path):
 
 @pytest.mark.gpu
 def test_streaming_harness_equals_the_per_object_harness(tmp_path):
-    """The harness without an object per read (native reader and SAM formatter, batches streamed through several contexts: cli.run_streaming) writes the
+    """The harness without an object per read (native reader and SAM formatter, batches streamed through several contexts: cli.stream over hostio's reader and Writer) writes the
     files of the per-object harness (--per-object: api.Query, sam.records - the reference for the formats) byte for byte: single reads from FASTQ with
     unaligned queries kept, pairs with --spacing, long reads cut by --split-queries-past-size; batches smaller than the job, two contexts."""
     import numpy as np
@@ -143,3 +143,25 @@ def test_streaming_harness_equals_the_per_object_harness(tmp_path):
         assert outs["stream"][1] == outs["object"][1], name
         assert outs["stream"][2] == outs["object"][2], name   # the statistics lines
         assert outs["stream"][0].count("\n") > {"single": 4000, "paired": 4000, "split": 100}[name] and (name != "single" or outs["stream"][1].count("@r") >= 250)
+
+
+@pytest.mark.gpu
+def test_default_contexts_on_both_paths(tmp_path):
+    """No --contexts flag and three batches, the smallest job at which the default rule gives both paths more than one context (cli.default_contexts: three
+    for single reads of 150 bases): the native path and --per-object write the same SAM and the same statistics."""
+    import numpy as np
+    from mapper_amd import synth
+    ref = synth.synthetic_reference(120_000, seed=0xEC011)
+    dec = np.frombuffer(b"?ACMGRSVTWYHKDBN", dtype=np.uint8)
+    (tmp_path / "ref.fa").write_text(">chrA\n%s\n" % dec[ref].tobytes().decode())
+    reads = synth.synthetic_single_end(ref, 300, seed=15)[0]
+    (tmp_path / "se.fq").write_text("".join("@r%d\n%s\n+\n%s\n" % (i, dec[r].tobytes().decode(), "I" * len(r)) for i, r in enumerate(reads)))
+    outs = {}
+    for mode in ("native", "object"):
+        sam_path, log = str(tmp_path / (mode + ".sam")), io.StringIO()
+        argv = ["--reference", str(tmp_path / "ref.fa"), "--queries", str(tmp_path / "se.fq"), "--out-sam", sam_path, "--batch-size", "100"]
+        assert cli.run(argv + (["--per-object"] if mode == "object" else []), out=log) == 0
+        assert cli.last_timing["contexts"] == 3 and cli.last_timing["queries"] == 300, mode
+        outs[mode] = (open(sam_path).read(), log.getvalue())
+    assert outs["native"] == outs["object"]
+    assert outs["native"][0].count("\n") > 250 and "/300)" in outs["native"][1]   # (the comparison is not of two empty files)
