@@ -33,7 +33,7 @@
 #include <cstdlib>
 #include <cstdio>
 
-namespace xm { bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device); }  // xm_index_device.hip
+namespace xm { bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device, const BuildKnobs& knobs); }  // xm_index_device.hip
 using namespace xm;
 
 namespace {

@@ -189,8 +189,6 @@ __global__ void xmb_widen_kernel(const uint32_t* in, unsigned long long n, unsig
   if (r < n) out[r] = in[r];
 }
 
-struct TableDesc { unsigned long long bucketBase; int32_t capacity, maxCount; };  // bucketBase: first of the table's capacity + 1 offset entries in the group
-
 XM_INL int xmbTableOf(const TableDesc* t, int nTables, unsigned long long j) {  // table whose offset entries contain j
   int lo = 0, hi = nTables - 1;
   while (lo < hi) { int mid = (lo + hi + 1) >> 1; if (t[mid].bucketBase <= j) lo = mid; else hi = mid - 1; }
@@ -292,76 +290,99 @@ __global__ void __launch_bounds__(256) xmb_dup_candidates_kernel(DupArgs a, unsi
 
 static inline unsigned gridFor(unsigned long long n, int block = 256) { return (unsigned)((n + (unsigned long long)block - 1) / (unsigned long long)block); }
 
-static void scanU64(BuildBuf<uint8_t>& temp, const unsigned long long* in, unsigned long long* out, size_t n, hipStream_t s) {
+// rocPRIM's two-call idiom: call(nullptr, bytes) says how much temporary storage the operation wants, call(temp, bytes) runs it
+template <typename Call>
+static void withTemp(BuildBuf<uint8_t>& temp, Call call) {
   size_t bytes = 0;
-  XMB_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, out, 0ull, n, rocprim::plus<unsigned long long>(), s));
+  XMB_CHECK(call((void*)nullptr, bytes));
   temp.ensure(bytes);
-  XMB_CHECK(rocprim::exclusive_scan(temp.p, bytes, in, out, 0ull, n, rocprim::plus<unsigned long long>(), s));
+  XMB_CHECK(call((void*)temp.p, bytes));
+}
+template <typename In, typename T>
+static void exclusiveScan(BuildBuf<uint8_t>& temp, In in, T* out, size_t n, hipStream_t s) {
+  withTemp(temp, [&](void* t, size_t& bytes) { return rocprim::exclusive_scan(t, bytes, in, out, T(0), n, rocprim::plus<T>(), s); });
+}
+static void scanU32(BuildBuf<uint8_t>& temp, uint32_t* in, uint32_t* out, size_t n, hipStream_t s) { exclusiveScan(temp, in, out, n, s); }
+static void scanU64(BuildBuf<uint8_t>& temp, const unsigned long long* in, unsigned long long* out, size_t n, hipStream_t s) { exclusiveScan(temp, in, out, n, s); }
+// stable sort of (key, value) pairs by the low `bits` bits of the key
+static void sortPairs(BuildBuf<uint8_t>& temp, unsigned long long* keyIn, unsigned long long* keyOut, unsigned long long* valIn, unsigned long long* valOut, size_t n, unsigned bits, hipStream_t s) {
+  withTemp(temp, [&](void* t, size_t& bytes) { return rocprim::radix_sort_pairs(t, bytes, keyIn, keyOut, valIn, valOut, n, 0, bits, s); });
 }
 
-// hashLengths(minLen, maxLen) of xm_index_host.h on the GPU.  false: not done (the caller hashes on the host).
-bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device) {
-  const bool trace = getenv("XM_TRACE_BUILD") != nullptr;
-  auto t0 = std::chrono::steady_clock::now();
-  XMB_CHECK(hipSetDevice(device));
+// (XM_TRACE_BUILD) seconds per stage of the groups; the stream is synchronised at the marks then
+struct StageTimer {
+  bool on = false;
   hipStream_t s = nullptr;
-  XMB_CHECK(hipStreamCreate(&s));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{s};
-
-  // capacities and per-key limits exactly as the host builder chooses them
-  std::vector<int32_t> capacity((size_t)maxLen + 1, 0), maxCount((size_t)maxLen + 1, 0);
-  const int lo = std::max(minLen, h.minInterestingSize);
-  for (int L = lo; L <= maxLen; L++) {
-    int cap = h.estimateRequiredCapacity(L);
-    if (cap < 1) cap = 1;
-    if (cap > INT32_MAX / 2) cap = INT32_MAX / 2;  // M/PackedMap.java:22-25
-    capacity[(size_t)L] = cap;
-    int mx = L * L;  // M/HashBlock_Database.java:569-576
-    if (mx < h.maxNumShortMatches) mx = h.maxNumShortMatches;
-    if (mx > 32766) mx = 32766;
-    if (mx < 1) mx = 1;
-    maxCount[(size_t)L] = mx;
+  std::chrono::steady_clock::time_point from;
+  double hash = 0, sort = 0, csr = 0, dup = 0, copy = 0;
+  void start() { from = std::chrono::steady_clock::now(); }
+  void mark(double& acc) {
+    if (!on) return;
+    (void)hipStreamSynchronize(s);
+    auto now = std::chrono::steady_clock::now();
+    acc += std::chrono::duration<double>(now - from).count();
+    from = now;
   }
+};
 
+// One build of the tables [minLen, maxLen]: the stream, the device buffers (kept from group to group) and the plan; deviceHashLengths runs its steps.
+struct DeviceBuild {
+  struct Stream { hipStream_t h = nullptr; operator hipStream_t() const { return h; } ~Stream() { if (h) (void)hipStreamDestroy(h); } };
+  struct Records { unsigned long long* key; unsigned long long* pos; unsigned long long n; };  // a group's records on the device
+
+  HostIndex& h;
+  const int minLen, maxLen, lo;
+  const BuildKnobs knobs;
+  Stream s;  // (before the buffers: destroyed after them)
+  StageTimer timer;
+  // capacities and per-key limits exactly as the host builder chooses them (xm_index_plan.h)
+  std::vector<TableShape> shapes;
+  // reference with ambiguity codes: the multi blocks' records come from the host (windows around the ambiguous bases), the GPU skips every block
+  // over an ambiguous base (prefix counts of the ambiguous bases of the contig being hashed)
+  bool amb = false;
+  std::vector<std::vector<HostIndex::Rec>> multiRecs;
+  std::vector<char> contigAmb;
   BuildBuf<uint8_t> dCodes, dTemp;
   BuildBuf<int32_t> dCapacity;
   BuildBuf<HBlock> dCur, dNext;
-  BuildBuf<uint32_t> dFlag, dOffset;
+  BuildBuf<uint32_t> dFlag, dOffset, dAmbFlag, dAmbPrefix;
   BuildBuf<unsigned long long> dHist;
   BuildBuf<LevelCtl> dCtl;
-  dCodes.ensure(h.refCodes.size());
-  XMB_CHECK(hipMemcpyAsync(dCodes.p, h.refCodes.data(), h.refCodes.size(), hipMemcpyHostToDevice, s));
-  dCapacity.ensure(capacity.size());
-  XMB_CHECK(hipMemcpyAsync(dCapacity.p, capacity.data(), capacity.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  dHist.ensure((size_t)maxLen + 1);
-  XMB_CHECK(hipMemsetAsync(dHist.p, 0, ((size_t)maxLen + 1) * sizeof(unsigned long long), s));
-  dCtl.ensure(1);
-  XMB_CHECK(hipMemsetAsync(dCtl.p, 0, sizeof(LevelCtl), s));
-  int32_t longest = 0;
-  for (int c = 0; c < h.numContigs(); c++) longest = std::max(longest, h.contigLen[(size_t)c]);
-  dCur.ensure((size_t)longest); dNext.ensure((size_t)longest); dFlag.ensure((size_t)longest); dOffset.ensure((size_t)longest);
-
+  // a group's records (hashContigs writes the A pair, at most recCap of them) and its tables
   BuildBuf<unsigned long long> dKeyA, dPosA, dKeyB, dPosB;
   unsigned long long recCap = 0;
+  BuildBuf<TableDesc> dTables;
+  BuildBuf<unsigned long long> dRaw, dRawOff, dStored, dStoredOff, dTableStored, dOutPos;
+  BuildBuf<uint32_t> dBucketOff;
 
-  // reference with ambiguity codes: the multi blocks' records come from the host (windows around the ambiguous bases), the GPU skips every block
-  // over an ambiguous base (prefix counts of the ambiguous bases of the contig being hashed)
-  const bool amb = h.referenceIsAmbiguous();
-  std::vector<std::vector<HostIndex::Rec>> multiRecs((size_t)maxLen + 1);
-  std::vector<char> contigAmb((size_t)h.numContigs(), 0);
-  BuildBuf<uint32_t> dAmbFlag, dAmbPrefix;
-  if (amb) {
-    std::vector<int> capInt(capacity.begin(), capacity.end());
-    h.multiRecordsNearAmbiguity(lo, maxLen, capInt, multiRecs);
-    for (int c = 0; c < h.numContigs(); c++) {
-      const uint8_t* b = h.refCodes.data() + h.contigStart[(size_t)c];
-      for (int32_t i = 0; i < h.contigLen[(size_t)c]; i++) if (bpIsAmbiguous(b[i])) { contigAmb[(size_t)c] = 1; break; }
+  DeviceBuild(HostIndex& h_, int minLen_, int maxLen_, int device, const BuildKnobs& knobs_)
+      : h(h_), minLen(minLen_), maxLen(maxLen_), lo(std::max(minLen_, h_.minInterestingSize)), knobs(knobs_), multiRecs((size_t)maxLen_ + 1), contigAmb((size_t)h_.numContigs(), 0) {
+    XMB_CHECK(hipSetDevice(device));
+    XMB_CHECK(hipStreamCreate(&s.h));
+    timer.on = knobs.trace; timer.s = s;
+    shapes = tableShapes(lo, maxLen, h.maxNumShortMatches, [this](int L) { return h.estimateRequiredCapacity(L); });
+    const std::vector<int32_t> capacity = capacitiesOf(shapes);
+    dCodes.ensure(h.refCodes.size());
+    XMB_CHECK(hipMemcpyAsync(dCodes.p, h.refCodes.data(), h.refCodes.size(), hipMemcpyHostToDevice, s));
+    dCapacity.ensure(capacity.size());
+    XMB_CHECK(hipMemcpyAsync(dCapacity.p, capacity.data(), capacity.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    dHist.ensure((size_t)maxLen + 1);
+    XMB_CHECK(hipMemsetAsync(dHist.p, 0, ((size_t)maxLen + 1) * sizeof(unsigned long long), s));
+    dCtl.ensure(1);
+    XMB_CHECK(hipMemsetAsync(dCtl.p, 0, sizeof(LevelCtl), s));
+    int32_t longest = 0;
+    for (int c = 0; c < h.numContigs(); c++) longest = std::max(longest, h.contigLen[(size_t)c]);
+    dCur.ensure((size_t)longest); dNext.ensure((size_t)longest); dFlag.ensure((size_t)longest); dOffset.ensure((size_t)longest);
+    amb = h.referenceIsAmbiguous();
+    if (amb) {
+      h.multiRecordsNearAmbiguity(lo, maxLen, capacity, multiRecs, knobs);
+      for (int c = 0; c < h.numContigs(); c++) contigAmb[(size_t)c] = h.contigIsAmbiguous(c) ? 1 : 0;
+      dAmbFlag.ensure((size_t)longest + 1); dAmbPrefix.ensure((size_t)longest + 1);
     }
-    dAmbFlag.ensure((size_t)longest + 1); dAmbPrefix.ensure((size_t)longest + 1);
   }
 
-  // every level of every contig: counting run (emit = 0) or the records of the tables [gLo, gHi]
-  auto hashAll = [&](int emit, int gLo, int gHi) {
+  // every level of every contig: counting run (emit = 0: records per table into dHist) or the records of the tables [g.gLo, g.gHi] into dKeyA / dPosA
+  void hashContigs(int emit, const TableGroup& g) {
     for (int c = 0; c < h.numContigs(); c++) {
       long long n = h.contigLen[(size_t)c];
       const uint8_t* contig = dCodes.p + h.contigStart[(size_t)c];
@@ -369,10 +390,7 @@ bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device) {
       const uint32_t* ambPrefix = nullptr;
       if (amb && contigAmb[(size_t)c]) {
         hipLaunchKernelGGL(xmb_amb_flag_kernel, dim3(gridFor((unsigned long long)n + 1)), dim3(256), 0, s, contig, n, dAmbFlag.p);
-        size_t bytes = 0;
-        XMB_CHECK(rocprim::exclusive_scan(nullptr, bytes, dAmbFlag.p, dAmbPrefix.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
-        dTemp.ensure(bytes);
-        XMB_CHECK(rocprim::exclusive_scan(dTemp.p, bytes, dAmbFlag.p, dAmbPrefix.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
+        scanU32(dTemp, dAmbFlag.p, dAmbPrefix.p, (size_t)n + 1, s);
         ambPrefix = dAmbPrefix.p;
       }
       HBlock* cur = dCur.p;
@@ -381,15 +399,12 @@ bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device) {
         XMB_CHECK(hipMemsetAsync(&dCtl.p->nNext, 0, sizeof(unsigned long long) + sizeof(unsigned int), s));  // nNext, anyShort
         LevelArgs a;
         a.cur = cur; a.n = n; a.contig = contig; a.contigLen = h.contigLen[(size_t)c]; a.enableGapmers = h.enableGapmers; a.lo = lo; a.maxLen = maxLen;
-        a.gLo = gLo; a.gHi = gHi; a.emit = emit; a.capacity = dCapacity.p;
+        a.gLo = g.gLo; a.gHi = g.gHi; a.emit = emit; a.capacity = dCapacity.p;
         a.fwdBase = h.encodePosition(c, false, 0); a.rcBase = h.encodePosition(c, true, 0);
         a.hist = dHist.p; a.recKey = dKeyA.p; a.recPos = dPosA.p; a.recCap = recCap; a.mergeFlag = dFlag.p; a.ctl = dCtl.p;
         a.ambPrefix = ambPrefix; a.posShift = amb ? 1 : 0;
         hipLaunchKernelGGL(xmb_level_kernel, dim3(gridFor((unsigned long long)n)), dim3(256), 0, s, a);
-        size_t bytes = 0;
-        XMB_CHECK(rocprim::exclusive_scan(nullptr, bytes, dFlag.p, dOffset.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
-        dTemp.ensure(bytes);
-        XMB_CHECK(rocprim::exclusive_scan(dTemp.p, bytes, dFlag.p, dOffset.p, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
+        scanU32(dTemp, dFlag.p, dOffset.p, (size_t)n, s);
         hipLaunchKernelGGL(xmb_merge_kernel, dim3(gridFor((unsigned long long)n)), dim3(256), 0, s, cur, n, dFlag.p, dOffset.p, next, dCtl.p);
         XMB_CHECK(hipGetLastError());
         LevelCtl ctl;
@@ -401,122 +416,82 @@ bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device) {
         std::swap(cur, next);
       }
     }
-  };
+  }
 
-  hashAll(0, 0, 0);
-  std::vector<unsigned long long> hist((size_t)maxLen + 1);
-  XMB_CHECK(hipMemcpy(hist.data(), dHist.p, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  for (int L = 0; L <= maxLen; L++) hist[(size_t)L] += multiRecs[(size_t)L].size();
-  auto t1 = std::chrono::steady_clock::now();
+  // records per table: the GPU's counting run + the host's multi records
+  std::vector<unsigned long long> countRecords() {
+    hashContigs(0, TableGroup{0, 0, 0});
+    std::vector<unsigned long long> hist((size_t)maxLen + 1);
+    XMB_CHECK(hipMemcpy(hist.data(), dHist.p, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (int L = 0; L <= maxLen; L++) hist[(size_t)L] += multiRecs[(size_t)L].size();
+    return hist;
+  }
 
-  // groups of consecutive tables whose records fit the budget (a sort needs both record arrays twice + its own scratch)
-  size_t freeB = 0, totalB = 0;
-  XMB_CHECK(hipMemGetInfo(&freeB, &totalB));
-  unsigned long long budgetRecs = (unsigned long long)(freeB / 2) / 40;
-  if (const char* e = getenv("XM_BUILD_GROUP_RECORDS")) { if (*e) budgetRecs = strtoull(e, nullptr, 10); }  // (testing: force several groups)
-  if (budgetRecs < 1) budgetRecs = 1;
+  unsigned long long groupBudget() {
+    size_t freeB = 0, totalB = 0;
+    XMB_CHECK(hipMemGetInfo(&freeB, &totalB));
+    return knobs.groupRecordsSet ? knobs.groupRecords : recordBudget(freeB);
+  }
 
-  if ((int)h.tables.size() < maxLen + 1) h.tables.resize((size_t)maxLen + 1);
-  BuildBuf<TableDesc> dTables;
-  BuildBuf<unsigned long long> dRaw, dRawOff, dStored, dStoredOff, dTableStored, dOutPos;
-  BuildBuf<uint32_t> dBucketOff;
-  int groups = 0;
-  unsigned long long totalRecs = 0;
-  double tHash = 0, tSort = 0, tCsr = 0, tDup = 0, tCopy = 0;  // (XM_TRACE_BUILD) seconds per stage; the stream is synchronised at the marks then
-  auto mark = [&](double& acc, std::chrono::steady_clock::time_point& from) {
-    if (!trace) return;
-    (void)hipStreamSynchronize(s);
-    auto now = std::chrono::steady_clock::now();
-    acc += std::chrono::duration<double>(now - from).count();
-    from = now;
-  };
-  for (int gLo = minLen; gLo <= maxLen;) {
-    int gHi = gLo;
-    unsigned long long nRecs = hist[(size_t)gLo];
-    while (gHi + 1 <= maxLen && nRecs + hist[(size_t)(gHi + 1)] <= budgetRecs) { gHi++; nRecs += hist[(size_t)gHi]; }
-    groups++;
-    totalRecs += nRecs;
-    const int nTables = gHi - gLo + 1;
-    std::vector<TableDesc> tdesc((size_t)nTables);
-    unsigned long long nEntries = 0;
-    for (int k = 0; k < nTables; k++) {
-      const int L = gLo + k;
-      const bool empty = hist[(size_t)L] == 0;
-      tdesc[(size_t)k].bucketBase = nEntries;
-      tdesc[(size_t)k].capacity = empty ? 1 : capacity[(size_t)L];  // PackedMap(1, 1) placeholder (M/HashBlock_Database.java:387-393)
-      tdesc[(size_t)k].maxCount = empty ? 1 : maxCount[(size_t)L];
-      nEntries += (unsigned long long)tdesc[(size_t)k].capacity + 1;
+  void uploadTables(const GroupLayout& lay) {
+    dTables.ensure(lay.tables.size());
+    XMB_CHECK(hipMemcpyAsync(dTables.p, lay.tables.data(), sizeof(TableDesc) * lay.tables.size(), hipMemcpyHostToDevice, s));
+  }
+
+  // the group's g.nRecs > 0 records into dKeyA / dPosA: the GPU's, and behind them the multi blocks' (host windows)
+  void emitGroupRecords(const TableGroup& g) {
+    recCap = g.nRecs;
+    dKeyA.ensure((size_t)g.nRecs); dPosA.ensure((size_t)g.nRecs); dKeyB.ensure((size_t)g.nRecs); dPosB.ensure((size_t)g.nRecs);
+    XMB_CHECK(hipMemsetAsync(dCtl.p, 0, sizeof(LevelCtl), s));
+    hashContigs(1, g);
+    LevelCtl ctl;
+    XMB_CHECK(hipMemcpy(&ctl, dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> hk, hp;
+    for (int L = g.gLo; L <= g.gHi; L++)
+      for (const HostIndex::Rec& r : multiRecs[(size_t)L]) { hk.push_back(sortKeyWord(L - g.gLo, r.bucket)); hp.push_back(sortPosWord(r.pos)); }
+    if (ctl.nRec + hk.size() != g.nRecs) throw std::runtime_error("internal error: index build counted " + std::to_string(g.nRecs) + " records and emitted " + std::to_string(ctl.nRec + hk.size()));
+    if (!hk.empty()) {
+      XMB_CHECK(hipMemcpyAsync(dKeyA.p + ctl.nRec, hk.data(), sizeof(unsigned long long) * hk.size(), hipMemcpyHostToDevice, s));
+      XMB_CHECK(hipMemcpyAsync(dPosA.p + ctl.nRec, hp.data(), sizeof(unsigned long long) * hp.size(), hipMemcpyHostToDevice, s));
+      XMB_CHECK(hipStreamSynchronize(s));
     }
-    dTables.ensure((size_t)nTables);
-    XMB_CHECK(hipMemcpyAsync(dTables.p, tdesc.data(), sizeof(TableDesc) * (size_t)nTables, hipMemcpyHostToDevice, s));
-    unsigned long long* sortedKey = nullptr;
-    unsigned long long* sortedPos = nullptr;
-    if (nRecs > 0) {
-      auto tm = std::chrono::steady_clock::now();
-      recCap = nRecs;
-      dKeyA.ensure((size_t)nRecs); dPosA.ensure((size_t)nRecs); dKeyB.ensure((size_t)nRecs); dPosB.ensure((size_t)nRecs);
-      XMB_CHECK(hipMemsetAsync(dCtl.p, 0, sizeof(LevelCtl), s));
-      hashAll(1, gLo, gHi);
-      LevelCtl ctl;
-      XMB_CHECK(hipMemcpy(&ctl, dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost));
-      unsigned long long hostRecs = 0;
-      for (int L = gLo; L <= gHi; L++) hostRecs += multiRecs[(size_t)L].size();
-      if (ctl.nRec + hostRecs != nRecs) throw std::runtime_error("internal error: index build counted " + std::to_string(nRecs) + " records and emitted " + std::to_string(ctl.nRec + hostRecs));
-      if (hostRecs > 0) {  // the multi blocks' records (host windows) behind the GPU's: key = (table, bucket), position << 1 | 1
-        std::vector<unsigned long long> hk((size_t)hostRecs), hp((size_t)hostRecs);
-        size_t at = 0;
-        for (int L = gLo; L <= gHi; L++)
-          for (const HostIndex::Rec& r : multiRecs[(size_t)L]) {
-            hk[at] = ((unsigned long long)(unsigned)(L - gLo) << 32) | r.bucket;
-            hp[at] = ((r.pos & ~HostIndex::REC_MULTI) << 1) | 1ull;
-            at++;
-          }
-        XMB_CHECK(hipMemcpyAsync(dKeyA.p + ctl.nRec, hk.data(), sizeof(unsigned long long) * hk.size(), hipMemcpyHostToDevice, s));
-        XMB_CHECK(hipMemcpyAsync(dPosA.p + ctl.nRec, hp.data(), sizeof(unsigned long long) * hp.size(), hipMemcpyHostToDevice, s));
-        XMB_CHECK(hipStreamSynchronize(s));
-      }
-      mark(tHash, tm);
-      // (L, bucket, position): stable sort by position, then by (L, bucket)
-      unsigned posBits = 1;
-      while (posBits < 64 && ((unsigned long long)h.seqCumStart.back() >> posBits) != 0) posBits++;
-      if (amb) posBits++;  // (positions are shifted left by one, bit 0 = multi: single before multi at the same position)
-      unsigned tableBits = 1;
-      while ((1 << tableBits) < nTables) tableBits++;
-      size_t bytes = 0;
-      XMB_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, dPosA.p, dPosB.p, dKeyA.p, dKeyB.p, (size_t)nRecs, 0, posBits, s));
-      dTemp.ensure(bytes);
-      XMB_CHECK(rocprim::radix_sort_pairs(dTemp.p, bytes, dPosA.p, dPosB.p, dKeyA.p, dKeyB.p, (size_t)nRecs, 0, posBits, s));
-      XMB_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, dKeyB.p, dKeyA.p, dPosB.p, dPosA.p, (size_t)nRecs, 0, 32 + tableBits, s));
-      dTemp.ensure(bytes);
-      XMB_CHECK(rocprim::radix_sort_pairs(dTemp.p, bytes, dKeyB.p, dKeyA.p, dPosB.p, dPosA.p, (size_t)nRecs, 0, 32 + tableBits, s));
-      sortedKey = dKeyA.p; sortedPos = dPosA.p;
-      if (amb) {  // duplicate suppression of the multi records, positions back to their plain form, records compacted into the other pair of arrays
-        BuildBuf<uint32_t> dKeep;
-        BuildBuf<unsigned long long> dKeep64, dSlot;
-        dKeep.ensure((size_t)nRecs); dKeep64.ensure((size_t)nRecs); dSlot.ensure((size_t)nRecs);
-        hipLaunchKernelGGL(xmb_keep_kernel, dim3(gridFor(nRecs)), dim3(256), 0, s, sortedKey, sortedPos, nRecs, dKeep.p);
-        hipLaunchKernelGGL(xmb_widen_kernel, dim3(gridFor(nRecs)), dim3(256), 0, s, dKeep.p, nRecs, dKeep64.p);
-        scanU64(dTemp, dKeep64.p, dSlot.p, (size_t)nRecs, s);
-        hipLaunchKernelGGL(xmb_compact_kernel, dim3(gridFor(nRecs)), dim3(256), 0, s, sortedKey, sortedPos, nRecs, dKeep.p, dSlot.p, dKeyB.p, dPosB.p);
-        XMB_CHECK(hipGetLastError());
-        unsigned long long lastSlot = 0;
-        uint32_t lastKeep = 0;
-        XMB_CHECK(hipMemcpyAsync(&lastSlot, dSlot.p + (nRecs - 1), sizeof(lastSlot), hipMemcpyDeviceToHost, s));
-        XMB_CHECK(hipMemcpyAsync(&lastKeep, dKeep.p + (nRecs - 1), sizeof(lastKeep), hipMemcpyDeviceToHost, s));
-        XMB_CHECK(hipStreamSynchronize(s));
-        totalRecs -= nRecs;
-        nRecs = lastSlot + lastKeep;
-        totalRecs += nRecs;
-        sortedKey = dKeyB.p; sortedPos = dPosB.p;
-      }
-      mark(tSort, tm);
-    }
-    auto tm2 = std::chrono::steady_clock::now();
-    // CSR: records per bucket, what each bucket stores, offsets, slots
+  }
+
+  // (L, bucket, position): stable sort by position, then by (L, bucket); the sorted records are in the A pair again
+  Records sortGroup(unsigned long long nRecs, int nTables) {
+    const SortKeyBits bits = sortKeyBits((unsigned long long)h.seqCumStart.back(), amb, nTables);
+    sortPairs(dTemp, dPosA.p, dPosB.p, dKeyA.p, dKeyB.p, (size_t)nRecs, bits.posBits, s);
+    sortPairs(dTemp, dKeyB.p, dKeyA.p, dPosB.p, dPosA.p, (size_t)nRecs, 32 + bits.tableBits, s);
+    return Records{dKeyA.p, dPosA.p, nRecs};
+  }
+
+  // reference with ambiguity codes: duplicate suppression of the multi records, positions back to their plain form, records compacted into the B pair
+  Records dropRepeatedMultiRecords(const Records& in) {
+    BuildBuf<uint32_t> dKeep;
+    BuildBuf<unsigned long long> dKeep64, dSlot;
+    dKeep.ensure((size_t)in.n); dKeep64.ensure((size_t)in.n); dSlot.ensure((size_t)in.n);
+    hipLaunchKernelGGL(xmb_keep_kernel, dim3(gridFor(in.n)), dim3(256), 0, s, in.key, in.pos, in.n, dKeep.p);
+    hipLaunchKernelGGL(xmb_widen_kernel, dim3(gridFor(in.n)), dim3(256), 0, s, dKeep.p, in.n, dKeep64.p);
+    scanU64(dTemp, dKeep64.p, dSlot.p, (size_t)in.n, s);
+    hipLaunchKernelGGL(xmb_compact_kernel, dim3(gridFor(in.n)), dim3(256), 0, s, in.key, in.pos, in.n, dKeep.p, dSlot.p, dKeyB.p, dPosB.p);
+    XMB_CHECK(hipGetLastError());
+    unsigned long long lastSlot = 0;
+    uint32_t lastKeep = 0;
+    XMB_CHECK(hipMemcpyAsync(&lastSlot, dSlot.p + (in.n - 1), sizeof(lastSlot), hipMemcpyDeviceToHost, s));
+    XMB_CHECK(hipMemcpyAsync(&lastKeep, dKeep.p + (in.n - 1), sizeof(lastKeep), hipMemcpyDeviceToHost, s));
+    XMB_CHECK(hipStreamSynchronize(s));
+    return Records{dKeyB.p, dPosB.p, lastSlot + lastKeep};
+  }
+
+  // CSR: records per bucket, what each bucket stores, offsets, slots -> what every table stores (the positions are in dOutPos, the offset entries in dBucketOff)
+  struct Cut { std::vector<unsigned long long> tableStored; unsigned long long groupStored; };
+  Cut cutCsr(const Records& r, const GroupLayout& lay) {
+    const unsigned long long nEntries = lay.nEntries;
+    const int nTables = (int)lay.tables.size();
     dRaw.ensure((size_t)nEntries); dRawOff.ensure((size_t)nEntries); dStored.ensure((size_t)nEntries); dStoredOff.ensure((size_t)nEntries + 1); dBucketOff.ensure((size_t)nEntries);
     dTableStored.ensure((size_t)nTables);
     XMB_CHECK(hipMemsetAsync(dRaw.p, 0, sizeof(unsigned long long) * (size_t)nEntries, s));
-    if (nRecs > 0) hipLaunchKernelGGL(xmb_count_kernel, dim3(gridFor(nRecs)), dim3(256), 0, s, sortedKey, nRecs, dTables.p, dRaw.p);
+    if (r.n > 0) hipLaunchKernelGGL(xmb_count_kernel, dim3(gridFor(r.n)), dim3(256), 0, s, r.key, r.n, dTables.p, dRaw.p);
     hipLaunchKernelGGL(xmb_stored_kernel, dim3(gridFor(nEntries)), dim3(256), 0, s, dRaw.p, nEntries, dTables.p, nTables, dStored.p);
     scanU64(dTemp, dRaw.p, dRawOff.p, (size_t)nEntries, s);
     scanU64(dTemp, dStored.p, dStoredOff.p, (size_t)nEntries, s);
@@ -525,74 +500,94 @@ bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device) {
     std::vector<unsigned long long> tableStored((size_t)nTables);
     XMB_CHECK(hipMemcpyAsync(tableStored.data(), dTableStored.p, sizeof(unsigned long long) * (size_t)nTables, hipMemcpyDeviceToHost, s));
     XMB_CHECK(hipStreamSynchronize(s));
-    unsigned long long groupStored = 0;
-    for (int k = 0; k < nTables; k++) {
-      if (tableStored[(size_t)k] > 0x7FFFFFFFull) throw std::runtime_error("table too large for 31-bit bucket offsets");
-      groupStored += tableStored[(size_t)k];
-    }
+    const unsigned long long groupStored = storedTotal(tableStored);  // (refuses a table that is too large)
     dOutPos.ensure((size_t)groupStored);
-    if (nRecs > 0) hipLaunchKernelGGL(xmb_place_kernel, dim3(gridFor(nRecs)), dim3(256), 0, s, sortedKey, sortedPos, nRecs, dTables.p, dRaw.p, dRawOff.p, dStoredOff.p, dOutPos.p);
+    if (r.n > 0) hipLaunchKernelGGL(xmb_place_kernel, dim3(gridFor(r.n)), dim3(256), 0, s, r.key, r.pos, r.n, dTables.p, dRaw.p, dRawOff.p, dStoredOff.p, dOutPos.p);
     XMB_CHECK(hipGetLastError());
-    mark(tCsr, tm2);
-    // duplication map: the buckets of this group's tables that are worth the host's ordered pass (first build only)
-    if (!h.dupDone && h.dupMinCopies >= 2 && gHi >= h.dupMinLength && gLo <= h.dupMaxLength && groupStored > 0) {
-      std::vector<long long> cs(h.contigStart.begin(), h.contigStart.end()), sc(h.seqCumStart.begin(), h.seqCumStart.end());
-      BuildBuf<long long> dContigStart, dSeqCum;
-      BuildBuf<int32_t> dContigLen;
-      BuildBuf<unsigned long long> dFlagged, dFlagCount;
-      dContigStart.ensure(cs.size()); dSeqCum.ensure(sc.size()); dContigLen.ensure(h.contigLen.size()); dFlagCount.ensure(1);
-      XMB_CHECK(hipMemcpyAsync(dContigStart.p, cs.data(), cs.size() * sizeof(long long), hipMemcpyHostToDevice, s));
-      XMB_CHECK(hipMemcpyAsync(dSeqCum.p, sc.data(), sc.size() * sizeof(long long), hipMemcpyHostToDevice, s));
-      XMB_CHECK(hipMemcpyAsync(dContigLen.p, h.contigLen.data(), h.contigLen.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-      XMB_CHECK(hipMemsetAsync(dFlagCount.p, 0, sizeof(unsigned long long), s));
-      const unsigned long long cap = std::min<unsigned long long>(nEntries, 1ull << 26);
-      dFlagged.ensure((size_t)cap);
-      DupArgs da;
-      da.stored = dStored.p; da.storedOff = dStoredOff.p; da.positions = dOutPos.p; da.tables = dTables.p; da.nTables = nTables; da.gLo = gLo;
-      da.dupMinLength = h.dupMinLength; da.dupMaxLength = h.dupMaxLength; da.dupMinCopies = h.dupMinCopies;
-      da.codes = dCodes.p; da.contigStart = dContigStart.p; da.contigLen = dContigLen.p; da.seqCumStart = dSeqCum.p; da.nSeq = h.numContigs() * 2;
-      da.out = dFlagged.p; da.outCap = cap; da.outCount = dFlagCount.p;
-      hipLaunchKernelGGL(xmb_dup_candidates_kernel, dim3(gridFor(nEntries)), dim3(256), 0, s, da, nEntries);
-      XMB_CHECK(hipGetLastError());
-      unsigned long long nFlagged = 0;
-      XMB_CHECK(hipMemcpyAsync(&nFlagged, dFlagCount.p, sizeof(nFlagged), hipMemcpyDeviceToHost, s));
-      XMB_CHECK(hipStreamSynchronize(s));
-      if (nFlagged <= cap) {  // (more than the list holds: the host walks these tables itself)
-        std::vector<unsigned long long> flagged((size_t)nFlagged);
-        if (nFlagged) XMB_CHECK(hipMemcpy(flagged.data(), dFlagged.p, sizeof(unsigned long long) * (size_t)nFlagged, hipMemcpyDeviceToHost));
-        std::sort(flagged.begin(), flagged.end());
-        for (int k = 0; k < nTables; k++) {
-          const int L = gLo + k;
-          if (L >= h.dupMinLength && L <= h.dupMaxLength) h.dupCandidates[L];  // (an empty list is an answer too)
-        }
-        for (unsigned long long v : flagged) h.dupCandidates[gLo + (int)(v >> 32)].push_back((int)(v & 0xFFFFFFFFull));
-      }
-    }
-    mark(tDup, tm2);
-    // append to the host index (the duplication pass, the inspection API and the cache read the tables there)
+    return Cut{tableStored, groupStored};
+  }
+
+  // duplication map: the buckets of this group's tables that are worth the host's ordered pass (first build only)
+  void flagDupCandidates(const TableGroup& g, const GroupLayout& lay, unsigned long long groupStored) {
+    if (h.dupDone || h.dupMinCopies < 2 || g.gHi < h.dupMinLength || g.gLo > h.dupMaxLength || groupStored == 0) return;
+    const unsigned long long nEntries = lay.nEntries;
+    const int nTables = (int)lay.tables.size();
+    std::vector<long long> cs(h.contigStart.begin(), h.contigStart.end()), sc(h.seqCumStart.begin(), h.seqCumStart.end());
+    BuildBuf<long long> dContigStart, dSeqCum;
+    BuildBuf<int32_t> dContigLen;
+    BuildBuf<unsigned long long> dFlagged, dFlagCount;
+    dContigStart.ensure(cs.size()); dSeqCum.ensure(sc.size()); dContigLen.ensure(h.contigLen.size()); dFlagCount.ensure(1);
+    XMB_CHECK(hipMemcpyAsync(dContigStart.p, cs.data(), cs.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    XMB_CHECK(hipMemcpyAsync(dSeqCum.p, sc.data(), sc.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    XMB_CHECK(hipMemcpyAsync(dContigLen.p, h.contigLen.data(), h.contigLen.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    XMB_CHECK(hipMemsetAsync(dFlagCount.p, 0, sizeof(unsigned long long), s));
+    const unsigned long long cap = std::min<unsigned long long>(nEntries, 1ull << 26);
+    dFlagged.ensure((size_t)cap);
+    DupArgs da;
+    da.stored = dStored.p; da.storedOff = dStoredOff.p; da.positions = dOutPos.p; da.tables = dTables.p; da.nTables = nTables; da.gLo = g.gLo;
+    da.dupMinLength = h.dupMinLength; da.dupMaxLength = h.dupMaxLength; da.dupMinCopies = h.dupMinCopies;
+    da.codes = dCodes.p; da.contigStart = dContigStart.p; da.contigLen = dContigLen.p; da.seqCumStart = dSeqCum.p; da.nSeq = h.numContigs() * 2;
+    da.out = dFlagged.p; da.outCap = cap; da.outCount = dFlagCount.p;
+    hipLaunchKernelGGL(xmb_dup_candidates_kernel, dim3(gridFor(nEntries)), dim3(256), 0, s, da, nEntries);
+    XMB_CHECK(hipGetLastError());
+    unsigned long long nFlagged = 0;
+    XMB_CHECK(hipMemcpyAsync(&nFlagged, dFlagCount.p, sizeof(nFlagged), hipMemcpyDeviceToHost, s));
+    XMB_CHECK(hipStreamSynchronize(s));
+    if (nFlagged > cap) return;  // (more than the list holds: the host walks these tables itself)
+    std::vector<unsigned long long> flagged((size_t)nFlagged);
+    if (nFlagged) XMB_CHECK(hipMemcpy(flagged.data(), dFlagged.p, sizeof(unsigned long long) * (size_t)nFlagged, hipMemcpyDeviceToHost));
+    std::sort(flagged.begin(), flagged.end());
+    for (int L = std::max(g.gLo, h.dupMinLength); L <= std::min(g.gHi, h.dupMaxLength); L++) h.dupCandidates[L];  // (an empty list is an answer too)
+    for (unsigned long long v : flagged) h.dupCandidates[g.gLo + (int)(v >> 32)].push_back((int)(v & 0xFFFFFFFFull));
+  }
+
+  // append the group's arrays to the host index (the duplication pass, the inspection API and the cache read the tables there) and place its tables
+  void appendGroupToHost(const TableGroup& g, const GroupLayout& lay, const std::vector<unsigned long long>& tableStored, unsigned long long groupStored) {
     const size_t offBase = h.bucketOff.size(), posBase = h.positions.size();
-    h.bucketOff.resize(offBase + (size_t)nEntries);
+    h.bucketOff.resize(offBase + (size_t)lay.nEntries);
     h.positions.resize(posBase + (size_t)groupStored);
-    XMB_CHECK(hipMemcpyAsync(h.bucketOff.data() + offBase, dBucketOff.p, sizeof(uint32_t) * (size_t)nEntries, hipMemcpyDeviceToHost, s));
+    XMB_CHECK(hipMemcpyAsync(h.bucketOff.data() + offBase, dBucketOff.p, sizeof(uint32_t) * (size_t)lay.nEntries, hipMemcpyDeviceToHost, s));
     if (groupStored) XMB_CHECK(hipMemcpyAsync(h.positions.data() + posBase, dOutPos.p, sizeof(uint64_t) * (size_t)groupStored, hipMemcpyDeviceToHost, s));
     XMB_CHECK(hipStreamSynchronize(s));
-    mark(tCopy, tm2);
-    unsigned long long posAt = 0;
-    for (int k = 0; k < nTables; k++) {
-      Table t;
-      t.capacity = tdesc[(size_t)k].capacity; t.maxCount = tdesc[(size_t)k].maxCount;
-      t.offBase = (int64_t)(offBase + (size_t)tdesc[(size_t)k].bucketBase);
-      t.posBase = (int64_t)(posBase + (size_t)posAt);
-      posAt += tableStored[(size_t)k];
-      h.tables[(size_t)(gLo + k)] = t;
-    }
-    gLo = gHi + 1;
+    placeTables(h.tables, g.gLo, lay.tables, tableStored, offBase, posBase);
   }
-  if (trace) {
-    auto t2 = std::chrono::steady_clock::now();
+};
+
+// hashLengths(minLen, maxLen) of xm_index_host.h on the GPU.  false: not done (the caller hashes on the host).
+bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device, const BuildKnobs& knobs) {
+  const auto t0 = std::chrono::steady_clock::now();
+  DeviceBuild b(h, minLen, maxLen, device, knobs);
+  const std::vector<unsigned long long> hist = b.countRecords();
+  const auto t1 = std::chrono::steady_clock::now();
+  const std::vector<TableGroup> groups = planGroups(hist, minLen, maxLen, b.groupBudget());
+  if ((int)h.tables.size() < maxLen + 1) h.tables.resize((size_t)maxLen + 1);
+  unsigned long long totalRecs = 0;
+  for (const TableGroup& g : groups) {
+    const GroupLayout lay = layoutGroup(g, hist, b.shapes);
+    b.uploadTables(lay);
+    DeviceBuild::Records recs{nullptr, nullptr, 0};
+    if (g.nRecs > 0) {
+      b.timer.start();
+      b.emitGroupRecords(g);
+      b.timer.mark(b.timer.hash);
+      recs = b.sortGroup(g.nRecs, (int)lay.tables.size());
+      if (b.amb) recs = b.dropRepeatedMultiRecords(recs);
+      b.timer.mark(b.timer.sort);
+    }
+    totalRecs += recs.n;
+    b.timer.start();
+    const DeviceBuild::Cut cut = b.cutCsr(recs, lay);
+    b.timer.mark(b.timer.csr);
+    b.flagDupCandidates(g, lay, cut.groupStored);
+    b.timer.mark(b.timer.dup);
+    b.appendGroupToHost(g, lay, cut.tableStored, cut.groupStored);
+    b.timer.mark(b.timer.copy);
+  }
+  if (b.knobs.trace) {
+    const auto t2 = std::chrono::steady_clock::now();
     fprintf(stderr, "[xm] index build on the GPU: tables %d..%d, %llu records in %d group(s): counting run %.3f s, then %.3f s (hashing %.3f, sorts %.3f, CSR %.3f, "
-            "duplication candidates %.3f, copy to the host %.3f)\n", minLen, maxLen, totalRecs, groups, std::chrono::duration<double>(t1 - t0).count(),
-            std::chrono::duration<double>(t2 - t1).count(), tHash, tSort, tCsr, tDup, tCopy);
+            "duplication candidates %.3f, copy to the host %.3f)\n", minLen, maxLen, totalRecs, (int)groups.size(), std::chrono::duration<double>(t1 - t0).count(),
+            std::chrono::duration<double>(t2 - t1).count(), b.timer.hash, b.timer.sort, b.timer.csr, b.timer.dup, b.timer.copy);
   }
   return true;
 }

@@ -13,6 +13,7 @@
 // (possibilities under conditions), see nextLevelMulti below.
 #pragma once
 #include "xm_seed.h"
+#include "xm_index_plan.h"
 #include <vector>
 #include <map>
 #include <string>
@@ -114,14 +115,14 @@ struct HostIndex {
   }
 
   // host threads for the build (the reference's workers cooperate through helpHash/helpPack, M/HashBlock_Database.java:237-242)
-  static int buildThreads(size_t work) {
+  static int buildThreads(size_t work, const BuildKnobs& knobs) {
     if (work < 200000) return 1;
     unsigned hc = std::thread::hardware_concurrency();
     int t = hc ? (int)hc : 1;
-    const char* e = getenv("XM_BUILD_THREADS");
-    if (e && *e) t = atoi(e);
+    if (knobs.threadsSet) t = knobs.threads;
     return t < 1 ? 1 : (t > 64 ? 64 : t);
   }
+  static int buildThreads(size_t work) { return work < 200000 ? 1 : buildThreads(work, readBuildKnobs()); }  // (outside a build: the cache check, the duplication map)
   // fn(part, begin, end) over [0, n) cut into nThreads consecutive parts
   static void parallelParts(size_t n, int nThreads, const std::function<void(int, size_t, size_t)>& fn) {
     if (nThreads <= 1 || n < 2) { fn(0, 0, n); return; }
@@ -136,7 +137,7 @@ struct HostIndex {
   }
 
   struct Rec { uint32_t bucket; uint64_t pos; };  // pos bit 63: the record comes from a possibility of a multi block
-  static constexpr uint64_t REC_MULTI = 1ull << 63;
+  static constexpr uint64_t REC_MULTI = XM_REC_MULTI;
 
   // ---- contigs with ambiguous bases: blocks over such a base are lists of conditional possibilities (M/MultiHashBlock.java,
   // M/ConditionalHashBlock.java, M/SequenceCondition.java, the multi branch of M/HashBlock_ParentRow.java:69-191 and
@@ -341,13 +342,12 @@ struct HostIndex {
   // the multi blocks of the windows around them (a block that is emitted is at most maxLen long, so maxLen + 2 bases on either side of a run of
   // ambiguous bases hold every such block whole).  Ambiguous bases less than two margins apart share a window; all host threads work on the
   // windows.  recs[L] += the multi records.
-  void multiRecordsNearAmbiguity(int lo, int maxLen, const std::vector<int>& capacity, std::vector<std::vector<Rec>>& recs) const {
+  void multiRecordsNearAmbiguity(int lo, int maxLen, const std::vector<int>& capacity, std::vector<std::vector<Rec>>& recs, const BuildKnobs& knobs) const {
     struct Win { int c, ws, we, ws2, we2; };
     std::vector<Win> wins;
     const int margin = maxLen + 2;
     // a run of N longer than this is not held whole: 2 * half positions of it stay in the window (XM_BUILD_SPLICE_MIN: test hook)
-    int spliceMin = 2048;
-    if (const char* e = getenv("XM_BUILD_SPLICE_MIN")) { if (*e) spliceMin = std::max(64, atoi(e)); }
+    const int spliceMin = knobs.spliceMin;
     const int half = std::max(32, spliceMin / 4);
     for (int c = 0; c < numContigs(); c++) {
       SeqView seq = contigView(c, false);
@@ -368,7 +368,7 @@ struct HostIndex {
         i = last + 1;
       }
     }
-    const int nT = buildThreads(wins.size() * 4096);
+    const int nT = buildThreads(wins.size() * 4096, knobs);
     std::vector<std::vector<std::vector<Rec>>> part((size_t)nT, std::vector<std::vector<Rec>>((size_t)maxLen + 1));
     std::vector<size_t> nextJob(1, 0);
     std::mutex jobMu;
@@ -390,7 +390,7 @@ struct HostIndex {
         std::vector<Rec>().swap(part[(size_t)t][(size_t)L]);
       }
     lastSplitWindows = nSplit.load(); lastWholeWindows = (int)wins.size() - nSplit.load(); lastSplitRefused = nWholeAfterAll.load();
-    if (getenv("XM_TRACE_BUILD")) fprintf(stderr, "[xm] multi blocks near ambiguous bases: %zu windows (%d with the middle of a long run of N left out, %d such runs taken whole after all)\n",
+    if (knobs.trace) fprintf(stderr, "[xm] multi blocks near ambiguous bases: %zu windows (%d with the middle of a long run of N left out, %d such runs taken whole after all)\n",
                                           wins.size(), nSplit.load(), nWholeAfterAll.load());
   }
   mutable int lastSplitWindows = 0, lastWholeWindows = 0, lastSplitRefused = 0;
@@ -398,172 +398,158 @@ struct HostIndex {
   // Hash every gapmer with minLen <= used <= maxLen and append tables [minLen..maxLen].  Tables below minInterestingSize and
   // tables that receive no record are the reference's PackedMap(1, 1) placeholders (M/HashBlock_Database.java:387-393).
   // set by the library when a GPU is there (xm_index_device.hip): the same tables, hashed, sorted and cut into CSR form on the device
-  bool (*deviceHasher)(HostIndex&, int, int, int) = nullptr;
+  bool (*deviceHasher)(HostIndex&, int, int, int, const BuildKnobs&) = nullptr;
   int deviceForBuild = -1;
   int hasAmbiguity = -1;  // (cached) a contig holds a base code other than A C G T
   bool builtOnDevice = false;
   std::map<int, std::vector<int>> dupCandidates;  // (GPU build) per table: the hashcodes that can hold a duplication, ascending
   double hashSeconds = 0, dupSeconds = 0;
+  bool contigIsAmbiguous(int c) const {  // contig c holds a base code other than A C G T
+    const uint8_t* b = refCodes.data() + contigStart[(size_t)c];
+    for (int32_t i = 0; i < contigLen[(size_t)c]; i++) if (bpIsAmbiguous(b[i])) return true;
+    return false;
+  }
   bool referenceIsAmbiguous() {
     if (hasAmbiguity < 0) {
       hasAmbiguity = 0;
-      for (uint8_t c : refCodes) if (bpIsAmbiguous(c)) { hasAmbiguity = 1; break; }
+      for (int c = 0; c < numContigs() && !hasAmbiguity; c++) if (contigIsAmbiguous(c)) hasAmbiguity = 1;
     }
     return hasAmbiguity != 0;
   }
+  std::vector<uint32_t> ambiguousPrefix(int c) const {  // [contigLen + 1]: ambiguous bases of contig c before position i
+    const SeqView seq = contigView(c, false);
+    std::vector<uint32_t> prefix((size_t)seq.len + 1, 0);
+    for (int i = 0; i < seq.len; i++) prefix[(size_t)i + 1] = prefix[(size_t)i] + (bpIsAmbiguous(seq.base[i]) ? 1u : 0u);
+    return prefix;
+  }
+  // The plain rule over the whole of contig c: every level is cut into consecutive parts, one per host thread; a part emits the records of its blocks and
+  // merges its pairs (the pair that straddles two parts belongs to the left one); parts are concatenated in order.  ambPrefix: empty, or ambiguousPrefix(c) -
+  // a block over an ambiguous base emits nothing here (its records are those of the multi blocks, multiRecordsNearAmbiguity).  recs[L] += the records.
+  void hashPlainContig(int c, const std::vector<uint32_t>& ambPrefix, int lo, int maxLen, const std::vector<int>& capacity, const BuildKnobs& knobs, std::vector<std::vector<Rec>>& recs) const {
+    const SeqView seq = contigView(c, false);
+    const int n = seq.len;
+    std::vector<HBlock> cur((size_t)n), next;
+    for (int i = 0; i < n; i++) cur[(size_t)i] = hblock0(seq.base[i], i);
+    const int nT = buildThreads((size_t)n, knobs);
+    std::vector<std::vector<std::vector<Rec>>> partRecs((size_t)nT, std::vector<std::vector<Rec>>((size_t)maxLen + 1));
+    std::vector<std::vector<HBlock>> partNext((size_t)nT);
+    std::vector<char> partShort((size_t)nT);
+    while (!cur.empty()) {
+      parallelParts(cur.size(), nT, [this, c, lo, maxLen, &seq, &capacity, &ambPrefix, &cur, &partRecs, &partNext, &partShort](int t, size_t b, size_t e) {
+        bool anyShort = false;
+        std::vector<HBlock>& nx = partNext[(size_t)t];
+        nx.clear();
+        for (size_t i = b; i < e; i++) {
+          const HBlock& blk = cur[i];
+          if (blk.len <= maxLen) {  // (a longer block's gapmer uses at least blk.len bases)
+            anyShort = true;
+            if (ambPrefix.empty() || ambPrefix[(size_t)(blk.start + blk.len)] == ambPrefix[(size_t)blk.start]) emitBlockRecords(seq, c, blk, 0, lo, maxLen, capacity, partRecs[(size_t)t]);
+          }
+          if (i + 1 < cur.size() && shouldMergeBlocks(blk, cur[i + 1])) nx.push_back(mergeBlocks(blk, cur[i + 1]));
+        }
+        partShort[(size_t)t] = anyShort ? 1 : 0;
+      });
+      bool anyShort = false;
+      for (int t = 0; t < nT; t++) if (partShort[(size_t)t]) anyShort = true;
+      if (!anyShort) break;  // (the level after a level without short blocks is never looked at)
+      next.clear();
+      for (int t = 0; t < nT; t++) next.insert(next.end(), partNext[(size_t)t].begin(), partNext[(size_t)t].end());
+      cur.swap(next);
+    }
+    for (int t = 0; t < nT; t++)
+      for (int L = 0; L <= maxLen; L++) {
+        std::vector<Rec>& src = partRecs[(size_t)t][(size_t)L];
+        recs[(size_t)L].insert(recs[(size_t)L].end(), src.begin(), src.end());
+        std::vector<Rec>().swap(src);
+      }
+  }
+  // One table from its records (which are consumed): sorted, the repeated multi records dropped, cut into CSR form - the capacity + 1 offset entries (a bucket
+  // that received more than maxCount records is marked overfull and stores nothing) and the stored positions.  A table with more positions than 31-bit offsets hold
+  // is cut like any other (its offsets wrap) and refused afterwards, by storedTotal on the calling thread, as the GPU build refuses it: on what a table stores.
+  struct CutTable { std::vector<uint32_t> off; std::vector<uint64_t> pos; };
+  static CutTable cutTable(std::vector<Rec>& v, const TableShape& shape) {
+    std::sort(v.begin(), v.end(), [](const Rec& a, const Rec& b) { return a.bucket != b.bucket ? a.bucket < b.bucket : sortPosWord(a.pos) < sortPosWord(b.pos); });
+    {  // PackedMap.add with preventDuplicates (:124-153): a record that comes from a multi block is not added when its bucket already holds
+       // that position ([approximation, see DESIGN.md] "already" is taken as: among all single-block records and the earlier multi records)
+      size_t w = 0;
+      for (size_t r = 0; r < v.size(); r++) {
+        const bool multi = (v[r].pos & REC_MULTI) != 0;
+        const uint64_t pos = v[r].pos & ~REC_MULTI;
+        if (multi && w > 0 && v[w - 1].bucket == v[r].bucket && v[w - 1].pos == pos) continue;
+        v[w].bucket = v[r].bucket; v[w].pos = pos;
+        w++;
+      }
+      v.resize(w);
+    }
+    CutTable t;
+    t.off.reserve((size_t)shape.capacity + 1);
+    size_t i = 0;
+    for (int b = 0; b < shape.capacity; b++) {
+      size_t j = i;
+      while (j < v.size() && v[j].bucket == (uint32_t)b) j++;
+      if ((int64_t)(j - i) > (int64_t)shape.maxCount) {
+        t.off.push_back((uint32_t)t.pos.size() | XM_OVERFULL);
+      } else {
+        t.off.push_back((uint32_t)t.pos.size());
+        for (size_t x = i; x < j; x++) t.pos.push_back(v[x].pos);
+      }
+      i = j;
+    }
+    t.off.push_back((uint32_t)t.pos.size());  // (a table that does not fit 31-bit offsets is refused when the tables are placed: storedTotal)
+    std::vector<Rec>().swap(v);
+    return t;
+  }
+  // Hash every gapmer with minLen <= used <= maxLen and append tables [minLen..maxLen]; what the tables' shapes and places depend on is xm_index_plan.h's,
+  // shared with the GPU build.
   void hashLengths(int minLen, int maxLen) {
-    if (deviceHasher && deviceForBuild >= 0) {  // (references with ambiguity codes too: the GPU hashes what lies clear of them, multiRecordsNearAmbiguity the rest)
-      const char* e = getenv("XM_DEVICE_BUILD");  // 0: hash on the host even though a GPU is there
-      if (!(e && *e && atoi(e) == 0) && deviceHasher(*this, minLen, maxLen, deviceForBuild)) { builtOnDevice = true; return; }
-    }
-    std::vector<int> capacity((size_t)maxLen + 1, 0), maxCount((size_t)maxLen + 1, 0);
-    for (int L = std::max(minLen, minInterestingSize); L <= maxLen; L++) {
-      int cap = estimateRequiredCapacity(L);
-      if (cap < 1) cap = 1;
-      if (cap > INT32_MAX / 2) cap = INT32_MAX / 2;  // M/PackedMap.java:22-25
-      capacity[(size_t)L] = cap;
-      int mx = L * L;  // M/HashBlock_Database.java:569-576
-      if (mx < maxNumShortMatches) mx = maxNumShortMatches;
-      if (mx > 32766) mx = 32766;
-      if (mx < 1) mx = 1;
-      maxCount[(size_t)L] = mx;
-    }
+    const BuildKnobs knobs = readBuildKnobs();
+    // (references with ambiguity codes too: the GPU hashes what lies clear of them, multiRecordsNearAmbiguity the rest)
+    if (deviceHasher && deviceForBuild >= 0 && knobs.deviceBuild && deviceHasher(*this, minLen, maxLen, deviceForBuild, knobs)) { builtOnDevice = true; return; }
+    const int lo = std::max(minLen, minInterestingSize);
+    const std::vector<TableShape> shapes = tableShapes(lo, maxLen, maxNumShortMatches, [this](int L) { return estimateRequiredCapacity(L); });
+    const std::vector<int> capacity = capacitiesOf(shapes);
     std::vector<std::vector<Rec>> recs((size_t)maxLen + 1);
-    int lo = std::max(minLen, minInterestingSize);
-    const char* hy = getenv("XM_BUILD_HYBRID_ON_HOST");
-    const bool hybridOnHost = hy && *hy && atoi(hy) != 0;
     bool anyHybrid = false;
     for (int c = 0; c < numContigs(); c++) {
-      SeqView seq = contigView(c, false);
-      int n = seq.len;
-      auto emit = [&](const HBlock& b, uint32_t fromMulti, std::vector<std::vector<Rec>>& recs) { emitBlockRecords(seq, c, b, fromMulti, lo, maxLen, capacity, recs); };
-      bool ambiguous = false;
-      for (int i = 0; i < n && !ambiguous; i++) if (bpIsAmbiguous(seq.base[i])) ambiguous = true;
-      // XM_BUILD_HYBRID_ON_HOST=1 (test hook): the composition the GPU build uses for references with ambiguity codes, on the host - the plain
-      // rule over the whole contig for the blocks that lie clear of the ambiguous bases + the multi blocks of the windows around them
-      if (ambiguous && !hybridOnHost) {
-        hashAmbiguousWindow(c, 0, n, false, lo, maxLen, capacity, recs);
-        continue;
-      }
-      std::vector<uint32_t> ambPrefix;
-      if (ambiguous) {
-        ambPrefix.assign((size_t)n + 1, 0);
-        for (int i = 0; i < n; i++) ambPrefix[(size_t)i + 1] = ambPrefix[(size_t)i] + (bpIsAmbiguous(seq.base[i]) ? 1u : 0u);
+      if (!contigIsAmbiguous(c)) hashPlainContig(c, std::vector<uint32_t>(), lo, maxLen, capacity, knobs, recs);
+      else if (!knobs.hybridOnHost) hashAmbiguousWindow(c, 0, contigLen[(size_t)c], false, lo, maxLen, capacity, recs);
+      else {  // the GPU build's composition: the plain rule for the blocks that lie clear of the ambiguous bases + the multi blocks of the windows around them
+        hashPlainContig(c, ambiguousPrefix(c), lo, maxLen, capacity, knobs, recs);
         anyHybrid = true;
       }
-      // plain ACGT contig: every level is cut into consecutive parts, one per host thread; a part emits the records of its blocks and
-      // merges its pairs (the pair that straddles two parts belongs to the left one); parts are concatenated in order
-      std::vector<HBlock> cur((size_t)n), next;
-      for (int i = 0; i < n; i++) cur[(size_t)i] = hblock0(seq.base[i], i);
-      const int nT = buildThreads((size_t)n);
-      std::vector<std::vector<std::vector<Rec>>> partRecs((size_t)nT, std::vector<std::vector<Rec>>((size_t)maxLen + 1));
-      std::vector<std::vector<HBlock>> partNext((size_t)nT);
-      std::vector<char> partShort((size_t)nT);
-      while (!cur.empty()) {
-        parallelParts(cur.size(), nT, [&](int t, size_t b, size_t e) {
-          bool anyShort = false;
-          std::vector<HBlock>& nx = partNext[(size_t)t];
-          nx.clear();
-          for (size_t i = b; i < e; i++) {
-            const HBlock& blk = cur[i];
-            if (blk.len <= maxLen) {  // (a longer block's gapmer uses at least blk.len bases)
-              anyShort = true;
-              if (ambPrefix.empty() || ambPrefix[(size_t)(blk.start + blk.len)] == ambPrefix[(size_t)blk.start]) emit(blk, 0, partRecs[(size_t)t]);
-            }
-            if (i + 1 < cur.size() && shouldMergeBlocks(blk, cur[i + 1])) nx.push_back(mergeBlocks(blk, cur[i + 1]));
-          }
-          partShort[(size_t)t] = anyShort ? 1 : 0;
-        });
-        bool anyShort = false;
-        for (int t = 0; t < nT; t++) if (partShort[(size_t)t]) anyShort = true;
-        if (!anyShort) break;  // (the level after a level without short blocks is never looked at)
-        next.clear();
-        for (int t = 0; t < nT; t++) next.insert(next.end(), partNext[(size_t)t].begin(), partNext[(size_t)t].end());
-        cur.swap(next);
-      }
-      for (int t = 0; t < nT; t++)
-        for (int L = 0; L <= maxLen; L++) {
-          std::vector<Rec>& src = partRecs[(size_t)t][(size_t)L];
-          recs[(size_t)L].insert(recs[(size_t)L].end(), src.begin(), src.end());
-          std::vector<Rec>().swap(src);
-        }
     }
-    if (anyHybrid) multiRecordsNearAmbiguity(lo, maxLen, capacity, recs);
-    if ((int)tables.size() < maxLen + 1) tables.resize((size_t)maxLen + 1);
-    // every table on its own (sort, duplicate suppression, CSR), tables in parallel; then concatenated in order of L
+    if (anyHybrid) multiRecordsNearAmbiguity(lo, maxLen, capacity, recs, knobs);
+    // the tables [minLen, maxLen] as one group; every table is cut on its own, tables in parallel, large tables first
+    std::vector<unsigned long long> hist((size_t)maxLen + 1, 0);
+    TableGroup all{minLen, maxLen, 0};
+    for (int L = minLen; L <= maxLen; L++) { hist[(size_t)L] = recs[(size_t)L].size(); all.nRecs += hist[(size_t)L]; }
+    const GroupLayout lay = layoutGroup(all, hist, shapes);
     const int nTables = maxLen - minLen + 1;
-    std::vector<std::vector<uint32_t>> tOff((size_t)nTables);
-    std::vector<std::vector<uint64_t>> tPos((size_t)nTables);
-    std::vector<Table> tHdr((size_t)nTables);
-    size_t totalRecs = 0;
-    for (int L = minLen; L <= maxLen; L++) totalRecs += recs[(size_t)L].size();
-    const int nT2 = std::min(buildThreads(totalRecs), nTables);
+    std::vector<CutTable> cut((size_t)nTables);
     std::vector<int> order((size_t)nTables);
     for (int k = 0; k < nTables; k++) order[(size_t)k] = k;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return recs[(size_t)(minLen + a)].size() > recs[(size_t)(minLen + b)].size(); });  // large tables first
+    std::sort(order.begin(), order.end(), [&hist, minLen](int a, int b) { return hist[(size_t)(minLen + a)] > hist[(size_t)(minLen + b)]; });
+    const int nT = std::min(buildThreads((size_t)all.nRecs, knobs), nTables);
     std::vector<size_t> nextJob(1, 0);
     std::mutex jobMu;
-    parallelParts((size_t)nT2, nT2, [&](int, size_t, size_t) {
+    parallelParts((size_t)nT, nT, [minLen, nTables, &jobMu, &nextJob, &order, &recs, &lay, &cut](int, size_t, size_t) {
       while (true) {
         size_t job;
         { std::lock_guard<std::mutex> lock(jobMu); job = nextJob[0]++; }
         if (job >= (size_t)nTables) break;
         const int k = order[job];
-        const int L = minLen + k;
-        Table t;
-        std::vector<Rec>& v = recs[(size_t)L];
-        if (v.empty()) { t.capacity = 1; t.maxCount = 1; }
-        else { t.capacity = capacity[(size_t)L]; t.maxCount = maxCount[(size_t)L]; }
-        // (bucket, position, single before multi): the flag is the top bit of pos, so plain order on (pos << 1 | flag)
-        std::sort(v.begin(), v.end(), [](const Rec& a, const Rec& b) {
-          if (a.bucket != b.bucket) return a.bucket < b.bucket;
-          return ((a.pos << 1) | (a.pos >> 63)) < ((b.pos << 1) | (b.pos >> 63));
-        });
-        {  // PackedMap.add with preventDuplicates (:124-153): a record that comes from a multi block is not added when its bucket already holds
-           // that position ([approximation, see DESIGN.md] "already" is taken as: among all single-block records and the earlier multi records)
-          size_t w = 0;
-          for (size_t r = 0; r < v.size(); r++) {
-            const bool multi = (v[r].pos & REC_MULTI) != 0;
-            const uint64_t pos = v[r].pos & ~REC_MULTI;
-            if (multi && w > 0 && v[w - 1].bucket == v[r].bucket && v[w - 1].pos == pos) continue;
-            v[w].bucket = v[r].bucket; v[w].pos = pos;
-            w++;
-          }
-          v.resize(w);
-        }
-        std::vector<uint32_t>& off = tOff[(size_t)k];
-        std::vector<uint64_t>& pos = tPos[(size_t)k];
-        off.reserve((size_t)t.capacity + 1);
-        size_t i = 0;
-        uint64_t stored = 0;
-        for (int b = 0; b < t.capacity; b++) {
-          size_t j = i;
-          while (j < v.size() && v[j].bucket == (uint32_t)b) j++;
-          size_t cnt = j - i;
-          if (stored + cnt > 0x7FFFFFFFull) throw std::runtime_error("table too large for 31-bit bucket offsets");
-          if ((int64_t)cnt > (int64_t)t.maxCount) {
-            off.push_back((uint32_t)stored | XM_OVERFULL);
-          } else {
-            off.push_back((uint32_t)stored);
-            for (size_t x = i; x < j; x++) pos.push_back(v[x].pos);
-            stored += cnt;
-          }
-          i = j;
-        }
-        off.push_back((uint32_t)stored);
-        tHdr[(size_t)k] = t;
-        std::vector<Rec>().swap(v);
+        cut[(size_t)k] = cutTable(recs[(size_t)(minLen + k)], TableShape{lay.tables[(size_t)k].capacity, lay.tables[(size_t)k].maxCount});
       }
     });
-    for (int k = 0; k < nTables; k++) {
-      Table t = tHdr[(size_t)k];
-      t.offBase = (int64_t)bucketOff.size();
-      t.posBase = (int64_t)positions.size();
-      bucketOff.insert(bucketOff.end(), tOff[(size_t)k].begin(), tOff[(size_t)k].end());
-      positions.insert(positions.end(), tPos[(size_t)k].begin(), tPos[(size_t)k].end());
-      tables[(size_t)(minLen + k)] = t;
-      std::vector<uint32_t>().swap(tOff[(size_t)k]);
-      std::vector<uint64_t>().swap(tPos[(size_t)k]);
+    std::vector<unsigned long long> stored((size_t)nTables);
+    for (int k = 0; k < nTables; k++) stored[(size_t)k] = cut[(size_t)k].pos.size();
+    (void)storedTotal(stored);  // (refuses a table that is too large)
+    if ((int)tables.size() < maxLen + 1) tables.resize((size_t)maxLen + 1);
+    placeTables(tables, minLen, lay.tables, stored, bucketOff.size(), positions.size());
+    for (CutTable& t : cut) {
+      bucketOff.insert(bucketOff.end(), t.off.begin(), t.off.end());
+      positions.insert(positions.end(), t.pos.begin(), t.pos.end());
+      t = CutTable();
     }
   }
 
@@ -578,7 +564,7 @@ struct HostIndex {
     int want = maxHashed > 0 ? maxHashed : chooseMaxDuplicationLength();
     want = std::max(want, std::max(dupMaxLength, dupMinLength + 1));
     want = std::max(want, 1);
-    const bool trace = getenv("XM_TRACE_BUILD") != nullptr;
+    const bool trace = readBuildKnobs().trace;
     auto t0 = std::chrono::steady_clock::now();
     hashLengths(0, want);
     maxHashedLength = want;

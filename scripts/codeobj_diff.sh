@@ -1,7 +1,7 @@
 #!/bin/bash
-# Device code of two builds of xm_capi.o, symbol by symbol: the gfx950 code object of each is unbundled and disassembled (llvm-objdump -d), addresses and
+# Device code of two builds of an object (xm_capi.o, xm_index_device.o, ...), symbol by symbol: the gfx950 code object of each is unbundled and disassembled (llvm-objdump -d), addresses and
 # encodings dropped, and the instruction text of every kernel and out-of-line device function compared.  Runs on the CPU.  Exit status 0: equal for every symbol.
-# usage: scripts/codeobj_diff.sh BEFORE/xm_capi.o AFTER/xm_capi.o
+# usage: scripts/codeobj_diff.sh BEFORE/xm_capi.o AFTER/xm_capi.o   (any two objects with a gfx950 bundle)
 set -e
 LL=/opt/rocm/lib/llvm/bin
 T=$(mktemp -d)
@@ -11,16 +11,23 @@ for v in a b; do
   $LL/clang-offload-bundler --unbundle --type=o --input=$T/$v.fatbin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$T/$v.co
   # "0000000000001000 <symbol>:" opens a symbol; an instruction line is "\tmnemonic operands // address: encoding"
   $LL/llvm-objdump -d $T/$v.co | awk -v dir=$T/$v 'BEGIN { system("mkdir -p " dir) }
-    /^[0-9a-f]+ <.*>:$/ { name = $2; gsub(/[<>:]/, "", name); n++; file = dir "/" name; order[n] = name; next }
-    file != "" && /^\t/ { sub(/[ \t]*\/\/.*$/, ""); print > file; count[name]++ }
-    END { for (i = 1; i <= n; i++) print order[i], count[order[i]] > (dir ".symbols") }'
+  # (the instructions of a symbol go to a numbered file: the mangled names of library kernels are longer than a file name may be)
+    /^[0-9a-f]+ <.*>:$/ { name = $2; gsub(/[<>:]/, "", name); n++; if (file != "") close(file); file = dir "/" n; order[n] = name; next }
+    file != "" && /^\t/ { sub(/[ \t]*\/\/.*$/, ""); print > file; count[n]++ }
+    END { for (i = 1; i <= n; i++) print order[i], count[i] + 0, i > (dir ".symbols") }'
 done
 rc=0
-while read name n; do
-  if [ ! -f $T/b/$name ]; then echo "$name ($n instructions): missing after"; rc=1
-  elif cmp -s $T/a/$name $T/b/$name; then echo "$name ($n instructions): equal"
+declare -A after before
+while read name n i; do after[$name]=$i; done < $T/b.symbols
+while read name n i; do
+  before[$name]=$i
+  j=${after[$name]}
+  [ -f $T/a/$i ] || : > $T/a/$i
+  [ -z "$j" ] || [ -f $T/b/$j ] || : > $T/b/$j
+  if [ -z "$j" ]; then echo "$name ($n instructions): missing after"; rc=1
+  elif cmp -s $T/a/$i $T/b/$j; then echo "$name ($n instructions): equal"
   else echo "$name ($n instructions): DIFFERENT"; rc=1; fi
 done < $T/a.symbols
-while read name n; do [ -f $T/a/$name ] || { echo "$name ($n instructions): new"; rc=1; }; done < $T/b.symbols
+while read name n i; do [ -n "${before[$name]}" ] || { echo "$name ($n instructions): new"; rc=1; }; done < $T/b.symbols
 rm -rf $T
 exit $rc

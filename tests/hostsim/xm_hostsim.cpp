@@ -592,6 +592,32 @@ int xmsim_next_pass(const int64_t* facts, int64_t* state, const uint64_t* ctl, i
   } catch (std::exception& e) { g_err = e.what(); return 1; }
 }
 
+// ---- the index-build planner (mapper_amd/csrc/xm_index_plan.h, what the host builder and the GPU builder share) for tests/test_index_plan.py
+// out (2): capacity, maxCount
+void xmsim_table_shape(int64_t estimatedCapacity, int L, int maxNumShortMatches, int64_t* out) {
+  const TableShape t = tableShape(estimatedCapacity, L, maxNumShortMatches);
+  out[0] = t.capacity; out[1] = t.maxCount;
+}
+// hist [maxLen + 1]; out (3 per group): gLo, gHi, nRecs (the first capGroups of them) -> how many groups
+int64_t xmsim_plan_groups(const uint64_t* hist, int minLen, int maxLen, uint64_t budgetRecs, int64_t* out, int64_t capGroups) {
+  const std::vector<TableGroup> groups = planGroups(std::vector<unsigned long long>(hist, hist + maxLen + 1), minLen, maxLen, budgetRecs);
+  for (size_t i = 0; i < groups.size() && (int64_t)i < capGroups; i++) { out[3 * i] = groups[i].gLo; out[3 * i + 1] = groups[i].gHi; out[3 * i + 2] = (int64_t)groups[i].nRecs; }
+  return (int64_t)groups.size();
+}
+// hist, capacity, maxCount [gHi + 1] (the planned shapes); out (3 per table of [gLo, gHi]): bucketBase, capacity, maxCount -> nEntries
+int64_t xmsim_layout_group(const uint64_t* hist, const int32_t* capacity, const int32_t* maxCount, int gLo, int gHi, int64_t* out) {
+  std::vector<TableShape> shapes((size_t)gHi + 1);
+  for (int L = 0; L <= gHi; L++) shapes[(size_t)L] = TableShape{capacity[L], maxCount[L]};
+  const GroupLayout lay = layoutGroup(TableGroup{gLo, gHi, 0}, std::vector<unsigned long long>(hist, hist + gHi + 1), shapes);
+  for (size_t k = 0; k < lay.tables.size(); k++) { out[3 * k] = (int64_t)lay.tables[k].bucketBase; out[3 * k + 1] = lay.tables[k].capacity; out[3 * k + 2] = lay.tables[k].maxCount; }
+  return (int64_t)lay.nEntries;
+}
+// out (2): posBits, tableBits
+void xmsim_sort_key_bits(uint64_t lastCumStart, int ambiguous, int nTables, int64_t* out) {
+  const SortKeyBits b = sortKeyBits(lastCumStart, ambiguous != 0, nTables);
+  out[0] = b.posBits; out[1] = b.tableBits;
+}
+
 // ---- the host's confidence table (mapper_amd/csrc/xm_conf_table.h) for tests/test_conf_table.py: a ConfTable driven as a context drives it, and read with the
 // kernels' own lookup (confLookup, xm_defs.h)
 void* xmsim_conf_new(void) { return new ConfTable(); }

@@ -60,6 +60,14 @@ def lib():
         L.xmsim_pass_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.xmsim_plan_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
         L.xmsim_next_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xmsim_table_shape.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_void_p]
+        L.xmsim_table_shape.restype = None
+        L.xmsim_plan_groups.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_int64]
+        L.xmsim_plan_groups.restype = C.c_int64
+        L.xmsim_layout_group.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.xmsim_layout_group.restype = C.c_int64
+        L.xmsim_sort_key_bits.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p]
+        L.xmsim_sort_key_bits.restype = None
         L.xmsim_conf_new.restype = C.c_void_p
         L.xmsim_conf_free.argtypes = [C.c_void_p]
         L.xmsim_conf_prepare.argtypes = [C.c_void_p, C.POINTER(_capi.XmParams), C.c_void_p, C.c_int64, C.c_double, C.c_int64, C.c_int64]
@@ -243,6 +251,39 @@ def next_pass(state, ctl, longest_mate, paired=False, contexts=1):
     c = np.array([ctl.get("nHeavy", 0), ctl.get("nHeavyLate", 0)] + list(ctl.get("nScale", (0, 0))) + list(ctl.get("nOut", (0, 0))) + [2 ** 64 - 1] + list(ctl.get("nConf", (0, 0))), dtype=np.uint64)
     _check(lib().xmsim_next_pass(f.ctypes.data, st.ctypes.data, c.ctypes.data, nxt.ctypes.data))
     return PASS_KINDS[int(nxt[0])], int(nxt[1]), int(nxt[2]), int(nxt[3]), dict(zip(STATE_FIELDS, map(int, st)))
+
+
+# ---- the index-build planner (mapper_amd/csrc/xm_index_plan.h), shared by the host builder and the GPU builder
+def table_shape(estimated_capacity, L_, max_num_short_matches):
+    """-> (capacity, maxCount) of table L_"""
+    out = np.zeros(2, dtype=np.int64)
+    lib().xmsim_table_shape(estimated_capacity, L_, max_num_short_matches, out.ctypes.data)
+    return int(out[0]), int(out[1])
+
+
+def plan_groups(hist, min_len, budget):
+    """hist[L] = records of table L, L = 0 .. len(hist) - 1 -> [(gLo, gHi, nRecs)] of the tables [min_len, len(hist) - 1]"""
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    out = np.zeros((len(h) + 1, 3), dtype=np.int64)
+    n = lib().xmsim_plan_groups(h.ctypes.data, min_len, len(h) - 1, budget, out.ctypes.data, len(out))
+    assert 0 <= n <= len(out)
+    return [tuple(int(v) for v in row) for row in out[:n]]
+
+
+def layout_group(hist, capacity, max_count, g_lo, g_hi):
+    """the planned shapes and the records of the tables 0 .. g_hi -> ([(bucketBase, capacity, maxCount)] of the tables [g_lo, g_hi], nEntries)"""
+    h, cap, mx = np.ascontiguousarray(hist, dtype=np.uint64), np.ascontiguousarray(capacity, dtype=np.int32), np.ascontiguousarray(max_count, dtype=np.int32)
+    assert len(h) == len(cap) == len(mx) == g_hi + 1
+    out = np.zeros((g_hi - g_lo + 1, 3), dtype=np.int64)
+    n = lib().xmsim_layout_group(h.ctypes.data, cap.ctypes.data, mx.ctypes.data, g_lo, g_hi, out.ctypes.data)
+    return [tuple(int(v) for v in row) for row in out], int(n)
+
+
+def sort_key_bits(last_cum_start, ambiguous, n_tables):
+    """-> (posBits, tableBits) of the GPU build's two radix sorts"""
+    out = np.zeros(2, dtype=np.int64)
+    lib().xmsim_sort_key_bits(last_cum_start, 1 if ambiguous else 0, n_tables, out.ctypes.data)
+    return int(out[0]), int(out[1])
 
 
 # ---- the host's confidence table (mapper_amd/csrc/xm_conf_table.h)
