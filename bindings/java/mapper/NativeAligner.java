@@ -70,6 +70,15 @@ final class NativeAligner implements AutoCloseable {
     return new NativeAligner(this);
   }
 
+  /**
+   * The run-wide half of AlignerWorker.checkCacheAndAlign (AlignerWorker.java:264-291): this aligner (one GPU context) remembers the queries it aligns in up to
+   * maxBytes of HBM and serves byte-identical queries of later batches from there; the results are the same.  0 switches it off.  Per view: each worker's
+   * view has a memory of its own.
+   */
+  void rememberQueries(long maxBytes) {
+    setMemo(indexHandle, maxBytes);
+  }
+
   /** The batch form of AlignerWorker.align(Query) (AlignerWorker.java:256-261): element q of the result belongs to batch.get(q). */
   List<QueryAlignments> align(List<Query> batch) {
     int nq = batch.size();
@@ -181,6 +190,7 @@ final class NativeAligner implements AutoCloseable {
 
   private static native long buildIndex(byte[][] contigCodes, String[] names, boolean enableGapmers, int duplicationWindow, int maxQueryLength, int device);
   private static native long newContext(long handle);
+  private static native void setMemo(long handle, long maxBytes);
   private static native void freeIndex(long handle);
   private static native boolean alignBatch(long handle, double[] parameters9, int maxNumMatches, int[] mateCount, long[] mateOffset, int[] mateLength, ByteBuffer codes,
                                            double[] expectedInnerDistance, double[] spacingDeviationPerUnitPenalty, ResultStreams out);

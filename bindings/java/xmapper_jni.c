@@ -19,7 +19,7 @@
 #include <string.h>
 #include "xmapper_hip.h"
 
-#define XMJ_ABI_VERSION 3  /* include/xmapper_hip.h: xm_context_set_collapse, xm_result.extra[7] */
+#define XMJ_ABI_VERSION 4  /* include/xmapper_hip.h: xm_context_set_memo, xm_context_memo_info, xm_result.extra[6] */
 
 /* ---------------------------------------------------------------- part 1: marshalling on plain C arrays ---------------------------------------- */
 
@@ -141,6 +141,13 @@ JNIEXPORT jlong JNICALL Java_mapper_NativeAligner_newContext(JNIEnv* env, jclass
   (void)cls;
   if (xm_context_new((xm_index*)(intptr_t)handle, &ctx) != 0) { xmj_throw(env, "Failed to make a context of the reference index: "); return 0; }
   return (jlong)(intptr_t)ctx;
+}
+
+/* private static native void setMemo(long handle, long maxBytes): this context remembers the queries it aligns in up to maxBytes of HBM and serves repeats
+ * in later batches from there (xm_context_set_memo: the run-wide AlignmentCache of AlignerWorker.checkCacheAndAlign, AlignerWorker.java:264-291); 0 = off */
+JNIEXPORT void JNICALL Java_mapper_NativeAligner_setMemo(JNIEnv* env, jclass cls, jlong handle, jlong maxBytes) {
+  (void)cls;
+  if (xm_context_set_memo((xm_index*)(intptr_t)handle, (int64_t)maxBytes) != 0) xmj_throw(env, "Failed to set the memory of aligned queries: ");
 }
 
 /* private static native void freeIndex(long handle) */

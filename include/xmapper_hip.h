@@ -92,16 +92,17 @@ typedef struct xm_result {
    * 12-15 kernel microseconds by pass: 12 wave-per-read light tier (+ lane-per-read light pass of what the wave form left), 13 wave-per-read
    * chain tier, 14 wave-per-read search tier, 15 lane-per-read gapped / rerun passes */
   int64_t counters[16];
-  double kernel_ms;   /* sum of the align (and search, and collapse) kernels' launch durations (HIP events on the launch stream) */
+  double kernel_ms;   /* sum of the align (and search, collapse and memory) kernels' launch durations (HIP events on the launch stream) */
   double h2d_ms, d2h_ms;  /* batch upload; prefix sums + query-order gather + copy of the four streams to the host */
-  int32_t kernel_launches;  /* align + search (+ collapse) kernel launches of this call */
+  int32_t kernel_launches;  /* align + search (+ collapse, + memory) kernel launches of this call */
   int32_t reserved;
   int64_t prof[16];   /* diagnostic builds (-DXM_PROFILE=1: summed over lanes, =2: per wave) only: shader-clock ticks per phase; otherwise 0 */
   /* (appended in ABI version 2; xm_abi_version())  the rejection filter in front of PathAligner (batches of long reads): 0 searches it examined, 1 searches it
    * proved null without running them (PathAligner.java:169: the search would have returned null after exploring every node within the budget; their nodes
    * are not in counters[6]), 2 cells of the bounding recurrence it computed, 3 = 1 when a pass of this call ran with the filter; 4 pieces (BlockAligner.alignPiece,
    * BlockAligner.java:215-249) the filter examined, 5 pieces it proved unalignable within their budget before their chain ran (their PathAligner calls and nodes are in neither counters[5] nor
-   * counters[6]); 6 reserved (0); 7 (ABI version 3) queries of this call whose results were copied from a byte-identical query of the batch instead of being
+   * counters[6]); 6 (ABI version 4) queries of this call whose results were replayed from the context's memory of
+   * earlier calls instead of being aligned (xm_context_set_memo; 0 when it is off); 7 (ABI version 3) queries of this call whose results were copied from a byte-identical query of the batch instead of being
    * aligned (xm_context_set_collapse; 0 when collapsing is off) */
   int64_t extra[8];
 } xm_result;
@@ -121,7 +122,7 @@ const char* xm_last_error(void);
  * time: lets a caller check that the loaded library was built from the sources it sits beside. */
 const char* xm_build_stamp(void);
 /* Version of this header's structs and entry points: 2 = xm_result.extra[] appended, xm_seed_probe_packed replaces xm_seed_probe; 3 = xm_context_set_collapse,
- * xm_result.extra[7].  A binding checks it once
+ * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6].  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -156,6 +157,20 @@ int xm_device_memory(int32_t device, int64_t* free_bytes, int64_t* total_bytes);
  * aligned queries only, and extra[7] the queries served as copies.  That is why it is not on by default: bench.py and the GPU tests compare those
  * counters with the oracle read by read.  "Failed to align query q" names the lowest index of the group. */
 int xm_context_set_collapse(xm_index* context, int32_t enable);
+/* The run-wide half of the same cache (AlignmentCache.java spans the run, not a batch).  max_bytes > 0 gives this context a memory of that many bytes of HBM
+ * (a fingerprint table and an arena of records; at least 65 536 bytes, less fails); 0 switches it off and frees it; setting it again forgets what it held.
+ * With it, every later align call of the context looks each query up first and serves it from a byte-identical query - identical as above - that THIS
+ * context aligned in an earlier call under bit-identical xm_params; whatever it aligns itself it remembers afterwards, until the memory is full (nothing
+ * is evicted: full means nothing more is remembered).  The memory implies the within-batch collapse for the context.  The four streams are the same as
+ * without it.  A call whose xm_params differ in any bit from the ones the memory was filled under empties it first; a call that fails remembers nothing;
+ * the memory survives xm_index_ensure_length and growth of the tables by another context (a read only reads the tables of lengths up to its own).
+ * Counters: extra[6] = the queries served from the memory, extra[7] = the within-batch copies, counters[0] = num_queries - extra[6] - extra[7], and
+ * counters[0..10], extra[0..5] count the work done, as with collapsing.  Per context: a query seen k times over N contexts is aligned at most min(k, N)
+ * times.  Off by default. */
+int xm_context_set_memo(xm_index* context, int64_t max_bytes);
+/* out[0] queries remembered, out[1] bytes of HBM in use for them (the table and the records), out[2] the most queries the table takes (the records' arena
+ * may fill first), out[3] how often a change of xm_params emptied the memory.  All 0 while the memory is off (out[3] keeps counting over the context's life). */
+int xm_context_memo_info(xm_index* context, int64_t out[4]);
 /* Binary index cache, in the spirit of --cache-dir (DirCache.java:19-60, HashBlock_Database.java:106-114,477-487, PackedMap.java:249-279:
  * the reference writes one "length-<n>" file per PackedMap under a directory keyed by its property map).  xm_index_save writes the
  * reference, every table hashed so far and the duplication map into ONE file (beside `path`, then renamed: concurrent writers are safe).

@@ -145,6 +145,12 @@ class BatchResult:
         ReferenceDatabase.set_collapse(True))."""
         return int(self.extra[7])
 
+    @property
+    def remembered(self):
+        """Queries of the batch whose results were replayed from the context's memory of earlier batches instead of being aligned (xm_result.extra[6]; 0 unless
+        ReferenceDatabase.set_memo(bytes))."""
+        return int(self.extra[6])
+
     def query_alignments(self, q):
         return decode_streams(self.ints, self.dbls, self.int_off, self.dbl_off, q)
 
@@ -265,6 +271,18 @@ class ReferenceDatabase:
         others (AlignerWorker.checkCacheAndAlign, AlignerWorker.java:264-291, within a batch).  Same results; the work counters then count the queries
         aligned, and BatchResult.copies the ones served as copies.  Off by default."""
         _check(self._L.xm_context_set_collapse(self._h, 1 if enable else 0))
+
+    def set_memo(self, max_bytes):
+        """xm_context_set_memo: this context remembers the queries it aligns in up to max_bytes of HBM and serves byte-identical queries of later batches from
+        there (the run-wide AlignmentCache of AlignerWorker.checkCacheAndAlign, AlignerWorker.java:264-291); it implies set_collapse within a batch.  Same
+        results; BatchResult.remembered counts the queries served.  0 switches it off and frees it.  Off by default."""
+        _check(self._L.xm_context_set_memo(self._h, int(max_bytes)))
+
+    def memo_info(self):
+        """xm_context_memo_info -> {entries, bytes_used, capacity, times_emptied}."""
+        out = (C.c_int64 * 4)()
+        _check(self._L.xm_context_memo_info(self._h, out))
+        return {"entries": out[0], "bytes_used": out[1], "capacity": out[2], "times_emptied": out[3]}
 
     def close(self):
         if getattr(self, "_h", None):

@@ -11,9 +11,11 @@ live in the un-vendored QuickVariants module: the header written here is the min
 VCF / ancestry outputs stay with the Java host (`--cache-dir` is
 honoured: the index goes to one file under it, api.index_cache_path) and are refused here with a message saying so.
 
-Flags of this harness that Mapper does not have: --batch-size <n>, --gpus <n>, --contexts <n>, --devices <i,j,...>, --device <i>, --per-object, and
+Flags of this harness that Mapper does not have: --batch-size <n>, --gpus <n>, --contexts <n>, --devices <i,j,...>, --device <i>, --per-object,
 --collapse-identical-queries (byte-identical queries of a batch are aligned once and share the results, as the reference's alignment cache does; the
-outputs are the same, and one line on stderr says how many queries were served as copies).
+outputs are the same, and one line on stderr says how many queries were served as copies), and --remember-queries <MiB> (every context keeps the queries
+it has aligned in that much HBM and serves byte-identical queries of its later batches from there: the same cache across batches; same outputs, one line on
+stderr).
 """
 import contextlib
 import gzip
@@ -178,6 +180,10 @@ def parse_args(argv):
             o["devices"] = [int(x) for x in argv[i + 1].split(",")]; i += 1
         elif a == "--collapse-identical-queries":  # (not a Mapper flag) identical queries of a batch aligned once (api.ReferenceDatabase.set_collapse; AlignerWorker.java:264-291)
             o["collapse"] = True
+        elif a == "--remember-queries":  # (not a Mapper flag) MiB of HBM per context for the queries it has aligned (api.ReferenceDatabase.set_memo): repeats in later batches are served from there
+            o["remember"] = int(argv[i + 1]) << 20; i += 1
+            if o["remember"] < 0:
+                raise UsageError("--remember-queries must be >= 0")
         elif a == "--per-object":  # (not a Mapper flag) the harness's first implementation: one Python object per read and per alignment (the reference for the formats; tests)
             o["per_object"] = True
         elif a == "--device":  # (not a Mapper flag) which GPU
@@ -282,15 +288,17 @@ def context_devices(o, batches, single_short):
     return [d for d in (explicit or [o["device"]]) for _ in range(contexts)]
 
 
-def open_gpu_database(contigs, devices, max_query_length, enable_gapmers=True, collapse=False, cache_dir=None, per_context_extra=0):
+def open_gpu_database(contigs, devices, max_query_length, enable_gapmers=True, collapse=False, cache_dir=None, per_context_extra=0, memo_bytes=0):
     """The index of `contigs` (in api.sort_reference order) with one context per entry of `devices`.  per_context_extra: what every context will allocate
-    beside its scratch (api.divide_scratch).  (A job whose later reads are longer than max_query_length grows the index on demand: xm_index_ensure_length.)"""
+    beside its scratch (api.divide_scratch; memo_bytes, every context's memory of aligned queries, is part of it).  (A job whose later reads are longer than max_query_length grows the index on demand: xm_index_ensure_length.)"""
     if len(devices) > 1:
         from . import multi
-        return multi.MultiGpuDatabase(contigs, devices, collapse=collapse, mode="mapper", enable_gapmers=enable_gapmers, max_query_length=max_query_length,
+        return multi.MultiGpuDatabase(contigs, devices, collapse=collapse, memo_bytes=memo_bytes, mode="mapper", enable_gapmers=enable_gapmers, max_query_length=max_query_length,
                                       cache_dir=cache_dir, per_context_extra=per_context_extra)
     db = api.ReferenceDatabase(contigs, mode="mapper", enable_gapmers=enable_gapmers, device=devices[0], max_query_length=max_query_length, cache_dir=cache_dir)
     db.set_collapse(collapse)
+    if memo_bytes:
+        db.set_memo(memo_bytes)
     return db
 
 
@@ -381,11 +389,12 @@ class ObjectSink:
                 f.write("%s\t%d\n" % (",".join(key), count))
 
 
-def stream(db, batches, params, sink, depth, on_aligned=None):
+def stream(db, batches, params, sink, depth, on_aligned=None, tally=None):
     """The job: the batches stream through the GPU contexts (align_stream: the copy of batch k + 1 overlaps the alignment of batch k; several contexts align
     side by side) and a writer thread hands each batch and its result streams to the sink while the next batches are being aligned; at most `depth` results
     wait for it.  Every batch taken from `batches` is closed, and the first exception - the reader's, the GPU's or the sink's - reaches the caller.
-    -> the queries that were served as copies (BatchResult.copies)."""
+    -> the queries that were served as copies (BatchResult.copies); tally["remembered"], if given, grows by the ones served from the contexts' memories
+    (BatchResult.remembered)."""
     in_flight = queue.Queue()  # batches in the order they were dealt to the GPUs
     to_write = queue.Queue(maxsize=depth)
     failure = []
@@ -414,6 +423,8 @@ def stream(db, batches, params, sink, depth, on_aligned=None):
             if failure:
                 break
             copies += r.copies
+            if tally is not None:
+                tally["remembered"] = tally.get("remembered", 0) + r.remembered
             to_write.put((in_flight.get(), r))
     finally:
         to_write.put(None)
@@ -441,6 +452,11 @@ def report_copies(copies, n):
     sys.stderr.write("Identical queries: %d of %d queries were served as copies of an identical query of their batch\n" % (copies, n))
 
 
+def report_remembered(remembered, n):
+    """--remember-queries: the one statistics line of the flag (stderr, like report_copies)."""
+    sys.stderr.write("Remembered queries: %d of %d queries were served from an identical query of an earlier batch\n" % (remembered, n))
+
+
 def run(argv, out=sys.stdout, open_database=None):
     """open_database: called as open_gpu_database is, in its place (tests hand in a database that needs no GPU)."""
     o = parse_args(argv)
@@ -464,8 +480,9 @@ def run(argv, out=sys.stdout, open_database=None):
         # (--out-mutations: every context accumulates its own pile-up on its GPU - depth 8 B, four alternative counts 32 B and, with a query-end fraction, the
         # middle depth 8 B per reference base: 149 GB for a 3.1 Gb reference - so the contexts of a GPU are counted with it)
         pile_up = (48 if o.get("query_end_fraction", 0.1) > 0 else 40) * sum(len(t) for _, t in ordered) + (64 << 20) if o.get("out_mutations") else 0
+        memo = {"memo_bytes": o["remember"]} if o.get("remember") else {}  # (--remember-queries: every context's memory, counted beside its scratch)
         db = (open_database or open_gpu_database)(ordered, devices, max_len, enable_gapmers=o["enable_gapmers"], collapse=o.get("collapse", False),
-                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up)
+                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0), **memo)
         job.callback(db.close)
         sam_out = un_out = None
         if o["out_sam"]:
@@ -483,7 +500,8 @@ def run(argv, out=sys.stdout, open_database=None):
             def on_aligned(*at):  # ReferenceDatabase.align_stream calls it with (batch), MultiGpuDatabase's with (replica, batch), on the replica's thread
                 match_db.add_last(batches[at[-1]].queries, replica=at[0] if len(at) > 1 else 0)
         t_stream = time.perf_counter()
-        copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned)
+        tally = {}
+        copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned, tally)
         if o.get("out_refs_map_count"):
             sink.write_refs_map(o["out_refs_map_count"])
         if match_db is not None:  # Mapper.java:758-785
@@ -497,6 +515,8 @@ def run(argv, out=sys.stdout, open_database=None):
     last_timing = {"queries": n, "stream_seconds": time.perf_counter() - t_stream, "contexts": len(devices)}  # first batch to the GPUs .. last byte of the outputs (bench.py's end_to_end leg)
     if o.get("collapse"):
         report_copies(copies, n)
+    if o.get("remember"):
+        report_remembered(tally.get("remembered", 0), n)
     write_statistics(out, sink.stats)
     return 0
 

@@ -17,6 +17,7 @@
 #include "xm_kernel_common.h"
 #include "xm_pass_plan.h"
 #include "xm_collapse.h"
+#include "xm_memo.h"
 #include "xm_conf_table.h"
 #include "xm_device_rt.h"
 #include <hip/hip_runtime.h>
@@ -439,6 +440,31 @@ struct CollapseBuffers {
   DevBuf<int64_t> dRepOf, dRepList;
   DevBuf<long long> dCollapseBlocks;
 };
+// the run-wide memory of aligned queries (xm_context_set_memo; xm_memo.h, xm_memo_plan.h; allocated only when it is on).  What a stored result depends on
+// besides the query: the index - fixed for the context; the parameters - `filledUnder`, memoMustEmpty; and NOT the hashed length: a read only probes the
+// tables of gapmer lengths up to its own length, those tables never change once they are hashed (growth adds tables of greater lengths), and a read that
+// needs a table that is not there fails its call (XM_ST_NEED_GROW; ensureTablesFor makes that unreachable through the batch entries) instead of aligning
+// differently.  So the memory survives xm_index_ensure_length and growth by another context.  A call that throws never reaches the insert.
+struct MemoState {
+  MemoPlan plan{0, 0, 0};     // slots == 0: off
+  int fingerprintBits = 64;
+  DevBuf<unsigned long long> dKeys, dOffs, dState, dTotals, dFp;
+  DevBuf<uint8_t> dArena;
+  DevBuf<int64_t> dHit, dMissList;
+  unsigned long long claimed = 0, cursor = 0, records = 0;  // the host's copy of dState after the last insert
+  int64_t timesEmptied = 0;
+  bool filled = false;        // something was inserted under `filledUnder`
+  xm_params filledUnder;
+  bool on() const { return plan.slots > 0; }
+  MemoView view() const { return MemoView{dKeys.p, dOffs.p, (unsigned long long)plan.slots - 1, dArena.p, (unsigned long long)plan.arenaBytes, dState.p, fingerprintBits}; }
+  void clear(hipStream_t s) {  // every slot empty, nothing in the arena
+    HIP_CHECK(hipMemsetAsync(dKeys.p, 0, sizeof(unsigned long long) * (size_t)plan.slots, s));
+    HIP_CHECK(hipMemsetAsync(dOffs.p, 0xFF, sizeof(unsigned long long) * (size_t)plan.slots, s));
+    HIP_CHECK(hipMemsetAsync(dState.p, 0, sizeof(unsigned long long) * 4, s));
+    claimed = cursor = records = 0;
+    filled = false;
+  }
+};
 
 // An xm_index handle is a CONTEXT of an index: what one host thread needs to align batches on one GPU - a stream, batch buffers, scratch and a
 // result pool of its own - over tables it shares with every other context of the same index (HostShare: all of them; DeviceTables: those on
@@ -472,6 +498,7 @@ struct xm_index {
   DevBuf<double> dFinalDbls;
   DevBuf<DevCounters> dCounters;
   CollapseBuffers collapseBufs;
+  MemoState memo;
   // confidence table (IndexView::conf): the host's table, its copy in HBM, the miss list the kernels write, the reads that wait for a value
   ConfTable conf;
   static constexpr size_t kConfMissCap = 1 << 16;
@@ -526,12 +553,16 @@ struct AlignCall {
   int numCUs;
   IndexView view;
   Params params;
+  xm_params cParams;                 // the caller's, bit for bit (what the run-wide memory is filled under)
   BatchView bv;
   const int64_t* todo = nullptr;  // device list of the current pass; null on the first pass = all reads
   long long nTodo = 0;
   double kernelMs = 0;
   int launches = 0;
   int64_t copies = 0, rerun = 0;
+  int64_t remembered = 0;            // representatives served from the run-wide memory (MemoState)
+  unsigned long long hitInts = 0, hitDbls = 0;  // what their slices need in the result arenas
+  long long nMisses = 0;             // idx->memo.dMissList: the representatives this call aligns
   unsigned long long intCap = 0, dblCap = 0;
   unsigned long long cursors[4] = {0, 0, 0, 0};
   bool boundFilterUsed = false;
@@ -640,9 +671,9 @@ static void collapseBuildList(AlignCall& c) {
   timedLaunch(c, 5, -1, [&] {
     hipLaunchKernelGGL(xm_collapse_fingerprint_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, idx->collapseBufs.dCollapseKeys.p, idx->collapseBufs.dCollapseReps.p, (unsigned long long)(cap - 1), idx->collapseBufs.dRepOf.p);
     hipLaunchKernelGGL(xm_collapse_verify_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, (const unsigned long long*)idx->collapseBufs.dCollapseReps.p, idx->collapseBufs.dRepOf.p);
-    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, idx->collapseBufs.dCollapseBlocks.p);
+    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)nullptr, idx->collapseBufs.dCollapseBlocks.p);
     hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dCollapseTotal.p);
-    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const long long*)idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dRepList.p);
+    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)nullptr, (const long long*)idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dRepList.p);
   }, [&] { HIP_CHECK(hipMemcpyAsync(&nReps, idx->collapseBufs.dCollapseTotal.p, sizeof(nReps), hipMemcpyDeviceToHost, s)); });
   if (nReps < 1 || (long long)nReps > nq) throw std::runtime_error("internal error: collapsing found " + std::to_string(nReps) + " distinct queries in a batch of " + std::to_string(nq));
   c.copies = nq - (int64_t)nReps;
@@ -657,6 +688,67 @@ static void collapseFanOut(AlignCall& c) {
     hipLaunchKernelGGL(xm_collapse_fanout_kernel, dim3((unsigned)((c.nq + 255) / 256)), dim3(256), 0, c.s, (long long)c.nq, (const int64_t*)idx->collapseBufs.dRepOf.p, idx->dIntOff.p, idx->dDblOff.p,
                        idx->dIntLen.p, idx->dDblLen.p);
   }, [] {});
+}
+
+// ---- the run-wide memory (xm_context_set_memo; MemoState, xm_memo.h), in the order of a call: lookup, replay, (the passes,) insert
+// after collapseBuildList: the representatives are looked up, and the first pass's list becomes the ones the memory did not hold
+static void memoLookup(AlignCall& c) {
+  xm_index* idx = c.idx;
+  MemoState& m = idx->memo;
+  const int64_t nq = c.nq;
+  hipStream_t s = c.s;
+  if (memoMustEmpty(m.filled, &m.filledUnder, &c.cParams, sizeof(xm_params))) { m.clear(s); m.timesEmptied++; }
+  const long long nReps = c.nTodo;
+  const long long nBlocks = (nq + XM_COLLAPSE_PER_BLOCK - 1) / XM_COLLAPSE_PER_BLOCK;
+  m.dHit.ensure((size_t)nq); m.dFp.ensure((size_t)nq); m.dMissList.ensure((size_t)nq); m.dTotals.ensure(4);
+  HIP_CHECK(hipMemsetAsync(m.dTotals.p, 0, sizeof(unsigned long long) * 4, s));
+  unsigned long long totals[4] = {0, 0, 0, 0}, nMisses = 0;
+  timedLaunch(c, 4, -1, [&] {
+    hipLaunchKernelGGL(xm_memo_lookup_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, s, c.bv, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), m.dHit.p, m.dFp.p, m.dTotals.p);
+    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)m.dHit.p, idx->collapseBufs.dCollapseBlocks.p);
+    hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dCollapseTotal.p);
+    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)m.dHit.p,
+                       (const long long*)idx->collapseBufs.dCollapseBlocks.p, m.dMissList.p);
+  }, [&] {
+    HIP_CHECK(hipMemcpyAsync(totals, m.dTotals.p, sizeof(totals), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&nMisses, idx->collapseBufs.dCollapseTotal.p, sizeof(nMisses), hipMemcpyDeviceToHost, s));
+  });
+  if ((long long)totals[0] + (long long)nMisses != nReps)
+    throw std::runtime_error("internal error: of " + std::to_string(nReps) + " distinct queries the memory held " + std::to_string(totals[0]) + " and " + std::to_string(nMisses) + " are left");
+  c.remembered = (int64_t)totals[0]; c.hitInts = totals[1]; c.hitDbls = totals[2];
+  c.nMisses = (long long)nMisses;
+  c.todo = m.dMissList.p;
+  c.nTodo = c.nMisses;
+}
+
+// before the passes: the hits' slices into the result arenas, through the call's cursors (a hit is then what a read a pass finished is)
+static void memoReplay(AlignCall& c) {
+  xm_index* idx = c.idx;
+  MemoState& m = idx->memo;
+  const long long nReps = c.remembered + c.nMisses;
+  unsigned long long totals[4] = {0, 0, 0, 0};
+  timedLaunch(c, 1, -1, [&] {
+    hipLaunchKernelGGL(xm_memo_replay_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, c.s, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), (const int64_t*)m.dHit.p, c.outView(), m.dTotals.p);
+  }, [&] {
+    HIP_CHECK(hipMemcpyAsync(totals, m.dTotals.p, sizeof(totals), hipMemcpyDeviceToHost, c.s));
+    HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, c.s));
+  });
+  if (totals[3] != 0) throw std::runtime_error("internal error: " + std::to_string(totals[3]) + " remembered results found no room in the result arenas");
+}
+
+// after the last pass has succeeded: the representatives this call aligned are remembered, as far as the table and the arena have room (memoRoom, memoFull)
+static void memoInsert(AlignCall& c) {
+  xm_index* idx = c.idx;
+  MemoState& m = idx->memo;
+  const long long n = std::min<long long>(c.nMisses, memoRoom(m.plan, m.claimed));
+  if (n < 1 || memoFull(m.plan, m.claimed, m.cursor)) return;
+  unsigned long long state[4] = {0, 0, 0, 0};
+  m.filledUnder = c.cParams;
+  m.filled = true;
+  timedLaunch(c, 1, -1, [&] {
+    hipLaunchKernelGGL(xm_memo_insert_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c.s, c.bv, (const int64_t*)m.dMissList.p, n, m.view(), (const unsigned long long*)m.dFp.p, c.outView());
+  }, [&] { HIP_CHECK(hipMemcpyAsync(state, m.dState.p, sizeof(state), hipMemcpyDeviceToHost, c.s)); });
+  m.claimed = state[0]; m.cursor = state[1]; m.records = state[2];
 }
 
 // ---- passes 0 (XM_WAVE=1; off by default: measured slower than the lane-per-read passes on MI355X this round, profiles/r02/NOTES.md):
@@ -945,6 +1037,7 @@ static void finishStreams(AlignCall& c) {
   countersToResult(dc, res);
   res->counters[11] = c.rerun;
   res->extra[3] = c.boundFilterUsed ? 1 : 0;
+  res->extra[6] = c.remembered;
   res->extra[7] = c.copies;
   for (int i = 0; i < 16; i++) res->prof[i] = (int64_t)dc.t[i];
   res->kernel_ms = c.kernelMs;
@@ -958,7 +1051,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 3; }
+int32_t xm_abi_version(void) { return 4; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();
@@ -1066,7 +1159,48 @@ int xm_context_set_collapse(xm_index* idx, int32_t enable) {
   if (!idx) return fail("xm_context_set_collapse: null argument");
   std::lock_guard<std::mutex> lock(idx->mu);
   idx->collapse = enable != 0;
-  if (!idx->collapse) idx->collapseBufs = CollapseBuffers();
+  if (!idx->collapse && !idx->memo.on()) idx->collapseBufs = CollapseBuffers();
+  return 0;
+}
+
+int xm_context_set_memo(xm_index* idx, int64_t max_bytes) {
+  if (!idx) return fail("xm_context_set_memo: null argument");
+  if (max_bytes < 0) return fail("xm_context_set_memo: negative size");
+  if (idx->hostOnly) return fail("xm_context_set_memo: index was built with host_only=1");
+  const MemoPlan plan = memoPlan(max_bytes);
+  if (max_bytes > 0 && plan.slots == 0) return fail("xm_context_set_memo: the smallest memory is " + std::to_string(XM_MEMO_MIN_BYTES) + " bytes");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    HIP_CHECK(hipSetDevice(idx->device));
+    HIP_CHECK(hipStreamSynchronize(idx->stream));
+    const int64_t emptied = idx->memo.timesEmptied;
+    idx->memo = MemoState();  // (what was remembered goes with the old budget)
+    idx->memo.timesEmptied = emptied;
+    if (max_bytes == 0) {
+      if (!idx->collapse) idx->collapseBufs = CollapseBuffers();
+      return 0;
+    }
+    MemoState& m = idx->memo;
+    m.dKeys.ensure((size_t)plan.slots); m.dOffs.ensure((size_t)plan.slots); m.dState.ensure(4); m.dArena.ensure((size_t)plan.arenaBytes);
+    m.plan = plan;
+    m.fingerprintBits = (int)envKnob("XM_MEMO_FINGERPRINT_BITS", 64, 1, 64);  // (test knob: fewer bits make different queries share a fingerprint)
+    m.clear(idx->stream);
+    HIP_CHECK(hipStreamSynchronize(idx->stream));
+    return 0;
+  } catch (std::exception& e) {
+    idx->memo = MemoState();
+    return fail(std::string("xm_context_set_memo: ") + e.what());
+  }
+}
+
+int xm_context_memo_info(xm_index* idx, int64_t out[4]) {
+  if (!idx || !out) return fail("xm_context_memo_info: null argument");
+  std::lock_guard<std::mutex> lock(idx->mu);
+  const MemoState& m = idx->memo;
+  out[0] = (int64_t)m.records;
+  out[1] = m.on() ? (int64_t)(memoTableBytes(m.plan) + (long long)memoArenaUsed(m.plan, m.cursor)) : 0;
+  out[2] = m.on() ? (int64_t)m.plan.capacity : 0;
+  out[3] = m.timesEmptied;
   return 0;
 }
 
@@ -1363,19 +1497,23 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
     c.idx = idx; c.box = box; c.res = res; c.nq = nq; c.s = idx->stream; c.numCUs = idx->dt->numCUs;
     c.view = idx->dt->view;
     c.params = paramsFromC(*p);
+    c.cParams = *p;
     c.bv = idx->resident.view();
     prepareCall(c);
-    if (idx->collapse) collapseBuildList(c);
+    if (idx->collapse || idx->memo.on()) collapseBuildList(c);  // (a run-wide memory includes the batch)
+    if (idx->memo.on()) memoLookup(c);
     const BatchFacts facts{idx->resident.maxLen, idx->resident.anyPaired, idx->dt->contexts.load(), idx->scratchBytes};
     const BatchPolicy pol = makePolicy(facts, readPassKnobs(facts));
-    idx->dOutInts.ensure((size_t)nq * 40 + 4096); idx->dOutDbls.ensure((size_t)nq * 12 + 4096);
+    idx->dOutInts.ensure((size_t)nq * 40 + 4096 + (size_t)c.hitInts); idx->dOutDbls.ensure((size_t)nq * 12 + 4096 + (size_t)c.hitDbls);  // (the remembered results on top)
     c.intCap = idx->dOutInts.n; c.dblCap = idx->dOutDbls.n;
+    if (c.remembered > 0) memoReplay(c);
     if (pol.k.handOver) {
       idx->dRegionOf.ensure((size_t)nq);
       HIP_CHECK(hipMemsetAsync(idx->dRegionOf.p, 0xFF, sizeof(int32_t) * (size_t)nq, c.s));
     }
-    if (pol.k.waveForm && idx->resident.maxLen <= 256) runWaveForm(c, pol.k.tracePasses);
-    runLanePasses(c, pol);
+    if (pol.k.waveForm && idx->resident.maxLen <= 256 && c.nTodo > 0) runWaveForm(c, pol.k.tracePasses);
+    runLanePasses(c, pol);  // (nothing left to align: no pass runs)
+    if (idx->memo.on()) memoInsert(c);
     if (c.copies > 0) collapseFanOut(c);
     finishStreams(c);
     *out = res;

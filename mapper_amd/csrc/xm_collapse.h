@@ -8,7 +8,8 @@
 //   2 xm_collapse_verify_kernel       one wave per query: a query whose slot holds a lower index is compared with that query byte for byte; any
 //                                     difference (a fingerprint collision) makes it its own representative.  repOf[q] = the query q is served from.
 //   3 xm_collapse_count_kernel, xm_collapse_scan_kernel, xm_collapse_compact_kernel
-//                                     the representatives in ascending query order: the first pass's work list
+//                                     the representatives in ascending query order: the first pass's work list (with the run-wide memory, xm_memo.h, a
+//                                     second time over the representatives it did not hold: the predicate is an argument)
 //   4 xm_collapse_fanout_kernel       after the last pass: every copy's slice (offsets and lengths in the result arena) is its representative's
 // Invariant: a query is only ever served from a byte-identical query of the same batch; the fingerprint decides how much is saved, never the output.
 #pragma once
@@ -29,11 +30,9 @@ __device__ __forceinline__ unsigned long long xmCollapseMix(unsigned long long z
 
 __device__ __forceinline__ unsigned long long xmBits(double x) { return (unsigned long long)__double_as_longlong(x); }
 
-// table: keys[cap] (0 = empty), reps[cap] (lowest query index of the slot; ~0 = none), cap a power of two >= 2 nq.  repOf[q] <- q's slot.
-__global__ void __launch_bounds__(256) xm_collapse_fingerprint_kernel(BatchView batch, unsigned long long* keys, unsigned long long* reps, unsigned long long mask, int64_t* repOf) {
-  const long long q = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int lane = (int)(threadIdx.x & 63u);
-  if (q >= batch.nq) return;
+// The fingerprint of query q, computed by one wave (lane = 0..63) and returned in every lane: 64 bits over everything the alignment of the query reads.  Never 0.
+// (xm_collapse_fingerprint_kernel and the run-wide memory's xm_memo_lookup_kernel, xm_memo.h, both key their tables with it.)
+__device__ __forceinline__ unsigned long long xmQueryFingerprint(const BatchView& batch, long long q, int lane) {
   const int mc = batch.mateCount[q];
   // the sum over the bases of mix(mate, position, code): order-sensitive (the position is in every term), reduced across the lanes
   unsigned long long acc = 0;
@@ -46,11 +45,19 @@ __global__ void __launch_bounds__(256) xm_collapse_fingerprint_kernel(BatchView 
       acc += xmCollapseMix(((((unsigned long long)m << 16) | (unsigned)i) << 8 | codes[i]) + 0x9E3779B97F4A7C15ull);
   }
   for (int d = 32; d > 0; d >>= 1) acc += (unsigned long long)__shfl_xor((long long)acc, d);
-  if (lane != 0) return;
   unsigned long long h = xmCollapseMix(acc ^ xmCollapseMix((unsigned long long)mc | ((unsigned long long)lens[0] << 2) | ((unsigned long long)lens[1] << 33)));
   h = xmCollapseMix(h ^ xmBits(batch.expectedInner[q]));
   h = xmCollapseMix(h ^ xmCollapseMix(xmBits(batch.deviation[q]) + 0xD1B54A32D192ED03ull));
-  if (h == 0) h = 1;  // (0 marks an empty slot)
+  return h == 0 ? 1 : h;  // (0 marks an empty slot)
+}
+
+// table: keys[cap] (0 = empty), reps[cap] (lowest query index of the slot; ~0 = none), cap a power of two >= 2 nq.  repOf[q] <- q's slot.
+__global__ void __launch_bounds__(256) xm_collapse_fingerprint_kernel(BatchView batch, unsigned long long* keys, unsigned long long* reps, unsigned long long mask, int64_t* repOf) {
+  const long long q = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = (int)(threadIdx.x & 63u);
+  if (q >= batch.nq) return;
+  const unsigned long long h = xmQueryFingerprint(batch, q, lane);
+  if (lane != 0) return;
   unsigned long long slot = h & mask;
   while (true) {  // (at most half the slots are taken: the probe ends)
     const unsigned long long was = atomicCAS(&keys[slot], 0ull, h);
@@ -92,17 +99,21 @@ __device__ __forceinline__ long long xmBlockSum(long long a, long long* sh) {
   return sh[0];
 }
 
-// representatives per block of XM_COLLAPSE_PER_BLOCK queries
-__global__ void __launch_bounds__(256) xm_collapse_count_kernel(long long nq, const int64_t* repOf, long long* blockCount) {
+// The work list's predicate: q is a representative and, where the run-wide memory looked the representatives up (xm_memo.h: hit[q] = the record's offset, -1 =
+// a miss; null without the memory), it missed.
+__device__ __forceinline__ bool xmListed(const int64_t* repOf, const int64_t* hit, long long q) { return repOf[q] == q && (hit == nullptr || hit[q] < 0); }
+
+// listed queries per block of XM_COLLAPSE_PER_BLOCK queries
+__global__ void __launch_bounds__(256) xm_collapse_count_kernel(long long nq, const int64_t* repOf, const int64_t* hit, long long* blockCount) {
   __shared__ long long sh[256];
   const long long base = (long long)blockIdx.x * XM_COLLAPSE_PER_BLOCK + (long long)threadIdx.x * XM_COLLAPSE_PER_THREAD;
   long long a = 0;
-  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && repOf[base + k] == base + k) a++;
+  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && xmListed(repOf, hit, base + k)) a++;
   a = xmBlockSum(a, sh);
   if (threadIdx.x == 0) blockCount[blockIdx.x] = a;
 }
 
-// exclusive prefix of the block counts; total[0] = number of representatives
+// exclusive prefix of the block counts; total[0] = number of listed queries
 __global__ void xm_collapse_scan_kernel(long long nBlocks, long long* blockCount, unsigned long long* total) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   long long a = 0;
@@ -110,12 +121,12 @@ __global__ void xm_collapse_scan_kernel(long long nBlocks, long long* blockCount
   total[0] = (unsigned long long)a;
 }
 
-// list[0 .. representatives) = the representatives in ascending query order
-__global__ void __launch_bounds__(256) xm_collapse_compact_kernel(long long nq, const int64_t* repOf, const long long* blockCount, int64_t* list) {
+// list[0 .. total) = the listed queries in ascending query order
+__global__ void __launch_bounds__(256) xm_collapse_compact_kernel(long long nq, const int64_t* repOf, const int64_t* hit, const long long* blockCount, int64_t* list) {
   __shared__ long long sh[256];
   const long long base = (long long)blockIdx.x * XM_COLLAPSE_PER_BLOCK + (long long)threadIdx.x * XM_COLLAPSE_PER_THREAD;
   long long a = 0;
-  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && repOf[base + k] == base + k) a++;
+  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && xmListed(repOf, hit, base + k)) a++;
   sh[threadIdx.x] = a;
   __syncthreads();
   for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the 256 thread counts
@@ -126,7 +137,7 @@ __global__ void __launch_bounds__(256) xm_collapse_compact_kernel(long long nq, 
     __syncthreads();
   }
   long long at = blockCount[blockIdx.x] + sh[threadIdx.x] - a;
-  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && repOf[base + k] == base + k) list[at++] = base + k;
+  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && xmListed(repOf, hit, base + k)) list[at++] = base + k;
 }
 
 // every copy's slice is its representative's (the representatives were written by the passes, in earlier launches; no copy is a representative)

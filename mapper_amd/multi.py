@@ -18,9 +18,11 @@ import numpy as np
 
 
 class MultiGpuDatabase:
-    def __init__(self, contigs, devices, collapse=False, **kw):
+    def __init__(self, contigs, devices, collapse=False, memo_bytes=0, **kw):
         """devices: GPU ordinals, e.g. [0, 1, 2, 3]; a repeated ordinal gives that GPU two independent contexts (tests on one-GPU machines).
         collapse: every context aligns identical queries of a batch once (ReferenceDatabase.set_collapse).
+        memo_bytes: every context remembers the queries it aligns in that many bytes of HBM and serves repeats in its later batches from there
+        (ReferenceDatabase.set_memo; 0: off).  Per context: a query seen k times over N contexts is aligned at most min(k, N) times.
         kw: ReferenceDatabase's build options (mode, enable_gapmers, max_query_length, cache_dir)."""
         from . import api
         if not devices:
@@ -56,6 +58,8 @@ class MultiGpuDatabase:
         self.contigs = first.contigs
         for r in self.replicas:
             r.set_collapse(collapse)
+            if memo_bytes:
+                r.set_memo(memo_bytes)
 
     def info(self):
         return self.replicas[0].info()
