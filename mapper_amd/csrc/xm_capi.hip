@@ -150,7 +150,8 @@ __global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_align_kernel(IndexV
 #endif
     if (st != XM_OK) local = before;  // work of a read that is rerun by a later pass is counted there
     if (second) continue;             // (pair mode: the first lane of the read publishes)
-    // (a read that found the result arena full is run again too: round 6 - its work used to be counted twice, PathAligner calls and nodes of the first call on a fresh context)
+    // (a read that found the result arena full is run again too: round 6 - its work used to be counted twice, PathAligner calls and nodes of the first call on a fresh context;
+    // pinned by tests/test_gpu_result_stage.py, test_light_pass_overflows_both_arenas: the same batch fresh and warm, equal counters)
     if (publishRead(out, q, rr, cx, local, lists) == XM_ST_OUT_OVERFLOW) local = before;
   }
   if (!second) addCounters(counters, local);
@@ -184,7 +185,7 @@ __global__ void __launch_bounds__(256) xm_wave_classify_kernel(const int64_t* to
 
 // Exclusive prefix sums of the per-query stream lengths (query order), three small kernels: block totals, scan of the totals,
 // final offsets.  4096 queries per block.
-constexpr int XM_SCAN_PER_THREAD = 16;
+constexpr int XM_SCAN_PER_THREAD = 16;  // (the edges this gives - 16 per thread, 256 per gather block, 4096 per scan block - are walked by tests/test_gpu_result_stage.py)
 constexpr int XM_SCAN_PER_BLOCK = 256 * XM_SCAN_PER_THREAD;
 
 __device__ __forceinline__ void blockReduce2(long long& a, long long& b, long long* shA, long long* shB) {

@@ -54,6 +54,63 @@ def pe_batch(m1, m2, expected=100.0, dev=50.0):
     return oracle_lib.QueryBatch.from_arrays(mc, mo, ml, codes, np.full(nq, expected), np.full(nq, dev))
 
 
+def _gather_slices(data, starts, lens):
+    """data[starts[i] : starts[i] + lens[i]] for every i, concatenated -> (array, offsets of the pieces in it: len(starts) + 1 of them, by np.cumsum)."""
+    starts, lens = np.asarray(starts, np.int64), np.asarray(lens, np.int64)
+    off = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=off[1:])
+    take = np.repeat(starts - off[:-1], lens) + np.arange(off[-1], dtype=np.int64)
+    return np.ascontiguousarray(np.asarray(data)[take]), off
+
+
+def compose_batch(U, idx):
+    """The batch whose query j is query idx[j] of the oracle_lib.QueryBatch U (its mates, expected inner distance and deviation): the bases are copied,
+    every query of the result has bases of its own."""
+    idx = np.asarray(idx, np.int64)
+    ml = np.ascontiguousarray(U.mate_length.reshape(-1, 2)[idx].reshape(-1))
+    codes, off = _gather_slices(U.codes, U.mate_offset.reshape(-1, 2)[idx].reshape(-1), ml)
+    mo = np.where(ml > 0, off[:-1], 0)
+    if len(codes) == 0:
+        codes = np.zeros(1, np.uint8)
+    return oracle_lib.QueryBatch.from_arrays(U.mate_count[idx].copy(), np.ascontiguousarray(mo), ml, codes, U.expected_inner[idx].copy(), U.deviation[idx].copy())
+
+
+def alignments_per_query(s):
+    """The number of alignments in every query's slice of the streams s (the sum over its components)."""
+    out = np.zeros(len(s.int_off) - 1, np.int64)
+    for q in range(len(out)):
+        out[q] = sum(len(als) for als in s.query(q))
+    return out
+
+
+def align_each(R, U, params, threads=1):
+    """The oracle's streams of the batch U (one call of R.align) with what compose_streams needs beside them: .per_query, an int64 array [U.nq, 24] of every
+    query's own contribution to the oracle's counters - the oracle reports counters per call, so each query is aligned again in a batch of its own - and
+    .alignments, the alignments in every query's slice.  A query's result does not depend on its batch: the one-query calls must return the slices of the
+    call over U and their counters must add up to its counters, which is asserted here."""
+    want = R.align(U, params, threads=threads)
+    want.alignments = alignments_per_query(want)
+    want.per_query = np.zeros((U.nq, 24), np.int64)
+    for q in range(U.nq):
+        one = R.align(compose_batch(U, [q]), params, threads=1)
+        assert np.array_equal(one.ints, want.ints[want.int_off[q]:want.int_off[q + 1]]), ("a query's result depends on its batch", q)
+        want.per_query[q] = one.counters
+    assert want.per_query.sum(axis=0).tolist() == [int(x) for x in want.counters], (want.per_query.sum(axis=0).tolist(), want.counters)
+    return want
+
+
+def compose_streams(want_U, idx):
+    """What a batch of the queries idx of U (compose_batch) must give, from the oracle's run over U (align_each), in plain numpy: every query's int and
+    double slices in batch order, the offsets by np.cumsum, .counters = the sum of the queries' own contributions to the oracle's counters and
+    .alignments_out = the alignments in the slices."""
+    idx = np.asarray(idx, np.int64)
+    ints, int_off = _gather_slices(want_U.ints, want_U.int_off[idx], want_U.int_off[idx + 1] - want_U.int_off[idx])
+    dbls, dbl_off = _gather_slices(want_U.dbls, want_U.dbl_off[idx], want_U.dbl_off[idx + 1] - want_U.dbl_off[idx])
+    s = oracle_lib.Streams(ints, dbls, int_off, dbl_off, [int(x) for x in want_U.per_query[idx].sum(axis=0)])
+    s.alignments_out = int(want_U.alignments[idx].sum())
+    return s
+
+
 def check_align_case(case, comps, ref_codes):
     """Checks the expectations a reference JUnit case pins on the decoded QueryAlignments (list of components)."""
     e = case["expect"]
