@@ -19,7 +19,7 @@
 #include <string.h>
 #include "xmapper_hip.h"
 
-#define XMJ_ABI_VERSION 4  /* include/xmapper_hip.h: xm_context_set_memo, xm_context_memo_info, xm_result.extra[6] */
+#define XMJ_ABI_VERSION 5  /* include/xmapper_hip.h: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free */
 
 /* ---------------------------------------------------------------- part 1: marshalling on plain C arrays ---------------------------------------- */
 

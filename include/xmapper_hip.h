@@ -95,14 +95,14 @@ typedef struct xm_result {
   double kernel_ms;   /* sum of the align (and search, collapse and memory) kernels' launch durations (HIP events on the launch stream) */
   double h2d_ms, d2h_ms;  /* batch upload; prefix sums + query-order gather + copy of the four streams to the host */
   int32_t kernel_launches;  /* align + search (+ collapse, + memory) kernel launches of this call */
-  int32_t reserved;
+  int32_t reserved;  /* (ABI version 5) microseconds of host time this call waited for the mutex of its memory of aligned queries (both critical sections; 0 without one) */
   int64_t prof[16];   /* diagnostic builds (-DXM_PROFILE=1: summed over lanes, =2: per wave) only: shader-clock ticks per phase; otherwise 0 */
   /* (appended in ABI version 2; xm_abi_version())  the rejection filter in front of PathAligner (batches of long reads): 0 searches it examined, 1 searches it
    * proved null without running them (PathAligner.java:169: the search would have returned null after exploring every node within the budget; their nodes
    * are not in counters[6]), 2 cells of the bounding recurrence it computed, 3 = 1 when a pass of this call ran with the filter; 4 pieces (BlockAligner.alignPiece,
    * BlockAligner.java:215-249) the filter examined, 5 pieces it proved unalignable within their budget before their chain ran (their PathAligner calls and nodes are in neither counters[5] nor
    * counters[6]); 6 (ABI version 4) queries of this call whose results were replayed from the context's memory of
-   * earlier calls instead of being aligned (xm_context_set_memo; 0 when it is off); 7 (ABI version 3) queries of this call whose results were copied from a byte-identical query of the batch instead of being
+   * earlier calls - or, with xm_context_attach_memory, from the GPU's memory, either generation - instead of being aligned (xm_context_set_memo; 0 when it is off); 7 (ABI version 3) queries of this call whose results were copied from a byte-identical query of the batch instead of being
    * aligned (xm_context_set_collapse; 0 when collapsing is off) */
   int64_t extra[8];
 } xm_result;
@@ -122,7 +122,8 @@ const char* xm_last_error(void);
  * time: lets a caller check that the loaded library was built from the sources it sits beside. */
 const char* xm_build_stamp(void);
 /* Version of this header's structs and entry points: 2 = xm_result.extra[] appended, xm_seed_probe_packed replaces xm_seed_probe; 3 = xm_context_set_collapse,
- * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6].  A binding checks it once
+ * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6]; 5 = xm_memory_new, xm_context_attach_memory, xm_memory_info,
+ * xm_memory_free, xm_result.reserved carries the wait for a memory.  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -166,11 +167,41 @@ int xm_context_set_collapse(xm_index* context, int32_t enable);
  * the memory survives xm_index_ensure_length and growth of the tables by another context (a read only reads the tables of lengths up to its own).
  * Counters: extra[6] = the queries served from the memory, extra[7] = the within-batch copies, counters[0] = num_queries - extra[6] - extra[7], and
  * counters[0..10], extra[0..5] count the work done, as with collapsing.  Per context: a query seen k times over N contexts is aligned at most min(k, N)
- * times.  Off by default. */
+ * times (one memory for all contexts of a GPU, which also keeps remembering when it is full: xm_memory_new below).  Off by default.  A non-zero size
+ * fails on a context that is attached to a shared memory. */
 int xm_context_set_memo(xm_index* context, int64_t max_bytes);
 /* out[0] queries remembered, out[1] bytes of HBM in use for them (the table and the records), out[2] the most queries the table takes (the records' arena
  * may fill first), out[3] how often a change of xm_params emptied the memory.  All 0 while the memory is off (out[3] keeps counting over the context's life). */
 int xm_context_memo_info(xm_index* context, int64_t out[4]);
+/* One memory of aligned queries per GPU, shared and never full (the reference's AlignmentCache is one map for the whole run that every AlignerWorker reads and
+ * fills, Api.java:62,82, AlignerWorker.java:264-291).  xm_memory_new makes a memory of max_bytes of HBM on the GPU of `context`, for the contexts of that index
+ * on that GPU; it belongs to no context.  generations = 1 or 2: every generation is a table and an arena as above for max_bytes / generations (at least
+ * generations * 65 536 bytes, less fails).  xm_context_attach_memory: this context looks its queries up in `memory` and remembers what it aligns there, as
+ * with xm_context_set_memo (the within-batch collapse included); NULL detaches.  It fails - xm_last_error says which case - for a context of another index
+ * or another GPU (the records depend on the tables), for a context that has xm_context_set_memo on, and for host_only.
+ * The rules (mapper_amd/csrc/xm_memo_plan.h states them as code):
+ *   lookup   the young generation is probed first, then the old one; a key match whose record is another query does not end the lookup; a query held in
+ *            both is served from the young one.
+ *   insert   before it, the call knows the exact number of queries it aligned and the exact bytes of their records.  If the young generation takes all of
+ *            them they are inserted; otherwise, with two generations and a young one that is not empty, the generations TURN first - the old one is dropped,
+ *            the young becomes the old, the dropped one is emptied and becomes the young.  A batch larger than a generation is inserted as far as room goes.
+ *            With one generation nothing ever turns: full means nothing more is remembered.
+ *   second   the queries a call was served from the old generation only are copied into the young one, if it takes all of them (else none in that call;
+ *   chance   never a turn): queries that keep coming back survive the turns.
+ *   params   one set per memory: a call from any attached context whose xm_params differ in any bit empties both generations first.
+ * The one concurrency rule: launches of different contexts never touch a memory at the same time.  The memory carries a host mutex, which a call holds
+ * twice: from before its lookup until replay and promotion have completed on its stream, and from before it measures what it aligned until the insert (and a
+ * turn's clears) have completed on its stream.  Between the two, while the passes run, the mutex is free, so the contexts of a GPU keep overlapping their
+ * passes; another context may meanwhile insert the same query (the later insert is dropped) or turn the generations.  Results never change: a query is only
+ * ever served from a byte-identical query aligned earlier under bit-identical parameters.
+ * Lifetime: the memory lives until its handle is freed AND its last context has detached or been freed, in any order; all of its HBM is back with the GPU
+ * after that.  xm_memory_info: out[0] records held, 1 bytes of HBM in use (tables and records), 2 records the tables take, 3 times a change of xm_params
+ * emptied it, 4 turns of the generations, 5 records promoted, 6 contexts attached, 7 generations. */
+typedef struct xm_memory xm_memory;
+int xm_memory_new(xm_index* context, int64_t max_bytes, int32_t generations, xm_memory** out);
+int xm_context_attach_memory(xm_index* context, xm_memory* memory);
+int xm_memory_info(xm_memory* memory, int64_t out[8]);
+void xm_memory_free(xm_memory* memory);
 /* Binary index cache, in the spirit of --cache-dir (DirCache.java:19-60, HashBlock_Database.java:106-114,477-487, PackedMap.java:249-279:
  * the reference writes one "length-<n>" file per PackedMap under a directory keyed by its property map).  xm_index_save writes the
  * reference, every table hashed so far and the duplication map into ONE file (beside `path`, then renamed: concurrent writers are safe).

@@ -40,7 +40,7 @@ class XmResult(C.Structure):
                 ("kernel_launches", C.c_int32), ("reserved", C.c_int32), ("prof", C.c_int64 * 16), ("extra", C.c_int64 * 8)]
 
 
-ABI_VERSION = 4  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]
+ABI_VERSION = 5  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free
 
 
 class XmIndexInfo(C.Structure):
@@ -50,7 +50,7 @@ class XmIndexInfo(C.Structure):
                 ("hash_seconds", C.c_double), ("duplication_seconds", C.c_double)]
 
 
-EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
+EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
            "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_free"]
 
 
@@ -112,6 +112,11 @@ def lib():
         L.xm_context_set_collapse.argtypes = [C.c_void_p, C.c_int32]
         L.xm_context_set_memo.argtypes = [C.c_void_p, C.c_int64]
         L.xm_context_memo_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.xm_memory_new.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p)]
+        L.xm_context_attach_memory.argtypes = [C.c_void_p, C.c_void_p]
+        L.xm_memory_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.xm_memory_free.argtypes = [C.c_void_p]
+        L.xm_memory_free.restype = None
         L.xm_device_memory.argtypes = [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.xm_index_load.argtypes = [C.c_char_p, C.POINTER(XmRef), C.POINTER(XmBuildOpts), C.POINTER(C.c_void_p)]
         L.xm_index_ensure_length.argtypes = [C.c_void_p, C.c_int32]
@@ -176,7 +181,8 @@ def copy_result(r):
     io = np.ctypeslib.as_array(r.int_off, shape=(r.num_queries + 1,)).copy()
     do = np.ctypeslib.as_array(r.dbl_off, shape=(r.num_queries + 1,)).copy()
     return dict(ints=ints, dbls=dbls, int_off=io, dbl_off=do, counters=list(r.counters), kernel_ms=r.kernel_ms, h2d_ms=r.h2d_ms,
-                d2h_ms=r.d2h_ms, kernel_launches=r.kernel_launches, prof=list(r.prof), extra=list(r.extra))
+                d2h_ms=r.d2h_ms, kernel_launches=r.kernel_launches, prof=list(r.prof), extra=list(r.extra),
+                memory_wait_us=int(r.reserved))  # (xm_result.reserved: host microseconds the call waited for its memory's mutex)
 
 
 class _ResultOwner:
@@ -205,7 +211,8 @@ def view_result(L, res):
 
     return dict(ints=view(r.ints, C.c_int32, r.num_ints), dbls=view(r.dbls, C.c_double, r.num_dbls), int_off=view(r.int_off, C.c_int64, r.num_queries + 1),
                 dbl_off=view(r.dbl_off, C.c_int64, r.num_queries + 1), counters=list(r.counters), kernel_ms=r.kernel_ms, h2d_ms=r.h2d_ms,
-                d2h_ms=r.d2h_ms, kernel_launches=r.kernel_launches, prof=list(r.prof), extra=list(r.extra))
+                d2h_ms=r.d2h_ms, kernel_launches=r.kernel_launches, prof=list(r.prof), extra=list(r.extra),
+                memory_wait_us=int(r.reserved))  # (xm_result.reserved: host microseconds the call waited for its memory's mutex)
 
 
 def pinned_host_bytes():

@@ -148,7 +148,7 @@ class BatchResult:
     @property
     def remembered(self):
         """Queries of the batch whose results were replayed from the context's memory of earlier batches instead of being aligned (xm_result.extra[6]; 0 unless
-        ReferenceDatabase.set_memo(bytes))."""
+        ReferenceDatabase.set_memo(bytes) or ReferenceDatabase.attach_memory(QueryMemory))."""
         return int(self.extra[6])
 
     def query_alignments(self, q):
@@ -283,6 +283,13 @@ class ReferenceDatabase:
         out = (C.c_int64 * 4)()
         _check(self._L.xm_context_memo_info(self._h, out))
         return {"entries": out[0], "bytes_used": out[1], "capacity": out[2], "times_emptied": out[3]}
+
+    def attach_memory(self, memory):
+        """xm_context_attach_memory: this context looks its queries up in `memory` (a QueryMemory of this index on this GPU, shared with the other contexts
+        attached to it) and remembers what it aligns there; None detaches.  Same results; BatchResult.remembered counts the queries served."""
+        if memory is not None and not getattr(memory, "_h", None):
+            raise ValueError("the QueryMemory is closed")
+        _check(self._L.xm_context_attach_memory(self._h, memory._h if memory is not None else None))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -464,6 +471,38 @@ class ReferenceDatabase:
         return counts, pos, ms.value
 
 
+class QueryMemory:
+    """xm_memory_new: one memory of aligned queries on the GPU of `db`, for any number of contexts of that index on that GPU (ReferenceDatabase.attach_memory):
+    the reference's AlignmentCache is one map for the run that every AlignerWorker reads and fills (Api.java:62,82).  Two generations keep it remembering
+    however long the run is: when the young one is full they turn - the old one is dropped, the young becomes the old - and a query served from the old one
+    is copied into the young one (a second chance), so queries that keep coming back stay.  generations=1: full means nothing more is remembered.
+    The memory lives until it is closed and its last context has detached or been closed, in any order."""
+    FIELDS = ("entries", "bytes_used", "capacity", "times_emptied", "turns", "promoted", "contexts", "generations")
+
+    def __init__(self, db, max_bytes, generations=2):
+        self._L = _capi.lib()
+        h = C.c_void_p()
+        _check(self._L.xm_memory_new(db._h, int(max_bytes), int(generations), C.byref(h)))
+        self._h = h
+
+    def info(self):
+        """xm_memory_info -> {entries, bytes_used, capacity, times_emptied, turns, promoted, contexts, generations}."""
+        out = (C.c_int64 * 8)()
+        _check(self._L.xm_memory_info(self._h, out))
+        return dict(zip(self.FIELDS, (int(x) for x in out)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.xm_memory_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
 def measure_random_gather(table_bytes=4 << 30, accesses=1 << 26, device=0):
     """Random 64-byte-sector reads per second the GPU sustains (xm_measure_random_gather) -> (sectors/s, kernel ms)."""
     L = _capi.lib()
@@ -480,14 +519,16 @@ def device_memory(device=0):
     return f.value, t.value
 
 
-def divide_scratch(contexts, device, reserve=24 << 30, most=200 << 30, per_context_extra=0):
+def divide_scratch(contexts, device, reserve=24 << 30, most=200 << 30, per_context_extra=0, shared_extra=0):
     """Several contexts on one GPU: what is free now (the index is resident) minus a reserve for batches and result arenas and minus what every
     context will allocate beside its scratch (per_context_extra: a pile-up of 40-48 bytes per reference base with --out-mutations), in equal
-    parts; a context that would get less than 8 GiB is not worth having -> (how many of `contexts` to use, bytes each)."""
+    parts; a context that would get less than 8 GiB is not worth having -> (how many of `contexts` to use, bytes each).  shared_extra: what will be
+    allocated on this GPU once, however many contexts it has (the GPU's QueryMemory)."""
     for c in contexts:
         c.set_scratch(1 << 20)  # (a context that already holds scratch gives it back first: what is free is then what there is to divide)
     free, _ = device_memory(device)
     reserve = min(int(reserve), int(free) // 4)  # (a small or busy GPU: the reserve is a share of what there is, not a fixed claim)
+    free -= int(shared_extra)
     n = len(contexts)
     while n > 1 and (free - reserve - n * per_context_extra) // n < (8 << 30):
         n -= 1

@@ -13,9 +13,10 @@ honoured: the index goes to one file under it, api.index_cache_path) and are ref
 
 Flags of this harness that Mapper does not have: --batch-size <n>, --gpus <n>, --contexts <n>, --devices <i,j,...>, --device <i>, --per-object,
 --collapse-identical-queries (byte-identical queries of a batch are aligned once and share the results, as the reference's alignment cache does; the
-outputs are the same, and one line on stderr says how many queries were served as copies), and --remember-queries <MiB> (every context keeps the queries
+outputs are the same, and one line on stderr says how many queries were served as copies), --remember-queries <MiB> (every context keeps the queries
 it has aligned in that much HBM and serves byte-identical queries of its later batches from there: the same cache across batches; same outputs, one line on
-stderr).
+stderr), and --remember-queries-per-gpu <MiB> (one such memory per GPU, which all its contexts share and which keeps remembering when it is full; not
+together with --remember-queries).
 """
 import contextlib
 import gzip
@@ -184,6 +185,10 @@ def parse_args(argv):
             o["remember"] = int(argv[i + 1]) << 20; i += 1
             if o["remember"] < 0:
                 raise UsageError("--remember-queries must be >= 0")
+        elif a == "--remember-queries-per-gpu":  # (not a Mapper flag) MiB of HBM per GPU for one memory of aligned queries that all contexts of the GPU share (api.QueryMemory): two generations, never full
+            o["remember_per_gpu"] = int(argv[i + 1]) << 20; i += 1
+            if o["remember_per_gpu"] < 0:
+                raise UsageError("--remember-queries-per-gpu must be >= 0")
         elif a == "--per-object":  # (not a Mapper flag) the harness's first implementation: one Python object per read and per alignment (the reference for the formats; tests)
             o["per_object"] = True
         elif a == "--device":  # (not a Mapper flag) which GPU
@@ -197,6 +202,8 @@ def parse_args(argv):
         else:
             raise UsageError("Unrecognized argument: " + a)
         i += 1
+    if o.get("remember") and o.get("remember_per_gpu"):
+        raise UsageError("--remember-queries (a memory per context) and --remember-queries-per-gpu (one per GPU) exclude each other")
     return o
 
 
@@ -288,12 +295,13 @@ def context_devices(o, batches, single_short):
     return [d for d in (explicit or [o["device"]]) for _ in range(contexts)]
 
 
-def open_gpu_database(contigs, devices, max_query_length, enable_gapmers=True, collapse=False, cache_dir=None, per_context_extra=0, memo_bytes=0):
+def open_gpu_database(contigs, devices, max_query_length, enable_gapmers=True, collapse=False, cache_dir=None, per_context_extra=0, memo_bytes=0, shared_memo_bytes=0):
     """The index of `contigs` (in api.sort_reference order) with one context per entry of `devices`.  per_context_extra: what every context will allocate
-    beside its scratch (api.divide_scratch; memo_bytes, every context's memory of aligned queries, is part of it).  (A job whose later reads are longer than max_query_length grows the index on demand: xm_index_ensure_length.)"""
-    if len(devices) > 1:
+    beside its scratch (api.divide_scratch; memo_bytes, every context's memory of aligned queries, is part of it; shared_memo_bytes, the one memory
+    of each GPU, is not: it is counted once per GPU).  (A job whose later reads are longer than max_query_length grows the index on demand: xm_index_ensure_length.)"""
+    if len(devices) > 1 or shared_memo_bytes:
         from . import multi
-        return multi.MultiGpuDatabase(contigs, devices, collapse=collapse, memo_bytes=memo_bytes, mode="mapper", enable_gapmers=enable_gapmers, max_query_length=max_query_length,
+        return multi.MultiGpuDatabase(contigs, devices, collapse=collapse, memo_bytes=memo_bytes, shared_memo_bytes=shared_memo_bytes, mode="mapper", enable_gapmers=enable_gapmers, max_query_length=max_query_length,
                                       cache_dir=cache_dir, per_context_extra=per_context_extra)
     db = api.ReferenceDatabase(contigs, mode="mapper", enable_gapmers=enable_gapmers, device=devices[0], max_query_length=max_query_length, cache_dir=cache_dir)
     db.set_collapse(collapse)
@@ -453,7 +461,7 @@ def report_copies(copies, n):
 
 
 def report_remembered(remembered, n):
-    """--remember-queries: the one statistics line of the flag (stderr, like report_copies)."""
+    """--remember-queries, --remember-queries-per-gpu: the one statistics line of the flag (stderr, like report_copies)."""
     sys.stderr.write("Remembered queries: %d of %d queries were served from an identical query of an earlier batch\n" % (remembered, n))
 
 
@@ -481,6 +489,8 @@ def run(argv, out=sys.stdout, open_database=None):
         # middle depth 8 B per reference base: 149 GB for a 3.1 Gb reference - so the contexts of a GPU are counted with it)
         pile_up = (48 if o.get("query_end_fraction", 0.1) > 0 else 40) * sum(len(t) for _, t in ordered) + (64 << 20) if o.get("out_mutations") else 0
         memo = {"memo_bytes": o["remember"]} if o.get("remember") else {}  # (--remember-queries: every context's memory, counted beside its scratch)
+        if o.get("remember_per_gpu"):  # (--remember-queries-per-gpu: one memory per GPU, counted once per GPU when its contexts divide the scratch)
+            memo = {"shared_memo_bytes": o["remember_per_gpu"]}
         db = (open_database or open_gpu_database)(ordered, devices, max_len, enable_gapmers=o["enable_gapmers"], collapse=o.get("collapse", False),
                                                   cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0), **memo)
         job.callback(db.close)
@@ -515,7 +525,7 @@ def run(argv, out=sys.stdout, open_database=None):
     last_timing = {"queries": n, "stream_seconds": time.perf_counter() - t_stream, "contexts": len(devices)}  # first batch to the GPUs .. last byte of the outputs (bench.py's end_to_end leg)
     if o.get("collapse"):
         report_copies(copies, n)
-    if o.get("remember"):
+    if o.get("remember") or o.get("remember_per_gpu"):
         report_remembered(tally.get("remembered", 0), n)
     write_statistics(out, sink.stats)
     return 0

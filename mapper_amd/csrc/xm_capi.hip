@@ -441,30 +441,62 @@ struct CollapseBuffers {
   DevBuf<int64_t> dRepOf, dRepList;
   DevBuf<long long> dCollapseBlocks;
 };
-// the run-wide memory of aligned queries (xm_context_set_memo; xm_memo.h, xm_memo_plan.h; allocated only when it is on).  What a stored result depends on
-// besides the query: the index - fixed for the context; the parameters - `filledUnder`, memoMustEmpty; and NOT the hashed length: a read only probes the
+// the run-wide memory of aligned queries (xm_memory_new: one per GPU, shared by the contexts attached to it; xm_context_set_memo: a private one of one
+// generation; xm_memo.h, xm_memo_plan.h).  What a stored result depends on
+// besides the query: the index - a memory belongs to the tables of one index on one GPU; the parameters - `filledUnder`, memoMustEmpty; and NOT the hashed length: a read only probes the
 // tables of gapmer lengths up to its own length, those tables never change once they are hashed (growth adds tables of greater lengths), and a read that
 // needs a table that is not there fails its call (XM_ST_NEED_GROW; ensureTablesFor makes that unreachable through the batch entries) instead of aligning
 // differently.  So the memory survives xm_index_ensure_length and growth by another context.  A call that throws never reaches the insert.
-struct MemoState {
-  MemoPlan plan{0, 0, 0};     // slots == 0: off
+//
+// THE ONE CONCURRENCY RULE: launches of different contexts never touch a memory at the same time.  A call holds `mu` twice: (a) from before its lookup until
+// replay and promotion have completed on its stream (the sizing of the result arenas between lookup and replay is inside), and (b) from before the measure
+// kernel until the insert (and a turn's clears) have completed on its stream.  Between (a) and (b), while the passes run, `mu` is free: the contexts of a
+// GPU keep overlapping their passes.  A call carries nothing across that gap but fp[] and its own results: another context may have inserted the same key
+// meanwhile (the claim drops it), turned the generations, or emptied the memory for other parameters.  Lock order: the context's mu, then the memory's.
+struct Memory {
+  std::mutex mu;
+  int device = 0;
+  std::weak_ptr<DeviceTables> dt;   // the tables its records were aligned against (only their contexts attach)
+  std::weak_ptr<HostShare> hs;
+  bool isPrivate = false;           // xm_context_set_memo's: one context, one generation
+  MemoPlan plan{0, 0, 0};           // of one generation
+  MemoGenerations gens;             // the host's copy of dState after the last launch that changed it, which generation is young, turns, promotions
   int fingerprintBits = 64;
-  DevBuf<unsigned long long> dKeys, dOffs, dState, dTotals, dFp;
-  DevBuf<uint8_t> dArena;
-  DevBuf<int64_t> dHit, dMissList;
-  unsigned long long claimed = 0, cursor = 0, records = 0;  // the host's copy of dState after the last insert
+  DevBuf<unsigned long long> dKeys, dOffs, dState;  // [generations * slots], [generations * slots], [generations * 4]
+  DevBuf<uint8_t> dArena;                           // [generations * arenaBytes]
   int64_t timesEmptied = 0;
-  bool filled = false;        // something was inserted under `filledUnder`
+  bool filled = false;              // something was inserted under `filledUnder`
   xm_params filledUnder;
-  bool on() const { return plan.slots > 0; }
-  MemoView view() const { return MemoView{dKeys.p, dOffs.p, (unsigned long long)plan.slots - 1, dArena.p, (unsigned long long)plan.arenaBytes, dState.p, fingerprintBits}; }
-  void clear(hipStream_t s) {  // every slot empty, nothing in the arena
-    HIP_CHECK(hipMemsetAsync(dKeys.p, 0, sizeof(unsigned long long) * (size_t)plan.slots, s));
-    HIP_CHECK(hipMemsetAsync(dOffs.p, 0xFF, sizeof(unsigned long long) * (size_t)plan.slots, s));
-    HIP_CHECK(hipMemsetAsync(dState.p, 0, sizeof(unsigned long long) * 4, s));
-    claimed = cursor = records = 0;
+  std::atomic<int> attached{0};     // contexts that look their queries up here
+  MemoView view() const {
+    return MemoView{dKeys.p, dOffs.p, (unsigned long long)plan.slots - 1, dArena.p, (unsigned long long)plan.arenaBytes, dState.p, fingerprintBits, gens.generations, gens.young};
+  }
+  void allocate(const MemoPlan& p, int generations) {
+    const size_t g = (size_t)generations;
+    dKeys.ensure(g * (size_t)p.slots); dOffs.ensure(g * (size_t)p.slots); dState.ensure(g * 4); dArena.ensure(g * (size_t)p.arenaBytes);
+    plan = p;
+    gens = MemoGenerations();
+    gens.generations = generations;
+  }
+  void clearGeneration(int g, hipStream_t s) {  // every slot empty, nothing in the arena (enqueued on s: the caller waits for s before it lets go of mu)
+    HIP_CHECK(hipMemsetAsync(dKeys.p + (size_t)g * (size_t)plan.slots, 0, sizeof(unsigned long long) * (size_t)plan.slots, s));
+    HIP_CHECK(hipMemsetAsync(dOffs.p + (size_t)g * (size_t)plan.slots, 0xFF, sizeof(unsigned long long) * (size_t)plan.slots, s));
+    HIP_CHECK(hipMemsetAsync(dState.p + (size_t)g * 4, 0, sizeof(unsigned long long) * 4, s));
+    memoEmptyGeneration(gens, g);
+  }
+  void clear(hipStream_t s) {
+    for (int g = 0; g < gens.generations; g++) clearGeneration(g, s);
     filled = false;
   }
+  ~Memory() {
+    (void)hipSetDevice(device);
+    dKeys.release(); dOffs.release(); dState.release(); dArena.release();
+  }
+};
+// what belongs to a call stays with the context: where each representative's record is, its fingerprint, the ones that missed, the control words
+struct MemoCallBuffers {
+  DevBuf<unsigned long long> dTotals, dFp;  // dTotals: [0..2] hits, their ints, their doubles, [3] replays without room, [4..5] old-generation hits and their bytes (then: what the insert measures), [6] promoted
+  DevBuf<int64_t> dHit, dMissList;
 };
 
 // An xm_index handle is a CONTEXT of an index: what one host thread needs to align batches on one GPU - a stream, batch buffers, scratch and a
@@ -499,7 +531,15 @@ struct xm_index {
   DevBuf<double> dFinalDbls;
   DevBuf<DevCounters> dCounters;
   CollapseBuffers collapseBufs;
-  MemoState memo;
+  std::shared_ptr<Memory> memo;      // xm_context_attach_memory / xm_context_set_memo: where this context looks its queries up and remembers what it aligns (null: nowhere)
+  MemoCallBuffers memoCall;
+  int64_t memoEmptiedBefore = 0;     // xm_context_memo_info's out[3] over the private memories this context has had
+  bool memoOn() const { return (bool)memo; }
+  void dropMemo() {                  // (caller holds mu; the stream is idle)
+    if (memo) { if (memo->isPrivate) memoEmptiedBefore = memo->timesEmptied; memo->attached.fetch_sub(1); }
+    memo.reset();
+    memoCall = MemoCallBuffers();
+  }
   // confidence table (IndexView::conf): the host's table, its copy in HBM, the miss list the kernels write, the reads that wait for a value
   ConfTable conf;
   static constexpr size_t kConfMissCap = 1 << 16;
@@ -535,6 +575,7 @@ struct xm_index {
     if (dt) dt->contexts.fetch_sub(1);
     if (hostOnly) return;
     (void)hipSetDevice(device);
+    if (memo) memo->attached.fetch_sub(1);  // (the memory itself goes with its last holder: the handle or a context)
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
     if (cev0) (void)hipEventDestroy(cev0);
@@ -561,9 +602,11 @@ struct AlignCall {
   double kernelMs = 0;
   int launches = 0;
   int64_t copies = 0, rerun = 0;
-  int64_t remembered = 0;            // representatives served from the run-wide memory (MemoState)
+  int64_t remembered = 0;            // representatives served from the run-wide memory (Memory)
   unsigned long long hitInts = 0, hitDbls = 0;  // what their slices need in the result arenas
-  long long nMisses = 0;             // idx->memo.dMissList: the representatives this call aligns
+  unsigned long long oldHits = 0, oldHitBytes = 0;  // the ones served from the old generation only, the bytes of their records (memoPromotes)
+  long long nMisses = 0;             // idx->memoCall.dMissList: the representatives this call aligns
+  double memoWaitUs = 0;             // host time this call waited for the memory's mutex (both critical sections)
   unsigned long long intCap = 0, dblCap = 0;
   unsigned long long cursors[4] = {0, 0, 0, 0};
   bool boundFilterUsed = false;
@@ -691,65 +734,117 @@ static void collapseFanOut(AlignCall& c) {
   }, [] {});
 }
 
-// ---- the run-wide memory (xm_context_set_memo; MemoState, xm_memo.h), in the order of a call: lookup, replay, (the passes,) insert
-// after collapseBuildList: the representatives are looked up, and the first pass's list becomes the ones the memory did not hold
+// ---- the run-wide memory (xm_memory_new, xm_context_set_memo; Memory, xm_memo.h), in the order of a call: lookup, replay, promotion, (the passes,) measure, insert
+// the memory's mutex, taken with the wait on the host's clock
+static std::unique_lock<std::mutex> memoLock(AlignCall& c) {
+  const auto t0 = std::chrono::steady_clock::now();
+  std::unique_lock<std::mutex> lock(c.idx->memo->mu);
+  c.memoWaitUs += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+  return lock;
+}
+// after collapseBuildList: the representatives are looked up, and the first pass's list becomes the ones the memory did not hold (caller holds the memory's mu)
 static void memoLookup(AlignCall& c) {
   xm_index* idx = c.idx;
-  MemoState& m = idx->memo;
+  Memory& m = *idx->memo;
+  MemoCallBuffers& mc = idx->memoCall;
   const int64_t nq = c.nq;
   hipStream_t s = c.s;
   if (memoMustEmpty(m.filled, &m.filledUnder, &c.cParams, sizeof(xm_params))) { m.clear(s); m.timesEmptied++; }
   const long long nReps = c.nTodo;
   const long long nBlocks = (nq + XM_COLLAPSE_PER_BLOCK - 1) / XM_COLLAPSE_PER_BLOCK;
-  m.dHit.ensure((size_t)nq); m.dFp.ensure((size_t)nq); m.dMissList.ensure((size_t)nq); m.dTotals.ensure(4);
-  HIP_CHECK(hipMemsetAsync(m.dTotals.p, 0, sizeof(unsigned long long) * 4, s));
-  unsigned long long totals[4] = {0, 0, 0, 0}, nMisses = 0;
+  mc.dHit.ensure((size_t)nq); mc.dFp.ensure((size_t)nq); mc.dMissList.ensure((size_t)nq); mc.dTotals.ensure(8);
+  HIP_CHECK(hipMemsetAsync(mc.dTotals.p, 0, sizeof(unsigned long long) * 8, s));
+  unsigned long long totals[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nMisses = 0;
   timedLaunch(c, 4, -1, [&] {
-    hipLaunchKernelGGL(xm_memo_lookup_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, s, c.bv, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), m.dHit.p, m.dFp.p, m.dTotals.p);
-    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)m.dHit.p, idx->collapseBufs.dCollapseBlocks.p);
+    hipLaunchKernelGGL(xm_memo_lookup_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, s, c.bv, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), mc.dHit.p, mc.dFp.p, mc.dTotals.p);
+    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)mc.dHit.p, idx->collapseBufs.dCollapseBlocks.p);
     hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dCollapseTotal.p);
-    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)m.dHit.p,
-                       (const long long*)idx->collapseBufs.dCollapseBlocks.p, m.dMissList.p);
+    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)mc.dHit.p,
+                       (const long long*)idx->collapseBufs.dCollapseBlocks.p, mc.dMissList.p);
   }, [&] {
-    HIP_CHECK(hipMemcpyAsync(totals, m.dTotals.p, sizeof(totals), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(totals, mc.dTotals.p, sizeof(totals), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&nMisses, idx->collapseBufs.dCollapseTotal.p, sizeof(nMisses), hipMemcpyDeviceToHost, s));
   });
   if ((long long)totals[0] + (long long)nMisses != nReps)
     throw std::runtime_error("internal error: of " + std::to_string(nReps) + " distinct queries the memory held " + std::to_string(totals[0]) + " and " + std::to_string(nMisses) + " are left");
   c.remembered = (int64_t)totals[0]; c.hitInts = totals[1]; c.hitDbls = totals[2];
+  c.oldHits = totals[4]; c.oldHitBytes = totals[5];
   c.nMisses = (long long)nMisses;
-  c.todo = m.dMissList.p;
+  c.todo = mc.dMissList.p;
   c.nTodo = c.nMisses;
 }
 
 // before the passes: the hits' slices into the result arenas, through the call's cursors (a hit is then what a read a pass finished is)
 static void memoReplay(AlignCall& c) {
   xm_index* idx = c.idx;
-  MemoState& m = idx->memo;
+  Memory& m = *idx->memo;
+  MemoCallBuffers& mc = idx->memoCall;
   const long long nReps = c.remembered + c.nMisses;
   unsigned long long totals[4] = {0, 0, 0, 0};
   timedLaunch(c, 1, -1, [&] {
-    hipLaunchKernelGGL(xm_memo_replay_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, c.s, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), (const int64_t*)m.dHit.p, c.outView(), m.dTotals.p);
+    hipLaunchKernelGGL(xm_memo_replay_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, c.s, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), (const int64_t*)mc.dHit.p, c.outView(), mc.dTotals.p);
   }, [&] {
-    HIP_CHECK(hipMemcpyAsync(totals, m.dTotals.p, sizeof(totals), hipMemcpyDeviceToHost, c.s));
+    HIP_CHECK(hipMemcpyAsync(totals, mc.dTotals.p, sizeof(totals), hipMemcpyDeviceToHost, c.s));
     HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, c.s));
   });
   if (totals[3] != 0) throw std::runtime_error("internal error: " + std::to_string(totals[3]) + " remembered results found no room in the result arenas");
 }
 
-// after the last pass has succeeded: the representatives this call aligned are remembered, as far as the table and the arena have room (memoRoom, memoFull)
+// second chance: the records this call was served from the old generation are copied into the young one, all of them or none (memoPromotes); never a turn
+static void memoPromote(AlignCall& c) {
+  xm_index* idx = c.idx;
+  Memory& m = *idx->memo;
+  MemoCallBuffers& mc = idx->memoCall;
+  if (!memoPromotes(m.plan, m.gens, c.oldHits, c.oldHitBytes)) return;
+  const long long nReps = c.remembered + c.nMisses;
+  const int young = m.gens.young;
+  unsigned long long state[4] = {0, 0, 0, 0}, promoted = 0;
+  timedLaunch(c, 1, -1, [&] {
+    hipLaunchKernelGGL(xm_memo_promote_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, c.s, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), (const int64_t*)mc.dHit.p,
+                       (const unsigned long long*)mc.dFp.p, mc.dTotals.p);
+  }, [&] {
+    HIP_CHECK(hipMemcpyAsync(state, m.dState.p + (size_t)young * 4, sizeof(state), hipMemcpyDeviceToHost, c.s));
+    HIP_CHECK(hipMemcpyAsync(&promoted, mc.dTotals.p + 6, sizeof(promoted), hipMemcpyDeviceToHost, c.s));
+  });
+  m.gens.claimed[young] = state[0]; m.gens.cursor[young] = state[1]; m.gens.records[young] = state[2];
+  m.gens.promoted += (long long)promoted;
+}
+
+// after the last pass has succeeded: the representatives this call aligned are remembered in the young generation.  With two generations the call first
+// measures what it brings (xm_memo_measure_kernel: their number and the bytes of their records) and turns the generations when the young one does not take
+// all of it (memoMustTurn); with one generation nothing turns and nothing needs measuring.  Then as far as the table and the arena have room (memoInsertCount).
+// Takes the memory's mu for all of it, and lets go once everything has completed on the stream.
 static void memoInsert(AlignCall& c) {
   xm_index* idx = c.idx;
-  MemoState& m = idx->memo;
-  const long long n = std::min<long long>(c.nMisses, memoRoom(m.plan, m.claimed));
-  if (n < 1 || memoFull(m.plan, m.claimed, m.cursor)) return;
+  Memory& m = *idx->memo;
+  MemoCallBuffers& mc = idx->memoCall;
+  if (c.nMisses < 1) return;
+  std::unique_lock<std::mutex> lock = memoLock(c);
+  bool queued = false;  // clears on the stream that no timedLaunch has waited for yet
+  // (another context may have filled the memory under other parameters since this call's lookup: what this call aligned is not of them)
+  if (memoMustEmpty(m.filled, &m.filledUnder, &c.cParams, sizeof(xm_params))) { m.clear(c.s); m.timesEmptied++; queued = true; }
+  if (m.gens.generations > 1) {
+    unsigned long long measured[2] = {0, 0};
+    HIP_CHECK(hipMemsetAsync(mc.dTotals.p + 4, 0, sizeof(unsigned long long) * 2, c.s));
+    timedLaunch(c, 1, -1, [&] {
+      hipLaunchKernelGGL(xm_memo_measure_kernel, dim3((unsigned)((c.nMisses + 255) / 256)), dim3(256), 0, c.s, c.bv, (const int64_t*)mc.dMissList.p, c.nMisses, c.outView(), mc.dTotals.p);
+    }, [&] { HIP_CHECK(hipMemcpyAsync(measured, mc.dTotals.p + 4, sizeof(measured), hipMemcpyDeviceToHost, c.s)); });
+    queued = false;
+    if (memoMustTurn(m.plan, m.gens, measured[0], measured[1])) { m.clearGeneration(memoTurn(m.gens), c.s); queued = true; }
+  }
+  const long long n = memoInsertCount(m.plan, m.gens, c.nMisses);
+  if (n < 1) {
+    if (queued) HIP_CHECK(hipStreamSynchronize(c.s));
+    return;
+  }
+  const int young = m.gens.young;
   unsigned long long state[4] = {0, 0, 0, 0};
   m.filledUnder = c.cParams;
   m.filled = true;
   timedLaunch(c, 1, -1, [&] {
-    hipLaunchKernelGGL(xm_memo_insert_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c.s, c.bv, (const int64_t*)m.dMissList.p, n, m.view(), (const unsigned long long*)m.dFp.p, c.outView());
-  }, [&] { HIP_CHECK(hipMemcpyAsync(state, m.dState.p, sizeof(state), hipMemcpyDeviceToHost, c.s)); });
-  m.claimed = state[0]; m.cursor = state[1]; m.records = state[2];
+    hipLaunchKernelGGL(xm_memo_insert_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c.s, c.bv, (const int64_t*)mc.dMissList.p, n, m.view().generation(young), (const unsigned long long*)mc.dFp.p, c.outView());
+  }, [&] { HIP_CHECK(hipMemcpyAsync(state, m.dState.p + (size_t)young * 4, sizeof(state), hipMemcpyDeviceToHost, c.s)); });
+  m.gens.claimed[young] = state[0]; m.gens.cursor[young] = state[1]; m.gens.records[young] = state[2];
 }
 
 // ---- passes 0 (XM_WAVE=1; off by default: measured slower than the lane-per-read passes on MI355X this round, profiles/r02/NOTES.md):
@@ -1052,7 +1147,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 4; }
+int32_t xm_abi_version(void) { return 5; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();
@@ -1160,8 +1255,22 @@ int xm_context_set_collapse(xm_index* idx, int32_t enable) {
   if (!idx) return fail("xm_context_set_collapse: null argument");
   std::lock_guard<std::mutex> lock(idx->mu);
   idx->collapse = enable != 0;
-  if (!idx->collapse && !idx->memo.on()) idx->collapseBufs = CollapseBuffers();
+  if (!idx->collapse && !idx->memoOn()) idx->collapseBufs = CollapseBuffers();
   return 0;
+}
+
+// a memory of `generations` generations within max_bytes for the tables of `idx` on its GPU, emptied (the caller has set the device); -> null and *why
+static std::shared_ptr<Memory> newMemory(xm_index* idx, int64_t max_bytes, int generations, bool isPrivate, std::string* why) {
+  const MemoPlan plan = memoGenerationPlan(max_bytes, generations);
+  if (generations < 1 || generations > XM_MEMO_MAX_GENERATIONS) { *why = "generations must be 1 or 2"; return nullptr; }
+  if (plan.slots == 0) { *why = "the smallest memory is " + std::to_string(memoMinBytes(generations)) + " bytes" + (generations > 1 ? " (" + std::to_string(XM_MEMO_MIN_BYTES) + " per generation)" : ""); return nullptr; }
+  auto m = std::make_shared<Memory>();
+  m->device = idx->device; m->dt = idx->dt; m->hs = idx->hs; m->isPrivate = isPrivate;
+  m->allocate(plan, generations);
+  m->fingerprintBits = (int)envKnob("XM_MEMO_FINGERPRINT_BITS", 64, 1, 64);  // (test knob: fewer bits make different queries share a fingerprint)
+  m->clear(idx->stream);
+  HIP_CHECK(hipStreamSynchronize(idx->stream));
+  return m;
 }
 
 int xm_context_set_memo(xm_index* idx, int64_t max_bytes) {
@@ -1172,24 +1281,25 @@ int xm_context_set_memo(xm_index* idx, int64_t max_bytes) {
   if (max_bytes > 0 && plan.slots == 0) return fail("xm_context_set_memo: the smallest memory is " + std::to_string(XM_MEMO_MIN_BYTES) + " bytes");
   try {
     std::lock_guard<std::mutex> lock(idx->mu);
+    if (idx->memo && !idx->memo->isPrivate) {
+      if (max_bytes > 0) return fail("xm_context_set_memo: the context is attached to a shared memory (xm_context_attach_memory); detach it first");
+      return 0;  // (no memory of its own to switch off)
+    }
     HIP_CHECK(hipSetDevice(idx->device));
     HIP_CHECK(hipStreamSynchronize(idx->stream));
-    const int64_t emptied = idx->memo.timesEmptied;
-    idx->memo = MemoState();  // (what was remembered goes with the old budget)
-    idx->memo.timesEmptied = emptied;
+    idx->dropMemo();  // (what was remembered goes with the old budget)
     if (max_bytes == 0) {
       if (!idx->collapse) idx->collapseBufs = CollapseBuffers();
       return 0;
     }
-    MemoState& m = idx->memo;
-    m.dKeys.ensure((size_t)plan.slots); m.dOffs.ensure((size_t)plan.slots); m.dState.ensure(4); m.dArena.ensure((size_t)plan.arenaBytes);
-    m.plan = plan;
-    m.fingerprintBits = (int)envKnob("XM_MEMO_FINGERPRINT_BITS", 64, 1, 64);  // (test knob: fewer bits make different queries share a fingerprint)
-    m.clear(idx->stream);
-    HIP_CHECK(hipStreamSynchronize(idx->stream));
+    std::string why;
+    std::shared_ptr<Memory> m = newMemory(idx, max_bytes, 1, true, &why);
+    if (!m) return fail("xm_context_set_memo: " + why);
+    m->timesEmptied = idx->memoEmptiedBefore;
+    m->attached.fetch_add(1);
+    idx->memo = m;
     return 0;
   } catch (std::exception& e) {
-    idx->memo = MemoState();
     return fail(std::string("xm_context_set_memo: ") + e.what());
   }
 }
@@ -1197,13 +1307,75 @@ int xm_context_set_memo(xm_index* idx, int64_t max_bytes) {
 int xm_context_memo_info(xm_index* idx, int64_t out[4]) {
   if (!idx || !out) return fail("xm_context_memo_info: null argument");
   std::lock_guard<std::mutex> lock(idx->mu);
-  const MemoState& m = idx->memo;
-  out[0] = (int64_t)m.records;
-  out[1] = m.on() ? (int64_t)(memoTableBytes(m.plan) + (long long)memoArenaUsed(m.plan, m.cursor)) : 0;
-  out[2] = m.on() ? (int64_t)m.plan.capacity : 0;
-  out[3] = m.timesEmptied;
+  const Memory* m = idx->memo && idx->memo->isPrivate ? idx->memo.get() : nullptr;
+  out[0] = m ? (int64_t)memoRecordsHeld(m->gens) : 0;
+  out[1] = m ? (int64_t)memoBytesInUse(m->plan, m->gens) : 0;
+  out[2] = m ? (int64_t)m->plan.capacity : 0;
+  out[3] = m ? m->timesEmptied : idx->memoEmptiedBefore;
   return 0;
 }
+
+// ---- the memory of a GPU: an object of its own that any number of the GPU's contexts of one index attach to
+struct xm_memory {
+  std::shared_ptr<Memory> m;
+};
+
+int xm_memory_new(xm_index* idx, int64_t max_bytes, int32_t generations, xm_memory** out) {
+  if (!idx || !out) return fail("xm_memory_new: null argument");
+  if (max_bytes < 0) return fail("xm_memory_new: negative size");
+  if (idx->hostOnly) return fail("xm_memory_new: index was built with host_only=1");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    HIP_CHECK(hipSetDevice(idx->device));
+    std::string why;
+    std::shared_ptr<Memory> m = newMemory(idx, max_bytes, (int)generations, false, &why);
+    if (!m) return fail("xm_memory_new: " + why);
+    *out = new xm_memory{m};
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_memory_new: ") + e.what()); }
+}
+
+int xm_context_attach_memory(xm_index* idx, xm_memory* memory) {
+  if (!idx) return fail("xm_context_attach_memory: null argument");
+  if (idx->hostOnly) return fail("xm_context_attach_memory: index was built with host_only=1");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (idx->memo && idx->memo->isPrivate) return fail("xm_context_attach_memory: the context has a memory of its own (xm_context_set_memo); switch it off first");
+    if (memory) {
+      if (memory->m->hs.lock() != idx->hs) return fail("xm_context_attach_memory: the memory belongs to another index (its records depend on the tables)");
+      if (memory->m->device != idx->device || memory->m->dt.lock() != idx->dt)
+        return fail("xm_context_attach_memory: the memory is on GPU " + std::to_string(memory->m->device) + ", the context on GPU " + std::to_string(idx->device));
+      if (idx->memo == memory->m) return 0;
+    }
+    HIP_CHECK(hipSetDevice(idx->device));
+    HIP_CHECK(hipStreamSynchronize(idx->stream));
+    idx->dropMemo();
+    if (memory) {
+      memory->m->attached.fetch_add(1);
+      idx->memo = memory->m;
+    } else if (!idx->collapse) {
+      idx->collapseBufs = CollapseBuffers();
+    }
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_context_attach_memory: ") + e.what()); }
+}
+
+int xm_memory_info(xm_memory* memory, int64_t out[8]) {
+  if (!memory || !out) return fail("xm_memory_info: null argument");
+  Memory& m = *memory->m;
+  std::lock_guard<std::mutex> lock(m.mu);
+  out[0] = (int64_t)memoRecordsHeld(m.gens);
+  out[1] = (int64_t)memoBytesInUse(m.plan, m.gens);
+  out[2] = (int64_t)m.plan.capacity * m.gens.generations;
+  out[3] = m.timesEmptied;
+  out[4] = m.gens.turns;
+  out[5] = m.gens.promoted;
+  out[6] = m.attached.load();
+  out[7] = m.gens.generations;
+  return 0;
+}
+
+void xm_memory_free(xm_memory* memory) { delete memory; }  // (the HBM goes with the last context that is attached, or now)
 
 int xm_device_memory(int32_t device, int64_t* free_bytes, int64_t* total_bytes) {
   try {
@@ -1501,20 +1673,36 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
     c.cParams = *p;
     c.bv = idx->resident.view();
     prepareCall(c);
-    if (idx->collapse || idx->memo.on()) collapseBuildList(c);  // (a run-wide memory includes the batch)
-    if (idx->memo.on()) memoLookup(c);
+    if (idx->collapse || idx->memoOn()) collapseBuildList(c);  // (a run-wide memory includes the batch)
+    std::unique_lock<std::mutex> memoInUse;  // (a): from before the lookup until replay and promotion have completed on the stream
+    if (idx->memoOn()) {
+      // The result arenas are sized between lookup and replay, inside (a) - but they never GROW there: a buffer that grows is freed first, and that waits for
+      // the whole device, the other contexts' running passes included, while their lookups and inserts would be locked out.  A call whose hits need more room
+      // than the arenas have lets go of the memory, grows them (with an eighth to spare) and looks everything up again: the memory may have changed meanwhile.
+      const long long nReps = c.nTodo;
+      for (;;) {
+        memoInUse = memoLock(c);
+        c.nTodo = nReps;
+        memoLookup(c);
+        const size_t needInts = (size_t)nq * 40 + 4096 + (size_t)c.hitInts, needDbls = (size_t)nq * 12 + 4096 + (size_t)c.hitDbls;
+        if (idx->dOutInts.p && idx->dOutInts.n >= needInts && idx->dOutDbls.p && idx->dOutDbls.n >= needDbls) break;
+        memoInUse.unlock();
+        idx->dOutInts.ensure(needInts + (size_t)c.hitInts / 8); idx->dOutDbls.ensure(needDbls + (size_t)c.hitDbls / 8);
+      }
+    }
     const BatchFacts facts{idx->resident.maxLen, idx->resident.anyPaired, idx->dt->contexts.load(), idx->scratchBytes};
     const BatchPolicy pol = makePolicy(facts, readPassKnobs(facts));
-    idx->dOutInts.ensure((size_t)nq * 40 + 4096 + (size_t)c.hitInts); idx->dOutDbls.ensure((size_t)nq * 12 + 4096 + (size_t)c.hitDbls);  // (the remembered results on top)
+    idx->dOutInts.ensure((size_t)nq * 40 + 4096 + (size_t)c.hitInts); idx->dOutDbls.ensure((size_t)nq * 12 + 4096 + (size_t)c.hitDbls);  // (the remembered results on top; with a memory: there already)
     c.intCap = idx->dOutInts.n; c.dblCap = idx->dOutDbls.n;
     if (c.remembered > 0) memoReplay(c);
+    if (idx->memoOn()) { memoPromote(c); memoInUse.unlock(); }
     if (pol.k.handOver) {
       idx->dRegionOf.ensure((size_t)nq);
       HIP_CHECK(hipMemsetAsync(idx->dRegionOf.p, 0xFF, sizeof(int32_t) * (size_t)nq, c.s));
     }
     if (pol.k.waveForm && idx->resident.maxLen <= 256 && c.nTodo > 0) runWaveForm(c, pol.k.tracePasses);
     runLanePasses(c, pol);  // (nothing left to align: no pass runs)
-    if (idx->memo.on()) memoInsert(c);
+    if (idx->memoOn()) { memoInsert(c); res->reserved = (int32_t)std::min<double>(c.memoWaitUs, 2147483647.0); }  // (b), under the memory's mu
     if (c.copies > 0) collapseFanOut(c);
     finishStreams(c);
     *out = res;

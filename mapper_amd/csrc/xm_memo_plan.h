@@ -1,7 +1,7 @@
-// The plan and the table logic of the run-wide memory of aligned queries (xm_context_set_memo; DESIGN.md "Identical queries"), as plain C++: what a
-// byte budget buys, the size of a record, when insertion stops, when the memory is emptied, and the probe / claim / dead-slot rules of the
-// open-addressing table.  The kernels of xm_memo.h call the same functions on the device (they are host+device there, and plain inline functions
-// everywhere else), so tests/test_memo_plan.py checks without a GPU the very code the GPU runs.  No HIP, no threads.
+// The plan and the table logic of the run-wide memory of aligned queries (xm_context_set_memo, xm_memory_new; DESIGN.md "Identical queries"), as plain C++: what a
+// byte budget buys, the size of a record, when insertion stops, when the memory is emptied, the probe / claim / dead-slot rules of the
+// open-addressing table, and - at the end of the file - the generations of a shared memory: lookup order, turn, promotion.  The kernels of xm_memo.h call the same functions on the device (they are host+device there, and plain inline functions
+// everywhere else), so tests/test_memo_plan.py and tests/test_memo_generations.py check without a GPU the very code the GPU runs.  No HIP, no threads.
 //
 // The table: keys[slots] (0 = empty) and offs[slots], slots a power of two.  A slot's key is written once, by a compare-and-swap that claims it, and
 // never changes until the whole memory is emptied.  offs[slot] is the record's offset in the byte arena, or XM_MEMO_DEAD: the slot is taken and
@@ -114,6 +114,99 @@ template <class Add>
 XM_MEMO_FN unsigned long long memoReserve(unsigned long long* cursor, unsigned long long arenaBytes, unsigned long long bytes, Add add) {
   const unsigned long long at = add(cursor, bytes);
   return (at + bytes <= arenaBytes && at + bytes >= at) ? at : XM_MEMO_DEAD;
+}
+
+// ================================================================ the memory of a GPU (xm_memory_new): one or two generations
+// A memory that several contexts share, and that keeps remembering however long the run is, is one or two tables as above - GENERATIONS - in one
+// allocation each of keys, offsets, records and state words: generation g has keys[g * slots ..), offs[g * slots ..), the arena's bytes
+// [g * arenaBytes ..) and state[g * 4 ..), so a record's offset in the whole arena (what hit[q] holds) says which generation it is in.  One generation
+// is the YOUNG one: inserts go there.  The other, if there is one, is the OLD one: it is only read.  A TURN drops the old generation, makes the
+// young one the old one, and the dropped one, emptied, the young one.  With one generation nothing ever turns: full means nothing more is remembered.
+constexpr int XM_MEMO_MAX_GENERATIONS = 2;
+
+// ---- the plan: every generation is memoPlan(budget / generations); slots == 0: refused (generations other than 1 or 2, or less than generations * XM_MEMO_MIN_BYTES)
+inline long long memoMinBytes(int generations) { return (long long)generations * XM_MEMO_MIN_BYTES; }
+inline MemoPlan memoGenerationPlan(long long budgetBytes, int generations) {
+  if (generations < 1 || generations > XM_MEMO_MAX_GENERATIONS || budgetBytes < 0) return MemoPlan{0, 0, 0};
+  return memoPlan(budgetBytes / generations);
+}
+
+// ---- what the host knows of the generations: its copy of each one's state words after the last launch that changed them, which one is young, the counts
+struct MemoGenerations {
+  int generations = 1;
+  int young = 0;
+  unsigned long long claimed[XM_MEMO_MAX_GENERATIONS] = {0, 0}, cursor[XM_MEMO_MAX_GENERATIONS] = {0, 0}, records[XM_MEMO_MAX_GENERATIONS] = {0, 0};
+  long long turns = 0, promoted = 0;
+};
+XM_MEMO_FN int memoOldOf(int generations, int young) { return generations > 1 ? 1 - young : -1; }  // (-1: there is none)
+XM_MEMO_FN int memoGenerationOf(unsigned long long at, unsigned long long arenaBytes) { return (int)(at / arenaBytes); }  // of a record's offset in the whole arena
+inline unsigned long long memoRecordsHeld(const MemoGenerations& g) { return g.records[0] + (g.generations > 1 ? g.records[1] : 0ull); }
+inline unsigned long long memoBytesInUse(const MemoPlan& p, const MemoGenerations& g) {
+  unsigned long long b = 0;
+  for (int k = 0; k < g.generations; k++) b += (unsigned long long)memoTableBytes(p) + memoArenaUsed(p, g.cursor[k]);
+  return b;
+}
+inline void memoEmptyGeneration(MemoGenerations& g, int k) { g.claimed[k] = g.cursor[k] = g.records[k] = 0; }
+
+// ---- lookup order: the young generation first, then the old one.  same(at) says whether the record at offset `at` of the whole arena is this query,
+// byte for byte.  A key match whose record is another query (two queries, one fingerprint) does not end the lookup: the other generation is still
+// probed.  A query held in both generations is served from the young one.  -> the record's offset in the whole arena (*generation: where), or -1
+template <class Same>
+XM_MEMO_FN long long memoLookupGenerations(const unsigned long long* keys, const unsigned long long* offs, unsigned long long mask, unsigned long long arenaBytes, int generations, int young,
+                                           unsigned long long h, Same same, int* generation) {
+  for (int k = 0; k < generations && k < XM_MEMO_MAX_GENERATIONS; k++) {
+    const int g = k == 0 ? young : 1 - young;
+    const unsigned long long* gk = keys + (unsigned long long)g * (mask + 1);
+    const unsigned long long* go = offs + (unsigned long long)g * (mask + 1);
+    const long long rec = memoSlotRecord(go, memoProbe(gk, mask, h));
+    if (rec < 0) continue;
+    const long long at = (long long)((unsigned long long)g * arenaBytes) + rec;
+    if (same(at)) { *generation = g; return at; }
+  }
+  return -1;
+}
+
+// ---- insert.  Before the insert of a call the exact number n of representatives it aligned and the exact sum B of their memoRecordBytes are known
+// (xm_memo_measure_kernel).  The young generation takes all of them, or - with two generations and a young one that holds something - the generations
+// turn first and the insert goes to the fresh young one.  A batch larger than a whole generation is inserted as far as room goes (memoRoom, memoFull,
+// memoReserve: which of its queries fit is then not determined).
+inline bool memoTakesAll(const MemoPlan& p, unsigned long long claimed, unsigned long long cursor, unsigned long long n, unsigned long long bytes) {
+  return claimed + n <= (unsigned long long)p.capacity && cursor + bytes <= (unsigned long long)p.arenaBytes && cursor + bytes >= cursor;
+}
+inline bool memoMustTurn(const MemoPlan& p, const MemoGenerations& g, unsigned long long n, unsigned long long bytes) {
+  return g.generations > 1 && g.claimed[g.young] > 0 && !memoTakesAll(p, g.claimed[g.young], g.cursor[g.young], n, bytes);
+}
+// the turn, on the host's copy: -> the generation the caller has to empty in HBM (it is the young one now)
+inline int memoTurn(MemoGenerations& g) {
+  g.young = 1 - g.young;
+  memoEmptyGeneration(g, g.young);
+  g.turns++;
+  return g.young;
+}
+// how many of a call's k aligned representatives the insert launch is given (the first ones of its list)
+inline long long memoInsertCount(const MemoPlan& p, const MemoGenerations& g, long long k) {
+  if (memoFull(p, g.claimed[g.young], g.cursor[g.young])) return 0;
+  const long long room = memoRoom(p, g.claimed[g.young]);
+  return k < room ? k : room;
+}
+
+// ---- promotion (second chance).  The lookup counts the hits it found in the old generation only, and the exact bytes of their records.  If the young
+// generation takes all of them, xm_memo_promote_kernel copies those records into it (claim the key, reserve room, copy the record verbatim; a promotion
+// that meets its own key in the young table is dropped); otherwise none is promoted in this call.  Promotion never turns the generations.
+inline bool memoPromotes(const MemoPlan& p, const MemoGenerations& g, unsigned long long oldHits, unsigned long long oldHitBytes) {
+  return g.generations > 1 && oldHits > 0 && memoTakesAll(p, g.claimed[g.young], g.cursor[g.young], oldHits, oldHitBytes);
+}
+// one record's promotion: -> its offset in the young generation's arena, or XM_MEMO_DEAD (dropped).  *slot: the claimed slot of the young table; the
+// caller copies memoRecordBytes from the old record and then sets offs[*slot].
+template <class Cas, class Add>
+XM_MEMO_FN unsigned long long memoPromoteClaim(unsigned long long* youngKeys, unsigned long long mask, unsigned long long* youngState, unsigned long long arenaBytes, unsigned long long h,
+                                               unsigned long long bytes, Cas cas, Add add, long long* slot) {
+  *slot = memoClaim(youngKeys, mask, h, cas);
+  if (*slot < 0) return XM_MEMO_DEAD;
+  add(&youngState[0], 1ull);
+  const unsigned long long at = memoReserve(&youngState[1], arenaBytes, bytes, add);
+  if (at != XM_MEMO_DEAD) add(&youngState[2], 1ull);
+  return at;
 }
 
 }  // namespace xm

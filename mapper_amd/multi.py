@@ -18,15 +18,21 @@ import numpy as np
 
 
 class MultiGpuDatabase:
-    def __init__(self, contigs, devices, collapse=False, memo_bytes=0, **kw):
+    def __init__(self, contigs, devices, collapse=False, memo_bytes=0, shared_memo_bytes=0, **kw):
         """devices: GPU ordinals, e.g. [0, 1, 2, 3]; a repeated ordinal gives that GPU two independent contexts (tests on one-GPU machines).
         collapse: every context aligns identical queries of a batch once (ReferenceDatabase.set_collapse).
         memo_bytes: every context remembers the queries it aligns in that many bytes of HBM and serves repeats in its later batches from there
         (ReferenceDatabase.set_memo; 0: off).  Per context: a query seen k times over N contexts is aligned at most min(k, N) times.
+        shared_memo_bytes: one two-generation memory of that many bytes per distinct GPU of `devices` (api.QueryMemory), which every context of that GPU
+        is attached to: a query aligned by any of them is served to all, and the memory keeps remembering when it is full.  `.memories` holds them, in the
+        order the GPUs first appear in `devices`; they are closed with the database.  An error together with memo_bytes.
         kw: ReferenceDatabase's build options (mode, enable_gapmers, max_query_length, cache_dir)."""
         from . import api
         if not devices:
             raise ValueError("at least one device")
+        if memo_bytes and shared_memo_bytes:
+            raise ValueError("memo_bytes (a memory per context) and shared_memo_bytes (one per GPU) exclude each other")
+        self.memories = []
         kw.pop("device", None)
         # what every context will allocate beside its scratch (the command line's --out-mutations: one pile-up per context, 40-48 bytes per reference base)
         per_context_extra = kw.pop("per_context_extra", 0)
@@ -47,7 +53,7 @@ class MultiGpuDatabase:
         keep = []
         for d in by_device:
             mine = [r for r, dd in zip(self.replicas, self.devices) if dd == d]
-            n = api.divide_scratch(mine, d, per_context_extra=int(per_context_extra))[0] if len(mine) > 1 else 1
+            n = api.divide_scratch(mine, d, per_context_extra=int(per_context_extra), shared_extra=int(shared_memo_bytes))[0] if len(mine) > 1 else 1
             keep += mine[:n]
             for r in mine[n:]:
                 r.close()
@@ -60,6 +66,16 @@ class MultiGpuDatabase:
             r.set_collapse(collapse)
             if memo_bytes:
                 r.set_memo(memo_bytes)
+        if shared_memo_bytes:
+            try:
+                for d in dict.fromkeys(self.devices):
+                    mine = [r for r, dd in zip(self.replicas, self.devices) if dd == d]
+                    self.memories.append(api.QueryMemory(mine[0], shared_memo_bytes))
+                    for r in mine:
+                        r.attach_memory(self.memories[-1])
+            except BaseException:
+                self.close()
+                raise
 
     def info(self):
         return self.replicas[0].info()
@@ -68,6 +84,9 @@ class MultiGpuDatabase:
         for r in self.replicas:
             r.close()
         self.replicas = []
+        for m in self.memories:
+            m.close()
+        self.memories = []
 
     def align_stream(self, batches, parameters, depth=2, on_aligned=None):
         """batches: iterable of upload_arrays' six-array tuples; yields their BatchResults in order.  Batch k is aligned by replica k mod N.

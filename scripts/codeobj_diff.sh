@@ -1,8 +1,12 @@
 #!/bin/bash
 # Device code of two builds of an object (xm_capi.o, xm_index_device.o, ...), symbol by symbol: the gfx950 code object of each is unbundled and disassembled (llvm-objdump -d), addresses and
 # encodings dropped, and the instruction text of every kernel and out-of-line device function compared.  Runs on the CPU.  Exit status 0: equal for every symbol.
+# A displacement from the program counter to another symbol (s_getpc_b64, s_add_u32 with a literal) is compared as the symbol and offset it points at
+# (scripts/codeobj_resolve.py): adding or resizing a kernel moves everything behind it, and with that every such literal, without changing an instruction.
+# The s_nop 0 padding behind a symbol's last instruction is not compared either: it follows the address the function happens to start at.  Every other s_nop is.
 # usage: scripts/codeobj_diff.sh BEFORE/xm_capi.o AFTER/xm_capi.o   (any two objects with a gfx950 bundle)
 set -e
+HERE=$(cd "$(dirname "$0")" && pwd)
 LL=/opt/rocm/lib/llvm/bin
 T=$(mktemp -d)
 for v in a b; do
@@ -10,7 +14,8 @@ for v in a b; do
   $LL/llvm-objcopy --dump-section .hip_fatbin=$T/$v.fatbin $o /dev/null
   $LL/clang-offload-bundler --unbundle --type=o --input=$T/$v.fatbin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$T/$v.co
   # "0000000000001000 <symbol>:" opens a symbol; an instruction line is "\tmnemonic operands // address: encoding"
-  $LL/llvm-objdump -d $T/$v.co | awk -v dir=$T/$v 'BEGIN { system("mkdir -p " dir) }
+  $LL/llvm-objdump -t $T/$v.co > $T/$v.symtab
+  $LL/llvm-objdump -d $T/$v.co | python3 $HERE/codeobj_resolve.py $T/$v.symtab | awk -v dir=$T/$v 'BEGIN { system("mkdir -p " dir) }
   # (the instructions of a symbol go to a numbered file: the mangled names of library kernels are longer than a file name may be)
     /^[0-9a-f]+ <.*>:$/ { name = $2; gsub(/[<>:]/, "", name); n++; if (file != "") close(file); file = dir "/" n; order[n] = name; next }
     file != "" && /^\t/ { sub(/[ \t]*\/\/.*$/, ""); print > file; count[n]++ }
