@@ -1,14 +1,17 @@
-// libxmapper_hip.so: the align call and the C ABI of include/xmapper_hip.h, one translation unit.
+// libxmapper_hip.so: the host side of the align call and the C ABI of include/xmapper_hip.h, one translation unit.
 //
-// In this file, in this order: the lane-per-read align kernel (one read per lane, persistent lanes that draw reads from a counter; the per-read
-// state machine is xm_worker.h) and the small kernels of the pass bookkeeping (work lists, prefix sums, the gather of the result streams into
-// query order on the device); the tables of a reference on the host and in HBM (HostShare, DeviceTables); a context (xm_index): its stream, its
+// In this file, in this order: the small kernels of the pass bookkeeping (work lists, prefix sums, the gather of the result streams into query
+// order on the device); the tables of a reference on the host and in HBM (HostShare, DeviceTables); a context (xm_index): its stream, its
 // resident and its staged batch (DeviceBatch), its scratch, the device copy of its confidence table; the steps of an align call (AlignCall ...
 // finishStreams), which launch what xm_pass_plan.h plans - reads a pass could not finish are run again by a later pass on the GPU, never on the
 // CPU; the C entries for indexes, contexts, batches and alignment.
 // Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_conf_table.h (the host's confidence table),
-// xm_capi_probe.h (seed-probe and random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries).  The
-// wave-per-read kernels are xm_wave_kernel.hip, the index build on the device is xm_index_device.hip.
+// xm_capi_probe.h (seed-probe and random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries).
+// The big kernels are objects of their own, reached through launch functions: the lane-per-read align kernel is xm_align_kernel.hip (xmAlignLaunch,
+// xm_kernel_common.h), the wave-per-read kernels are xm_wave_kernel.hip (xmWaveLaunch, xm_kernel_args.h), the index build on the device is
+// xm_index_device.hip.  This unit uses the host-side pieces of the shared headers only (makeCaps, searchPoolBytes, the pass planner's sizes):
+// nothing of the per-read state machine is compiled for the device from here.
+#define XM_NOINL_LINKAGE inline  // the out-of-line functions of the shared headers are defined (strongly) by xm_align_kernel.hip
 #include "../../include/xmapper_hip.h"
 #include "xm_worker.h"
 #include "xm_wsearch.h"
@@ -39,130 +42,6 @@ using namespace xm;
 
 namespace {
 
-#ifndef XM_WAVES_PER_SIMD
-#define XM_WAVES_PER_SIMD 4  // 128 registers per lane: the path is latency-bound, four waves per SIMD hide more of it than the spills cost
-#endif
-
-#ifdef XM_READ_TIMES
-// diagnostic builds (-DXM_READ_TIMES, XM_READ_TIMES_FILE=path): shader-clock ticks the last pass spent on every read, written to the file
-__device__ unsigned long long* xm_read_times = nullptr;
-#endif
-// One lane aligns one read at a time (AlignerWorker.align, M/AlignerWorker.java:256-484) and loops until the batch is drained.
-__global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_align_kernel(IndexView ix, Params params, BatchView batch, const int64_t* todo, long long nTodo, int scale, int heavyAllowed, int lanesPerWave,
-                                                       uint8_t* arenas, unsigned long long arenaBytes, OutView out, unsigned long long* nextItem, DevCounters* counters,
-                                                       long long taperUnit, long long firstStride, PNode* waveNodes, HandOver ho, int pairLanes,
-                                                       SearchPool searchPool, PassLists lists, int boundFilter) {
-  // lanesPerWave < 64 (gapped pass): the extension chain diverges so much that a wave runs its reads nearly one after another, so
-  // spreading them over more, partly filled waves shortens the critical path; the idle lanes own no scratch arena
-  xmSetWaveNodes(waveNodes);
-  xmSetPairMode(pairLanes);
-  xmSetSearchPool(searchPool);
-  xmSetBoundFilter(boundFilter);  // gapped passes of long reads: the rejection filter in front of PathAligner's searches (xm_bound.h)
-  xmLoadMergeRule();  // (every thread of the block: it ends with a barrier)
-  // pairLanes (gapped pass, lanesPerWave <= 32): a read is run by 2^pairLanes adjacent lanes doing the same work (xm_extend.h, xmSetPairMode: 1 = two lanes,
-  // 3 = eight, passes of long reads); `laneInWave` below is the read's slot in the wave, `second` marks the lanes that leave atomics and result writes to the first
-  const int physLane = (int)(threadIdx.x & 63u);
-  const int groupMask = (1 << pairLanes) - 1;
-  const int laneInWave = physLane >> pairLanes;
-  const bool second = (physLane & groupMask) != 0;
-  if (laneInWave >= lanesPerWave) return;
-  unsigned long long lane = ((unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * (unsigned)lanesPerWave + (unsigned)laneInWave;
-  uint8_t* arena = arenas + lane * arenaBytes;
-  long long myRegion = (long long)lane;  // (mode 1) the pool's first regions are the lanes' initial ones, the cursor starts behind them
-  DevCounters local;
-  memset(&local, 0, sizeof(local));
-  ReadCtx cx;
-  // Gapped pass: the list starts with the reads that look expensive.  The first read of every lane is dealt out lane-major (items
-  // 0..waves-1 to lane 0 of every wave, the next `waves` items to lane 1, ...), so that every wave gets the same number of them and
-  // they all start at once; after that the lanes draw from the counter, which the host has set behind the dealt items.
-  bool dealt = firstStride > 0;
-  const long long waveIndex = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  while (true) {
-    unsigned long long item;
-    const long long mine = (long long)laneInWave * firstStride + waveIndex;
-    if (dealt && mine < nTodo) {
-      dealt = false;
-      item = (unsigned long long)mine;
-    } else {
-      dealt = false;
-      {
-        // End of the work list (gapped pass): the lanes of a wave run their reads mostly one after the other, so when the list runs dry
-        // every wave would still hold lanesPerWave unfinished reads and the launch would end with that long serial tail.  The higher
-        // lanes therefore stop taking reads early; the last reads are spread one per wave.
-        // (pair mode: the read's first lane decides for both - two separate loads of the counter could differ, and a lane that left alone
-        // would leave its partner exchanging values with an inactive lane)
-        int leave = 0;
-        if (taperUnit > 0 && laneInWave > 0 && !second) {
-          long long remaining = nTodo - (long long)__hip_atomic_load(nextItem, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          leave = remaining < (long long)laneInWave * taperUnit;
-        }
-        if (pairLanes) leave = __shfl(leave, physLane & ~groupMask);
-        if (leave) break;
-      }
-      item = 0;
-      if (!second) item = atomicAdd(nextItem, 1ull);
-      if (pairLanes) item = (unsigned long long)__shfl((long long)item, physLane & ~groupMask);
-      if ((long long)item >= nTodo) break;
-    }
-    int64_t q = todo ? todo[item] : (int64_t)item;
-    ReadIn in;
-    in.nMates = batch.mateCount[q];
-    for (int m = 0; m < 2; m++) {
-      in.mate[m] = batch.codes + batch.mateOffset[q * 2 + m];
-      in.mateLen[m] = m < in.nMates ? batch.mateLength[q * 2 + m] : 0;
-    }
-    // single-end Query: expectedInnerDistance 0, deviation 1 (spacing penalty is always 0, T/SamWriter_Test.java:26)
-    in.expectedInner = in.nMates > 1 ? batch.expectedInner[q] : 0.0;
-    in.deviation = in.nMates > 1 ? batch.deviation[q] : 1.0;
-    ReadResult rr;
-#ifdef XM_READ_TIMES
-    const unsigned long long readT0 = clock64();
-#endif
-    DevCounters before = local;
-    if (ho.mode == 1) {
-      uint8_t* region = ho.regions + (unsigned long long)myRegion * ho.regionBytes;
-      runReadRetaining(cx, &ix, params, in, scale, region, (size_t)ho.regionBytes, arena, (size_t)arenaBytes, &local, rr, heavyAllowed);
-      if (cx.status == XM_ST_NEED_HEAVY && savedReadOf(region, (size_t)ho.regionBytes)->valid) {
-        // the read keeps this region; the lane needs a fresh one only if it will take another read (the list counter only grows, so a
-        // lane that sees the list drained here finds it drained at its next fetch and leaves)
-        const bool drained = (long long)__hip_atomic_load(nextItem, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= nTodo;
-        if (drained) {
-          ho.regionOf[q] = (int32_t)myRegion;
-        } else {
-          long long fresh = (long long)atomicAdd(ho.cursor, 1ull);
-          if (fresh < ho.nRegions) { ho.regionOf[q] = (int32_t)myRegion; myRegion = fresh; }  // (pool used up: the read is seeded again by the gapped pass)
-        }
-      }
-    } else if (ho.mode == 2) {
-      const int32_t rg = ho.regionOf[q];
-      uint8_t* tmp = arena + ho.regionBytes;
-      const size_t tmpBytes = (size_t)(arenaBytes - ho.regionBytes);
-      if (rg >= 0) runReadResumed(cx, savedReadOf(ho.regions + (unsigned long long)rg * ho.regionBytes, (size_t)ho.regionBytes), &ix, scale, tmp, tmpBytes, &local, rr);
-      else runReadRetaining(cx, &ix, params, in, ho.seedScale, arena, (size_t)ho.regionBytes, tmp, tmpBytes, &local, rr, 2, scale);
-    } else {
-      runRead(cx, &ix, params, in, scale, arena, (size_t)arenaBytes, &local, rr, heavyAllowed);
-    }
-    XM_PAIR_CHECK(0, cx.status);
-    XM_PAIR_CHECK(1, ((long long)rr.nComponents << 40) ^ ((long long)rr.single[0] << 20) ^ (long long)rr.empty[0] ^ ((long long)local.pathAlignerNodes << 4));
-    int32_t st = cx.status;
-#ifdef XM_READ_TIMES
-    if (xm_read_times && !second) xm_read_times[q] = clock64() - readT0;
-#endif
-    if (st != XM_OK) local = before;  // work of a read that is rerun by a later pass is counted there
-    if (second) continue;             // (pair mode: the first lane of the read publishes)
-    // (a read that found the result arena full is run again too: round 6 - its work used to be counted twice, PathAligner calls and nodes of the first call on a fresh context;
-    // pinned by tests/test_gpu_result_stage.py, test_light_pass_overflows_both_arenas: the same batch fresh and warm, equal counters)
-    if (publishRead(out, q, rr, cx, local, lists) == XM_ST_OUT_OVERFLOW) local = before;
-  }
-  if (!second) addCounters(counters, local);
-}
-
-}  // namespace
-
-#include "xm_capi_test.h"  // (the test-only entries run parts of the align kernel alone: their kernels stand behind it)
-
-namespace {
-
 // ---------------------------------------------------------------- pass bookkeeping on the device (PassCtl, PassLists: xm_kernel_common.h)
 // after a pass of the wave-per-read form (xm_wave_kernel.hip): reads for the next tier, reads with a waiting search request, reads left
 // to the lane-per-read passes
@@ -174,12 +53,12 @@ __global__ void __launch_bounds__(256) xm_wave_classify_kernel(const int64_t* to
   const int64_t q = todo ? todo[i] : (int64_t)i;
   const int32_t st = status[q] & 0xFF;
   if (st == XM_OK) return;
-  if (st == 9 /* XM_ST_WAVE_GAPPED */ && listNext) {
+  if (st == XM_ST_WAVE_GAPPED && listNext) {
     const unsigned long long pos = atomicAdd(&ctl->nNext, 1ull);
     listNext[pos] = q;
     if (slotOfOut) slotOfOut[q] = (int32_t)pos;  // the read's memo (it keeps it through the later tiers)
-  } else if (st == 10 /* XM_ST_WAVE_SEARCH */ && listSearch) listSearch[atomicAdd(&ctl->nSearch, 1ull)] = q;
-  else if (st == 8 /* XM_ST_WAVE_FALLBACK */ || st == 9 || st == 10) listFallback[atomicAdd(&ctl->nFallback, 1ull)] = q;
+  } else if (st == XM_ST_WAVE_SEARCH && listSearch) listSearch[atomicAdd(&ctl->nSearch, 1ull)] = q;
+  else if (st == XM_ST_WAVE_FALLBACK || st == XM_ST_WAVE_GAPPED || st == XM_ST_WAVE_SEARCH) listFallback[atomicAdd(&ctl->nFallback, 1ull)] = q;
   else atomicMin(&ctl->errQuery, (unsigned long long)q);
 }
 
@@ -689,8 +568,7 @@ static void prepareCall(AlignCall& c) {
   if (c.readTimesFile && *c.readTimesFile) {
     c.dReadTimes.ensure((size_t)nq);
     HIP_CHECK(hipMemset(c.dReadTimes.p, 0, sizeof(unsigned long long) * (size_t)nq));
-    unsigned long long* ptr = c.dReadTimes.p;
-    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_read_times), &ptr, sizeof(ptr)));
+    HIP_CHECK((hipError_t)xmSetReadTimes(c.dReadTimes.p));
   }
 #endif
   c.todo = nullptr;
@@ -980,13 +858,23 @@ static float launchAlignPass(AlignCall& c, const BatchPolicy& pol, const PassSta
   }
   idx->dListScale[st.ts].ensure((size_t)c.nq); idx->dListOut[st.to].ensure((size_t)c.nq);
   HIP_CHECK(hipMemcpyAsync(idx->dCursors.p + 2, &pl.firstItem, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
-  const OutView ov = c.outView();
+  AlignLaunch a{};
+  a.grid = pl.grid; a.block = pl.block;
+  a.ix = c.view; a.params = c.params; a.batch = c.bv;
+  a.todo = c.todo; a.nTodo = c.nTodo;
+  a.scale = st.scale; a.heavyAllowed = st.heavy ? 2 : (int)pol.k.lightLevel; a.lanesPerWave = pl.lpw;
+  a.arenas = laneArenas; a.arenaBytes = (unsigned long long)pl.arenaBytes;
+  a.out = c.outView();
+  a.nextItem = idx->dCursors.p + 2; a.counters = idx->dCounters.p;
+  a.taperUnit = pl.taperUnit; a.firstStride = pl.firstStride;
+  a.waveNodes = idx->dWaveNodes.p;
+  a.ho = ho; a.pairLanes = pl.pairLanes; a.searchPool = pool;
   // the lanes file the reads they could not finish into the work lists of the passes to come as they publish them (PassLists; no kernel behind the pass)
-  PassLists lists{idx->dListHeavy.p, idx->dListHeavyLate.p, idx->dListScale[st.ts].p, idx->dListOut[st.to].p, idx->dListConf[st.tc].p, (int)pol.k.heavyHint, st.ts, st.to, st.tc, idx->dCtl.p};
+  a.lists = PassLists{idx->dListHeavy.p, idx->dListHeavyLate.p, idx->dListScale[st.ts].p, idx->dListOut[st.to].p, idx->dListConf[st.tc].p, (int)pol.k.heavyHint, st.ts, st.to, st.tc, idx->dCtl.p};
+  a.boundFilter = pl.boundFilterArg;
   return timedLaunch(c, 1, !st.heavy ? 12 : 15, [&] {  // kernel microseconds: light pass / gapped pass and reruns
-    hipLaunchKernelGGL(xm_align_kernel, dim3(pl.grid), dim3(pl.block), 0, s, c.view, c.params, c.bv, c.todo, c.nTodo, st.scale, st.heavy ? 2 : (int)pol.k.lightLevel, pl.lpw,
-                       laneArenas, (unsigned long long)pl.arenaBytes, ov, idx->dCursors.p + 2, idx->dCounters.p,
-                       pl.taperUnit, pl.firstStride, idx->dWaveNodes.p, ho, pl.pairLanes, pool, lists, pl.boundFilterArg);
+    const int rc = xmAlignLaunch(a, (void*)s);
+    if (rc != 0) throw std::runtime_error(std::string("align kernel launch: ") + hipGetErrorString((hipError_t)rc));
   }, [&] {
     HIP_CHECK(hipMemcpyAsync(&ctl, idx->dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, s));
@@ -1026,9 +914,8 @@ static void runLanePasses(AlignCall& c, const BatchPolicy& pol) {
                                    !st.heavy ? "light" : "gapped", c.nTodo, st.scale, pl.lpw, pl.nWaves, 1 << pl.pairLanes, pl.boundFilter, ms, ctl.nHeavy + ctl.nHeavyLate, ctl.nScale[st.ts], ctl.nOut[st.to]);
 #ifdef XM_PROFILE
     if (pol.k.tracePasses && st.heavy) {  // reads of a wave that stood at a PathAligner call together, this pass
-      unsigned long long a[16] = {0}, z[16] = {0};
-      HIP_CHECK(hipMemcpyFromSymbol(a, HIP_SYMBOL(xm_arrive_prof), sizeof(a)));
-      HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_arrive_prof), z, sizeof(z)));
+      unsigned long long a[16] = {0};
+      HIP_CHECK((hipError_t)xmTakeArriveProf(a));
       fprintf(stderr, "[xm] pass %d: pair checks (status, result, search problem, search outcome): %llu %llu %llu %llu\n", c.launches, a[4], a[5], a[6], a[7]);
       fprintf(stderr, "[xm] pass %d: PathAligner arrivals %llu with %llu reads (%.2f per arrival); arrivals of four reads or more: %llu with %llu reads\n", c.launches, a[0], a[1], a[0] ? (double)a[1] / (double)a[0] : 0.0, a[2], a[3]);
     }
@@ -1091,8 +978,7 @@ static void finishStreams(AlignCall& c) {
   if (c.dReadTimes.p) {
     std::vector<unsigned long long> t((size_t)nq);
     HIP_CHECK(hipMemcpy(t.data(), c.dReadTimes.p, sizeof(unsigned long long) * (size_t)nq, hipMemcpyDeviceToHost));
-    unsigned long long* none = nullptr;
-    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(xm_read_times), &none, sizeof(none)));
+    HIP_CHECK((hipError_t)xmSetReadTimes(nullptr));
     if (FILE* f = fopen(c.readTimesFile, "wb")) { fwrite(t.data(), sizeof(unsigned long long), t.size(), f); fclose(f); }
     c.dReadTimes.release();
   }
@@ -1717,3 +1603,4 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 
 #include "xm_capi_probe.h"
 #include "xm_capi_pileup.h"
+#include "xm_capi_test.h"

@@ -1,88 +1,6 @@
-// The test-only entries of libxmapper_hip.so (included once, by xm_capi.hip): components of the align kernel run alone on given inputs.
+// The test-only entries of libxmapper_hip.so (included once, by xm_capi.hip): components of the align kernel run alone on given inputs.  Buffers and the
+// error contract are here; the kernels stand behind the align kernel in xm_align_kernel.hip (TestLocalLaunch, TestBoundLaunch: xm_kernel_common.h).
 #pragma once
-
-namespace {
-
-// Test entry (xm_test_local_align): the reference's component-level known-answer tests (PathAligner_Test.java:10-39: PathAligner alone;
-// HashBlockAligner_Test.java:10-48: HashBlock_Aligner -> StraightAligner -> PathAligner_Runner) over two given texts, run by the code the align
-// kernel runs.  chain 0: one search, in the wave's LDS slot (mode 0), in HBM mode (mode 1) or in the lane-private form (mode 4); chain 1: hashBlockAlign with the searches
-// slot-first as in the kernel (mode 0), all in HBM mode (mode 1) or all in the lane-private form of xm_wsearch.h (mode 4).  One lane works; out: found, nb, status, nodes, blocks; penalties.
-__global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_test_local_kernel(int chain, int mode, Params params, const uint8_t* query, int queryLength, const uint8_t* reference, int referenceLength,
-                                                            double maxIns, double maxDel, int scale, uint8_t* arena, unsigned long long arenaBytes, PNode* waveNodes, int blockCap,
-                                                            int32_t* outInts, double* outDbls) {
-  xmSetWaveNodes(waveNodes);
-  xmSetPairMode(0);
-  xmSetSearchPool(SearchPool{nullptr, 0, 0, 0});
-  xmSetBoundFilter(mode >= 8 ? 1 : 0);  // (mode + 8: the search behind the rejection filter of xm_bound.h)
-  mode &= 7;
-  xmLoadMergeRule();  // (every thread of the block: it ends with a barrier)
-  if (threadIdx.x != 0) return;
-  DevCounters local;
-  memset(&local, 0, sizeof(local));
-  Caps caps = makeCaps(scale);
-  caps.searchInHbmOnly = mode == 1 ? 1 : (mode == 4 ? 2 : 0);
-  Arena tmp;
-  tmp.init(arena, (size_t)arenaBytes);
-  int32_t status = XM_OK;
-  float hint = 0;
-  ExtEnv e;
-  e.caps = &caps; e.dc = &local; e.status = &status; e.tmp = &tmp;
-  e.query.base = query; e.query.len = queryLength; e.query.rc = 0; e.query.id = 0;
-  e.reference.base = reference; e.reference.len = referenceLength; e.reference.rc = 0; e.reference.id = 0;
-  e.contig = 0;
-  e.heavyHint = &hint;
-  Matcher* slots = arenaArray<Matcher>(tmp, 3);
-  for (int i = 0; i < 3; i++) {
-    slots[i].present = arenaArray<uint8_t>(tmp, caps.maxSections);
-    slots[i].tables = arenaArray<int16_t>(tmp, caps.matcherEntries);
-    slots[i].tableCap = caps.matcherEntries;
-    slots[i].maxSections = caps.maxSections;
-    slots[i].nSections = 0;
-    slots[i].presentMask = 0;
-    slots[i].sectionLength = 0;
-  }
-  e.slotA = &slots[0]; e.slotB = &slots[1]; e.slotT = &slots[2];
-  SeqAl out;
-  out.blocks = arenaArray<ABlock>(tmp, caps.maxBlocks);
-  out.nb = 0; out.contig = 0; out.referenceReversed = 0; out.seqAId = 0; out.totalPenalty = 0; out.alignedPenalty = 0;
-  bool found = false;
-  if (tmp.overflow) status = XM_ST_OVERFLOW;
-  else {
-    const Section qs{0, queryLength}, rs{0, referenceLength};
-    Analysis an;  // AlignmentAnalysis as the tests construct it: nothing known about the offset, the two extension limits given
-    an.matcher = nullptr; an.predictedBestOffset = 0; an.lastCheckedOffset = 0; an.confidentAboutBestOffset = false;
-    an.maxInsertionExtensionPenalty = maxIns; an.maxDeletionExtensionPenalty = maxDel;
-    if (chain == 0) found = pathAlign(e, qs, rs, params, an, out);
-    else found = hashBlockAlign(e, qs, rs, params, an, out, e.slotB, NextStraight3());
-  }
-  outInts[0] = found && status == XM_OK ? 1 : 0; outInts[1] = found ? out.nb : 0; outInts[2] = status; outInts[3] = (int32_t)local.pathAlignerNodes;
-  outInts[4 + 4 * blockCap] = (int32_t)local.boundChecks; outInts[5 + 4 * blockCap] = (int32_t)local.boundRejects; outInts[6 + 4 * blockCap] = (int32_t)local.boundCells;  // (behind the blocks)
-  if (found) {
-    for (int i = 0; i < out.nb && i < blockCap; i++) { outInts[4 + 4 * i] = out.blocks[i].startA; outInts[5 + 4 * i] = out.blocks[i].startB; outInts[6 + 4 * i] = out.blocks[i].lenA; outInts[7 + 4 * i] = out.blocks[i].lenB; }
-    outDbls[0] = out.totalPenalty; outDbls[1] = out.alignedPenalty;
-  }
-}
-
-// Test entry (xm_test_bound): the rejection filter of xm_bound.h alone, on one problem - a section of a query against a window of a reference - as a lane of a
-// long-read chain runs it (lane 0 of a wave, its region of the wave's slot; pair = 1: lanes 0 and 1 together, 3: lanes 0 .. 7).  out: taken, rejected, cells.
-__global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_test_bound_kernel(Params params, const uint8_t* query, int queryLength, int queryRc, int startA, int endA, const uint8_t* reference, int referenceLength,
-                                                            int startB, int endB, int predictedBestOffset, int pair, uint8_t* arena, unsigned long long arenaBytes, int64_t* out) {
-  xmSetWaveNodes(nullptr);
-  xmSetPairMode(pair);
-  xmSetSearchPool(SearchPool{nullptr, 0, 0, 0});
-  xmSetBoundFilter(3);
-  xmLoadMergeRule();  // (every thread of the block: it ends with a barrier)
-  if (threadIdx.x >= (1u << pair)) return;
-  const BoundProblem bp = boundTestProblem(params, query, queryLength, queryRc, startA, endA, reference, referenceLength, startB, endB, predictedBestOffset);
-  bool taken = false;
-  unsigned long long cells = 0;
-  Arena tmp;
-  tmp.init(arena, (size_t)arenaBytes);  // (the two lanes of a pair keep the same band in the same memory, as they do in the passes: same values twice)
-  const bool rejected = boundRejects(bp, pair, tmp, taken, cells);
-  if (threadIdx.x == 0) { out[0] = taken ? 1 : 0; out[1] = rejected ? 1 : 0; out[2] = (int64_t)cells; }
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -104,16 +22,18 @@ int xm_test_bound(int32_t device, const xm_params* p, const uint8_t* query, int3
     HIP_CHECK(hipMemcpy(dq.p, query, (size_t)query_length, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dr.p, reference, (size_t)reference_length, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemset(dOut.p, 0, sizeof(int64_t) * 4));
-    hipLaunchKernelGGL(xm_test_bound_kernel, dim3(1), dim3(256), 0, 0, params, (const uint8_t*)dq.p, (int)query_length, (int)query_rc, (int)start_a, (int)end_a, (const uint8_t*)dr.p, (int)reference_length,
-                       (int)start_b, (int)end_b, (int)predicted_best_offset, (int)(pair == 3 ? 3 : (pair ? 1 : 0)), dArena.p, (unsigned long long)(64 * 1024), dOut.p);
-    HIP_CHECK(hipGetLastError());
+    TestBoundLaunch t{};
+    t.params = params; t.query = dq.p; t.queryLength = query_length; t.queryRc = query_rc; t.startA = start_a; t.endA = end_a;
+    t.reference = dr.p; t.referenceLength = reference_length; t.startB = start_b; t.endB = end_b; t.predictedBestOffset = predicted_best_offset;
+    t.pair = pair == 3 ? 3 : (pair ? 1 : 0); t.arena = dArena.p; t.arenaBytes = 64 * 1024; t.out = dOut.p;
+    HIP_CHECK((hipError_t)xmTestBoundLaunch(t, nullptr));
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemcpy(out3, dOut.p, sizeof(int64_t) * 3, hipMemcpyDeviceToHost));
     return 0;
   } catch (std::exception& e) { return fail(std::string("xm_test_bound: ") + e.what()); }
 }
 
-// Test-only entry (tests/test_gpu_kat.py): see xm_test_local_kernel above and xm_test_wave_search_kernel (xm_wave_kernel.hip).
+// Test-only entry (tests/test_gpu_kat.py): see xm_test_local_kernel (xm_align_kernel.hip) and xm_test_wave_search_kernel (xm_wave_kernel.hip).
 int xm_test_local_align(int32_t device, int32_t chain, int32_t mode, const xm_params* p, const uint8_t* query, int32_t query_length, const uint8_t* reference, int32_t reference_length,
                         double max_ins_ext, double max_del_ext, int32_t block_cap, int32_t* blocks, int32_t* num_blocks, double* penalties, int64_t* nodes_put) {
   if (!p || !query || !reference || !blocks || !num_blocks || !penalties) { fail("xm_test_local_align: null argument"); return -1; }
@@ -156,9 +76,11 @@ int xm_test_local_align(int32_t device, int32_t chain, int32_t mode, const xm_pa
       const size_t arenaBytes = (size_t)XM_ARENA_KB_DEFAULT * 1024 * scale;
       arena.ensure(arenaBytes);
       nodes.ensure((size_t)XM_PAL_NODES * 4 * sizeof(PNode));
-      hipLaunchKernelGGL(xm_test_local_kernel, dim3(1), dim3(256), 0, 0, (int)chain, (int)mode + (withBound ? 8 : 0), params, (const uint8_t*)dq.p, (int)query_length, (const uint8_t*)dr.p, (int)reference_length,
-                         max_ins_ext, max_del_ext, scale, arena.p, (unsigned long long)arenaBytes, (PNode*)nodes.p, cap, dInts.p, dDbls.p);
-      HIP_CHECK(hipGetLastError());
+      TestLocalLaunch t{};
+      t.chain = chain; t.mode = mode + (withBound ? 8 : 0); t.params = params; t.query = dq.p; t.queryLength = query_length; t.reference = dr.p; t.referenceLength = reference_length;
+      t.maxIns = max_ins_ext; t.maxDel = max_del_ext; t.scale = scale; t.arena = arena.p; t.arenaBytes = arenaBytes; t.waveNodes = (PNode*)nodes.p; t.blockCap = cap;
+      t.outInts = dInts.p; t.outDbls = dDbls.p;
+      HIP_CHECK((hipError_t)xmTestLocalLaunch(t, nullptr));
     }
     HIP_CHECK(hipDeviceSynchronize());
     std::vector<int32_t> ints((size_t)8 + 4 * (size_t)cap);

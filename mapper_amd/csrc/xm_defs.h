@@ -24,7 +24,7 @@
 #endif
 #define XM_INL __host__ __device__ __forceinline__
 #ifndef XM_NOINL_LINKAGE
-#define XM_NOINL_LINKAGE  // (a second translation unit of the library that includes these headers makes the out-of-line functions inline)
+#define XM_NOINL_LINKAGE  // (xm_align_kernel.hip: the strong definitions.  Every other translation unit of the library that includes these headers makes the out-of-line functions inline)
 #endif
 #define XM_NOINL XM_NOINL_LINKAGE __host__ __device__ __noinline__
 #define XM_NOINL_DECL XM_NOINL_LINKAGE __host__ __device__
@@ -50,7 +50,11 @@ enum : int32_t {
   XM_ST_NEED_HEAVY = 6,    // light pass only: the read needs the gapped extension chain; the full pass reruns it
                            // (7 and 12 are not in use)
   XM_ST_NEED_CONF = 11,    // quicklyConfidentInBestAlignment needs a value of the confidence table the host has not put there yet (ConfView): the
-                           // read left its key in the miss list; the host evaluates it and the read runs again  (8-10: the wave form's, xm_wave.h)
+                           // read left its key in the miss list; the host evaluates it and the read runs again
+  // the wave-per-read form's (xm_wave.h); the host files such reads into the lists of the next tier, the search kernel or the lane-per-read passes
+  XM_ST_WAVE_FALLBACK = 8,  // the wave form does not take this read: the lane-per-read passes align it
+  XM_ST_WAVE_GAPPED = 9,    // light tier: the read needs the heavy tier of the wave form (gapped chain, or a structure outgrew the light capacities)
+  XM_ST_WAVE_SEARCH = 10,   // chain tier: a PathAligner search request is waiting in the read's memo (search kernel, then the read runs again)
 };
 
 // ---------------------------------------------------------------- Java arithmetic

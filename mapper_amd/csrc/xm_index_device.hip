@@ -15,7 +15,7 @@
 // on the bases of its own span only, so those are the blocks of the plain rule), the conditional multi blocks over the ambiguous bases
 // (M/MultiHashBlock.java, M/HashBlock_ParentRow.java:109-165) come from the host's windows around them (HostIndex::multiRecordsNearAmbiguity) and
 // join the records before the sort; PackedMap.add's duplicate suppression for multi records (:124-153) is a pass over the sorted records.
-#define XM_NOINL_LINKAGE inline  // the out-of-line functions of the shared headers are defined (strongly) by xm_capi.hip
+#define XM_NOINL_LINKAGE inline  // the out-of-line functions of the shared headers are defined (strongly) by xm_align_kernel.hip
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>

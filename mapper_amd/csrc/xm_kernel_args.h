@@ -1,4 +1,5 @@
-// Argument structures shared by the kernels of xm_capi.hip (lane-per-read passes) and xm_wave_kernel.hip (wave-per-read passes).
+// Argument structures shared by the kernels of xm_align_kernel.hip (lane-per-read passes), xm_wave_kernel.hip (wave-per-read passes) and the small
+// kernels of the host unit, xm_capi.hip.
 #pragma once
 #include <stdint.h>
 #include "xm_defs.h"

@@ -1,4 +1,4 @@
-// Device helpers and launch structures of the kernels of xm_capi.hip (lane-per-read passes); the structures are what the host passes.
+// Device helpers and launch structures of the kernels of xm_align_kernel.hip (lane-per-read passes); the structures are what the host (xm_capi.hip) passes.
 #pragma once
 #include "xm_worker.h"
 #include "xm_kernel_args.h"
@@ -34,6 +34,62 @@ struct PassLists {
   int hintThreshold, ts, to, tc;
   PassCtl* ctl;
 };
+
+// One launch of xm_align_kernel (xm_align_kernel.hip): grid and block, then one member per kernel parameter, named as the parameter and in its order.
+struct AlignLaunch {
+  int grid, block;
+  IndexView ix;
+  Params params;
+  BatchView batch;
+  const int64_t* todo;       // null: all reads
+  long long nTodo;
+  int scale;
+  int heavyAllowed;
+  int lanesPerWave;
+  uint8_t* arenas;           // the lanes' scratch, arenaBytes each
+  unsigned long long arenaBytes;
+  OutView out;
+  unsigned long long* nextItem;
+  DevCounters* counters;
+  long long taperUnit;       // (taperUnit, firstStride: the gapped pass's end and start of the work list; they change speed, not results)
+  long long firstStride;
+  PNode* waveNodes;          // per wave: node payloads of its LDS-mode search
+  HandOver ho;
+  int pairLanes;
+  SearchPool searchPool;
+  PassLists lists;
+  int boundFilter;
+};
+int xmAlignLaunch(const AlignLaunch& a, void* stream);  // (the launches return hipError_t as int)
+// The test kernels behind the align kernel (entries: xm_capi_test.h), one block of 256 lanes each; members named as the kernels' parameters, in their order.
+struct TestLocalLaunch {
+  int chain, mode;
+  Params params;
+  const uint8_t* query; int queryLength;
+  const uint8_t* reference; int referenceLength;
+  double maxIns, maxDel;
+  int scale;
+  uint8_t* arena; unsigned long long arenaBytes;
+  PNode* waveNodes;
+  int blockCap;
+  int32_t* outInts; double* outDbls;
+};
+int xmTestLocalLaunch(const TestLocalLaunch& t, void* stream);
+struct TestBoundLaunch {
+  Params params;
+  const uint8_t* query; int queryLength, queryRc, startA, endA;
+  const uint8_t* reference; int referenceLength, startB, endB, predictedBestOffset, pair;
+  uint8_t* arena; unsigned long long arenaBytes;
+  int64_t* out;
+};
+int xmTestBoundLaunch(const TestBoundLaunch& t, void* stream);
+// The align kernel's diagnostic device symbols live in its unit, and so does the host's access to them (hipError_t as int).
+#ifdef XM_READ_TIMES
+int xmSetReadTimes(unsigned long long* perRead);    // -DXM_READ_TIMES: where the passes write every read's ticks; null: nowhere
+#endif
+#ifdef XM_PROFILE
+int xmTakeArriveProf(unsigned long long* out16);    // -DXM_PROFILE: xm_arrive_prof (xm_extend.h) read and cleared
+#endif
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ void addCounters(DevCounters* g, const DevCounters& l) {

@@ -22,9 +22,7 @@
 
 namespace xm {
 
-constexpr int32_t XM_ST_WAVE_FALLBACK = 8;  // the wave form does not take this read: the lane-per-read passes align it
-constexpr int32_t XM_ST_WAVE_SEARCH = 10;   // chain tier: a PathAligner search request is waiting in the read's memo (search kernel, then the read runs again)
-constexpr int32_t XM_ST_WAVE_GAPPED = 9;    // light tier: the read needs the heavy tier of the wave form (gapped chain, or a structure outgrew the light capacities)
+// (the statuses a read leaves the wave form with, XM_ST_WAVE_FALLBACK / GAPPED / SEARCH, are in the status enum of xm_defs.h: the host's classification reads them too)
 
 #if defined(__HIP_DEVICE_COMPILE__)
 #define XM_LDSP(T) T __attribute__((address_space(3)))

@@ -4,8 +4,8 @@
 //   config 4:     the chain tier with the largest capacities
 // A tier hands a read it cannot finish to the next one (XM_ST_WAVE_GAPPED).  PathAligner's searches are requests in the reads' memos
 // (XM_ST_WAVE_SEARCH): xm_wave_search_kernel runs them, one wavefront per search, and the chain tier runs those reads again.
-// A read the wave form does not take leaves with XM_ST_WAVE_FALLBACK and is aligned by the lane-per-read kernel of xm_capi.hip.
-#define XM_NOINL_LINKAGE inline  // the out-of-line functions of the shared headers are defined (strongly) by xm_capi.hip
+// A read the wave form does not take leaves with XM_ST_WAVE_FALLBACK and is aligned by the lane-per-read kernel of xm_align_kernel.hip.
+#define XM_NOINL_LINKAGE inline  // the out-of-line functions of the shared headers are defined (strongly) by xm_align_kernel.hip
 #include <hip/hip_runtime.h>
 #ifndef WV_CONFIG
 #error "compile with -DWV_CONFIG=0..4 (one wave-per-read kernel configuration), 5 (search kernel) or 100 (geometry, dispatch)"

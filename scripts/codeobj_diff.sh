@@ -1,16 +1,21 @@
 #!/bin/bash
-# Device code of two builds of an object (xm_capi.o, xm_index_device.o, ...), symbol by symbol: the gfx950 code object of each is unbundled and disassembled (llvm-objdump -d), addresses and
+# Device code of two builds of an object (xm_align_kernel.o, xm_capi.o, xm_index_device.o, ...), symbol by symbol: the gfx950 code object of each is unbundled and disassembled (llvm-objdump -d), addresses and
 # encodings dropped, and the instruction text of every kernel and out-of-line device function compared.  Runs on the CPU.  Exit status 0: equal for every symbol.
 # A displacement from the program counter to another symbol (s_getpc_b64, s_add_u32 with a literal) is compared as the symbol and offset it points at
 # (scripts/codeobj_resolve.py): adding or resizing a kernel moves everything behind it, and with that every such literal, without changing an instruction.
 # The s_nop 0 padding behind a symbol's last instruction is not compared either: it follows the address the function happens to start at.  Every other s_nop is.
-# usage: scripts/codeobj_diff.sh BEFORE/xm_capi.o AFTER/xm_capi.o   (any two objects with a gfx950 bundle)
+# Nor is the "..." line llvm-objdump prints for the zero bytes that pad the last symbol of a section.
+# With more than one AFTER object (a unit that was split), a symbol of BEFORE is looked up in the union of them; one found in two of them is an error.
+# usage: scripts/codeobj_diff.sh BEFORE/xm_align_kernel.o AFTER/xm_align_kernel.o [AFTER/another.o ...]   (any objects with a gfx950 bundle)
 set -e
 HERE=$(cd "$(dirname "$0")" && pwd)
 LL=/opt/rocm/lib/llvm/bin
 T=$(mktemp -d)
-for v in a b; do
-  o=$1; [ $v = b ] && o=$2
+[ $# -ge 2 ] || { echo "usage: $0 BEFORE.o AFTER.o [AFTER.o ...]" >&2; exit 2; }
+nb=$(($# - 1))
+for k in $(seq 0 $nb); do
+  v=b$k; [ $k = 0 ] && v=a
+  o=$1; shift
   $LL/llvm-objcopy --dump-section .hip_fatbin=$T/$v.fatbin $o /dev/null
   $LL/clang-offload-bundler --unbundle --type=o --input=$T/$v.fatbin --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=$T/$v.co
   # "0000000000001000 <symbol>:" opens a symbol; an instruction line is "\tmnemonic operands // address: encoding"
@@ -23,16 +28,23 @@ for v in a b; do
 done
 rc=0
 declare -A after before
-while read name n i; do after[$name]=$i; done < $T/b.symbols
+for k in $(seq 1 $nb); do
+  while read name n i; do
+    [ -z "${after[$name]}" ] || { echo "$name ($n instructions): in more than one object after"; rc=1; }
+    after[$name]=b$k/$i
+  done < $T/b$k.symbols
+done
 while read name n i; do
   before[$name]=$i
   j=${after[$name]}
   [ -f $T/a/$i ] || : > $T/a/$i
-  [ -z "$j" ] || [ -f $T/b/$j ] || : > $T/b/$j
+  [ -z "$j" ] || [ -f $T/$j ] || : > $T/$j
   if [ -z "$j" ]; then echo "$name ($n instructions): missing after"; rc=1
-  elif cmp -s $T/a/$i $T/b/$j; then echo "$name ($n instructions): equal"
+  elif cmp -s $T/a/$i $T/$j; then echo "$name ($n instructions): equal"
   else echo "$name ($n instructions): DIFFERENT"; rc=1; fi
 done < $T/a.symbols
-while read name n i; do [ -n "${before[$name]}" ] || { echo "$name ($n instructions): new"; rc=1; }; done < $T/b.symbols
+for k in $(seq 1 $nb); do
+  while read name n i; do [ -n "${before[$name]}" ] || { echo "$name ($n instructions): new"; rc=1; }; done < $T/b$k.symbols
+done
 rm -rf $T
 exit $rc

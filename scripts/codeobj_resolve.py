@@ -3,7 +3,8 @@ literal of the s_add_u32 that follows an s_getpc_b64 is a displacement to anothe
 anything in front of either moves, e.g. when a kernel is added to the object.  It is replaced by what it points at, <symbol+offset>, so that two builds
 compare equal exactly when the instructions and their targets are.  A run of "s_nop 0" behind the last instruction of a symbol is dropped for the same
 reason: it is the padding up to the next symbol's alignment, never executed, and how long it is depends on the address the function starts at.  Every
-s_nop that an instruction follows - the hazard nops, a loop head's padding - stays and is compared."""
+s_nop that an instruction follows - the hazard nops, a loop head's padding - stays and is compared.  The "..." line the disassembler prints in place of
+a run of zero bytes (the fill behind the last symbol of a section) is dropped too: it is not an instruction."""
 import bisect
 import re
 import sys
@@ -28,6 +29,8 @@ pc = None    # what the last s_getpc_b64 returns: the address of the instruction
 nops = []    # a run of "s_nop 0" lines whose end has not been seen yet
 
 for line in sys.stdin:
+    if line.strip() == "...":
+        continue
     m = re.search(r"//\s*([0-9A-Fa-f]+):", line)
     if re.match(r"\ts_nop 0\s", line):
         nops.append(line)
