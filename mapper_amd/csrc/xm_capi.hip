@@ -1,12 +1,14 @@
 // libxmapper_hip.so: the host side of the align call and the C ABI of include/xmapper_hip.h, one translation unit.
 //
-// In this file, in this order: the small kernels of the pass bookkeeping (work lists, prefix sums, the gather of the result streams into query
-// order on the device); the tables of a reference on the host and in HBM (HostShare, DeviceTables); a context (xm_index): its stream, its
-// resident and its staged batch (DeviceBatch), its scratch, the device copy of its confidence table; the steps of an align call (AlignCall ...
-// finishStreams), which launch what xm_pass_plan.h plans - reads a pass could not finish are run again by a later pass on the GPU, never on the
-// CPU; the C entries for indexes, contexts, batches and alignment.
-// Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_conf_table.h (the host's confidence table),
-// xm_capi_probe.h (seed-probe and random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries).
+// In this file, in this order: the two small kernels of its own (the wave form's work lists, the bucket lines); the tables of a reference on the host
+// and in HBM (HostShare, DeviceTables); the owners of a context's device buffers - DeviceBatch (the resident and the staged batch), PassBuffers (work
+// lists, control words, counters and scratch of the lane-per-read passes), DeviceConfTable (the confidence table and its copy in HBM), WaveFormBuffers,
+// CollapseBuffers, MemoCallBuffers - and the context (xm_index) that holds one of each beside its stream and its ResultStage; the steps of an align call
+// (AlignCall ... finishStreams), which launch what xm_pass_plan.h plans - reads a pass could not finish are run again by a later pass on the GPU, never
+// on the CPU; the C entries for indexes, contexts, batches and alignment (a first context is opened by openFirstContext, whichever entry asks).
+// Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_result_stage.h (ResultStage: the result arenas,
+// the scan and gather kernels, the canonical streams; throwFailedQuery), xm_conf_table.h (the host's confidence table), xm_capi_probe.h (seed-probe and
+// random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries).
 // The big kernels are objects of their own, reached through launch functions: the lane-per-read align kernel is xm_align_kernel.hip (xmAlignLaunch,
 // xm_kernel_common.h), the wave-per-read kernels are xm_wave_kernel.hip (xmWaveLaunch, xm_kernel_args.h), the index build on the device is
 // xm_index_device.hip.  This unit uses the host-side pieces of the shared headers only (makeCaps, searchPoolBytes, the pass planner's sizes):
@@ -39,6 +41,7 @@
 
 namespace xm { bool deviceHashLengths(HostIndex& h, int minLen, int maxLen, int device, const BuildKnobs& knobs); }  // xm_index_device.hip
 using namespace xm;
+#include "xm_result_stage.h"
 
 namespace {
 
@@ -60,72 +63,6 @@ __global__ void __launch_bounds__(256) xm_wave_classify_kernel(const int64_t* to
   } else if (st == XM_ST_WAVE_SEARCH && listSearch) listSearch[atomicAdd(&ctl->nSearch, 1ull)] = q;
   else if (st == XM_ST_WAVE_FALLBACK || st == XM_ST_WAVE_GAPPED || st == XM_ST_WAVE_SEARCH) listFallback[atomicAdd(&ctl->nFallback, 1ull)] = q;
   else atomicMin(&ctl->errQuery, (unsigned long long)q);
-}
-
-// Exclusive prefix sums of the per-query stream lengths (query order), three small kernels: block totals, scan of the totals,
-// final offsets.  4096 queries per block.
-constexpr int XM_SCAN_PER_THREAD = 16;  // (the edges this gives - 16 per thread, 256 per gather block, 4096 per scan block - are walked by tests/test_gpu_result_stage.py)
-constexpr int XM_SCAN_PER_BLOCK = 256 * XM_SCAN_PER_THREAD;
-
-__device__ __forceinline__ void blockReduce2(long long& a, long long& b, long long* shA, long long* shB) {
-  shA[threadIdx.x] = a; shB[threadIdx.x] = b;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) { shA[threadIdx.x] += shA[threadIdx.x + d]; shB[threadIdx.x] += shB[threadIdx.x + d]; }
-    __syncthreads();
-  }
-  a = shA[0]; b = shB[0];
-}
-
-__global__ void __launch_bounds__(256) xm_scan_totals_kernel(long long nq, const int32_t* intLen, const int32_t* dblLen, long long* blockI, long long* blockD) {
-  __shared__ long long shA[256], shB[256];
-  long long base = (long long)blockIdx.x * XM_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_SCAN_PER_THREAD;
-  long long a = 0, b = 0;
-  for (int k = 0; k < XM_SCAN_PER_THREAD; k++) if (base + k < nq) { a += intLen[base + k]; b += dblLen[base + k]; }
-  blockReduce2(a, b, shA, shB);
-  if (threadIdx.x == 0) { blockI[blockIdx.x] = a; blockD[blockIdx.x] = b; }
-}
-
-__global__ void xm_scan_blocks_kernel(long long nBlocks, long long nq, long long* blockI, long long* blockD, int64_t* finalIntOff, int64_t* finalDblOff) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long a = 0, b = 0;
-  for (long long i = 0; i < nBlocks; i++) { long long x = blockI[i], y = blockD[i]; blockI[i] = a; blockD[i] = b; a += x; b += y; }
-  finalIntOff[nq] = a; finalDblOff[nq] = b;
-}
-
-__global__ void __launch_bounds__(256) xm_scan_final_kernel(long long nq, const int32_t* intLen, const int32_t* dblLen, const long long* blockI, const long long* blockD,
-                                                            int64_t* finalIntOff, int64_t* finalDblOff) {
-  __shared__ long long shA[256], shB[256];
-  long long base = (long long)blockIdx.x * XM_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_SCAN_PER_THREAD;
-  long long a = 0, b = 0;
-  for (int k = 0; k < XM_SCAN_PER_THREAD; k++) if (base + k < nq) { a += intLen[base + k]; b += dblLen[base + k]; }
-  shA[threadIdx.x] = a; shB[threadIdx.x] = b;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the 256 thread totals
-    long long x = 0, y = 0;
-    if ((int)threadIdx.x >= d) { x = shA[threadIdx.x - d]; y = shB[threadIdx.x - d]; }
-    __syncthreads();
-    shA[threadIdx.x] += x; shB[threadIdx.x] += y;
-    __syncthreads();
-  }
-  long long offA = blockI[blockIdx.x] + shA[threadIdx.x] - a, offB = blockD[blockIdx.x] + shB[threadIdx.x] - b;
-  for (int k = 0; k < XM_SCAN_PER_THREAD; k++) if (base + k < nq) {
-    finalIntOff[base + k] = offA; finalDblOff[base + k] = offB;
-    offA += intLen[base + k]; offB += dblLen[base + k];
-  }
-}
-
-// canonical streams: every query's slice copied from where its pass left it to its place in query order
-__global__ void __launch_bounds__(256) xm_gather_kernel(long long nq, const int64_t* srcIntOff, const int64_t* srcDblOff, const int32_t* intLen, const int32_t* dblLen,
-                                                        const int64_t* finalIntOff, const int64_t* finalDblOff, const int32_t* srcInts, const double* srcDbls,
-                                                        int32_t* dstInts, double* dstDbls) {
-  long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  const int32_t* si = srcInts + srcIntOff[q]; int32_t* di = dstInts + finalIntOff[q];
-  const double* sd = srcDbls + srcDblOff[q]; double* dd = dstDbls + finalDblOff[q];
-  int ni = intLen[q], nd = dblLen[q];
-  for (int k = 0; k < ni; k++) di[k] = si[k];
-  for (int k = 0; k < nd; k++) dd[k] = sd[k];
 }
 
 // Bucket lines of one table from its CSR form (IndexView::lines32 / lines64): one lane per bucket.
@@ -240,9 +177,7 @@ struct DeviceTables {
         view.lines32 = dLines32.p; view.lines64 = dLines64.p;
       }
     }
-    view.numContigs = host.numContigs(); view.minInterestingSize = host.minInterestingSize; view.maxHashedLength = host.maxHashedLength;
-    view.enableGapmers = host.enableGapmers; view.posIs64 = posIs64 ? 1 : 0; view.dupWindow = host.dupWindow; view.dupGranularity = host.dupGranularity();
-    view.totalForwardAndReverseSize = host.totalForwardSize * 2;
+    fillHostFields(view, host, posIs64);
     view.contigStart = dContigStart.p; view.contigLen = dContigLen.p; view.seqCumStart = dSeqCumStart.p; view.refCodes = dRefCodes.p;
     view.tables = dTables.p; view.bucketOff = dBucketOff.p; view.positions32 = dPositions32.p; view.positions64 = dPositions64.p;
     view.dupKeyStart = dDupKeyStart.p; view.dupKeys = dDupKeys.p;
@@ -303,6 +238,119 @@ struct DeviceBatch {
     nq = n;
   }
   BatchView view() const { return BatchView{nq, mateCount.p, mateOffset.p, mateLength.p, codes.p, expected.p, deviation.p}; }
+};
+
+// What the lane-per-read passes of a call work with besides the batch and the result stage: the work lists the lanes file unfinished reads into and the
+// counts of those lists (PassLists, PassCtl: xm_kernel_common.h), the device counters, and the scratch - the lanes' arenas behind the pool of saved
+// regions (HandOver), a wave's search nodes, the pool of search buffers (SearchPool).  Kept across calls; which list a pass reads is xm_pass_plan.h's.
+struct PassBuffers {
+  DevBuf<int64_t> dListHeavy, dListHeavyLate, dListScale[2], dListOut[2], dListConf[2];
+  DevBuf<PassCtl> dCtl;
+  DevBuf<DevCounters> dCounters;
+  DevBuf<uint8_t> dArenas;      // [region pool | lane arenas] (LaunchPlan)
+  DevBuf<int32_t> dRegionOf;
+  DevBuf<PNode> dWaveNodes;     // per wave: node payloads of its LDS-mode search
+  DevBuf<uint8_t> dSearchPool;  // one buffer per wave for the arrays of HBM-mode searches (SearchPool, xm_extend.h)
+
+  // sized for a call of nq queries; counters and counts cleared, no query in error
+  void prepare(int64_t nq, hipStream_t s) {
+    dListConf[0].ensure((size_t)nq); dListConf[1].ensure((size_t)nq);
+    dCounters.ensure(1); dCtl.ensure(1);
+    dListHeavy.ensure((size_t)nq); dListHeavyLate.ensure((size_t)nq);
+    HIP_CHECK(hipMemsetAsync(dCounters.p, 0, sizeof(DevCounters), s));
+    PassCtl ctl0;
+    memset(&ctl0, 0, sizeof(ctl0));
+    ctl0.errQuery = ~0ull;
+    HIP_CHECK(hipMemcpyAsync(dCtl.p, &ctl0, sizeof(ctl0), hipMemcpyHostToDevice, s));
+  }
+  void forgetRegions(int64_t nq, hipStream_t s) {  // (calls with the hand-over: no read has a saved region)
+    dRegionOf.ensure((size_t)nq);
+    HIP_CHECK(hipMemsetAsync(dRegionOf.p, 0xFF, sizeof(int32_t) * (size_t)nq, s));
+  }
+  // the lists a pass in state st files into: the lanes file the reads they could not finish into the work lists of the passes to come as they publish them
+  // (no kernel behind the pass)
+  PassLists lists(const PassState& st, int64_t nq, int heavyHint) {
+    dListScale[st.ts].ensure((size_t)nq); dListOut[st.to].ensure((size_t)nq);
+    return PassLists{dListHeavy.p, dListHeavyLate.p, dListScale[st.ts].p, dListOut[st.to].p, dListConf[st.tc].p, heavyHint, st.ts, st.to, st.tc, dCtl.p};
+  }
+  // light pass -> gapped pass hand-over (HandOver, SavedRead): the reads the light pass stops in front of the gapped chain keep their seeding
+  // state in HBM and the gapped pass continues from it
+  HandOver handOver(const BatchPolicy& pol, const PassState& st, const LaunchPlan& pl, unsigned long long* regionCursor) const {
+    return HandOver{st.hoMode, pol.seedScale, dArenas.p, (unsigned long long)pol.regionBytes, pl.nRegions, dRegionOf.p, regionCursor};
+  }
+  SearchPool searchPool(const PassState& st, const LaunchPlan& pl) {
+    SearchPool pool{nullptr, 0, 0, 0};
+    if (pl.poolBuffers > 0) {
+      pool.bufBytes = searchPoolBytes(makeCaps(st.scale));
+      pool.n = (int32_t)pl.poolBuffers;
+      dSearchPool.ensure((size_t)pool.n * pool.bufBytes);
+      pool.base = dSearchPool.p;
+    }
+    return pool;
+  }
+  // The list nextPass chose for the next launch (np.kind is not Done; ctl: the counts the last launch left).  The count of the half that launch files into
+  // is cleared on s; the gapped pass gets the late list appended to the heavy one, and both their counts cleared (a gapped pass never adds to these lists).
+  const int64_t* take(const NextPass& np, const PassCtl& ctl, hipStream_t s) {
+    unsigned long long* count = nullptr;
+    const int64_t* list = nullptr;
+    switch (np.kind) {
+      case PassKind::Done: break;
+      case PassKind::OutRerun: list = dListOut[np.list].p; count = &dCtl.p->nOut[np.clear]; break;
+      case PassKind::ConfRerun: list = dListConf[np.list].p; count = &dCtl.p->nConf[np.clear]; break;
+      case PassKind::ScaleRerun: list = dListScale[np.list].p; count = &dCtl.p->nScale[np.clear]; break;
+      case PassKind::Gapped:
+        if (ctl.nHeavyLate > 0) HIP_CHECK(hipMemcpyAsync(dListHeavy.p + ctl.nHeavy, dListHeavyLate.p, sizeof(int64_t) * (size_t)ctl.nHeavyLate, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemsetAsync(&dCtl.p->nHeavy, 0, 2 * sizeof(unsigned long long), s));  // nHeavy, nHeavyLate
+        return dListHeavy.p;
+    }
+    if (count) HIP_CHECK(hipMemsetAsync(count, 0, sizeof(unsigned long long), s));
+    return list;
+  }
+};
+
+// The confidence table of a context (IndexView::conf): the host's table (xm_conf_table.h), its copy in HBM, the list the kernels leave the keys in that
+// the table did not hold.
+struct DeviceConfTable {
+  ConfTable host;
+  static constexpr size_t kMissCap = 1 << 16;
+  DevBuf<ConfEntry> dConf;
+  DevBuf<uint8_t> dConfMiss;   // ConfMiss: header and kMissCap keys
+
+  // the copy in HBM brought up to the host's
+  void upload(hipStream_t s) {
+    if (!host.dirty()) return;
+    HIP_CHECK(hipStreamSynchronize(s));   // (no kernel of this context reads the old copy any more)
+    dConf.ensure(host.size());
+    HIP_CHECK(hipMemcpy(dConf.p, host.data(), host.size() * sizeof(ConfEntry), hipMemcpyHostToDevice));
+    host.markUploaded();
+  }
+  // the table of one align call (ConfTable::prepare) in HBM, and an empty miss list (its header is written once: absorbMisses leaves it empty)
+  void prepare(const Params& params, const std::vector<int32_t>& lens, double granularity, int64_t totalSize, long long seedBudget, hipStream_t s) {
+    host.prepare(params, lens, granularity, totalSize, seedBudget);
+    upload(s);
+    if (dConfMiss.p) return;
+    dConfMiss.ensure(sizeof(ConfMiss) + kMissCap * sizeof(ConfMissKey));
+    ConfMiss hdr;
+    memset(&hdr, 0, sizeof(hdr));
+    hdr.cap = kMissCap;
+    HIP_CHECK(hipMemcpyAsync(dConfMiss.p, &hdr, offsetof(ConfMiss, keys), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  // after a pass with XM_ST_NEED_CONF reads: the keys they left in the miss list, evaluated and added
+  void absorbMisses(hipStream_t s) {
+    ConfMiss hdr;
+    HIP_CHECK(hipMemcpyAsync(&hdr, dConfMiss.p, offsetof(ConfMiss, keys), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const size_t n = (size_t)std::min<unsigned long long>(hdr.n, hdr.cap);
+    std::vector<ConfMissKey> keys(n);
+    if (n) HIP_CHECK(hipMemcpy(keys.data(), dConfMiss.p + offsetof(ConfMiss, keys), n * sizeof(ConfMissKey), hipMemcpyDeviceToHost));
+    const unsigned long long zero = 0;
+    HIP_CHECK(hipMemcpy(dConfMiss.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
+    for (const ConfMissKey& k : keys) { double pen; memcpy(&pen, &k.penaltyBits, 8); host.insert(pen, k.queryLength); }
+    upload(s);
+  }
+  // the three fields of a call's IndexView (again after absorbMisses: the table may have grown and moved)
+  void fillView(IndexView& v) const { v.conf = dConf.p; v.confMask = host.mask(); v.confMiss = (ConfMiss*)dConfMiss.p; }
 };
 
 // what only the wave-per-read passes use (runWaveForm)
@@ -393,22 +441,11 @@ struct xm_index {
   const HostIndex& host() const { return hs->host; }
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // per-call scratch kept across calls
-  DevBuf<uint8_t> dArenas;
-  DevBuf<int32_t> dStatus, dIntLen, dDblLen, dOutInts;
-  DevBuf<int64_t> dIntOff, dDblOff;
-  DevBuf<double> dOutDbls;
-  DevBuf<unsigned long long> dCursors;  // [0],[1] result cursors, [2] next item
-  DevBuf<int64_t> dListHeavy, dListHeavyLate, dListScale[2], dListOut[2], dFinalIntOff, dFinalDblOff;
-  DevBuf<int32_t> dRegionOf;
-  DevBuf<PNode> dWaveNodes;  // per wave: node payloads of its LDS-mode search
-  DevBuf<uint8_t> dSearchPool;  // one buffer per wave for the arrays of HBM-mode searches (SearchPool, xm_extend.h)
+  // what a call works with, kept across calls: every device buffer of a context belongs to one of these, to memoCall or to a batch below
+  ResultStage results;
+  PassBuffers passes;
+  DeviceConfTable conf;
   WaveFormBuffers wave;
-  DevBuf<PassCtl> dCtl;
-  DevBuf<long long> dBlockI, dBlockD;
-  DevBuf<int32_t> dFinalInts;
-  DevBuf<double> dFinalDbls;
-  DevBuf<DevCounters> dCounters;
   CollapseBuffers collapseBufs;
   std::shared_ptr<Memory> memo;      // xm_context_attach_memory / xm_context_set_memo: where this context looks its queries up and remembers what it aligns (null: nowhere)
   MemoCallBuffers memoCall;
@@ -419,16 +456,9 @@ struct xm_index {
     memo.reset();
     memoCall = MemoCallBuffers();
   }
-  // confidence table (IndexView::conf): the host's table, its copy in HBM, the miss list the kernels write, the reads that wait for a value
-  ConfTable conf;
-  static constexpr size_t kConfMissCap = 1 << 16;
-  DevBuf<ConfEntry> dConf;
-  DevBuf<uint8_t> dConfMiss;
-  DevBuf<int64_t> dListConf[2];
   // the batch the align calls work on (xm_batch_upload, xm_batch_commit), and the one xm_batch_stage copies in on its own stream meanwhile
   DeviceBatch resident, staged;
-  int64_t residentGen = 0, lastAlignedGen = -1;  // which resident batch the streams of the last align call belong to
-  int64_t lastAlignedNq = -1;  // queries whose result streams (dFinalInts / dFinalDbls / dFinalIntOff) are still in HBM from the last align call (xm_pileup_add_last)
+  int64_t residentGen = 0;     // which resident batch: a call's streams belong to one (ResultStage::lastStreams)
   std::mutex stageMu;
   hipEvent_t cev0 = nullptr, cev1 = nullptr;  // this context's events on the GPU's staging stream (DeviceTables::copyStream)
 
@@ -486,14 +516,11 @@ struct AlignCall {
   unsigned long long oldHits = 0, oldHitBytes = 0;  // the ones served from the old generation only, the bytes of their records (memoPromotes)
   long long nMisses = 0;             // idx->memoCall.dMissList: the representatives this call aligns
   double memoWaitUs = 0;             // host time this call waited for the memory's mutex (both critical sections)
-  unsigned long long intCap = 0, dblCap = 0;
-  unsigned long long cursors[4] = {0, 0, 0, 0};
   bool boundFilterUsed = false;
 #ifdef XM_READ_TIMES
   DevBuf<unsigned long long> dReadTimes;
   const char* readTimesFile = nullptr;
 #endif
-  OutView outView() const { return OutView{idx->dOutInts.p, idx->dOutDbls.p, intCap, dblCap, idx->dCursors.p, idx->dStatus.p, idx->dIntOff.p, idx->dDblOff.p, idx->dIntLen.p, idx->dDblLen.p}; }
 };
 
 // One timed step on the call's stream: record, launch(es), hipGetLastError, record, `after` (enqueues the copies of the control words the host reads
@@ -514,55 +541,16 @@ static float timedLaunch(AlignCall& c, int nKernels, int slot, Launch&& launch, 
   return ms;
 }
 
-// the confidence table's copy in HBM brought up to the host's
-static void uploadConfTable(xm_index* idx, hipStream_t s) {
-  if (!idx->conf.dirty()) return;
-  HIP_CHECK(hipStreamSynchronize(s));   // (no kernel of this context reads the old copy any more)
-  idx->dConf.ensure(idx->conf.size());
-  HIP_CHECK(hipMemcpy(idx->dConf.p, idx->conf.data(), idx->conf.size() * sizeof(ConfEntry), hipMemcpyHostToDevice));
-  idx->conf.markUploaded();
-}
-// after a pass with XM_ST_NEED_CONF reads: the keys they left in the miss list, evaluated and added
-static void absorbConfMisses(xm_index* idx, hipStream_t s) {
-  ConfMiss hdr;
-  HIP_CHECK(hipMemcpyAsync(&hdr, idx->dConfMiss.p, offsetof(ConfMiss, keys), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  const size_t n = (size_t)std::min<unsigned long long>(hdr.n, hdr.cap);
-  std::vector<ConfMissKey> keys(n);
-  if (n) HIP_CHECK(hipMemcpy(keys.data(), idx->dConfMiss.p + offsetof(ConfMiss, keys), n * sizeof(ConfMissKey), hipMemcpyDeviceToHost));
-  const unsigned long long zero = 0;
-  HIP_CHECK(hipMemcpy(idx->dConfMiss.p, &zero, sizeof(zero), hipMemcpyHostToDevice));
-  for (const ConfMissKey& k : keys) { double pen; memcpy(&pen, &k.penaltyBits, 8); idx->conf.insert(pen, k.queryLength); }
-  uploadConfTable(idx, s);
-}
-
 // buffers that follow the batch's size, the confidence table of these parameters, cleared counters and control words
 static void prepareCall(AlignCall& c) {
   xm_index* idx = c.idx;
   const int64_t nq = c.nq;
   hipStream_t s = c.s;
   // (XM_CONF_SEED = 0: nothing seeded, every key through the miss path - the tests run that)
-  idx->conf.prepare(c.params, idx->resident.lens, idx->host().dupGranularity(), idx->host().totalForwardSize * 2, envKnob("XM_CONF_SEED", 1 << 18, 0, 1 << 26));
-  uploadConfTable(idx, s);
-  if (!idx->dConfMiss.p) {
-    idx->dConfMiss.ensure(sizeof(ConfMiss) + xm_index::kConfMissCap * sizeof(ConfMissKey));
-    ConfMiss hdr;
-    memset(&hdr, 0, sizeof(hdr));
-    hdr.cap = xm_index::kConfMissCap;
-    HIP_CHECK(hipMemcpyAsync(idx->dConfMiss.p, &hdr, offsetof(ConfMiss, keys), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  c.view.conf = idx->dConf.p; c.view.confMask = idx->conf.mask(); c.view.confMiss = (ConfMiss*)idx->dConfMiss.p;
-  idx->dListConf[0].ensure((size_t)nq); idx->dListConf[1].ensure((size_t)nq);
-  idx->dStatus.ensure((size_t)nq); idx->dIntOff.ensure((size_t)nq); idx->dDblOff.ensure((size_t)nq); idx->dIntLen.ensure((size_t)nq); idx->dDblLen.ensure((size_t)nq);
-  idx->dCursors.ensure(4); idx->dCounters.ensure(1); idx->dCtl.ensure(1);
-  idx->dListHeavy.ensure((size_t)nq); idx->dListHeavyLate.ensure((size_t)nq);
-  HIP_CHECK(hipMemsetAsync(idx->dCounters.p, 0, sizeof(DevCounters), s));
-  HIP_CHECK(hipMemsetAsync(idx->dCursors.p, 0, sizeof(unsigned long long) * 4, s));
-  PassCtl ctl0;
-  memset(&ctl0, 0, sizeof(ctl0));
-  ctl0.errQuery = ~0ull;
-  HIP_CHECK(hipMemcpyAsync(idx->dCtl.p, &ctl0, sizeof(ctl0), hipMemcpyHostToDevice, s));
+  idx->conf.prepare(c.params, idx->resident.lens, idx->host().dupGranularity(), idx->host().totalForwardSize * 2, envKnob("XM_CONF_SEED", 1 << 18, 0, 1 << 26), s);
+  idx->conf.fillView(c.view);
+  idx->results.prepare(nq, s);
+  idx->passes.prepare(nq, s);
 #ifdef XM_READ_TIMES
   c.readTimesFile = getenv("XM_READ_TIMES_FILE");
   if (c.readTimesFile && *c.readTimesFile) {
@@ -607,8 +595,8 @@ static void collapseBuildList(AlignCall& c) {
 static void collapseFanOut(AlignCall& c) {
   xm_index* idx = c.idx;
   timedLaunch(c, 1, -1, [&] {
-    hipLaunchKernelGGL(xm_collapse_fanout_kernel, dim3((unsigned)((c.nq + 255) / 256)), dim3(256), 0, c.s, (long long)c.nq, (const int64_t*)idx->collapseBufs.dRepOf.p, idx->dIntOff.p, idx->dDblOff.p,
-                       idx->dIntLen.p, idx->dDblLen.p);
+    hipLaunchKernelGGL(xm_collapse_fanout_kernel, dim3((unsigned)((c.nq + 255) / 256)), dim3(256), 0, c.s, (long long)c.nq, (const int64_t*)idx->collapseBufs.dRepOf.p, idx->results.dIntOff.p, idx->results.dDblOff.p,
+                       idx->results.dIntLen.p, idx->results.dDblLen.p);
   }, [] {});
 }
 
@@ -660,10 +648,10 @@ static void memoReplay(AlignCall& c) {
   const long long nReps = c.remembered + c.nMisses;
   unsigned long long totals[4] = {0, 0, 0, 0};
   timedLaunch(c, 1, -1, [&] {
-    hipLaunchKernelGGL(xm_memo_replay_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, c.s, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), (const int64_t*)mc.dHit.p, c.outView(), mc.dTotals.p);
+    hipLaunchKernelGGL(xm_memo_replay_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, c.s, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), (const int64_t*)mc.dHit.p, idx->results.outView(), mc.dTotals.p);
   }, [&] {
     HIP_CHECK(hipMemcpyAsync(totals, mc.dTotals.p, sizeof(totals), hipMemcpyDeviceToHost, c.s));
-    HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, c.s));
+    idx->results.readCursors(c.s);
   });
   if (totals[3] != 0) throw std::runtime_error("internal error: " + std::to_string(totals[3]) + " remembered results found no room in the result arenas");
 }
@@ -705,7 +693,7 @@ static void memoInsert(AlignCall& c) {
     unsigned long long measured[2] = {0, 0};
     HIP_CHECK(hipMemsetAsync(mc.dTotals.p + 4, 0, sizeof(unsigned long long) * 2, c.s));
     timedLaunch(c, 1, -1, [&] {
-      hipLaunchKernelGGL(xm_memo_measure_kernel, dim3((unsigned)((c.nMisses + 255) / 256)), dim3(256), 0, c.s, c.bv, (const int64_t*)mc.dMissList.p, c.nMisses, c.outView(), mc.dTotals.p);
+      hipLaunchKernelGGL(xm_memo_measure_kernel, dim3((unsigned)((c.nMisses + 255) / 256)), dim3(256), 0, c.s, c.bv, (const int64_t*)mc.dMissList.p, c.nMisses, idx->results.outView(), mc.dTotals.p);
     }, [&] { HIP_CHECK(hipMemcpyAsync(measured, mc.dTotals.p + 4, sizeof(measured), hipMemcpyDeviceToHost, c.s)); });
     queued = false;
     if (memoMustTurn(m.plan, m.gens, measured[0], measured[1])) { m.clearGeneration(memoTurn(m.gens), c.s); queued = true; }
@@ -720,7 +708,7 @@ static void memoInsert(AlignCall& c) {
   m.filledUnder = c.cParams;
   m.filled = true;
   timedLaunch(c, 1, -1, [&] {
-    hipLaunchKernelGGL(xm_memo_insert_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c.s, c.bv, (const int64_t*)mc.dMissList.p, n, m.view().generation(young), (const unsigned long long*)mc.dFp.p, c.outView());
+    hipLaunchKernelGGL(xm_memo_insert_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c.s, c.bv, (const int64_t*)mc.dMissList.p, n, m.view().generation(young), (const unsigned long long*)mc.dFp.p, idx->results.outView());
   }, [&] { HIP_CHECK(hipMemcpyAsync(state, m.dState.p + (size_t)young * 4, sizeof(state), hipMemcpyDeviceToHost, c.s)); });
   m.gens.claimed[young] = state[0]; m.gens.cursor[young] = state[1]; m.gens.records[young] = state[2];
 }
@@ -740,7 +728,7 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
   idx->wave.dWaveSlotOf.ensure((size_t)nq);
   WaveCtl wctl{0, 0, 0, ~0ull};
   HIP_CHECK(hipMemcpyAsync(idx->wave.dWaveCtl.p, &wctl, sizeof(wctl), hipMemcpyHostToDevice, s));
-  const OutView ov = c.outView();
+  const OutView ov = idx->results.outView();
   const int lastTier = (int)envKnob("XM_WAVE_TIERS", 3, 1, 3) - 1;  // (experiment knob: 1 = light tier only, 2 = light + chain tier)
   int sWaves = 4, sLds = 1, sPerSimd = 4, memoBytes = 1, nodesPerWave = 1;
   xmSearchGeometry(&sWaves, &sLds, &sPerSimd, &memoBytes, &nodesPerWave);
@@ -757,31 +745,27 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
     long long blocks = std::min<long long>((long long)c.numCUs * blocksPerCU, (n + (long long)wavesPerBlock * wl.itemsPerFetch - 1) / ((long long)wavesPerBlock * wl.itemsPerFetch));
     if (blocks < 1) blocks = 1;
     wl.grid = (int)blocks; wl.block = wavesPerBlock * 64;
-    wl.ix = c.view; wl.params = c.params; wl.batch = c.bv; wl.todo = list; wl.nTodo = n; wl.out = ov; wl.nextItem = idx->dCursors.p + 2; wl.counters = idx->dCounters.p;
+    wl.ix = c.view; wl.params = c.params; wl.batch = c.bv; wl.todo = list; wl.nTodo = n; wl.out = ov; wl.nextItem = idx->results.nextItem(); wl.counters = idx->passes.dCounters.p;
     wl.memoBase = (WMemo*)idx->wave.dWaveMemo.p; wl.slotOf = idx->wave.dWaveSlotOf.p;
     wl.waveNodes = nullptr;
     if (tier >= 1 && envInt("XM_WAVE_INLINE_SEARCH", 1) != 0) {  // (0: every search through the memo and the search kernel)
       idx->wave.dWaveNodes2.ensure(((size_t)blocks * wavesPerBlock * (size_t)xmWaveInlineNodeBytes() + sizeof(PNode) - 1) / sizeof(PNode));
       wl.waveNodes = idx->wave.dWaveNodes2.p;
     }
-    HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
+    HIP_CHECK(hipMemsetAsync(idx->results.nextItem(), 0, sizeof(unsigned long long), s));
     HIP_CHECK(hipMemsetAsync(idx->wave.dWaveCtl.p, 0, 2 * sizeof(unsigned long long), s));  // nNext, nSearch
     const float ms = timedLaunch(c, 1, tier == 0 ? 12 : 13, [&] {  // kernel microseconds: light tier / chain tiers
       const int rc = xmWaveLaunch(wl, (void*)s);
       if (rc != 0) throw std::runtime_error(std::string("wave kernel launch: ") + hipGetErrorString((hipError_t)rc));
     }, [&] {  // (the classification is not part of the tier's time)
-      hipLaunchKernelGGL(xm_wave_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, list, n, idx->dStatus.p, listNext, slotOfOut, listSearch, idx->wave.dListFallback.p, idx->wave.dWaveCtl.p);
+      hipLaunchKernelGGL(xm_wave_classify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, list, n, idx->results.dStatus.p, listNext, slotOfOut, listSearch, idx->wave.dListFallback.p, idx->wave.dWaveCtl.p);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipMemcpyAsync(&wctl, idx->wave.dWaveCtl.p, sizeof(wctl), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, s));
+      idx->results.readCursors(s);
     });
     if (tracePasses) fprintf(stderr, "[xm] wave tier %d config %d: reads %lld, %d x %d threads: %.3f ms -> next tier %llu, searches %llu, lane-per-read %llu (so far)\n", tier, wl.config, n, wl.grid,
                              wl.block, ms, listNext ? wctl.nNext : 0ull, wctl.nSearch, wctl.nFallback);
-    if (wctl.errQuery != ~0ull) {
-      int32_t code = 0;
-      HIP_CHECK(hipMemcpy(&code, idx->dStatus.p + wctl.errQuery, sizeof(code), hipMemcpyDeviceToHost));
-      throw std::runtime_error("Failed to align query " + std::to_string(wctl.errQuery) + ": the reference implementation would have thrown here (status " + std::to_string(code & 0xFF) + ")");
-    }
+    if (wctl.errQuery != ~0ull) throwFailedQuery(idx->results.dStatus, wctl.errQuery);
     fallbackSoFar = wctl.nFallback;
   };
   auto launchSearches = [&](const int64_t* list, long long n) {
@@ -789,10 +773,10 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
     long long blocks = std::min<long long>((long long)c.numCUs * std::min<long long>((160 * 1024) / sLds, (long long)(sPerSimd * 4) / sWaves), (n + sWaves - 1) / sWaves);
     if (blocks < 1) blocks = 1;
     sl.grid = (int)blocks; sl.block = sWaves * 64;
-    sl.ix = c.view; sl.params = c.params; sl.batch = c.bv; sl.list = list; sl.n = n; sl.memoBase = (WMemo*)idx->wave.dWaveMemo.p; sl.slotOf = idx->wave.dWaveSlotOf.p; sl.nextItem = idx->dCursors.p + 2;
+    sl.ix = c.view; sl.params = c.params; sl.batch = c.bv; sl.list = list; sl.n = n; sl.memoBase = (WMemo*)idx->wave.dWaveMemo.p; sl.slotOf = idx->wave.dWaveSlotOf.p; sl.nextItem = idx->results.nextItem();
     idx->wave.dWaveArenas.ensure((size_t)blocks * sWaves * (size_t)nodesPerWave);  // (node payloads: bytes per wave)
-    sl.waveNodes = idx->wave.dWaveArenas.p; sl.counters = idx->dCounters.p;
-    HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
+    sl.waveNodes = idx->wave.dWaveArenas.p; sl.counters = idx->passes.dCounters.p;
+    HIP_CHECK(hipMemsetAsync(idx->results.nextItem(), 0, sizeof(unsigned long long), s));
     const float ms = timedLaunch(c, 1, 14, [&] {  // search kernel microseconds
       const int rc = xmSearchLaunch(sl, (void*)s);
       if (rc != 0) throw std::runtime_error(std::string("search kernel launch: ") + hipGetErrorString((hipError_t)rc));
@@ -826,7 +810,7 @@ static void runWaveForm(AlignCall& c, const bool tracePasses) {
   }
   c.todo = idx->wave.dListFallback.p;
   c.nTodo = (long long)fallbackSoFar;
-  HIP_CHECK(hipMemsetAsync(idx->dCursors.p + 2, 0, sizeof(unsigned long long), s));
+  HIP_CHECK(hipMemsetAsync(idx->results.nextItem(), 0, sizeof(unsigned long long), s));
 }
 
 // scratch a context may hold now: up to its limit (halved `shift` times), never more than 3/4 of what is free (+ what this context already holds)
@@ -834,7 +818,7 @@ static unsigned long long scratchBudget(xm_index* idx, const BatchPolicy& pol, i
   unsigned long long want = pol.scratchWanted >> shift;
   size_t freeB = 0, totalB = 0;
   if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-    const unsigned long long avail = (unsigned long long)(freeB + idx->dArenas.n) / 4 * 3;
+    const unsigned long long avail = (unsigned long long)(freeB + idx->passes.dArenas.n) / 4 * 3;
     if (want > avail) want = avail;
   }
   return want < (64ull << 20) ? (64ull << 20) : want;
@@ -843,45 +827,34 @@ static unsigned long long scratchBudget(xm_index* idx, const BatchPolicy& pol, i
 // one launch of xm_align_kernel as planned, over c.todo; the control words and cursors it left are on the host when it returns
 static float launchAlignPass(AlignCall& c, const BatchPolicy& pol, const PassState& st, const LaunchPlan& pl, PassCtl& ctl) {
   xm_index* idx = c.idx;
+  PassBuffers& pb = idx->passes;
+  ResultStage& rs = idx->results;
   hipStream_t s = c.s;
-  uint8_t* laneArenas = idx->dArenas.p + pl.regionsTotal;
-  // light pass -> gapped pass hand-over (HandOver, SavedRead): the reads the light pass stops in front of the gapped chain keep their seeding
-  // state in HBM and the gapped pass continues from it
-  HandOver ho{st.hoMode, pol.seedScale, idx->dArenas.p, (unsigned long long)pol.regionBytes, pl.nRegions, idx->dRegionOf.p, idx->dCursors.p + 3};
-  idx->dWaveNodes.ensure((size_t)pl.grid * (pl.block / 64) * XM_PAL_NODES);
-  SearchPool pool{nullptr, 0, 0, 0};
-  if (pl.poolBuffers > 0) {
-    pool.bufBytes = searchPoolBytes(makeCaps(st.scale));
-    pool.n = (int32_t)pl.poolBuffers;
-    idx->dSearchPool.ensure((size_t)pool.n * pool.bufBytes);
-    pool.base = idx->dSearchPool.p;
-  }
-  idx->dListScale[st.ts].ensure((size_t)c.nq); idx->dListOut[st.to].ensure((size_t)c.nq);
-  HIP_CHECK(hipMemcpyAsync(idx->dCursors.p + 2, &pl.firstItem, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+  pb.dWaveNodes.ensure((size_t)pl.grid * (pl.block / 64) * XM_PAL_NODES);
   AlignLaunch a{};
   a.grid = pl.grid; a.block = pl.block;
   a.ix = c.view; a.params = c.params; a.batch = c.bv;
   a.todo = c.todo; a.nTodo = c.nTodo;
   a.scale = st.scale; a.heavyAllowed = st.heavy ? 2 : (int)pol.k.lightLevel; a.lanesPerWave = pl.lpw;
-  a.arenas = laneArenas; a.arenaBytes = (unsigned long long)pl.arenaBytes;
-  a.out = c.outView();
-  a.nextItem = idx->dCursors.p + 2; a.counters = idx->dCounters.p;
+  a.arenas = pb.dArenas.p + pl.regionsTotal; a.arenaBytes = (unsigned long long)pl.arenaBytes;
+  a.out = rs.outView();
+  a.nextItem = rs.nextItem(); a.counters = pb.dCounters.p;
   a.taperUnit = pl.taperUnit; a.firstStride = pl.firstStride;
-  a.waveNodes = idx->dWaveNodes.p;
-  a.ho = ho; a.pairLanes = pl.pairLanes; a.searchPool = pool;
-  // the lanes file the reads they could not finish into the work lists of the passes to come as they publish them (PassLists; no kernel behind the pass)
-  a.lists = PassLists{idx->dListHeavy.p, idx->dListHeavyLate.p, idx->dListScale[st.ts].p, idx->dListOut[st.to].p, idx->dListConf[st.tc].p, (int)pol.k.heavyHint, st.ts, st.to, st.tc, idx->dCtl.p};
+  a.waveNodes = pb.dWaveNodes.p;
+  a.ho = pb.handOver(pol, st, pl, rs.regionCursor()); a.pairLanes = pl.pairLanes; a.searchPool = pb.searchPool(st, pl);
+  a.lists = pb.lists(st, c.nq, (int)pol.k.heavyHint);
   a.boundFilter = pl.boundFilterArg;
+  HIP_CHECK(hipMemcpyAsync(rs.nextItem(), &pl.firstItem, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
   return timedLaunch(c, 1, !st.heavy ? 12 : 15, [&] {  // kernel microseconds: light pass / gapped pass and reruns
     const int rc = xmAlignLaunch(a, (void*)s);
     if (rc != 0) throw std::runtime_error(std::string("align kernel launch: ") + hipGetErrorString((hipError_t)rc));
   }, [&] {
-    HIP_CHECK(hipMemcpyAsync(&ctl, idx->dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(c.cursors, idx->dCursors.p, sizeof(c.cursors), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&ctl, pb.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    rs.readCursors(s);
   });
 }
 
-// the lane-per-read passes over c.todo: plan -> allocate -> launch -> what follows, until no list is left
+// the lane-per-read passes over c.todo: plan -> allocate -> launch -> what follows (nextPass) -> take its list, until no list is left
 static void runLanePasses(AlignCall& c, const BatchPolicy& pol) {
   xm_index* idx = c.idx;
   hipStream_t s = c.s;
@@ -892,14 +865,14 @@ static void runLanePasses(AlignCall& c, const BatchPolicy& pol) {
     {
       // contexts of one GPU size and allocate their scratch one after the other: they all look at the same free memory
       std::lock_guard<std::mutex> sizing(idx->dt->allocMu);
-      pl = planLaunch(pol, st, c.nTodo, c.nq, c.numCUs, scratchBudget(idx, pol, scratchShift), idx->dArenas.n);
-      if (pl.scratchBytes > 0 && !idx->dArenas.tryEnsure(pl.scratchBytes)) {  // (sized again with half the budget)
+      pl = planLaunch(pol, st, c.nTodo, c.nq, c.numCUs, scratchBudget(idx, pol, scratchShift), idx->passes.dArenas.n);
+      if (pl.scratchBytes > 0 && !idx->passes.dArenas.tryEnsure(pl.scratchBytes)) {  // (sized again with half the budget)
         if (++scratchShift > 8) throw std::runtime_error("no room in HBM for the scratch of even a few lanes (" + std::to_string(pl.scratchBytes >> 20) + " MiB asked)");
         continue;
       }
       if (st.hoMode == 1) {  // the pool's first regions are the lanes' own
         const unsigned long long firstFree = (unsigned long long)pl.lanes;
-        HIP_CHECK(hipMemcpyAsync(idx->dCursors.p + 3, &firstFree, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(idx->results.regionCursor(), &firstFree, sizeof(unsigned long long), hipMemcpyHostToDevice, s));
       }
     }
     st.nRegions = pl.nRegions; st.regionsTotal = pl.regionsTotal;
@@ -920,51 +893,20 @@ static void runLanePasses(AlignCall& c, const BatchPolicy& pol) {
       fprintf(stderr, "[xm] pass %d: PathAligner arrivals %llu with %llu reads (%.2f per arrival); arrivals of four reads or more: %llu with %llu reads\n", c.launches, a[0], a[1], a[0] ? (double)a[1] / (double)a[0] : 0.0, a[2], a[3]);
     }
 #endif
-    if (ctl.errQuery != ~0ull) {
-      int32_t code = 0;
-      HIP_CHECK(hipMemcpy(&code, idx->dStatus.p + ctl.errQuery, sizeof(code), hipMemcpyDeviceToHost));
-      code &= 0xFF;
-      std::string q = std::to_string(ctl.errQuery);
-      if (code == XM_ST_NEED_GROW) throw std::runtime_error("Failed to align query " + q + ": gapmer longer than the hashed lengths");
-      throw std::runtime_error("Failed to align query " + q + ": the reference implementation would have thrown here (status " + std::to_string(code) + ")");
-    }
+    if (ctl.errQuery != ~0ull) throwFailedQuery(idx->results.dStatus, ctl.errQuery);
     const NextPass np = nextPass(pol, st, ctl);
     c.nTodo = np.nTodo;
-    switch (np.kind) {
-      case PassKind::Done: break;
-      case PassKind::OutRerun: {  // room to spare in the result arenas
-        c.todo = idx->dListOut[np.list].p;
-        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nOut[np.clear], 0, sizeof(unsigned long long), s));
-        unsigned long long keepI = std::min(c.cursors[0], c.intCap), keepD = std::min(c.cursors[1], c.dblCap);
-        unsigned long long newI = std::max(c.intCap * 4 + 65536, c.cursors[0] * 2), newD = std::max(c.dblCap * 4 + 65536, c.cursors[1] * 2);
-        idx->dOutInts.growKeep((size_t)newI, (size_t)keepI, s); idx->dOutDbls.growKeep((size_t)newD, (size_t)keepD, s);
-        c.intCap = idx->dOutInts.n; c.dblCap = idx->dOutDbls.n;
-        c.rerun += c.nTodo;
-        break;
-      }
-      case PassKind::Gapped:
-        if (ctl.nHeavyLate > 0) HIP_CHECK(hipMemcpyAsync(idx->dListHeavy.p + ctl.nHeavy, idx->dListHeavyLate.p, sizeof(int64_t) * (size_t)ctl.nHeavyLate, hipMemcpyDeviceToDevice, s));
-        c.todo = idx->dListHeavy.p;
-        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nHeavy, 0, 2 * sizeof(unsigned long long), s));  // nHeavy, nHeavyLate (a gapped pass never adds to these lists)
-        if (pol.k.profGappedOnly) HIP_CHECK(hipMemsetAsync((char*)idx->dCounters.p + offsetof(DevCounters, t), 0, sizeof(((DevCounters*)nullptr)->t), s));
-        break;
-      case PassKind::ConfRerun:
-        absorbConfMisses(idx, s);
-        c.view.conf = idx->dConf.p; c.view.confMask = idx->conf.mask();
-        c.todo = idx->dListConf[np.list].p;
-        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nConf[np.clear], 0, sizeof(unsigned long long), s));
-        c.rerun += c.nTodo;
-        break;
-      case PassKind::ScaleRerun:
-        c.todo = idx->dListScale[np.list].p;
-        HIP_CHECK(hipMemsetAsync(&idx->dCtl.p->nScale[np.clear], 0, sizeof(unsigned long long), s));
-        c.rerun += c.nTodo;
-        break;
-    }
+    if (np.kind == PassKind::Done) break;
+    // what the next pass needs besides its list: room to spare in the result arenas; the values its reads waited for; (profile builds) the gapped pass's timers alone
+    if (np.kind == PassKind::OutRerun) idx->results.growAfterOverflow(s);
+    if (np.kind == PassKind::ConfRerun) { idx->conf.absorbMisses(s); idx->conf.fillView(c.view); }
+    if (np.kind == PassKind::Gapped && pol.k.profGappedOnly) HIP_CHECK(hipMemsetAsync((char*)idx->passes.dCounters.p + offsetof(DevCounters, t), 0, sizeof(((DevCounters*)nullptr)->t), s));
+    c.todo = idx->passes.take(np, ctl, s);
+    if (np.kind != PassKind::Gapped) c.rerun += c.nTodo;
   }
 }
 
-// ---- canonical streams in query order: offsets by prefix sum, slices gathered on the device, one copy per stream to the host; the counters
+// ---- canonical streams in query order (ResultStage::toHost) and the counters, timed between the context's events
 static void finishStreams(AlignCall& c) {
   xm_index* idx = c.idx;
   xm_result* res = c.res;
@@ -972,8 +914,6 @@ static void finishStreams(AlignCall& c) {
   hipStream_t s = c.s;
   float ms = 0;
   HIP_CHECK(hipEventRecord(idx->ev0, s));
-  const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
-  idx->dBlockI.ensure((size_t)nBlocks); idx->dBlockD.ensure((size_t)nBlocks);
 #ifdef XM_READ_TIMES
   if (c.dReadTimes.p) {
     std::vector<unsigned long long> t((size_t)nq);
@@ -983,34 +923,9 @@ static void finishStreams(AlignCall& c) {
     c.dReadTimes.release();
   }
 #endif
-  idx->dFinalIntOff.ensure((size_t)nq + 1); idx->dFinalDblOff.ensure((size_t)nq + 1);
-  size_t usedI = (size_t)std::min(c.cursors[0], c.intCap), usedD = (size_t)std::min(c.cursors[1], c.dblCap);  // upper bounds of the totals
-  if (c.copies == 0) { idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD); }
-  hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, idx->dIntLen.p, idx->dDblLen.p, idx->dBlockI.p, idx->dBlockD.p);
-  hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, idx->dBlockI.p, idx->dBlockD.p, idx->dFinalIntOff.p, idx->dFinalDblOff.p);
-  if (c.copies > 0) {  // (a copy's slice is in the result arena once and in the streams once per copy: the totals are the scan's)
-    int64_t totals[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(&totals[0], idx->dFinalIntOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(&totals[1], idx->dFinalDblOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    usedI = (size_t)totals[0]; usedD = (size_t)totals[1];
-    idx->dFinalInts.ensure(usedI); idx->dFinalDbls.ensure(usedD);
-  }
-  hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, idx->dIntLen.p, idx->dDblLen.p, idx->dBlockI.p, idx->dBlockD.p,
-                     idx->dFinalIntOff.p, idx->dFinalDblOff.p);
-  hipLaunchKernelGGL(xm_gather_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, idx->dIntOff.p, idx->dDblOff.p, idx->dIntLen.p, idx->dDblLen.p,
-                     idx->dFinalIntOff.p, idx->dFinalDblOff.p, idx->dOutInts.p, idx->dOutDbls.p, idx->dFinalInts.p, idx->dFinalDbls.p);
-  HIP_CHECK(hipGetLastError());
-  res->ints = (int32_t*)g_pinned->get(sizeof(int32_t) * (usedI ? usedI : 1), &c.box->bytesInts);
-  res->dbls = (double*)g_pinned->get(sizeof(double) * (usedD ? usedD : 1), &c.box->bytesDbls);
-  idx->lastAlignedNq = nq;
-  idx->lastAlignedGen = idx->residentGen;
-  HIP_CHECK(hipMemcpyAsync(res->int_off, idx->dFinalIntOff.p, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(res->dbl_off, idx->dFinalDblOff.p, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToHost, s));
-  if (usedI) HIP_CHECK(hipMemcpyAsync(res->ints, idx->dFinalInts.p, sizeof(int32_t) * usedI, hipMemcpyDeviceToHost, s));
-  if (usedD) HIP_CHECK(hipMemcpyAsync(res->dbls, idx->dFinalDbls.p, sizeof(double) * usedD, hipMemcpyDeviceToHost, s));
+  idx->results.toHost(nq, c.copies, idx->residentGen, res, c.box, s);
   DevCounters dc;
-  HIP_CHECK(hipMemcpyAsync(&dc, idx->dCounters.p, sizeof(dc), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(&dc, idx->passes.dCounters.p, sizeof(dc), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipEventRecord(idx->ev1, s));
   HIP_CHECK(hipStreamSynchronize(s));
   HIP_CHECK(hipEventElapsedTime(&ms, idx->ev0, idx->ev1));
@@ -1024,6 +939,56 @@ static void finishStreams(AlignCall& c) {
   for (int i = 0; i < 16; i++) res->prof[i] = (int64_t)dc.t[i];
   res->kernel_ms = c.kernelMs;
   res->kernel_launches = c.launches;
+}
+
+// ---- opening a context
+// the caller's build options, or the defaults
+static xm_build_opts buildOptsOrDefaults(const xm_build_opts* optsIn) {
+  xm_build_opts o;
+  memset(&o, 0, sizeof(o));
+  o.enable_gapmers = 1; o.dup_window = 1000; o.dup_min_copies = 2; o.device = -1;
+  if (optsIn) o = *optsIn;
+  return o;
+}
+// the tables of hs in the HBM of `device`, uploaded: from the host, or with `peer` (the same tables on another GPU) from there (caller holds hs->mu where another context exists)
+static std::shared_ptr<DeviceTables> makeDeviceTables(const std::shared_ptr<HostShare>& hs, int device, const DeviceTables* peer = nullptr) {
+  auto dt = std::make_shared<DeviceTables>();
+  dt->hs = hs; dt->device = device;
+  std::unique_lock<std::shared_mutex> wr(dt->rw);
+  dt->upload(peer);
+  return dt;
+}
+// The first context of a new HostShare, for the entry named `entry`.  makeTables(host) fills the host tables - it builds them, or loads and completes them -
+// with the GPU chosen and the device hasher in place (host_only: neither).
+template <class MakeTables>
+static int openFirstContext(const char* entry, const xm_build_opts& o, xm_index** out, MakeTables&& makeTables) {
+  xm_index* idx = nullptr;
+  try {
+    idx = new xm_index();
+    idx->hs = std::make_shared<HostShare>();
+    idx->hostOnly = o.host_only != 0;
+    if (!idx->hostOnly) {
+      int n = 0;
+      if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+        throw std::runtime_error("no HIP device available: libxmapper_hip.so has no CPU path (pass host_only=1 only to inspect the index)");
+      int dev = o.device;
+      if (dev < 0) HIP_CHECK(hipGetDevice(&dev));
+      idx->device = dev;
+      idx->host().deviceHasher = &deviceHashLengths;  // the tables are hashed on this GPU (references without ambiguity codes)
+      idx->host().deviceForBuild = dev;
+    }
+    makeTables(idx->host());
+    idx->hs->hashedLength.store(idx->host().maxHashedLength);
+    if (!idx->hostOnly) {
+      idx->dt = makeDeviceTables(idx->hs, idx->device);
+      idx->initContext();
+    }
+    *out = idx;
+    return 0;
+  } catch (std::exception& e) {
+    delete idx;
+    return fail(std::string(entry) + ": " + e.what());
+  }
 }
 
 extern "C" {
@@ -1047,40 +1012,11 @@ int xm_device_count(void) {
 
 int xm_index_build(const xm_ref* ref, const xm_build_opts* optsIn, xm_index** out) {
   if (!ref || !out) return fail("xm_index_build: null argument");
-  xm_build_opts o;
-  memset(&o, 0, sizeof(o));
-  o.enable_gapmers = 1; o.dup_window = 1000; o.dup_min_copies = 2; o.device = -1;
-  if (optsIn) o = *optsIn;
-  xm_index* idx = nullptr;
-  try {
-    idx = new xm_index();
-    idx->hs = std::make_shared<HostShare>();
-    idx->host().setReference(ref->num_contigs, ref->names, ref->codes, ref->lengths);
-    idx->hostOnly = o.host_only != 0;
-    if (!idx->hostOnly) {
-      int n = 0;
-      if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-        throw std::runtime_error("no HIP device available: libxmapper_hip.so has no CPU path (pass host_only=1 only to inspect the index)");
-      int dev = o.device;
-      if (dev < 0) HIP_CHECK(hipGetDevice(&dev));
-      idx->device = dev;
-      idx->host().deviceHasher = &deviceHashLengths;  // the tables are hashed on this GPU (references without ambiguity codes)
-      idx->host().deviceForBuild = dev;
-    }
-    idx->host().build(o.enable_gapmers, o.min_interesting_size, o.max_hashed_length, o.dup_window, o.dup_min_copies, o.dup_min_length, o.dup_max_length);
-    idx->hs->hashedLength.store(idx->host().maxHashedLength);
-    if (!idx->hostOnly) {
-      idx->dt = std::make_shared<DeviceTables>();
-      idx->dt->hs = idx->hs; idx->dt->device = idx->device;
-      idx->dt->upload();
-      idx->initContext();
-    }
-    *out = idx;
-    return 0;
-  } catch (std::exception& e) {
-    delete idx;
-    return fail(std::string("xm_index_build: ") + e.what());
-  }
+  const xm_build_opts o = buildOptsOrDefaults(optsIn);
+  return openFirstContext("xm_index_build", o, out, [&](HostIndex& host) {
+    host.setReference(ref->num_contigs, ref->names, ref->codes, ref->lengths);
+    host.build(o.enable_gapmers, o.min_interesting_size, o.max_hashed_length, o.dup_window, o.dup_min_copies, o.dup_min_length, o.dup_max_length);
+  });
 }
 
 int xm_index_replicate(xm_index* src, int32_t device, xm_index** out) {
@@ -1104,11 +1040,8 @@ int xm_index_replicate(xm_index* src, int32_t device, xm_index** out) {
       if (can) { HIP_CHECK(hipSetDevice(device)); hipError_t e = hipDeviceEnablePeerAccess(src->device, 0); if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIP_CHECK(e); (void)hipGetLastError(); }
       std::lock_guard<std::mutex> lock(src->hs->mu);            // (not while the tables grow)
       std::shared_lock<std::shared_mutex> rd(src->dt->rw);      // (nor while the source's copy is brought up to them)
-      idx->dt = std::make_shared<DeviceTables>();
-      idx->dt->hs = idx->hs; idx->dt->device = device;
-      std::unique_lock<std::shared_mutex> wr(idx->dt->rw);
-      if (src->dt->uploadedLength == src->hs->host.maxHashedLength) idx->dt->upload(src->dt.get());  // HBM to HBM (xGMI)
-      else idx->dt->upload();
+      // HBM to HBM (xGMI) where the source's copy is up to date
+      idx->dt = makeDeviceTables(idx->hs, device, src->dt->uploadedLength == src->hs->host.maxHashedLength ? src->dt.get() : nullptr);
       HIP_CHECK(hipDeviceSynchronize());
     }
     idx->initContext();
@@ -1130,9 +1063,9 @@ int xm_context_set_scratch(xm_index* idx, int64_t bytes) {
   if (bytes < 0) return fail("xm_context_set_scratch: negative size");
   std::lock_guard<std::mutex> lock(idx->mu);
   idx->scratchBytes = bytes;
-  if (bytes > 0 && idx->dArenas.n > (size_t)bytes && !idx->hostOnly) {  // what the context holds beyond its new limit goes back to the GPU now
+  if (bytes > 0 && idx->passes.dArenas.n > (size_t)bytes && !idx->hostOnly) {  // what the context holds beyond its new limit goes back to the GPU now
     (void)hipSetDevice(idx->device);
-    idx->dArenas.release();
+    idx->passes.dArenas.release();
   }
   return 0;
 }
@@ -1285,46 +1218,17 @@ int xm_index_save(xm_index* idx, const char* path) {
 
 int xm_index_load(const char* path, const xm_ref* ref, const xm_build_opts* optsIn, xm_index** out) {
   if (!path || !out) return fail("xm_index_load: null argument");
-  xm_build_opts o;
-  memset(&o, 0, sizeof(o));
-  o.enable_gapmers = 1; o.dup_window = 1000; o.dup_min_copies = 2; o.device = -1;
-  if (optsIn) o = *optsIn;
-  xm_index* idx = nullptr;
-  try {
-    idx = new xm_index();
-    idx->hs = std::make_shared<HostShare>();
-    idx->host().load(path);
+  const xm_build_opts o = buildOptsOrDefaults(optsIn);
+  return openFirstContext("xm_index_load", o, out, [&](HostIndex& host) {
+    host.load(path);
     if (ref) {  // the file must answer exactly this build request (the reference's cache keys, M/HashBlock_Database.java:106-114)
       HostIndex want;
       want.setReference(ref->num_contigs, ref->names, ref->codes, ref->lengths);
-      if (!idx->host().matchesRequest(want, o.enable_gapmers, o.min_interesting_size, o.dup_window, o.dup_min_copies, o.dup_min_length, o.dup_max_length))
+      if (!host.matchesRequest(want, o.enable_gapmers, o.min_interesting_size, o.dup_window, o.dup_min_copies, o.dup_min_length, o.dup_max_length))
         throw std::runtime_error("the file was built from another reference or with other settings");
     }
-    idx->hostOnly = o.host_only != 0;
-    if (!idx->hostOnly) {
-      int n = 0;
-      if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-        throw std::runtime_error("no HIP device available: libxmapper_hip.so has no CPU path (pass host_only=1 only to inspect the index)");
-      int dev = o.device;
-      if (dev < 0) HIP_CHECK(hipGetDevice(&dev));
-      idx->device = dev;
-      idx->host().deviceHasher = &deviceHashLengths;
-      idx->host().deviceForBuild = dev;
-    }
-    if (o.max_hashed_length > idx->host().maxHashedLength) idx->host().ensureLength(o.max_hashed_length);
-    idx->hs->hashedLength.store(idx->host().maxHashedLength);
-    if (!idx->hostOnly) {
-      idx->dt = std::make_shared<DeviceTables>();
-      idx->dt->hs = idx->hs; idx->dt->device = idx->device;
-      idx->dt->upload();
-      idx->initContext();
-    }
-    *out = idx;
-    return 0;
-  } catch (std::exception& e) {
-    delete idx;
-    return fail(std::string("xm_index_load: ") + e.what());
-  }
+    if (o.max_hashed_length > host.maxHashedLength) host.ensureLength(o.max_hashed_length);
+  });
 }
 
 int xm_index_ensure_length(xm_index* idx, int32_t length) {
@@ -1570,22 +1474,17 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
         memoInUse = memoLock(c);
         c.nTodo = nReps;
         memoLookup(c);
-        const size_t needInts = (size_t)nq * 40 + 4096 + (size_t)c.hitInts, needDbls = (size_t)nq * 12 + 4096 + (size_t)c.hitDbls;
-        if (idx->dOutInts.p && idx->dOutInts.n >= needInts && idx->dOutDbls.p && idx->dOutDbls.n >= needDbls) break;
+        if (idx->results.arenasHold(nq, c.hitInts, c.hitDbls)) break;
         memoInUse.unlock();
-        idx->dOutInts.ensure(needInts + (size_t)c.hitInts / 8); idx->dOutDbls.ensure(needDbls + (size_t)c.hitDbls / 8);
+        idx->results.reserveArenas(nq, c.hitInts, c.hitDbls, true);
       }
     }
     const BatchFacts facts{idx->resident.maxLen, idx->resident.anyPaired, idx->dt->contexts.load(), idx->scratchBytes};
     const BatchPolicy pol = makePolicy(facts, readPassKnobs(facts));
-    idx->dOutInts.ensure((size_t)nq * 40 + 4096 + (size_t)c.hitInts); idx->dOutDbls.ensure((size_t)nq * 12 + 4096 + (size_t)c.hitDbls);  // (the remembered results on top; with a memory: there already)
-    c.intCap = idx->dOutInts.n; c.dblCap = idx->dOutDbls.n;
+    idx->results.reserveArenas(nq, c.hitInts, c.hitDbls);  // (the remembered results on top; with a memory: there already)
     if (c.remembered > 0) memoReplay(c);
     if (idx->memoOn()) { memoPromote(c); memoInUse.unlock(); }
-    if (pol.k.handOver) {
-      idx->dRegionOf.ensure((size_t)nq);
-      HIP_CHECK(hipMemsetAsync(idx->dRegionOf.p, 0xFF, sizeof(int32_t) * (size_t)nq, c.s));
-    }
+    if (pol.k.handOver) idx->passes.forgetRegions(nq, c.s);
     if (pol.k.waveForm && idx->resident.maxLen <= 256 && c.nTodo > 0) runWaveForm(c, pol.k.tracePasses);
     runLanePasses(c, pol);  // (nothing left to align: no pass runs)
     if (idx->memoOn()) { memoInsert(c); res->reserved = (int32_t)std::min<double>(c.memoWaitUs, 2147483647.0); }  // (b), under the memory's mu

@@ -165,18 +165,19 @@ int xm_pileup_add_last(xm_pileup* p, int64_t* num_events) {
   xm_index* idx = p->index;
   try {
     std::lock_guard<std::mutex> lock(idx->mu);
-    if (idx->lastAlignedNq < 0 || idx->lastAlignedNq != idx->resident.nq || idx->lastAlignedGen != idx->residentGen)
+    const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
+    if (last.nq < 0)
       throw std::runtime_error("the batch of the last align call is no longer resident (call xm_pileup_add_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
     HIP_CHECK(hipSetDevice(idx->device));
     hipStream_t s = idx->stream;
-    const int64_t nq = idx->lastAlignedNq;
+    const int64_t nq = last.nq;
     if (nq > 0) {
-      const unsigned long long cap = (unsigned long long)idx->dFinalInts.n / 4 + 1;  // (an event is a block: at least four ints of the stream)
+      const unsigned long long cap = (unsigned long long)last.intsHeld / 4 + 1;  // (an event is a block: at least four ints of the stream)
       p->dEvents.ensure((size_t)cap * 8);
       HIP_CHECK(hipMemsetAsync(p->dEventCount.p, 0, sizeof(unsigned long long), s));
       PileupView pv{p->dDepth.p, p->dAlt.p, p->total, p->dEvents.p, cap, p->dEventCount.p, p->queriesAdded, p->endFraction > 0 ? p->dMid.p : nullptr, p->endFraction};
       std::shared_lock<std::shared_mutex> tablesInUse(idx->dt->rw);
-      hipLaunchKernelGGL(xm_pileup_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, idx->dt->view, idx->resident.view(), (const int32_t*)idx->dFinalInts.p, (const int64_t*)idx->dFinalIntOff.p, pv);
+      hipLaunchKernelGGL(xm_pileup_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, idx->dt->view, idx->resident.view(), last.ints, last.intOff, pv);
       HIP_CHECK(hipGetLastError());
       unsigned long long n = 0;
       HIP_CHECK(hipMemcpyAsync(&n, p->dEventCount.p, sizeof(n), hipMemcpyDeviceToHost, s));

@@ -887,4 +887,12 @@ struct HostIndex {
   }
 };
 
+// The scalar fields of an IndexView, which are the host's whatever memory the view's pointers lead to (HBM: DeviceTables::upload; the host's own
+// vectors: the host simulation).  posIs64: the positions behind the view are the 64-bit ones.
+inline void fillHostFields(IndexView& view, const HostIndex& host, bool posIs64) {
+  view.numContigs = host.numContigs(); view.minInterestingSize = host.minInterestingSize; view.maxHashedLength = host.maxHashedLength;
+  view.enableGapmers = host.enableGapmers; view.posIs64 = posIs64 ? 1 : 0; view.dupWindow = host.dupWindow; view.dupGranularity = host.dupGranularity();
+  view.totalForwardAndReverseSize = host.totalForwardSize * 2;
+}
+
 }  // namespace xm

@@ -43,6 +43,12 @@ inline void countersToResult(const DevCounters& dc, xm_result* res) {
   res->extra[0] = (int64_t)dc.boundChecks; res->extra[1] = (int64_t)dc.boundRejects; res->extra[2] = (int64_t)dc.boundCells; res->extra[4] = (int64_t)dc.boundPieceChecks; res->extra[5] = (int64_t)dc.boundPieceRejects;
 }
 
+// The two result arenas of a context (ResultStage, xm_result_stage.h), in elements.  What a call of nq queries starts with: room for a typical batch
+// (40 ints and 12 doubles per query) plus `hits`, the elements of the slices a run-wide memory replays into the arena before the first pass.  What an
+// arena that a pass found full (cursor: what the pass asked for, beyond cap) grows to before the rerun: four times as much, and at least twice the need.
+inline size_t firstArenaSize(long long nq, unsigned long long hits, bool doubles) { return (size_t)nq * (doubles ? 12 : 40) + 4096 + (size_t)hits; }
+inline unsigned long long grownArenaSize(unsigned long long cap, unsigned long long cursor) { return std::max(cap * 4 + 65536, cursor * 2); }
+
 constexpr long long XM_ARENA_KB_DEFAULT = 288;  // scratch of a lane at scale 1
 
 // what the plan of a call depends on besides the knobs

@@ -44,9 +44,7 @@ struct SimIndex {
     bool is64 = host.seqCumStart.back() > 0xFFFFFFFFll;
     p32.clear();
     if (!is64) { p32.resize(host.positions.size()); for (size_t i = 0; i < p32.size(); i++) p32[i] = (uint32_t)host.positions[i]; }
-    view.numContigs = host.numContigs(); view.minInterestingSize = host.minInterestingSize; view.maxHashedLength = host.maxHashedLength;
-    view.enableGapmers = host.enableGapmers; view.posIs64 = is64 ? 1 : 0; view.dupWindow = host.dupWindow; view.dupGranularity = host.dupGranularity();
-    view.totalForwardAndReverseSize = host.totalForwardSize * 2;
+    fillHostFields(view, host, is64);
     view.contigStart = host.contigStart.data(); view.contigLen = host.contigLen.data(); view.seqCumStart = host.seqCumStart.data(); view.refCodes = host.refCodes.data();
     view.tables = host.tables.data(); view.bucketOff = host.bucketOff.data(); view.positions32 = p32.data(); view.positions64 = (const uint64_t*)host.positions.data();
     view.dupKeyStart = host.dupKeyStart.data(); view.dupKeys = host.dupKeys.data();
@@ -591,6 +589,9 @@ int xmsim_next_pass(const int64_t* facts, int64_t* state, const uint64_t* ctl, i
     return 0;
   } catch (std::exception& e) { g_err = e.what(); return 1; }
 }
+// the result arenas' sizes (elements): what a call of nq queries with `hits` replayed elements starts with (doubles: the doubles' arena), what a full one grows to
+uint64_t xmsim_first_arena_size(int64_t nq, uint64_t hits, int doubles) { return (uint64_t)firstArenaSize(nq, hits, doubles != 0); }
+uint64_t xmsim_grown_arena_size(uint64_t cap, uint64_t cursor) { return (uint64_t)grownArenaSize(cap, cursor); }
 
 // ---- the index-build planner (mapper_amd/csrc/xm_index_plan.h, what the host builder and the GPU builder share) for tests/test_index_plan.py
 // out (2): capacity, maxCount

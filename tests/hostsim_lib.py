@@ -60,6 +60,10 @@ def lib():
         L.xmsim_pass_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.xmsim_plan_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p]
         L.xmsim_next_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.xmsim_first_arena_size.argtypes = [C.c_int64, C.c_uint64, C.c_int]
+        L.xmsim_first_arena_size.restype = C.c_uint64
+        L.xmsim_grown_arena_size.argtypes = [C.c_uint64, C.c_uint64]
+        L.xmsim_grown_arena_size.restype = C.c_uint64
         L.xmsim_table_shape.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_void_p]
         L.xmsim_table_shape.restype = None
         L.xmsim_plan_groups.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_int64]
@@ -251,6 +255,16 @@ def next_pass(state, ctl, longest_mate, paired=False, contexts=1):
     c = np.array([ctl.get("nHeavy", 0), ctl.get("nHeavyLate", 0)] + list(ctl.get("nScale", (0, 0))) + list(ctl.get("nOut", (0, 0))) + [2 ** 64 - 1] + list(ctl.get("nConf", (0, 0))), dtype=np.uint64)
     _check(lib().xmsim_next_pass(f.ctypes.data, st.ctypes.data, c.ctypes.data, nxt.ctypes.data))
     return PASS_KINDS[int(nxt[0])], int(nxt[1]), int(nxt[2]), int(nxt[3]), dict(zip(STATE_FIELDS, map(int, st)))
+
+
+def first_arena_size(nq, hits=0, doubles=False):
+    """elements of a result arena (the ints', or the doubles') a call of nq queries starts with, `hits` of them for the slices a memory replays"""
+    return int(lib().xmsim_first_arena_size(nq, hits, 1 if doubles else 0))
+
+
+def grown_arena_size(cap, cursor):
+    """elements a result arena of `cap` grows to after a pass that asked for `cursor`"""
+    return int(lib().xmsim_grown_arena_size(cap, cursor))
 
 
 # ---- the index-build planner (mapper_amd/csrc/xm_index_plan.h), shared by the host builder and the GPU builder

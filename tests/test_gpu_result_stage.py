@@ -1,7 +1,7 @@
 """The last lines of every pass of xm_align_batch on the GPU: room in the two result arenas (publishRead, mapper_amd/csrc/xm_kernel_common.h; its copies in
 xm_wave_kernel.hip and xm_memo_replay_kernel), the rerun of the reads that found an arena full (PassKind::OutRerun: runLanePasses grows both arenas with
-growKeep and runs the `out` list in front of whatever else is pending), and the scan and gather that turn per-read lengths into the query-order streams
-(xm_scan_*_kernel, xm_gather_kernel, xm_collapse_fanout_kernel; finishStreams).
+ResultStage::growAfterOverflow and runs the `out` list in front of whatever else is pending), and the scan and gather that turn per-read lengths into the query-order streams
+(xm_scan_*_kernel, xm_gather_kernel, xm_collapse_fanout_kernel; ResultStage::toHost, mapper_amd/csrc/xm_result_stage.h).
 
 The arenas are per context and only ever grow, so the overflow path runs on the first call of a context whose reads have many alignments and never again:
 every overflow case takes a fresh context (db.new_context(): the tables are shared) and proves from the pass trace (XM_TRACE_PASSES=1, as
@@ -29,8 +29,8 @@ THREADS = min(16, os.cpu_count())
 MEMO = 64 << 20
 
 
-# the arenas a context's first call of nq queries starts with (xm_capi.hip, alignResidentLocked: dOutInts / dOutDbls .ensure) and what a rerun grows them to
-# (runLanePasses, case PassKind::OutRerun).  Written once: the cases below are sized by them, and assert from the oracle's lengths that they still overflow.
+# the arenas a context's first call of nq queries starts with (xm_pass_plan.h, firstArenaSize: ResultStage::reserveArenas) and what a rerun grows them to
+# (grownArenaSize: ResultStage::growAfterOverflow).  Written once here, independently of them (tests/test_pass_plan.py holds the two against each other): the cases below are sized by them, and assert from the oracle's lengths that they still overflow.
 def initial_int_cap(nq):
     return nq * 40 + 4096
 

@@ -236,3 +236,34 @@ def test_invalid_knobs_raise(monkeypatch, knob, value, message):
         monkeypatch.setenv("XM_GAPPED_FACTOR", value)
         with pytest.raises(RuntimeError, match="XM_GAPPED_FACTOR=%s is not valid" % value):
             hs.pass_policy(1000)
+
+
+ARENA_NQ = (0, 1, 255, 256, 4096, 4097, 1_000_000)
+ARENA_HITS = (0, 1, 2 ** 33)
+
+
+def test_result_arena_sizes_equal_their_independent_statement():
+    """firstArenaSize / grownArenaSize, which size every result arena of the product (ResultStage), against the formulas tests/test_gpu_result_stage.py
+    sizes its overflow cases by: the first size is that of nq queries plus the replayed hits; the grown size with the cursor below, at and far above
+    four times the capacity + 65536."""
+    from test_gpu_result_stage import initial_int_cap, initial_dbl_cap, grown_cap
+    for nq in ARENA_NQ:
+        for hits in ARENA_HITS:
+            assert hs.first_arena_size(nq, hits) == initial_int_cap(nq) + hits
+            assert hs.first_arena_size(nq, hits, doubles=True) == initial_dbl_cap(nq) + hits
+        for cap in (initial_int_cap(nq), initial_dbl_cap(nq), initial_int_cap(nq) + 2 ** 33):
+            edge = 4 * cap + 65536
+            for cursor in (0, cap, cap + 1, edge // 2 - 1, edge // 2, edge // 2 + 1, edge, 2 ** 40):
+                assert hs.grown_arena_size(cap, cursor) == grown_cap(cap, cursor), (cap, cursor)
+            assert hs.grown_arena_size(cap, edge // 2) == edge and hs.grown_arena_size(cap, edge // 2 + 1) == edge + 2 and hs.grown_arena_size(cap, 2 ** 40) == 2 ** 41
+
+
+def test_first_arena_size_is_monotone():
+    """more queries or more hits never start with a smaller arena, and the doubles' arena is never the larger one"""
+    for doubles in (False, True):
+        sizes = [[hs.first_arena_size(nq, hits, doubles) for hits in ARENA_HITS] for nq in ARENA_NQ]
+        for row, above in zip(sizes, sizes[1:]):
+            assert all(a < b for a, b in zip(row, above))
+        for row in sizes:
+            assert all(a < b for a, b in zip(row, row[1:]))
+    assert all(hs.first_arena_size(nq, h, True) <= hs.first_arena_size(nq, h) for nq in ARENA_NQ for h in ARENA_HITS)
