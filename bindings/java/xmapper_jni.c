@@ -19,7 +19,7 @@
 #include <string.h>
 #include "xmapper_hip.h"
 
-#define XMJ_ABI_VERSION 5  /* include/xmapper_hip.h: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free */
+#define XMJ_ABI_VERSION 6  /* include/xmapper_hip.h: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes (not used here: the Java host parses its own queries) */
 
 /* ---------------------------------------------------------------- part 1: marshalling on plain C arrays ---------------------------------------- */
 

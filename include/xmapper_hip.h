@@ -123,7 +123,7 @@ const char* xm_last_error(void);
 const char* xm_build_stamp(void);
 /* Version of this header's structs and entry points: 2 = xm_result.extra[] appended, xm_seed_probe_packed replaces xm_seed_probe; 3 = xm_context_set_collapse,
  * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6]; 5 = xm_memory_new, xm_context_attach_memory, xm_memory_info,
- * xm_memory_free, xm_result.reserved carries the wait for a memory.  A binding checks it once
+ * xm_memory_free, xm_result.reserved carries the wait for a memory; 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes.  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -240,6 +240,33 @@ int xm_align_resident(xm_index* index, const xm_params* params, xm_result** out)
  * the resident one (it waits for a running xm_align_resident).  xm_batch_upload = stage + commit without the overlap. */
 int xm_batch_stage(xm_index* index, const xm_query_batch* batch);
 int xm_batch_commit(xm_index* index);
+
+/* (ABI version 6) The batch staged from FASTQ text instead of from arrays: the host hands over a block of whole four-line records as it read them from the
+ * file - one text for single reads, two texts of equally many records for pairs (record i of each is query i) - and kernels build the arrays of
+ * xm_query_batch in HBM, so the host translates no base.  The texts may be pageable memory and are not needed after the call.  keep_qualities = 0: quals,
+ * qual_off and has_qual of the result are NULL. */
+typedef struct xm_fastq_text {
+  const char* text1; int64_t bytes1; int64_t records1;
+  const char* text2; int64_t bytes2; int64_t records2;   /* NULL / 0 / 0: single reads */
+  double expected_inner, deviation;                       /* of every pair; single queries get 0 and 1 */
+  int32_t keep_qualities, reserved;
+} xm_fastq_text;
+/* Host copies of what was built, in page-locked buffers of the library's pool: the fields of xmio_batch (include/xmapper_hostio.h) up to `store`, in its
+ * order and with its meaning, so that the harness's writers read it as they read a batch of the host reader; then the times of the call's three parts. */
+typedef struct xm_fastq_batch {
+  int64_t num_queries; int32_t* mate_count; int64_t* mate_offset; int32_t* mate_length;
+  uint8_t* codes; int64_t codes_length; char* names; int64_t* name_off;
+  char* quals; int64_t* qual_off; uint8_t* has_qual; void* store;
+  double h2d_ms, kernel_ms, d2h_ms;
+} xm_fastq_batch;
+/* Does what xm_batch_stage does (same stream, same buffers; xm_batch_commit follows as usual) and returns the arrays.  The device takes the strict form only:
+ * every record is four lines, the first starts with '@', the sequence has 1 .. 30000 bases, and records1 / records2 are the records the texts hold (a last
+ * line without its newline is a line).  Anything else fails the call with nothing staged; xm_last_error names the file (1 or 2), the 0-based record and
+ * the reason.  A text may hold up to 1 GiB. */
+int xm_batch_stage_fastq(xm_index* index, const xm_fastq_text* text, xm_fastq_batch** out);
+void xm_fastq_batch_free(xm_fastq_batch* batch);
+/* Bytes of text per workgroup of the kernels that find the line ends (test hook: tests/test_gpu_fastq.py puts newlines on both sides of the edges it gives). */
+int32_t xm_fastq_tile_bytes(void);
 
 /* Bulk form of Readable_HashBlock_Database.getNumMatchesLowerBound + matchBlock / PackedMap.get (PackedMap.java:160-172,
  * 228-236) for n (used_length, lookup key) pairs: counts[i] = number of stored positions, -1 when the bucket is overfull or

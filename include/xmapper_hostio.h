@@ -50,6 +50,26 @@ void xmio_close(xmio_reader* reader);
  * they came with qualities, else FASTA) to unaligned_fd; either descriptor may be -1.  Query order; `threads` formatting threads.  Adds to *stats. */
 int xmio_write_batch(const xmio_batch* batch, const int32_t* ints, const double* dbls, const int64_t* int_off, const int64_t* dbl_off, int32_t num_contigs,
                      const char* const* contig_names, int32_t sam_fd, int32_t unaligned_fd, int32_t threads, xmio_stats* stats);
+
+/* The query files cut into blocks of whole four-line FASTQ records, as text, for a parser that is not this library's (xm_batch_stage_fastq of
+ * include/xmapper_hip.h builds the batch arrays from such a block on the GPU).  The cutter looks for line ends only: no base is translated and nothing is
+ * looked up per base.  FASTA, multi-line records and --split-queries-past-size stay with xmio_open. */
+typedef struct xmio_text_reader xmio_text_reader;
+typedef struct xmio_text_block {
+  const char* text1; int64_t bytes1; int64_t records1;
+  int64_t longest1;          /* length of the longest sequence line (lines 1, 5, 9, ...) of text1 as it stands in the file: an upper bound of the longest mate */
+  const char* text2; int64_t bytes2; int64_t records2; int64_t longest2;   /* NULL / 0 / 0 / 0 for a single file */
+  void* store;               /* owner of the texts (xmio_text_block_free) */
+} xmio_text_block;
+/* path2 != NULL: paired files cut in step, a block holds the same number of records of each.  Files may be gzip-compressed. */
+xmio_text_reader* xmio_text_open(const char* path1, const char* path2);
+/* The next block: a contiguous copy of whole lines, at most max_queries records and at most 1 GiB per file; *out = NULL at the end of the input, where
+ * trailing empty lines are dropped (the last block may lack its final newline).  Returns 0, or -1 (xmio_last_error names the file and the line) when a file
+ * ends inside a record or the files of a pair hold different numbers of records. */
+int xmio_text_next(xmio_text_reader* reader, int64_t max_queries, xmio_text_block** out);
+void xmio_text_block_free(xmio_text_block* block);
+void xmio_text_close(xmio_text_reader* reader);
+
 /* Double.toString(x) as the AS:f: / cs:f: tags print it (test hook); returns the length, -1 if cap is too small. */
 int xmio_java_double(double x, char* out, int32_t cap);
 

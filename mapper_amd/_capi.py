@@ -40,7 +40,21 @@ class XmResult(C.Structure):
                 ("kernel_launches", C.c_int32), ("reserved", C.c_int32), ("prof", C.c_int64 * 16), ("extra", C.c_int64 * 8)]
 
 
-ABI_VERSION = 5  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free
+class XmFastqText(C.Structure):
+    """xm_fastq_text: a block of whole four-line FASTQ records as read from the file(s)."""
+    _fields_ = [("text1", C.c_void_p), ("bytes1", C.c_int64), ("records1", C.c_int64), ("text2", C.c_void_p), ("bytes2", C.c_int64), ("records2", C.c_int64),
+                ("expected_inner", C.c_double), ("deviation", C.c_double), ("keep_qualities", C.c_int32), ("reserved", C.c_int32)]
+
+
+class XmFastqBatch(C.Structure):
+    """xm_fastq_batch: hostio.XmioBatch's fields (pinned host copies of what the kernels built), then the times of the call's three parts."""
+    _fields_ = [("num_queries", C.c_int64), ("mate_count", C.POINTER(C.c_int32)), ("mate_offset", C.POINTER(C.c_int64)), ("mate_length", C.POINTER(C.c_int32)),
+                ("codes", C.POINTER(C.c_uint8)), ("codes_length", C.c_int64), ("names", C.c_void_p), ("name_off", C.POINTER(C.c_int64)),
+                ("quals", C.c_void_p), ("qual_off", C.POINTER(C.c_int64)), ("has_qual", C.POINTER(C.c_uint8)), ("store", C.c_void_p),
+                ("h2d_ms", C.c_double), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double)]
+
+
+ABI_VERSION = 6  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes
 
 
 class XmIndexInfo(C.Structure):
@@ -51,7 +65,7 @@ class XmIndexInfo(C.Structure):
 
 
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
-           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_free"]
+           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_stage_fastq", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_free"]
 
 
 def build_library(force=False):
@@ -133,6 +147,9 @@ def lib():
         L.xm_batch_upload.argtypes = [C.c_void_p, C.POINTER(XmQueryBatch)]
         L.xm_batch_stage.argtypes = [C.c_void_p, C.POINTER(XmQueryBatch)]
         L.xm_batch_commit.argtypes = [C.c_void_p]
+        L.xm_batch_stage_fastq.argtypes = [C.c_void_p, C.POINTER(XmFastqText), C.POINTER(C.POINTER(XmFastqBatch))]
+        L.xm_fastq_batch_free.argtypes = [C.POINTER(XmFastqBatch)]
+        L.xm_fastq_batch_free.restype = None
         L.xm_align_resident.argtypes = [C.c_void_p, C.POINTER(XmParams), C.POINTER(C.POINTER(XmResult))]
         L.xm_seed_probe_packed.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.xm_measure_random_gather.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_double)]

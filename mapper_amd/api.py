@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import numpy as np
 
-from . import _capi
+from . import _capi, hostio
 
 _CODE = np.full(256, 15, dtype=np.uint8)
 for _ch, _v in {"A": 1, "C": 2, "G": 4, "T": 8, "U": 8, "R": 5, "Y": 10, "S": 6, "W": 9, "K": 12, "M": 3, "B": 14, "D": 13, "H": 11, "V": 7, "N": 15}.items():
@@ -359,12 +359,26 @@ class ReferenceDatabase:
         b, keep = _capi.make_batch(mate_count, mate_offset, mate_length, codes, expected_inner, deviation)
         _check(self._L.xm_batch_stage(self._h, C.byref(b)))
 
+    def stage_fastq(self, block):
+        """xm_batch_stage_fastq: the NEXT batch from FASTQ text (a hostio.TextBlock) - the text is copied to HBM and parsed there by kernels; the block then
+        offers the arrays hostio.Batch offers (names and qualities included, for the writers).  A text that is not of the strict form (four lines a record, '@'
+        headers, 1 .. 30000 bases) is a hostio.StrictFormError (a ValueError) that names file, record and reason, and nothing is staged."""
+        if block._text is None:
+            raise ValueError("the block's text is gone: it has been staged or closed")
+        t = block._text.contents
+        text = _capi.XmFastqText(t.text1, t.bytes1, t.records1, t.text2, t.bytes2, t.records2, block.pair_spacing[0], block.pair_spacing[1], 1 if block.keep_qualities else 0, 0)
+        out = C.POINTER(_capi.XmFastqBatch)()
+        if self._L.xm_batch_stage_fastq(self._h, C.byref(text), C.byref(out)):
+            raise hostio.StrictFormError(self._L.xm_last_error().decode())
+        block.attach(out, self._L.xm_fastq_batch_free)
+        return block
+
     def commit_staged(self):
         """xm_batch_commit: the staged batch becomes the resident one."""
         _check(self._L.xm_batch_commit(self._h))
 
     def align_stream(self, batches, parameters, on_aligned=None):
-        """Aligns a sequence of batches (each a tuple of upload_arrays' six arrays) and yields their BatchResults in order.  The copy of
+        """Aligns a sequence of batches (each a tuple of upload_arrays' six arrays, or a hostio.TextBlock, which is staged with stage_fastq) and yields their BatchResults in order.  The copy of
         batch k+1 to HBM runs on a second host thread and a second stream while batch k is being aligned (the
         reference's workers fetch their next batch the same way, AlignerWorker.java:92-175)."""
         import queue
@@ -379,7 +393,10 @@ class ReferenceDatabase:
                 for arrays in batches:
                     if stop.is_set():
                         break
-                    self.stage_arrays(*arrays)
+                    if isinstance(arrays, hostio.TextBlock):  # FASTQ text: parsed on the GPU
+                        self.stage_fastq(arrays)
+                    else:
+                        self.stage_arrays(*arrays)
                     if not first:
                         aligned.acquire()  # the previous batch has been aligned: its buffers may be swapped away
                         if stop.is_set():

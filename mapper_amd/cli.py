@@ -16,7 +16,8 @@ Flags of this harness that Mapper does not have: --batch-size <n>, --gpus <n>, -
 outputs are the same, and one line on stderr says how many queries were served as copies), --remember-queries <MiB> (every context keeps the queries
 it has aligned in that much HBM and serves byte-identical queries of its later batches from there: the same cache across batches; same outputs, one line on
 stderr), and --remember-queries-per-gpu <MiB> (one such memory per GPU, which all its contexts share and which keeps remembering when it is full; not
-together with --remember-queries).
+together with --remember-queries), and --parse-on-gpu (the FASTQ files go to the GPU as text and are parsed there, api.ReferenceDatabase.stage_fastq: same outputs;
+four-line FASTQ records only, so a file the host reader takes may be refused with a message that says where; not with --per-object or a split size).
 """
 import contextlib
 import gzip
@@ -191,6 +192,8 @@ def parse_args(argv):
                 raise UsageError("--remember-queries-per-gpu must be >= 0")
         elif a == "--per-object":  # (not a Mapper flag) the harness's first implementation: one Python object per read and per alignment (the reference for the formats; tests)
             o["per_object"] = True
+        elif a == "--parse-on-gpu":  # (not a Mapper flag) the query files are cut into blocks of whole FASTQ records on the host and parsed on the GPU (api.ReferenceDatabase.stage_fastq)
+            o["parse_on_gpu"] = True
         elif a == "--device":  # (not a Mapper flag) which GPU
             o["device"] = int(argv[i + 1]); i += 1
         elif a == "--spacing":
@@ -202,6 +205,10 @@ def parse_args(argv):
         else:
             raise UsageError("Unrecognized argument: " + a)
         i += 1
+    if o.get("parse_on_gpu") and o.get("per_object"):
+        raise UsageError("--parse-on-gpu and --per-object exclude each other (the per-object path reads the queries into Python objects)")
+    if o.get("parse_on_gpu") and any(split > 0 for _, split in o["queries"]):
+        raise UsageError("--parse-on-gpu is not supported with --split-queries-past-size (the sections are cut by the host reader)")
     if o.get("remember") and o.get("remember_per_gpu"):
         raise UsageError("--remember-queries (a memory per context) and --remember-queries-per-gpu (one per GPU) exclude each other")
     return o
@@ -315,8 +322,15 @@ def native_source(o, batch_size, job):
     cannot know the job's size, so the first batch speaks for the job: a full one counts as three batches or more, a short one as the only one.
     -> (batches, batch count for default_contexts, single_short, longest mate)"""
     keep_qual = bool(o["out_unaligned"])
+    on_gpu = bool(o.get("parse_on_gpu"))  # the blocks are text (hostio.TextBlock) until a context stages them: the first one speaks through its longest line
 
     def read():
+        if on_gpu:
+            for path, _ in o["queries"]:
+                yield from hostio.read_text_blocks(path, None, batch_size, keep_qualities=keep_qual)
+            for left, right, expected, deviation in o["paired"]:
+                yield from hostio.read_text_blocks(left, right, batch_size, keep_qualities=keep_qual, expected_inner=expected, deviation=deviation)
+            return
         for path, split in o["queries"]:
             yield from hostio.read_batches(path, None, batch_size, split=split, keep_qualities=keep_qual)
         for left, right, expected, deviation in o["paired"]:
@@ -328,8 +342,18 @@ def native_source(o, batch_size, job):
     if first is None:
         raise UsageError("no queries found")
     job.callback(first.close)
-    max_len = int(first.mate_length.max())
-    return itertools.chain([first], rest), 3 if len(first) >= batch_size else 1, int(first.mate_count.max()) == 1 and max_len <= 320, max_len
+    max_len = max(first.longest_line, 1) if on_gpu else int(first.mate_length.max())
+    single = not first.paired if on_gpu else int(first.mate_count.max()) == 1
+    return itertools.chain([first], rest), 3 if len(first) >= batch_size else 1, single and max_len <= 320, max_len
+
+
+@contextlib.contextmanager
+def strict_form_hint():
+    """--parse-on-gpu: a query file the device parser does not take ends the job with the library's message and the way out."""
+    try:
+        yield
+    except hostio.StrictFormError as e:
+        raise UsageError("%s; run without --parse-on-gpu" % e) from e
 
 
 class ObjectBatch:
@@ -410,7 +434,7 @@ def stream(db, batches, params, sink, depth, on_aligned=None, tally=None):
     def feed():
         for b in batches:
             in_flight.put(b)
-            yield b.arrays()
+            yield b if isinstance(b, hostio.TextBlock) else b.arrays()  # (a text block is staged by the context that gets it: align_stream)
 
     def write_loop():  # (after a failure it keeps taking what comes, unwritten, up to the end mark: the main thread never waits on a full queue for good)
         for b, r in iter(to_write.get, None):
@@ -483,6 +507,7 @@ def run(argv, out=sys.stdout, open_database=None):
     batch_size = o.get("batch_size") or 1_000_000
     per_object = bool(o.get("out_mutations") or o.get("out_refs_map_count") or o.get("per_object"))  # (the outputs that need objects)
     with contextlib.ExitStack() as job:  # what the job opens is closed here, last opened first, also when a step raises
+        job.enter_context(strict_form_hint())
         batches, count, single_short, max_len = object_source(o, batch_size) if per_object else native_source(o, batch_size, job)
         devices = context_devices(o, count, single_short)
         # (--out-mutations: every context accumulates its own pile-up on its GPU - depth 8 B, four alternative counts 32 B and, with a query-end fraction, the

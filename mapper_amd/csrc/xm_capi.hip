@@ -8,7 +8,7 @@
 // on the CPU; the C entries for indexes, contexts, batches and alignment (a first context is opened by openFirstContext, whichever entry asks).
 // Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_result_stage.h (ResultStage: the result arenas,
 // the scan and gather kernels, the canonical streams; throwFailedQuery), xm_conf_table.h (the host's confidence table), xm_capi_probe.h (seed-probe and
-// random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries).
+// random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries), xm_capi_fastq.h (a batch staged from FASTQ text: the kernels of xm_fastq.h).
 // The big kernels are objects of their own, reached through launch functions: the lane-per-read align kernel is xm_align_kernel.hip (xmAlignLaunch,
 // xm_kernel_common.h), the wave-per-read kernels are xm_wave_kernel.hip (xmWaveLaunch, xm_kernel_args.h), the index build on the device is
 // xm_index_device.hip.  This unit uses the host-side pieces of the shared headers only (makeCaps, searchPoolBytes, the pass planner's sizes):
@@ -22,6 +22,7 @@
 #include "xm_kernel_common.h"
 #include "xm_pass_plan.h"
 #include "xm_collapse.h"
+#include "xm_fastq.h"
 #include "xm_memo.h"
 #include "xm_conf_table.h"
 #include "xm_device_rt.h"
@@ -238,6 +239,21 @@ struct DeviceBatch {
     nq = n;
   }
   BatchView view() const { return BatchView{nq, mateCount.p, mateOffset.p, mateLength.p, codes.p, expected.p, deviation.p}; }
+};
+
+// What xm_batch_stage_fastq works with besides the staged batch (xm_fastq.h; xm_capi_fastq.h): the text of a block in HBM, the line ends and the fields of its
+// records, the scans' block sums, and the names and qualities built for the host.  Empty until the first such call of the context.
+struct FastqStage {
+  DevBuf<char> dText[2];
+  DevBuf<int32_t> dLineEnd[2], dTileCount[2];
+  DevBuf<FastqMate> dMates;
+  DevBuf<long long> dBlockSums;
+  DevBuf<FastqCtl> dCtl;
+  DevBuf<int64_t> dNameOff, dQualOff;
+  DevBuf<uint8_t> dHasQual;
+  DevBuf<char> dNames, dQuals;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // on the GPU's staging stream: text up | stages 1-3 | (host sizes the arrays) | stage 4 | arrays down
+  ~FastqStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 // What the lane-per-read passes of a call work with besides the batch and the result stage: the work lists the lanes file unfinished reads into and the
@@ -461,6 +477,7 @@ struct xm_index {
   int64_t residentGen = 0;     // which resident batch: a call's streams belong to one (ResultStage::lastStreams)
   std::mutex stageMu;
   hipEvent_t cev0 = nullptr, cev1 = nullptr;  // this context's events on the GPU's staging stream (DeviceTables::copyStream)
+  FastqStage fastq;            // xm_batch_stage_fastq's buffers (under stageMu)
 
   void initContext() {  // stream and events of this context (the device tables exist)
     dt->contexts.fetch_add(1);
@@ -998,7 +1015,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 5; }
+int32_t xm_abi_version(void) { return 6; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();
@@ -1503,3 +1520,4 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 #include "xm_capi_probe.h"
 #include "xm_capi_pileup.h"
 #include "xm_capi_test.h"
+#include "xm_capi_fastq.h"

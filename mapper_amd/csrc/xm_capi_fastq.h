@@ -1,0 +1,186 @@
+// xm_batch_stage_fastq (included once, by xm_capi.hip): the staged batch built from FASTQ text by the kernels of xm_fastq.h.  What xm_batch_stage does -
+// stageMu, the context's `staged` DeviceBatch, the GPU's staging stream - with the text copied up instead of the arrays, and the arrays, names and
+// qualities copied down into pinned buffers for the host's writers.  The host does no work per record but the facts it needs of the returned
+// mate lengths (validateBatch: longest mate, any pair, the lengths the confidence table is seeded for).
+#pragma once
+
+namespace {
+
+// xm_fastq_batch plus what xm_fastq_batch_free needs to know about its buffers
+struct FastqBox {
+  xm_fastq_batch pub;
+  size_t bytes[9];
+};
+
+void freeFastqBox(FastqBox* box) {
+  xm_fastq_batch& b = box->pub;
+  void* const bufs[9] = {b.mate_count, b.mate_offset, b.mate_length, b.codes, b.names, b.name_off, b.quals, b.qual_off, b.has_qual};
+  for (int i = 0; i < 9; i++) g_pinned->put(bufs[i], box->bytes[i]);
+  free(box);
+}
+
+std::string fastqWhere(int file, long long record) { return "file " + std::to_string(file + 1) + " record " + std::to_string(record) + ": "; }
+
+// the stages of xm_fastq.h on stream s, up to the totals (queued; the caller waits for ev[2])
+void fastqParse(FastqStage& f, DeviceBatch& d, const xm_fastq_text* t, const FastqText texts[2], int64_t nq, bool paired, bool keepQual, hipStream_t s) {
+  const long long slots = 2 * nq;
+  FastqCtl ctl0;
+  memset(&ctl0, 0, sizeof(ctl0));
+  ctl0.firstError = XM_FASTQ_NO_ERROR;
+  HIP_CHECK(hipEventRecord(f.ev[0], s));
+  HIP_CHECK(hipMemcpyAsync(f.dCtl.p, &ctl0, sizeof(ctl0), hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(f.dText[0].p, t->text1, (size_t)t->bytes1, hipMemcpyHostToDevice, s));
+  if (paired) HIP_CHECK(hipMemcpyAsync(f.dText[1].p, t->text2, (size_t)t->bytes2, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipEventRecord(f.ev[1], s));
+  for (int k = 0; k < (paired ? 2 : 1); k++) {
+    const long long nTiles = (texts[k].bytes + XM_FASTQ_TILE_BYTES - 1) / XM_FASTQ_TILE_BYTES;
+    hipLaunchKernelGGL(xm_fastq_count_kernel, dim3((unsigned)nTiles), dim3(256), 0, s, texts[k]);
+    hipLaunchKernelGGL(xm_fastq_tiles_kernel, dim3(1), dim3(256), 0, s, texts[k], nTiles, k, f.dCtl.p);
+    hipLaunchKernelGGL(xm_fastq_ends_kernel, dim3((unsigned)nTiles), dim3(256), 0, s, texts[k]);
+  }
+  FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, f.dHasQual.p, f.dCtl.p};
+  hipLaunchKernelGGL(xm_fastq_fields_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, texts[0], texts[1], (long long)nq, paired ? 1 : 0, t->expected_inner, t->deviation, out);
+  const long long nBlocks = (slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
+  int64_t* qualOff = keepQual ? f.dQualOff.p : nullptr;
+  hipLaunchKernelGGL(xm_fastq_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, f.dBlockSums.p);
+  hipLaunchKernelGGL(xm_fastq_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, slots, f.dBlockSums.p, f.dNameOff.p, qualOff, f.dCtl.p);
+  hipLaunchKernelGGL(xm_fastq_offsets_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, (const long long*)f.dBlockSums.p, d.mateOffset.p,
+                     f.dNameOff.p, qualOff);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(f.ev[2], s));
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t xm_fastq_tile_bytes(void) { return XM_FASTQ_TILE_BYTES; }
+
+void xm_fastq_batch_free(xm_fastq_batch* b) {
+  if (b) freeFastqBox((FastqBox*)b);  // pub is the first member
+}
+
+int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch** outBatch) {
+  if (!idx || !t || !outBatch) return fail("xm_batch_stage_fastq: null argument");
+  *outBatch = nullptr;
+  if (idx->hostOnly) return fail("xm_batch_stage_fastq: index was built with host_only=1");
+  const bool paired = t->text2 != nullptr;
+  const bool keepQual = t->keep_qualities != 0;
+  const long long maxBytes = 1ll << 30;
+  if (!t->text1 || t->records1 < 1 || t->bytes1 < 1 || t->bytes1 > maxBytes) return fail("xm_batch_stage_fastq: file 1 record 0: a text holds 1 .. 2^30 bytes and at least one record");
+  if (paired && (t->records2 < 1 || t->bytes2 < 1 || t->bytes2 > maxBytes)) return fail("xm_batch_stage_fastq: file 2 record 0: a text holds 1 .. 2^30 bytes and at least one record");
+  if (paired && t->records1 != t->records2) {
+    const long long fewer = std::min(t->records1, t->records2);
+    return fail("xm_batch_stage_fastq: " + fastqWhere(t->records1 < t->records2 ? 0 : 1, fewer) + "paired texts have different numbers of records (" + std::to_string(t->records1) + ", " +
+                std::to_string(t->records2) + ")");
+  }
+  if (t->records1 > (1ll << 28)) return fail("xm_batch_stage_fastq: file 1 record 0: too many records for one text");
+  FastqBox* box = nullptr;
+  try {
+    std::lock_guard<std::mutex> stageLock(idx->stageMu);
+    DeviceBatch& d = idx->staged;
+    FastqStage& f = idx->fastq;
+    const int64_t nq = t->records1;
+    const long long slots = 2 * nq;
+    d.nq = -1;
+    d.h2dMs = 0;
+    HIP_CHECK(hipSetDevice(idx->device));
+    for (hipEvent_t& e : f.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+    box = (FastqBox*)calloc(1, sizeof(FastqBox));
+    if (!box) throw std::runtime_error("out of host memory");
+    xm_fastq_batch& b = box->pub;
+    // everything that is sized by the records and the bytes (a buffer that grows frees the old one, which waits for the device: before the stream is taken)
+    FastqText texts[2];
+    memset(texts, 0, sizeof(texts));
+    for (int k = 0; k < (paired ? 2 : 1); k++) {
+      const long long bytes = k ? t->bytes2 : t->bytes1, records = k ? t->records2 : t->records1;
+      f.dText[k].ensure((size_t)((bytes + 15) & ~15ll));
+      f.dLineEnd[k].ensure((size_t)(4 * records + 1));
+      f.dTileCount[k].ensure((size_t)((bytes + XM_FASTQ_TILE_BYTES - 1) / XM_FASTQ_TILE_BYTES));
+      texts[k] = FastqText{f.dText[k].p, bytes, records, f.dLineEnd[k].p, f.dTileCount[k].p};
+    }
+    f.dMates.ensure((size_t)slots); f.dHasQual.ensure((size_t)slots); f.dCtl.ensure(1);
+    f.dBlockSums.ensure((size_t)(3 * ((slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK)));
+    f.dNameOff.ensure((size_t)slots + 1);
+    if (keepQual) f.dQualOff.ensure((size_t)slots + 1);
+    d.mateCount.ensure((size_t)nq); d.mateOffset.ensure((size_t)slots); d.mateLength.ensure((size_t)slots);
+    d.expected.ensure((size_t)nq); d.deviation.ensure((size_t)nq);
+    b.num_queries = nq;
+    b.mate_count = (int32_t*)g_pinned->get(sizeof(int32_t) * (size_t)nq, &box->bytes[0]);
+    b.mate_offset = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)slots, &box->bytes[1]);
+    b.mate_length = (int32_t*)g_pinned->get(sizeof(int32_t) * (size_t)slots, &box->bytes[2]);
+    b.name_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[5]);
+    if (keepQual) {
+      b.qual_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[7]);
+      b.has_qual = (uint8_t*)g_pinned->get((size_t)slots, &box->bytes[8]);
+    }
+    // text up, stages 1 to 3, the control words down
+    FastqCtl ctl;
+    idx->dt->onStagingStream([&](hipStream_t s) {
+      fastqParse(f, d, t, texts, nq, paired, keepQual, s);
+      HIP_CHECK(hipMemcpyAsync(&ctl, f.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));  // (under the stream's lock: the copy lands in this frame)
+    });
+    // (a record that is not of the strict form comes first: an empty line between two records also makes the line count wrong)
+    if (ctl.firstError != XM_FASTQ_NO_ERROR)
+      throw std::runtime_error(fastqWhere((int)(ctl.firstError >> 48), (long long)((ctl.firstError >> 8) & 0xFFFFFFFFFFull)) + fastqErrorText((int)(ctl.firstError & 0xFF)));
+    for (int k = 0; k < (paired ? 2 : 1); k++)
+      if (ctl.lines[k] != 4 * texts[k].records)
+        throw std::runtime_error(fastqWhere(k, std::min(ctl.lines[k] / 4, texts[k].records)) + fastqErrorText(XM_FQ_LINE_COUNT) + " (" + std::to_string(ctl.lines[k]) + " lines, " +
+                                 std::to_string(texts[k].records) + " records announced)");
+    // the arrays the totals size, stage 4, everything down
+    const size_t nCodes = (size_t)ctl.totals[0], nNames = (size_t)ctl.totals[1], nQuals = (size_t)ctl.totals[2];
+    d.codes.ensure(nCodes);
+    f.dNames.ensure(nNames);
+    if (keepQual) f.dQuals.ensure(nQuals);
+    b.codes_length = (int64_t)nCodes;
+    b.codes = (uint8_t*)g_pinned->get(nCodes, &box->bytes[3]);
+    b.names = (char*)g_pinned->get(nNames, &box->bytes[4]);
+    if (keepQual) b.quals = (char*)g_pinned->get(nQuals, &box->bytes[6]);
+    idx->dt->onStagingStream([&](hipStream_t s) {
+      HIP_CHECK(hipEventRecord(f.ev[3], s));
+      hipLaunchKernelGGL(xm_fastq_gather_kernel, dim3((unsigned)((slots + 3) / 4)), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, (const char*)f.dText[0].p, (const char*)f.dText[1].p,
+                         (const int64_t*)d.mateOffset.p, (const int64_t*)f.dNameOff.p, (const int64_t*)(keepQual ? f.dQualOff.p : nullptr), d.codes.p, f.dNames.p,
+                         keepQual ? f.dQuals.p : nullptr);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(f.ev[4], s));
+      HIP_CHECK(hipMemcpyAsync(b.mate_count, d.mateCount.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(b.mate_offset, d.mateOffset.p, sizeof(int64_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(b.mate_length, d.mateLength.p, sizeof(int32_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(b.name_off, f.dNameOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
+      if (nCodes) HIP_CHECK(hipMemcpyAsync(b.codes, d.codes.p, nCodes, hipMemcpyDeviceToHost, s));
+      if (nNames) HIP_CHECK(hipMemcpyAsync(b.names, f.dNames.p, nNames, hipMemcpyDeviceToHost, s));
+      if (keepQual) {
+        HIP_CHECK(hipMemcpyAsync(b.qual_off, f.dQualOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(b.has_qual, f.dHasQual.p, (size_t)slots, hipMemcpyDeviceToHost, s));
+        if (nQuals) HIP_CHECK(hipMemcpyAsync(b.quals, f.dQuals.p, nQuals, hipMemcpyDeviceToHost, s));
+      }
+      HIP_CHECK(hipEventRecord(f.ev[5], s));
+    });
+    HIP_CHECK(hipEventSynchronize(f.ev[5]));
+    float up = 0, parse = 0, gather = 0, down = 0;
+    HIP_CHECK(hipEventElapsedTime(&up, f.ev[0], f.ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&parse, f.ev[1], f.ev[2]));
+    HIP_CHECK(hipEventElapsedTime(&gather, f.ev[3], f.ev[4]));
+    HIP_CHECK(hipEventElapsedTime(&down, f.ev[4], f.ev[5]));
+    b.h2d_ms = up; b.kernel_ms = (double)parse + gather; b.d2h_ms = down;
+    // the host's facts of the batch, from the returned mate lengths
+    xm_query_batch view;
+    memset(&view, 0, sizeof(view));
+    view.num_queries = nq; view.mate_count = b.mate_count; view.mate_offset = b.mate_offset; view.mate_length = b.mate_length; view.codes = b.codes; view.codes_length = b.codes_length;
+    bool anyPaired = false;
+    const int maxLen = validateBatch(&view, &anyPaired, &d.lens);
+    d.anyPaired = anyPaired;
+    idx->ensureTablesFor(maxLen);  // (tables that grow wait for the launches that read them: DeviceTables::rw)
+    d.maxLen = maxLen;
+    d.h2dMs = up;
+    d.nq = nq;
+    *outBatch = &box->pub;
+    return 0;
+  } catch (std::exception& e) {
+    if (box) freeFastqBox(box);
+    return fail(std::string("xm_batch_stage_fastq: ") + e.what());
+  }
+}
+
+}  // extern "C"

@@ -1,0 +1,281 @@
+// FASTQ text -> the batch arrays, in HBM (xm_batch_stage_fastq).  The host hands over blocks of whole four-line records as read from the
+// file (one text for single reads, two for pairs); the kernels below find the lines, apply the rules of xm_fastq_rules.h to every record, and build
+// what xm_batch_stage copies up (mateCount, mateOffset, mateLength, codes, expected, deviation) plus the names and qualities the host's writers read.
+// Separate launches, because no launch reads what another workgroup of the same launch wrote (the per-XCD L2s are not coherent):
+//   1 line ends   xm_fastq_count_kernel    a tile of XM_FASTQ_TILE_BYTES per block, 16 bytes per lane: the '\n' of the tile are counted
+//                 xm_fastq_tiles_kernel    one block: exclusive scan of the tile counts = the line index of each tile's first newline; a text that does
+//                                          not end in '\n' gets a virtual line end at `bytes`
+//                 xm_fastq_ends_kernel     the tile's lanes again: every newline writes its position to lineEnd[its line index]
+//   2 fields      xm_fastq_fields_kernel   a lane per mate slot: the four line bounds of its record -> name, sequence, quality (fastqRecord); the first
+//                                          record that is not of the strict form is kept with atomicMin on (file, record)
+//   3 offsets     xm_fastq_sums_kernel, xm_fastq_blocks_kernel, xm_fastq_offsets_kernel
+//                                          exclusive scans of the sequence, name and quality lengths in batch order (the three-kernel scan of
+//                                          xm_result_stage.h with three values); the host reads the totals to size codes, names, quals
+//   4 gather      xm_fastq_gather_kernel   a wave per mate, the code table in LDS: bases translated into codes, name and quality bytes copied, 64 bytes a round
+// Plain HIP.  Everything is sized by the host from `records` and `bytes`: lineEnd holds 4 * records + 1 entries, stage 1 writes no entry behind them and
+// stage 2 reads none that was not written, whatever the text holds; a text whose line count is not 4 * records is an error the host sees in FastqCtl.
+#pragma once
+#include "xm_fastq_rules.h"
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace xm {
+
+constexpr int XM_FASTQ_LANE_BYTES = 16;
+constexpr int XM_FASTQ_TILE_BYTES = 256 * XM_FASTQ_LANE_BYTES;  // (xm_fastq_tile_bytes(): tests/test_gpu_fastq.py walks the edges this gives)
+constexpr int XM_FASTQ_SCAN_PER_THREAD = 16;
+constexpr int XM_FASTQ_SCAN_PER_BLOCK = 256 * XM_FASTQ_SCAN_PER_THREAD;  // mate slots per block of the offset scan
+constexpr unsigned long long XM_FASTQ_NO_ERROR = ~0ull;
+
+// what the host reads back after stage 3
+struct FastqCtl {
+  unsigned long long firstError;  // XM_FASTQ_NO_ERROR, or (file << 48) | (record << 8) | FastqError of the lowest (file, record) that is not of the strict form
+  long long lines[2];             // lines found in each text
+  long long totals[3];            // bases, name bytes, quality bytes of the batch
+};
+
+struct FastqText {
+  const char* text;     // allocated up to the next multiple of 16 bytes
+  long long bytes, records;
+  int32_t* lineEnd;     // [4 * records + 1]
+  int32_t* tileCount;   // [tiles] newlines of each tile, then (xm_fastq_tiles_kernel) the line index of its first one
+};
+
+// a mate slot's fields as stage 2 leaves them for stages 3 and 4: positions in its file's text
+struct FastqMate {
+  long long nameAt, seqAt, qualAt;
+  int32_t nameLen, seqLen, qualLen, file;
+};
+
+// bit 7 of every byte of the word that is '\n' (exact: no carry crosses a byte)
+__device__ __forceinline__ uint32_t fastqNewlineBits(uint32_t w) {
+  const uint32_t x = w ^ 0x0A0A0A0Au;
+  const uint32_t t = (x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
+  return ~(t | x | 0x7F7F7F7Fu);
+}
+
+// the lane's 16 bytes of the text as newline bits per word (bytes behind the text never count); -> how many
+__device__ __forceinline__ int fastqLaneNewlines(const FastqText& t, long long at, uint32_t bits[4]) {
+  bits[0] = bits[1] = bits[2] = bits[3] = 0;
+  if (at >= t.bytes) return 0;
+  const uint4 v = *reinterpret_cast<const uint4*>(t.text + at);  // (the allocation is padded to 16 bytes)
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  const long long valid = t.bytes - at;  // > 0
+  int n = 0;
+  for (int k = 0; k < 4; k++) {
+    uint32_t b = fastqNewlineBits(w[k]);
+    const long long left = valid - 4 * k;  // bytes of this word inside the text
+    if (left <= 0) b = 0;
+    else if (left < 4) b &= (1u << (8 * (int)left)) - 1u;
+    bits[k] = b;
+    n += __popc(b);
+  }
+  return n;
+}
+
+__global__ void __launch_bounds__(256) xm_fastq_count_kernel(FastqText t) {
+  __shared__ int sh[256];
+  uint32_t bits[4];
+  const long long at = (long long)blockIdx.x * XM_FASTQ_TILE_BYTES + (long long)threadIdx.x * XM_FASTQ_LANE_BYTES;
+  sh[threadIdx.x] = fastqLaneNewlines(t, at, bits);
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) t.tileCount[blockIdx.x] = sh[0];
+}
+
+// one block: tileCount[] becomes its exclusive scan; lines found (with the virtual one) -> ctl->lines[file]
+__global__ void __launch_bounds__(256) xm_fastq_tiles_kernel(FastqText t, long long nTiles, int file, FastqCtl* ctl) {
+  __shared__ long long sh[256];
+  const long long per = (nTiles + 255) / 256;
+  const long long a = (long long)threadIdx.x * per, b = a + per < nTiles ? a + per : nTiles;
+  long long mine = 0;
+  for (long long i = a; i < b; i++) mine += t.tileCount[i];
+  sh[threadIdx.x] = mine;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the 256 thread totals
+    long long x = 0;
+    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
+    __syncthreads();
+    sh[threadIdx.x] += x;
+    __syncthreads();
+  }
+  long long run = sh[threadIdx.x] - mine;
+  for (long long i = a; i < b; i++) { const int c = t.tileCount[i]; t.tileCount[i] = (int32_t)run; run += c; }  // (a text holds less than 2^31 bytes)
+  if (threadIdx.x == 0) {
+    long long lines = sh[255];
+    if (t.bytes > 0 && t.text[t.bytes - 1] != '\n') {  // the last block of a file may lack the final newline
+      if (lines < 4 * t.records + 1) t.lineEnd[lines] = (int32_t)t.bytes;
+      lines++;
+    }
+    ctl->lines[file] = lines;
+  }
+}
+
+__global__ void __launch_bounds__(256) xm_fastq_ends_kernel(FastqText t) {
+  __shared__ int sh[256];
+  uint32_t bits[4];
+  const long long at = (long long)blockIdx.x * XM_FASTQ_TILE_BYTES + (long long)threadIdx.x * XM_FASTQ_LANE_BYTES;
+  const int mine = fastqLaneNewlines(t, at, bits);
+  sh[threadIdx.x] = mine;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    int x = 0;
+    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
+    __syncthreads();
+    sh[threadIdx.x] += x;
+    __syncthreads();
+  }
+  long long line = (long long)t.tileCount[blockIdx.x] + sh[threadIdx.x] - mine;
+  const long long cap = 4 * t.records + 1;
+  for (int k = 0; k < 4; k++) {
+    uint32_t b = bits[k];
+    while (b) {
+      const int byte = (__ffs((int)b) - 1) >> 3;
+      b &= b - 1;
+      if (line < cap) t.lineEnd[line] = (int32_t)(at + 4 * k + byte);
+      line++;
+    }
+  }
+}
+
+// What stage 2 writes: the fields of every mate slot, and of the batch arrays what needs no offsets.
+struct FastqFieldsOut {
+  FastqMate* mates;        // [2 nq]
+  int32_t* mateCount;      // [nq]
+  int32_t* mateLength;     // [2 nq]
+  double* expected;        // [nq]
+  double* deviation;       // [nq]
+  uint8_t* hasQual;        // [2 nq]
+  FastqCtl* ctl;
+};
+
+__global__ void __launch_bounds__(256) xm_fastq_fields_kernel(FastqText t0, FastqText t1, long long nq, int paired, double expectedInner, double deviation, FastqFieldsOut out) {
+  const long long slot = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= 2 * nq) return;
+  const long long q = slot >> 1;
+  const int file = paired ? (int)(slot & 1) : 0;
+  FastqMate m;
+  m.nameAt = m.seqAt = m.qualAt = 0;
+  m.nameLen = m.seqLen = m.qualLen = 0;
+  m.file = file;
+  const bool padding = fastqPaddingMate(slot, paired != 0);
+  if ((slot & 1) == 0) {
+    out.mateCount[q] = paired ? 2 : 1;
+    out.expected[q] = paired ? expectedInner : 0.0;  // (a single query: expected inner distance 0, deviation 1, as hostio.Batch gives them)
+    out.deviation[q] = paired ? deviation : 1.0;
+  }
+  const FastqText& t = file ? t1 : t0;
+  // a text that does not hold four lines per record (the host sees it in ctl->lines and stages nothing): the records whose four line ends were found and
+  // kept are still looked at, so that an empty line between two records is named where it stands
+  const long long l = 4 * q;
+  const long long found = out.ctl->lines[file], kept = 4 * t.records + 1;
+  if (!padding && l + 3 < (found < kept ? found : kept)) {
+    const long long s0 = l == 0 ? 0 : (long long)t.lineEnd[l - 1] + 1;
+    const long long e0 = t.lineEnd[l], e1 = t.lineEnd[l + 1], e2 = t.lineEnd[l + 2], e3 = t.lineEnd[l + 3];
+    FastqFields f;
+    const int err = fastqRecord(t.text, s0, e0, e0 + 1, e1, e2 + 1, e3, f);
+    if (err != XM_FQ_OK) atomicMin(&out.ctl->firstError, ((unsigned long long)file << 48) | ((unsigned long long)q << 8) | (unsigned long long)err);
+    else {
+      m.nameAt = f.nameAt; m.seqAt = f.seqAt; m.qualAt = f.qualAt;
+      m.nameLen = (int32_t)f.nameLen; m.seqLen = (int32_t)f.seqLen; m.qualLen = (int32_t)f.qualLen;
+    }
+  }
+  out.mates[slot] = m;
+  out.mateLength[slot] = m.seqLen;
+  out.hasQual[slot] = padding ? 0 : 1;
+}
+
+// ---- stage 3: the scans (xm_result_stage.h's, over three values; without qualities the third is 0)
+__device__ __forceinline__ void fastqLens(const FastqMate& m, int keepQual, long long v[3]) { v[0] = m.seqLen; v[1] = m.nameLen; v[2] = keepQual ? m.qualLen : 0; }
+
+__global__ void __launch_bounds__(256) xm_fastq_sums_kernel(long long slots, const FastqMate* mates, int keepQual, long long* blockSums) {
+  __shared__ long long sh[3][256];
+  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
+  long long a[3] = {0, 0, 0};
+  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < slots) {
+    long long v[3];
+    fastqLens(mates[base + k], keepQual, v);
+    a[0] += v[0]; a[1] += v[1]; a[2] += v[2];
+  }
+  for (int j = 0; j < 3; j++) sh[j][threadIdx.x] = a[j];
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) for (int j = 0; j < 3; j++) sh[j][threadIdx.x] += sh[j][threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) blockSums[3 * (long long)blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+__global__ void xm_fastq_blocks_kernel(long long nBlocks, long long slots, long long* blockSums, int64_t* nameOff, int64_t* qualOff, FastqCtl* ctl) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  long long run[3] = {0, 0, 0};
+  for (long long i = 0; i < nBlocks; i++)
+    for (int j = 0; j < 3; j++) { const long long x = blockSums[3 * i + j]; blockSums[3 * i + j] = run[j]; run[j] += x; }
+  for (int j = 0; j < 3; j++) ctl->totals[j] = run[j];
+  nameOff[slots] = run[1];
+  if (qualOff) qualOff[slots] = run[2];
+}
+
+__global__ void __launch_bounds__(256) xm_fastq_offsets_kernel(long long slots, const FastqMate* mates, int keepQual, const long long* blockSums, int64_t* mateOffset, int64_t* nameOff,
+                                                               int64_t* qualOff) {
+  __shared__ long long sh[3][256];
+  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
+  long long a[3] = {0, 0, 0};
+  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < slots) {
+    long long v[3];
+    fastqLens(mates[base + k], keepQual, v);
+    a[0] += v[0]; a[1] += v[1]; a[2] += v[2];
+  }
+  for (int j = 0; j < 3; j++) sh[j][threadIdx.x] = a[j];
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    long long x[3] = {0, 0, 0};
+    if ((int)threadIdx.x >= d) for (int j = 0; j < 3; j++) x[j] = sh[j][threadIdx.x - d];
+    __syncthreads();
+    for (int j = 0; j < 3; j++) sh[j][threadIdx.x] += x[j];
+    __syncthreads();
+  }
+  long long off[3];
+  for (int j = 0; j < 3; j++) off[j] = blockSums[3 * (long long)blockIdx.x + j] + sh[j][threadIdx.x] - a[j];
+  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < slots) {
+    long long v[3];
+    fastqLens(mates[base + k], keepQual, v);
+    mateOffset[base + k] = v[0] > 0 ? off[0] : 0;  // (the padding mate of a single query: offset 0)
+    nameOff[base + k] = off[1];
+    if (qualOff) qualOff[base + k] = off[2];
+    off[0] += v[0]; off[1] += v[1]; off[2] += v[2];
+  }
+}
+
+// ---- stage 4: a wave per mate slot, four to a block
+__global__ void __launch_bounds__(256) xm_fastq_gather_kernel(long long slots, const FastqMate* mates, const char* text0, const char* text1, const int64_t* mateOffset, const int64_t* nameOff,
+                                                              const int64_t* qualOff, uint8_t* codes, char* names, char* quals) {
+  __shared__ uint8_t table[256];
+  table[threadIdx.x] = fastqCode((unsigned char)threadIdx.x);
+  __syncthreads();
+  const long long slot = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const int lane = (int)(threadIdx.x & 63u);
+  if (slot >= slots) return;
+  const FastqMate m = mates[slot];
+  const char* text = m.file ? text1 : text0;
+  if (m.seqLen > 0) {
+    const unsigned char* src = (const unsigned char*)text + m.seqAt;
+    uint8_t* dst = codes + mateOffset[slot];
+    for (int i = lane; i < m.seqLen; i += 64) dst[i] = table[src[i]];
+  }
+  if (m.nameLen > 0) {
+    const char* src = text + m.nameAt;
+    char* dst = names + nameOff[slot];
+    for (int i = lane; i < m.nameLen; i += 64) dst[i] = src[i];
+  }
+  if (quals && m.qualLen > 0) {
+    const char* src = text + m.qualAt;
+    char* dst = quals + qualOff[slot];
+    for (int i = lane; i < m.qualLen; i += 64) dst[i] = src[i];
+  }
+}
+
+}  // namespace xm

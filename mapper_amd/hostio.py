@@ -96,6 +96,127 @@ def read_batches(path1, path2=None, batch_size=1_000_000, split=0, keep_qualitie
         L.xmio_close(r)
 
 
+class StrictFormError(ValueError):
+    """The query files are not what the device parser takes (four-line FASTQ records, '@' headers, 1 .. 30000 bases): the message names file and place."""
+
+
+class XmioTextBlock(C.Structure):
+    _fields_ = [("text1", C.c_void_p), ("bytes1", C.c_int64), ("records1", C.c_int64), ("longest1", C.c_int64),
+                ("text2", C.c_void_p), ("bytes2", C.c_int64), ("records2", C.c_int64), ("longest2", C.c_int64), ("store", C.c_void_p)]
+
+
+def _text_lib():
+    L = lib()
+    if not hasattr(L, "_xm_text_ready"):
+        L.xmio_text_open.restype = C.c_void_p
+        L.xmio_text_open.argtypes = [C.c_char_p, C.c_char_p]
+        L.xmio_text_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.POINTER(XmioTextBlock))]
+        L.xmio_text_block_free.argtypes = [C.POINTER(XmioTextBlock)]
+        L.xmio_text_block_free.restype = None
+        L.xmio_text_close.argtypes = [C.c_void_p]
+        L.xmio_text_close.restype = None
+        L._xm_text_ready = True
+    return L
+
+
+class TextBlock:
+    """A block of whole four-line FASTQ records as text (one file's, or a pair's in step), for api.ReferenceDatabase.stage_fastq: the GPU parses it.  Before it
+    is staged it offers num_queries and longest_line (an upper bound of the longest mate); once staged - the text is released then - it offers what Batch
+    does: the six arrays(), mate_count / mate_offset / mate_length / codes, and a _ptr that Writer.write takes (an XmioBatch over the arrays the library
+    returned, store NULL).  block[k] is the mates of query k, as pileup.MatchDatabase.add_last(queries=block) reads them."""
+
+    def __init__(self, ptr, keep_qualities, expected_inner, deviation):
+        self._text = ptr
+        t = ptr.contents
+        self.num_queries = int(t.records1)
+        self.paired = bool(t.text2)
+        self.longest_line = int(max(t.longest1, t.longest2))
+        self.keep_qualities = bool(keep_qualities)
+        self.pair_spacing = (float(expected_inner), float(deviation))
+        self._ptr = self._staged = self._free = None
+        self.times_ms = None
+
+    def text(self, which=0):
+        """The bytes of file `which` in this block (before it is staged)."""
+        t = self._text.contents
+        return C.string_at(t.text2 if which else t.text1, t.bytes2 if which else t.bytes1)
+
+    def records(self, which=0):
+        t = self._text.contents
+        return int(t.records2 if which else t.records1)
+
+    def attach(self, staged, free):
+        """stage_fastq's result: `staged` points to the library's xm_fastq_batch, free(staged) gives it back."""
+        self._release_staged()
+        f = staged.contents
+        n = self.num_queries
+        self._staged, self._free = staged, free
+        self._batch = XmioBatch(n, f.mate_count, f.mate_offset, f.mate_length, f.codes, f.codes_length, f.names, f.name_off, f.quals, f.qual_off, f.has_qual, None)
+        self._ptr = C.pointer(self._batch)
+        self.mate_count = np.ctypeslib.as_array(f.mate_count, shape=(n,))
+        self.mate_offset = np.ctypeslib.as_array(f.mate_offset, shape=(2 * n,))
+        self.mate_length = np.ctypeslib.as_array(f.mate_length, shape=(2 * n,))
+        self.codes = np.ctypeslib.as_array(f.codes, shape=(max(int(f.codes_length), 1),))
+        paired = self.mate_count > 1
+        self.expected_inner = np.where(paired, self.pair_spacing[0], 0.0)
+        self.deviation = np.where(paired, self.pair_spacing[1], 1.0)
+        self.times_ms = {"h2d": f.h2d_ms, "kernel": f.kernel_ms, "d2h": f.d2h_ms}
+        self._release_text()
+
+    def arrays(self):
+        if self._ptr is None:
+            raise ValueError("the block has not been staged (ReferenceDatabase.stage_fastq)")
+        return self.mate_count, self.mate_offset, self.mate_length, self.codes, self.expected_inner, self.deviation
+
+    def __len__(self):
+        return self.num_queries
+
+    def __getitem__(self, k):
+        self.arrays()
+        return [self.codes[self.mate_offset[2 * k + m]:self.mate_offset[2 * k + m] + self.mate_length[2 * k + m]] for m in range(int(self.mate_count[k]))]
+
+    def _release_text(self):
+        if self._text is not None:
+            lib().xmio_text_block_free(self._text)
+            self._text = None
+
+    def _release_staged(self):
+        if self._staged is not None:
+            self._ptr = None
+            self.mate_count = self.mate_offset = self.mate_length = self.codes = None
+            self._free(self._staged)
+            self._staged = None
+
+    def close(self):
+        self._release_text()
+        self._release_staged()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def read_text_blocks(path1, path2=None, batch_size=1_000_000, keep_qualities=False, expected_inner=0.0, deviation=1.0):
+    """Generator of TextBlock objects over a four-line FASTQ file (or a pair of them, cut in step): whole records as text, at most batch_size of them."""
+    L = _text_lib()
+    r = L.xmio_text_open(os.fsencode(path1), os.fsencode(path2) if path2 else None)
+    if not r:
+        raise OSError(L.xmio_last_error().decode())
+    r = C.c_void_p(r)
+    try:
+        while True:
+            ptr = C.POINTER(XmioTextBlock)()
+            if L.xmio_text_next(r, int(batch_size), C.byref(ptr)):
+                raise StrictFormError(L.xmio_last_error().decode())
+            if not ptr:
+                return
+            yield TextBlock(ptr, keep_qualities, expected_inner, deviation)
+    finally:
+        L.xmio_text_close(r)
+
+
 class Writer:
     """SAM records (and the unaligned-query file) of the batches of a job, written in query order through file descriptors; keeps Mapper.run's statistics."""
 

@@ -9,6 +9,7 @@
 // SequenceSplitter.java:9-38, the statistics of Mapper.run :786-796.  What they do not show follows the SAM specification and is marked [unpinned] in
 // mapper_amd/sam.py, whose records() this formatter reproduces byte for byte (tests/test_hostio.py compares the two on random result streams).
 #include "../../include/xmapper_hostio.h"
+#include "../csrc/xm_fastq_rules.h"
 #include <zlib.h>
 #include <algorithm>
 #include <atomic>
@@ -16,11 +17,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 #include <unistd.h>
 #include <fcntl.h>
+#include <sys/stat.h>
 
 namespace {
 
@@ -68,11 +71,11 @@ struct Source {
     return true;
   }
   void close() { if (f) gzclose(f); f = nullptr; if (fd >= 0) ::close(fd); fd = -1; }
-  bool fill() {  // keeps [pos, end), reads more behind it
+  bool fill(size_t most = 1u << 30) {  // keeps [pos, end), reads more behind it (at most `most` bytes)
     if (eof) return false;
     if (pos > 0) { memmove(buf.data(), buf.data() + pos, end - pos); end -= pos; pos = 0; }
     if (end == buf.size()) buf.resize(buf.size() * 2);
-    const size_t room = std::min<size_t>(buf.size() - end, 1u << 30);
+    const size_t room = std::min<size_t>(buf.size() - end, most);
     long n = f ? (long)gzread(f, buf.data() + end, (unsigned)room) : (long)::read(fd, buf.data() + end, room);
     if (n <= 0) { eof = true; return false; }
     end += (size_t)n;
@@ -324,6 +327,195 @@ int xmio_next(xmio_reader* r, int64_t max_queries, xmio_batch** out) {
   b->names = st->names.data(); b->name_off = st->nameOff.data();
   b->quals = r->keepQual ? st->quals.data() : nullptr; b->qual_off = r->keepQual ? st->qualOff.data() : nullptr; b->has_qual = r->keepQual ? st->hasQual.data() : nullptr;
   *out = b;
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- cutting (text blocks for the device parser: the rules are ../csrc/xm_fastq_rules.h)
+namespace {
+
+constexpr int64_t kTextBlockLimit = 1ll << 30;  // bytes of one file in one block
+constexpr size_t kTextFillBytes = 4u << 20;     // what the cutter reads at a time
+constexpr size_t kTextBufferBytes = 8u << 20;   // the smallest buffer of a source (Source::open)
+
+// The buffers the blocks' texts live in go round: a block of most of a source's buffer takes the buffer itself instead of a copy, the source goes on
+// in another one, and a freed block's buffer waits here for the next source that needs one (its pages are mapped: no faults on the way).
+std::mutex g_bufferMu;
+std::vector<std::vector<char>> g_buffers;
+std::vector<char> takeBuffer(size_t atLeast) {
+  {
+    std::lock_guard<std::mutex> lock(g_bufferMu);
+    for (size_t i = 0; i < g_buffers.size(); i++)
+      if (g_buffers[i].size() >= atLeast) { std::vector<char> b; b.swap(g_buffers[i]); g_buffers.erase(g_buffers.begin() + (long)i); return b; }
+  }
+  return std::vector<char>(std::max(atLeast, kTextBufferBytes));
+}
+void giveBuffer(std::vector<char>& b) {
+  if (b.size() < kTextBufferBytes) return;
+  std::lock_guard<std::mutex> lock(g_bufferMu);
+  size_t held = b.size();
+  for (const auto& x : g_buffers) held += x.size();
+  if (g_buffers.size() < 4 && held <= ((size_t)2 << 30)) { g_buffers.emplace_back(); g_buffers.back().swap(b); }  // (at most four, and 2 GiB, wait)
+}
+
+// What the next block takes of a source: found without taking anything (the pair's other file may allow fewer records, then this is done again).
+struct Cut {
+  int64_t records = 0, bytes = 0, longest = 0;
+  size_t consume = 0;   // bytes the source gives up: `bytes`, and at the end of the input the empty lines behind them
+  bool atEnd = false;   // the source ended within this scan
+};
+
+// Whole records from src.pos on: line ends are found with memchr, every fourth ends a record.  Records of nothing but empty lines at the end of the
+// block are left for the next one, which drops them if the input ends there.  false: the file ends inside a record, or a record is larger than a block.
+bool scanBlock(Source& src, int64_t maxRecords, Cut& c) {
+  c = Cut();
+  size_t off = 0, lineAt[4] = {0, 0, 0, 0}, lineTo[4] = {0, 0, 0, 0};  // (relative to src.pos: fill() moves the buffer)
+  int inRecord = 0;  // complete lines of the record in progress
+  bool someText = false;
+  int64_t records = 0, bytes = 0, longest = 0, fullRecords = 0, fullBytes = 0;  // all records so far | up to the last one that is more than empty lines
+  int64_t bytesAtMax = 0;
+  while (records < maxRecords || fullRecords == 0) {  // (records of nothing but empty lines: on to the text behind them, or to the end, where they are dropped)
+    const char* base = src.buf.data() + src.pos;
+    const size_t avail = src.end - src.pos;
+    const char* nl = off < avail ? (const char*)memchr(base + off, '\n', avail - off) : nullptr;
+    if (!nl) {
+      // a full buffer grows at once to what the block will need, as far as the records so far and the rest of a plain file tell (else fill() doubles it,
+      // and every doubling copies what is there)
+      if (src.pos == 0 && src.end == src.buf.size() && records >= 256 && src.fd >= 0) {
+        struct stat st;
+        const off_t at = lseek(src.fd, 0, SEEK_CUR);
+        if (fstat(src.fd, &st) == 0 && at >= 0) {
+          const double perRecord = (double)bytes / (double)records;
+          size_t want = (size_t)std::min<double>(perRecord * 1.125 * (double)maxRecords, (double)kTextBlockLimit) + 2 * kTextFillBytes;
+          want = std::min<size_t>(want, src.end + (size_t)std::max<off_t>(st.st_size - at, 0) + kTextFillBytes);
+          if (want > 2 * src.buf.size()) src.buf.resize(want);
+        }
+      }
+      if (!src.fill(kTextFillBytes)) { c.atEnd = true; break; }  // (a few MiB at a time: the lines are looked for while they are in the cache)
+      continue;
+    }
+    const size_t e = (size_t)(nl - base);
+    lineAt[inRecord] = off; lineTo[inRecord] = e;
+    if (!xm::fastqEmptyLine(base, (long long)off, (long long)e)) someText = true;
+    off = e + 1;
+    if (++inRecord < 4) continue;
+    if ((int64_t)off > kTextBlockLimit) {
+      if (records > 0) break;  // the block is full
+      g_error = src.path + ": a FASTQ record of more than 1 GiB at line " + std::to_string(src.line + 1);
+      return false;
+    }
+    records++; bytes = (int64_t)off;
+    if (records == maxRecords) bytesAtMax = bytes;
+    longest = std::max(longest, (int64_t)(lineTo[1] - lineAt[1]));
+    if (someText) { fullRecords = records; fullBytes = bytes; }
+    inRecord = 0; someText = false;
+  }
+  if (c.atEnd) {
+    const char* base = src.buf.data() + src.pos;
+    const size_t avail = src.end - src.pos;
+    int n = inRecord;
+    if (inRecord < 4 && off < avail) { lineAt[n] = off; lineTo[n] = avail; n++; }  // a last line without its newline
+    while (n > 0 && xm::fastqEmptyLine(base, (long long)lineAt[n - 1], (long long)lineTo[n - 1])) n--;  // trailing empty lines are dropped
+    if (n == 4) {  // (three lines and the one without newline)
+      if ((int64_t)avail > kTextBlockLimit && records > 0) { c.atEnd = false; }
+      else { records++; bytes = (int64_t)avail; longest = std::max(longest, (int64_t)(lineTo[1] - lineAt[1])); fullRecords = records; fullBytes = bytes; }
+    } else if (n > 0) {
+      g_error = src.path + ": the file ends after " + std::to_string(n) + " of the 4 lines of a FASTQ record, at line " + std::to_string(src.line + 4 * records + n);
+      return false;
+    }
+    if (c.atEnd) { c.records = fullRecords; c.bytes = fullBytes; c.longest = longest; c.consume = avail; return true; }
+  }
+  if (fullRecords > maxRecords) { fullRecords = maxRecords; fullBytes = bytesAtMax; }  // (a block of empty lines with text behind them: the parser will name them)
+  c.records = fullRecords; c.bytes = fullBytes; c.longest = longest; c.consume = (size_t)fullBytes;
+  return true;
+}
+
+struct TextStore { std::vector<char> a, b; };
+
+}  // namespace
+
+struct xmio_text_reader {
+  Source a, b;
+  bool paired = false;
+};
+
+extern "C" {
+
+xmio_text_reader* xmio_text_open(const char* path1, const char* path2) {
+  xmio_text_reader* r = new xmio_text_reader();
+  if (!path1 || !r->a.open(path1)) { g_error = std::string("cannot open ") + (path1 ? path1 : "(null)"); delete r; return nullptr; }
+  if (path2) {
+    if (!r->b.open(path2)) { g_error = std::string("cannot open ") + path2; r->a.close(); delete r; return nullptr; }
+    r->paired = true;
+  }
+  auto adopt = [](Source& src) {  // a waiting buffer that is larger than the fresh one: the source starts in it, and need not grow to a block's size again
+    std::lock_guard<std::mutex> lock(g_bufferMu);
+    for (size_t i = 0; i < g_buffers.size(); i++)
+      if (g_buffers[i].size() > src.buf.size()) { src.buf.swap(g_buffers[i]); g_buffers.erase(g_buffers.begin() + (long)i); return; }
+  };
+  adopt(r->a);
+  if (r->paired) adopt(r->b);
+  return r;
+}
+
+void xmio_text_close(xmio_text_reader* r) {
+  if (!r) return;
+  r->a.close(); r->b.close();
+  giveBuffer(r->a.buf); giveBuffer(r->b.buf);
+  delete r;
+}
+
+void xmio_text_block_free(xmio_text_block* b) {
+  if (!b) return;
+  TextStore* st = (TextStore*)b->store;
+  if (st) { giveBuffer(st->a); giveBuffer(st->b); }
+  delete st;
+  delete b;
+}
+
+int xmio_text_next(xmio_text_reader* r, int64_t max_queries, xmio_text_block** out) {
+  *out = nullptr;
+  if (max_queries < 1) return fail("xmio_text_next: max_queries must be >= 1");
+  Cut a, b;
+  if (!scanBlock(r->a, max_queries, a)) return -1;
+  if (r->paired) {
+    if (!scanBlock(r->b, a.records > 0 ? a.records : 1, b)) return -1;
+    if ((a.records == 0) != (b.records == 0) || (b.records < a.records && b.atEnd))
+      return fail("paired query files have different numbers of reads: " + r->a.path + ", " + r->b.path);
+    if (b.records < a.records && !scanBlock(r->a, b.records, a)) return -1;  // (the second file's block was full first)
+    if (a.records != b.records) return fail("paired query files cannot be cut in step: " + r->a.path + ", " + r->b.path);
+  }
+  // -> where the block's text lies: in the source's buffer, which the block then owns (the source gets another one with what is left), or in a copy
+  auto take = [](Source& src, const Cut& c, std::vector<char>& hold) -> const char* {
+    const char* text = src.buf.data() + src.pos;
+    const size_t avail = src.end - src.pos, rest = avail - c.consume;
+    src.line += 4 * c.records;
+    if ((size_t)c.bytes < kTextBufferBytes / 2 || rest > (size_t)c.bytes / 4) {  // a small block, or one of several in the buffer
+      hold.assign(text, text + c.bytes);
+      src.pos += c.consume;
+      return hold.data();
+    }
+    std::vector<char> next = takeBuffer(src.buf.size());  // (as large as the one that goes: the next block will need as much, and a buffer that grows is copied)
+    memcpy(next.data(), text + c.consume, rest);
+    hold.swap(src.buf);   // (a swap keeps the bytes where they are: `text` stays valid)
+    src.buf.swap(next);
+    src.pos = 0; src.end = rest;
+    return text;
+  };
+  if (a.records == 0) {  // the end of the input (what is left is empty lines)
+    r->a.pos += a.consume;
+    if (r->paired) r->b.pos += b.consume;
+    return 0;
+  }
+  TextStore* st = new TextStore();
+  const char* text1 = take(r->a, a, st->a);
+  const char* text2 = r->paired ? take(r->b, b, st->b) : nullptr;
+  xmio_text_block* blk = new xmio_text_block();
+  blk->store = st;
+  blk->text1 = text1; blk->bytes1 = a.bytes; blk->records1 = a.records; blk->longest1 = a.longest;
+  blk->text2 = text2; blk->bytes2 = r->paired ? b.bytes : 0; blk->records2 = r->paired ? b.records : 0; blk->longest2 = r->paired ? b.longest : 0;
+  *out = blk;
   return 0;
 }
 
