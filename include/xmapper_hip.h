@@ -123,7 +123,8 @@ const char* xm_last_error(void);
 const char* xm_build_stamp(void);
 /* Version of this header's structs and entry points: 2 = xm_result.extra[] appended, xm_seed_probe_packed replaces xm_seed_probe; 3 = xm_context_set_collapse,
  * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6]; 5 = xm_memory_new, xm_context_attach_memory, xm_memory_info,
- * xm_memory_free, xm_result.reserved carries the wait for a memory; 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes.  A binding checks it once
+ * xm_memory_free, xm_result.reserved carries the wait for a memory; 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7 = xm_sam_set_contigs,
+ * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles).  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -268,6 +269,26 @@ void xm_fastq_batch_free(xm_fastq_batch* batch);
 /* Bytes of text per workgroup of the kernels that find the line ends (test hook: tests/test_gpu_fastq.py puts newlines on both sides of the edges it gives). */
 int32_t xm_fastq_tile_bytes(void);
 
+/* (ABI version 7) The SAM records of the last align call formatted on the GPU: the output-side counterpart of xm_batch_stage_fastq.  When an align call
+ * returns, its four streams and its batch are still in HBM; kernels walk them there and build the text that the harness's host formatter
+ * (xmio_write_batch, include/xmapper_hostio.h) builds from the copied streams, byte for byte: one line per sequence of every alignment, in query order, no
+ * header.  The host is left with writing the bytes.  Not used by the Java host, which keeps its own writers.
+ * xm_sam_set_contigs: the RNAME / RNEXT names, once per context, before the first format call; num_contigs must be the index's.
+ * xm_sam_format_last has the contract of xm_pileup_add_last: it serialises with the context's other calls, runs on the context's stream, and fails with
+ * "no longer resident" once another batch has been uploaded or committed.  names == NULL: the names that xm_batch_stage_fastq built, which belong to the
+ * batch in HBM (they change hands with it in xm_batch_commit); a batch that was staged from arrays has none, and the call fails.  Otherwise the mates'
+ * names as xmio_batch holds them - name_off has 2 * num_queries + 1 entries, mate m of query q is names[name_off[2q + m] .. name_off[2q + m + 1]) - which
+ * are copied up and may be pageable memory.  A slice that is not of the layout above (xmio_write_batch's "malformed result streams") fails the call with the
+ * lowest such query in xm_last_error and no text.  *out: the text in a page-locked buffer of the library's pool (not NUL-terminated), its bytes and records
+ * (lines), and the times of the call's three parts - names up, kernels, text down; released with xm_sam_text_free.  An unaligned query adds nothing. */
+typedef struct xm_sam_names { const char* names; const int64_t* name_off; } xm_sam_names;
+typedef struct xm_sam_text { char* text; int64_t bytes, records; double h2d_ms, kernel_ms, d2h_ms; void* store; } xm_sam_text;
+int xm_sam_set_contigs(xm_index* context, int32_t num_contigs, const char* const* names);
+int xm_sam_format_last(xm_index* context, const xm_sam_names* names, xm_sam_text** out);
+void xm_sam_text_free(xm_sam_text* text);
+/* Bytes of text per tile of the kernel that writes the records (test hook: tests/test_gpu_sam.py puts record ends on both sides of the multiples). */
+int32_t xm_sam_tile_bytes(void);
+
 /* Bulk form of Readable_HashBlock_Database.getNumMatchesLowerBound + matchBlock / PackedMap.get (PackedMap.java:160-172,
  * 228-236) for n (used_length, lookup key) pairs: counts[i] = number of stored positions, -1 when the bucket is overfull or
  * holds more than the table's limit, -2 when used_length is not a hashed length.  Positions (at most max_per_probe <= 15 per probe, not reverse-complemented): the
@@ -339,7 +360,17 @@ void xm_test_bound_counters(int64_t* out3);
  * (PathAligner.java:169), cells it computed.  tests/test_gpu_bound.py compares with the oracle's observer of the same bound, which also runs the search. */
 int xm_test_bound(int32_t device, const xm_params* params, const uint8_t* query, int32_t query_length, int32_t query_rc, int32_t start_a, int32_t end_a, const uint8_t* reference,
                   int32_t reference_length, int32_t start_b, int32_t end_b, int32_t predicted_best_offset, int32_t pair, int64_t* out3);
-
+/* Test-only (tests/test_gpu_sam.py): the kernels of xm_sam_format_last over host-given arrays - a batch with its names, contig names and the four result
+ * streams - on `device`; no index and no alignment.  Same result, same errors. */
+typedef struct xm_test_sam_job {
+  int64_t num_queries; const int32_t* mate_count; const int64_t* mate_offset; const int32_t* mate_length; const uint8_t* codes; int64_t codes_length;
+  const char* names; const int64_t* name_off;
+  int32_t num_contigs, reserved; const char* const* contig_names;
+  const int32_t* ints; const double* dbls; const int64_t* int_off; const int64_t* dbl_off;
+} xm_test_sam_job;
+int xm_test_sam_format(int32_t device, const xm_test_sam_job* job, xm_sam_text** out);
+/* Test-only: Double.toString as the SAM tags print it, run by the device on n values: out24[24 * i ...] the string of x[i] (padded with NUL), len[i] its length. */
+int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,8 @@ void xmio_close(xmio_reader* reader);
  * they came with qualities, else FASTA) to unaligned_fd; either descriptor may be -1.  Query order; `threads` formatting threads.  Adds to *stats. */
 int xmio_write_batch(const xmio_batch* batch, const int32_t* ints, const double* dbls, const int64_t* int_off, const int64_t* dbl_off, int32_t num_contigs,
                      const char* const* contig_names, int32_t sam_fd, int32_t unaligned_fd, int32_t threads, xmio_stats* stats);
+/* Wall seconds of the calling thread's last xmio_write_batch call: formatting and counting, and the write() calls (either may be NULL). */
+void xmio_last_write_seconds(double* format_seconds, double* file_seconds);
 
 /* The query files cut into blocks of whole four-line FASTQ records, as text, for a parser that is not this library's (xm_batch_stage_fastq of
  * include/xmapper_hip.h builds the batch arrays from such a block on the GPU).  The cutter looks for line ends only: no base is translated and nothing is

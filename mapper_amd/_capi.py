@@ -54,7 +54,24 @@ class XmFastqBatch(C.Structure):
                 ("h2d_ms", C.c_double), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double)]
 
 
-ABI_VERSION = 6  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes
+class XmSamNames(C.Structure):
+    """xm_sam_names: the mates' names as hostio.XmioBatch holds them (name_off has 2 * num_queries + 1 entries)."""
+    _fields_ = [("names", C.c_void_p), ("name_off", C.c_void_p)]
+
+
+class XmSamText(C.Structure):
+    """xm_sam_text: the SAM records of a batch in a pinned buffer of the library, and the times of the call's three parts."""
+    _fields_ = [("text", C.c_void_p), ("bytes", C.c_int64), ("records", C.c_int64), ("h2d_ms", C.c_double), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("store", C.c_void_p)]
+
+
+class XmTestSamJob(C.Structure):
+    """xm_test_sam_job (test-only): a batch with its names, contig names and the four result streams, all on the host."""
+    _fields_ = [("num_queries", C.c_int64), ("mate_count", C.c_void_p), ("mate_offset", C.c_void_p), ("mate_length", C.c_void_p), ("codes", C.c_void_p), ("codes_length", C.c_int64),
+                ("names", C.c_void_p), ("name_off", C.c_void_p), ("num_contigs", C.c_int32), ("reserved", C.c_int32), ("contig_names", C.POINTER(C.c_char_p)),
+                ("ints", C.c_void_p), ("dbls", C.c_void_p), ("int_off", C.c_void_p), ("dbl_off", C.c_void_p)]
+
+
+ABI_VERSION = 7  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles
 
 
 class XmIndexInfo(C.Structure):
@@ -65,7 +82,7 @@ class XmIndexInfo(C.Structure):
 
 
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
-           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_stage_fastq", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_free"]
+           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_stage_fastq", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_free"]
 
 
 def build_library(force=False):
@@ -150,6 +167,12 @@ def lib():
         L.xm_batch_stage_fastq.argtypes = [C.c_void_p, C.POINTER(XmFastqText), C.POINTER(C.POINTER(XmFastqBatch))]
         L.xm_fastq_batch_free.argtypes = [C.POINTER(XmFastqBatch)]
         L.xm_fastq_batch_free.restype = None
+        L.xm_sam_set_contigs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]
+        L.xm_sam_format_last.argtypes = [C.c_void_p, C.POINTER(XmSamNames), C.POINTER(C.POINTER(XmSamText))]
+        L.xm_sam_text_free.argtypes = [C.POINTER(XmSamText)]
+        L.xm_sam_text_free.restype = None
+        L.xm_test_sam_format.argtypes = [C.c_int32, C.POINTER(XmTestSamJob), C.POINTER(C.POINTER(XmSamText))]
+        L.xm_test_format_doubles.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.xm_align_resident.argtypes = [C.c_void_p, C.POINTER(XmParams), C.POINTER(C.POINTER(XmResult))]
         L.xm_seed_probe_packed.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.xm_measure_random_gather.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_double)]

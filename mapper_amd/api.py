@@ -6,6 +6,7 @@ include/xmapper_hip.h.  Everything is aligned on the GPU by libxmapper_hip.so; t
 """
 import ctypes as C
 import os
+import time
 import numpy as np
 
 from . import _capi, hostio
@@ -155,6 +156,40 @@ class BatchResult:
         return decode_streams(self.ints, self.dbls, self.int_off, self.dbl_off, q)
 
 
+class SamText:
+    """The SAM records of one batch as ReferenceDatabase.format_sam_last built them: `bytes` of text (no header) in a page-locked buffer of the library, `records`
+    lines, and the milliseconds of the call's three parts (names up, kernels, text down).  memoryview(text) / text.view() reads it without a copy, bytes(text)
+    copies it; close() gives the buffer back."""
+
+    def __init__(self, L, ptr):
+        self._L, self._ptr = L, ptr
+        t = ptr.contents
+        self.bytes, self.records = int(t.bytes), int(t.records)
+        self.h2d_ms, self.kernel_ms, self.d2h_ms = t.h2d_ms, t.kernel_ms, t.d2h_ms
+
+    def view(self):
+        if self._ptr is None:
+            raise ValueError("the text has been closed")
+        return memoryview((C.c_char * self.bytes).from_address(self._ptr.contents.text)).cast("B") if self.bytes else memoryview(b"")
+
+    def __bytes__(self):
+        return bytes(self.view())
+
+    def __len__(self):
+        return self.bytes
+
+    def close(self):
+        if self._ptr is not None:
+            self._L.xm_sam_text_free(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _check(rc, prefix=""):
     """A C entry that returns non-zero has left its message in xm_last_error."""
     if rc:
@@ -220,6 +255,11 @@ class ReferenceDatabase:
         self._h = h
         if self.cache_file is not None:
             self.save(self.cache_file)
+
+    def _tick(self, phase, seconds):
+        """Host seconds this context has spent staging batches, in align calls and in format_sam_last (`seconds`: what the command line's phases sum up)."""
+        held = self.__dict__.setdefault("seconds", {"stage": 0.0, "align": 0.0, "format": 0.0})
+        held[phase] += seconds
 
     def save(self, path):
         """xm_index_save: the reference, every table hashed so far and the duplication map into one file."""
@@ -373,6 +413,26 @@ class ReferenceDatabase:
         block.attach(out, self._L.xm_fastq_batch_free)
         return block
 
+    def set_sam_contigs(self, names):
+        """xm_sam_set_contigs: the contig names of the SAM records format_sam_last builds (RNAME, RNEXT), one per contig of the index in its order; once per context."""
+        arr = (C.c_char_p * len(names))(*[n.encode() if isinstance(n, str) else bytes(n) for n in names])
+        _check(self._L.xm_sam_set_contigs(self._h, len(names), arr))
+
+    def format_sam_last(self, batch=None):
+        """xm_sam_format_last: the SAM records of the last align call, formatted on the GPU from the result streams and the batch where they lie in HBM, while
+        the batch is still resident (align_stream's on_aligned hook is the place) -> SamText.  batch: where the mates' names come from - None: the names that
+        stage_fastq built, which are in HBM with the batch; else a hostio.Batch (or anything whose _ptr is a hostio.XmioBatch), whose names are copied up.
+        The bytes equal hostio.Writer's for the same batch and streams."""
+        t0 = time.perf_counter()
+        out = C.POINTER(_capi.XmSamText)()
+        names = None
+        if batch is not None:
+            raw = batch._ptr.contents
+            names = _capi.XmSamNames(raw.names, C.cast(raw.name_off, C.c_void_p))
+        _check(self._L.xm_sam_format_last(self._h, C.byref(names) if names is not None else None, C.byref(out)))
+        self._tick("format", time.perf_counter() - t0)
+        return SamText(self._L, out)
+
     def commit_staged(self):
         """xm_batch_commit: the staged batch becomes the resident one."""
         _check(self._L.xm_batch_commit(self._h))
@@ -393,10 +453,12 @@ class ReferenceDatabase:
                 for arrays in batches:
                     if stop.is_set():
                         break
+                    t0 = time.perf_counter()
                     if isinstance(arrays, hostio.TextBlock):  # FASTQ text: parsed on the GPU
                         self.stage_fastq(arrays)
                     else:
                         self.stage_arrays(*arrays)
+                    self._tick("stage", time.perf_counter() - t0)
                     if not first:
                         aligned.acquire()  # the previous batch has been aligned: its buffers may be swapped away
                         if stop.is_set():
@@ -418,7 +480,9 @@ class ReferenceDatabase:
                     break
                 if isinstance(token, BaseException):
                     raise token
+                t0 = time.perf_counter()
                 r = self.align_resident(parameters)
+                self._tick("align", time.perf_counter() - t0)
                 if on_aligned is not None:  # (while the batch and its result streams are still resident: pileup.MatchDatabase.add_last)
                     on_aligned(count)
                 count += 1

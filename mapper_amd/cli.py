@@ -17,7 +17,10 @@ outputs are the same, and one line on stderr says how many queries were served a
 it has aligned in that much HBM and serves byte-identical queries of its later batches from there: the same cache across batches; same outputs, one line on
 stderr), and --remember-queries-per-gpu <MiB> (one such memory per GPU, which all its contexts share and which keeps remembering when it is full; not
 together with --remember-queries), and --parse-on-gpu (the FASTQ files go to the GPU as text and are parsed there, api.ReferenceDatabase.stage_fastq: same outputs;
-four-line FASTQ records only, so a file the host reader takes may be refused with a message that says where; not with --per-object or a split size).
+four-line FASTQ records only, so a file the host reader takes may be refused with a message that says where; not with --per-object or a split size),
+--format-on-gpu (the SAM records are formatted on the GPU while a batch and its results are resident, api.ReferenceDatabase.format_sam_last, and the host
+only writes the bytes: same outputs; --out-unaligned stays with the host; not with --per-object, --out-mutations or --out-refs-map-count; nothing to do
+without --out-sam), and --format-threads <n> (threads of the host's SAM formatter).
 """
 import contextlib
 import gzip
@@ -194,6 +197,12 @@ def parse_args(argv):
             o["per_object"] = True
         elif a == "--parse-on-gpu":  # (not a Mapper flag) the query files are cut into blocks of whole FASTQ records on the host and parsed on the GPU (api.ReferenceDatabase.stage_fastq)
             o["parse_on_gpu"] = True
+        elif a == "--format-on-gpu":  # (not a Mapper flag) the SAM records are formatted on the GPU from the result streams while the batch is resident (api.ReferenceDatabase.format_sam_last)
+            o["format_on_gpu"] = True
+        elif a == "--format-threads":  # (not a Mapper flag) threads of the host's SAM formatter (hostio.Writer; default: the CPUs, 32 at the most)
+            o["format_threads"] = int(argv[i + 1]); i += 1
+            if o["format_threads"] < 1:
+                raise UsageError("--format-threads must be >= 1")
         elif a == "--device":  # (not a Mapper flag) which GPU
             o["device"] = int(argv[i + 1]); i += 1
         elif a == "--spacing":
@@ -209,6 +218,9 @@ def parse_args(argv):
         raise UsageError("--parse-on-gpu and --per-object exclude each other (the per-object path reads the queries into Python objects)")
     if o.get("parse_on_gpu") and any(split > 0 for _, split in o["queries"]):
         raise UsageError("--parse-on-gpu is not supported with --split-queries-past-size (the sections are cut by the host reader)")
+    for other, key in (("--per-object", "per_object"), ("--out-mutations", "out_mutations"), ("--out-refs-map-count", "out_refs_map_count")):
+        if o.get("format_on_gpu") and o.get(key):
+            raise UsageError("--format-on-gpu and %s exclude each other (that output goes through the per-object path, which formats on the host)" % other)
     if o.get("remember") and o.get("remember_per_gpu"):
         raise UsageError("--remember-queries (a memory per context) and --remember-queries-per-gpu (one per GPU) exclude each other")
     return o
@@ -421,49 +433,76 @@ class ObjectSink:
                 f.write("%s\t%d\n" % (",".join(key), count))
 
 
-def stream(db, batches, params, sink, depth, on_aligned=None, tally=None):
+def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format_on_gpu=False):
     """The job: the batches stream through the GPU contexts (align_stream: the copy of batch k + 1 overlaps the alignment of batch k; several contexts align
     side by side) and a writer thread hands each batch and its result streams to the sink while the next batches are being aligned; at most `depth` results
     wait for it.  Every batch taken from `batches` is closed, and the first exception - the reader's, the GPU's or the sink's - reaches the caller.
     -> the queries that were served as copies (BatchResult.copies); tally["remembered"], if given, grows by the ones served from the contexts' memories
-    (BatchResult.remembered)."""
+    (BatchResult.remembered).  format_on_gpu: the context that aligned a batch formats its SAM records while the batch is resident (format_sam_last, in the
+    on_aligned hook: between two align calls of that context), and the writer thread writes the text; tally["read"] grows by the seconds the feeder waited for
+    the reader."""
     in_flight = queue.Queue()  # batches in the order they were dealt to the GPUs
     to_write = queue.Queue(maxsize=depth)
     failure = []
+    dealt, texts = {}, {}      # by batch number: the batch on its way to a context; the text its context made of it
 
     def feed():
-        for b in batches:
+        it = iter(batches)
+        k = 0
+        while True:
+            t0 = time.perf_counter()
+            b = next(it, None)
+            if tally is not None:
+                tally["read"] = tally.get("read", 0.0) + time.perf_counter() - t0
+            if b is None:
+                return
             in_flight.put(b)
+            if format_on_gpu:
+                dealt[k] = b
+            k += 1
             yield b if isinstance(b, hostio.TextBlock) else b.arrays()  # (a text block is staged by the context that gets it: align_stream)
 
+    hook = on_aligned
+    if format_on_gpu:
+        def hook(*at):  # ReferenceDatabase.align_stream calls it with (batch), MultiGpuDatabase's with (replica, batch), on the replica's thread
+            b = dealt.pop(at[-1])
+            context = db.replicas[at[0]] if len(at) > 1 else db
+            texts[at[-1]] = context.format_sam_last(None if isinstance(b, hostio.TextBlock) else b)  # (a text block's names are in HBM with the batch)
+            if on_aligned is not None:
+                on_aligned(*at)
+
     def write_loop():  # (after a failure it keeps taking what comes, unwritten, up to the end mark: the main thread never waits on a full queue for good)
-        for b, r in iter(to_write.get, None):
+        for b, r, text in iter(to_write.get, None):
             try:
                 if not failure:
-                    sink.write(b, r)
+                    sink.write(b, r, **({"sam_text": text} if text is not None else {}))
             except BaseException as e:  # noqa: BLE001  (handed to the main thread)
                 failure.append(e)
             finally:
                 b.close()
+                if text is not None:
+                    text.close()
 
     wt = threading.Thread(target=write_loop, daemon=True)
     wt.start()
     copies = 0
-    results = db.align_stream(feed(), params, on_aligned=on_aligned)
+    results = db.align_stream(feed(), params, on_aligned=hook)
     try:
-        for r in results:
+        for k, r in enumerate(results):
             if failure:
                 break
             copies += r.copies
             if tally is not None:
                 tally["remembered"] = tally.get("remembered", 0) + r.remembered
-            to_write.put((in_flight.get(), r))
+            to_write.put((in_flight.get(), r, texts.pop(k, None)))
     finally:
         to_write.put(None)
         wt.join()
         results.close()  # (ends the threads that deal and upload: nothing takes from `batches` after this)
         while not in_flight.empty():
             in_flight.get().close()
+        for text in texts.values():
+            text.close()
     if failure:
         raise failure[0]
     return copies
@@ -516,16 +555,22 @@ def run(argv, out=sys.stdout, open_database=None):
         memo = {"memo_bytes": o["remember"]} if o.get("remember") else {}  # (--remember-queries: every context's memory, counted beside its scratch)
         if o.get("remember_per_gpu"):  # (--remember-queries-per-gpu: one memory per GPU, counted once per GPU when its contexts divide the scratch)
             memo = {"shared_memo_bytes": o["remember_per_gpu"]}
+        # (--format-on-gpu: every context keeps the text of a batch in HBM, and per query two counts and an offset; a record is the mate's bases and name and
+        # some 60 bytes of fields; with the host's names, those are copied up as well)
+        format_on_gpu = bool(o.get("format_on_gpu") and o["out_sam"]) and not per_object  # (without --out-sam there is nothing to format)
+        sam_text = batch_size * (2 * (max_len + 200) + 24) if format_on_gpu else 0
         db = (open_database or open_gpu_database)(ordered, devices, max_len, enable_gapmers=o["enable_gapmers"], collapse=o.get("collapse", False),
-                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0), **memo)
+                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0) + sam_text, **memo)
         job.callback(db.close)
+        if format_on_gpu:
+            db.set_sam_contigs(names)
         sam_out = un_out = None
         if o["out_sam"]:
             sam_out = sys.stdout if o["out_sam"] == "-" else job.enter_context(open(o["out_sam"], "w"))
             sam_out.write("\n".join(sam_header(contigs)) + "\n")
         if o["out_unaligned"]:
             un_out = job.enter_context(open(o["out_unaligned"], "w"))
-        sink = ObjectSink(names, sam_out, un_out, bool(o.get("out_refs_map_count"))) if per_object else hostio.Writer(names, sam_out, un_out)
+        sink = ObjectSink(names, sam_out, un_out, bool(o.get("out_refs_map_count"))) if per_object else hostio.Writer(names, sam_out, un_out, threads=o.get("format_threads"))
         match_db = on_aligned = None
         if o.get("out_mutations"):  # Mapper.java:700-708: the MatchDatabase listens to every batch; here it accumulates on the GPU while the batch is resident
             from . import pileup
@@ -536,7 +581,13 @@ def run(argv, out=sys.stdout, open_database=None):
                 match_db.add_last(batches[at[-1]].queries, replica=at[0] if len(at) > 1 else 0)
         t_stream = time.perf_counter()
         tally = {}
-        copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned, tally)
+        copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned, tally, format_on_gpu=format_on_gpu)
+        contexts = list(getattr(db, "replicas", [db]))
+        spent = lambda key: sum(getattr(c, "seconds", {}).get(key, 0.0) for c in contexts)  # noqa: E731
+        # seconds of the job by phase, summed over batches (and over contexts, which work side by side: the sum may exceed the wall time): the reader or cutter,
+        # staging (copy up, and the parse with --parse-on-gpu), the align calls, formatting SAM (on the host, or the GPU call with --format-on-gpu), file writes
+        phases = {"read": tally.get("read", 0.0), "stage": spent("stage"), "align": spent("align"),
+                  "format": spent("format") + getattr(sink, "seconds", {}).get("format", 0.0), "write": getattr(sink, "seconds", {}).get("write", 0.0)}
         if o.get("out_refs_map_count"):
             sink.write_refs_map(o["out_refs_map_count"])
         if match_db is not None:  # Mapper.java:758-785
@@ -547,7 +598,7 @@ def run(argv, out=sys.stdout, open_database=None):
                 match_db.write_mutations(f, filt)
     n = int(sink.stats.num_queries)
     global last_timing
-    last_timing = {"queries": n, "stream_seconds": time.perf_counter() - t_stream, "contexts": len(devices)}  # first batch to the GPUs .. last byte of the outputs (bench.py's end_to_end leg)
+    last_timing = {"queries": n, "stream_seconds": time.perf_counter() - t_stream, "contexts": len(devices), "phases": phases}  # first batch to the GPUs .. last byte of the outputs (bench.py's end_to_end leg)
     if o.get("collapse"):
         report_copies(copies, n)
     if o.get("remember") or o.get("remember_per_gpu"):

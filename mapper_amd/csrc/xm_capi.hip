@@ -8,7 +8,8 @@
 // on the CPU; the C entries for indexes, contexts, batches and alignment (a first context is opened by openFirstContext, whichever entry asks).
 // Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_result_stage.h (ResultStage: the result arenas,
 // the scan and gather kernels, the canonical streams; throwFailedQuery), xm_conf_table.h (the host's confidence table), xm_capi_probe.h (seed-probe and
-// random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries), xm_capi_fastq.h (a batch staged from FASTQ text: the kernels of xm_fastq.h).
+// random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries), xm_capi_fastq.h (a batch staged from FASTQ text: the kernels of xm_fastq.h),
+// xm_capi_sam.h (SAM records formatted from the resident results: the kernels of xm_sam.h).
 // The big kernels are objects of their own, reached through launch functions: the lane-per-read align kernel is xm_align_kernel.hip (xmAlignLaunch,
 // xm_kernel_common.h), the wave-per-read kernels are xm_wave_kernel.hip (xmWaveLaunch, xm_kernel_args.h), the index build on the device is
 // xm_index_device.hip.  This unit uses the host-side pieces of the shared headers only (makeCaps, searchPoolBytes, the pass planner's sizes):
@@ -23,6 +24,7 @@
 #include "xm_pass_plan.h"
 #include "xm_collapse.h"
 #include "xm_fastq.h"
+#include "xm_sam.h"
 #include "xm_memo.h"
 #include "xm_conf_table.h"
 #include "xm_device_rt.h"
@@ -205,6 +207,9 @@ struct DeviceBatch {
   DevBuf<int64_t> mateOffset;
   DevBuf<uint8_t> codes;
   DevBuf<double> expected, deviation;
+  DevBuf<char> names;         // the mates' names as xm_batch_stage_fastq built them (xmio_batch's layout: nameOff has 2 * nq + 1 entries), for xm_sam_format_last;
+  DevBuf<int64_t> nameOff;    // they belong to the batch, so that they swap with it in xm_batch_commit while the next block is staged
+  bool hasNames = false;      // false: a batch copied in from arrays, which have no names
   int64_t nq = -1;            // -1: no batch
   int maxLen = 0;             // longest mate
   bool anyPaired = false;
@@ -218,6 +223,7 @@ struct DeviceBatch {
     const int64_t n = b->num_queries;
     nq = -1;
     h2dMs = 0;
+    hasNames = false;
     if (n > 0) {
       mateCount.ensure((size_t)n); mateOffset.ensure((size_t)n * 2); mateLength.ensure((size_t)n * 2);
       codes.ensure((size_t)b->codes_length); expected.ensure((size_t)n); deviation.ensure((size_t)n);
@@ -242,18 +248,30 @@ struct DeviceBatch {
 };
 
 // What xm_batch_stage_fastq works with besides the staged batch (xm_fastq.h; xm_capi_fastq.h): the text of a block in HBM, the line ends and the fields of its
-// records, the scans' block sums, and the names and qualities built for the host.  Empty until the first such call of the context.
+// records, the scans' block sums, and the qualities built for the host (the names are the batch's: DeviceBatch).  Empty until the first such call of the context.
 struct FastqStage {
   DevBuf<char> dText[2];
   DevBuf<int32_t> dLineEnd[2], dTileCount[2];
   DevBuf<FastqMate> dMates;
   DevBuf<long long> dBlockSums;
   DevBuf<FastqCtl> dCtl;
-  DevBuf<int64_t> dNameOff, dQualOff;
+  DevBuf<int64_t> dQualOff;
   DevBuf<uint8_t> dHasQual;
-  DevBuf<char> dNames, dQuals;
+  DevBuf<char> dQuals;
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // on the GPU's staging stream: text up | stages 1-3 | (host sizes the arrays) | stage 4 | arrays down
   ~FastqStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+// What xm_sam_format_last works with (xm_sam.h; xm_capi_sam.h): the contig names, uploaded once per context; names the host handed in for a call; bytes and
+// records per query, the scan's block sums and the offsets; the control words; the text, which only grows; the call's events on the context's stream.
+struct SamStage {
+  int32_t numContigs = -1;     // -1: xm_sam_set_contigs has not been called
+  DevBuf<char> dContigNames, dNames, dText;
+  DevBuf<int64_t> dContigOff, dNameOff;
+  DevBuf<long long> dBytes, dRecords, dBlockSums, dOffset;
+  DevBuf<unsigned long long> dCtl;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // names up | measure and offsets | (host sizes the text) | write | text down
+  ~SamStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 // What the lane-per-read passes of a call work with besides the batch and the result stage: the work lists the lanes file unfinished reads into and the
@@ -478,6 +496,7 @@ struct xm_index {
   std::mutex stageMu;
   hipEvent_t cev0 = nullptr, cev1 = nullptr;  // this context's events on the GPU's staging stream (DeviceTables::copyStream)
   FastqStage fastq;            // xm_batch_stage_fastq's buffers (under stageMu)
+  SamStage sam;                // xm_sam_format_last's buffers (under mu)
 
   void initContext() {  // stream and events of this context (the device tables exist)
     dt->contexts.fetch_add(1);
@@ -1015,7 +1034,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 6; }
+int32_t xm_abi_version(void) { return 7; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();
@@ -1519,5 +1538,6 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 
 #include "xm_capi_probe.h"
 #include "xm_capi_pileup.h"
+#include "xm_capi_sam.h"
 #include "xm_capi_test.h"
 #include "xm_capi_fastq.h"

@@ -43,9 +43,9 @@ void fastqParse(FastqStage& f, DeviceBatch& d, const xm_fastq_text* t, const Fas
   const long long nBlocks = (slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
   int64_t* qualOff = keepQual ? f.dQualOff.p : nullptr;
   hipLaunchKernelGGL(xm_fastq_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, f.dBlockSums.p);
-  hipLaunchKernelGGL(xm_fastq_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, slots, f.dBlockSums.p, f.dNameOff.p, qualOff, f.dCtl.p);
+  hipLaunchKernelGGL(xm_fastq_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, slots, f.dBlockSums.p, d.nameOff.p, qualOff, f.dCtl.p);
   hipLaunchKernelGGL(xm_fastq_offsets_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, (const long long*)f.dBlockSums.p, d.mateOffset.p,
-                     f.dNameOff.p, qualOff);
+                     d.nameOff.p, qualOff);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipEventRecord(f.ev[2], s));
 }
@@ -84,6 +84,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     const long long slots = 2 * nq;
     d.nq = -1;
     d.h2dMs = 0;
+    d.hasNames = false;
     HIP_CHECK(hipSetDevice(idx->device));
     for (hipEvent_t& e : f.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
     box = (FastqBox*)calloc(1, sizeof(FastqBox));
@@ -101,7 +102,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     }
     f.dMates.ensure((size_t)slots); f.dHasQual.ensure((size_t)slots); f.dCtl.ensure(1);
     f.dBlockSums.ensure((size_t)(3 * ((slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK)));
-    f.dNameOff.ensure((size_t)slots + 1);
+    d.nameOff.ensure((size_t)slots + 1);
     if (keepQual) f.dQualOff.ensure((size_t)slots + 1);
     d.mateCount.ensure((size_t)nq); d.mateOffset.ensure((size_t)slots); d.mateLength.ensure((size_t)slots);
     d.expected.ensure((size_t)nq); d.deviation.ensure((size_t)nq);
@@ -131,7 +132,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     // the arrays the totals size, stage 4, everything down
     const size_t nCodes = (size_t)ctl.totals[0], nNames = (size_t)ctl.totals[1], nQuals = (size_t)ctl.totals[2];
     d.codes.ensure(nCodes);
-    f.dNames.ensure(nNames);
+    d.names.ensure(nNames);
     if (keepQual) f.dQuals.ensure(nQuals);
     b.codes_length = (int64_t)nCodes;
     b.codes = (uint8_t*)g_pinned->get(nCodes, &box->bytes[3]);
@@ -140,16 +141,16 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     idx->dt->onStagingStream([&](hipStream_t s) {
       HIP_CHECK(hipEventRecord(f.ev[3], s));
       hipLaunchKernelGGL(xm_fastq_gather_kernel, dim3((unsigned)((slots + 3) / 4)), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, (const char*)f.dText[0].p, (const char*)f.dText[1].p,
-                         (const int64_t*)d.mateOffset.p, (const int64_t*)f.dNameOff.p, (const int64_t*)(keepQual ? f.dQualOff.p : nullptr), d.codes.p, f.dNames.p,
+                         (const int64_t*)d.mateOffset.p, (const int64_t*)d.nameOff.p, (const int64_t*)(keepQual ? f.dQualOff.p : nullptr), d.codes.p, d.names.p,
                          keepQual ? f.dQuals.p : nullptr);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipEventRecord(f.ev[4], s));
       HIP_CHECK(hipMemcpyAsync(b.mate_count, d.mateCount.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipMemcpyAsync(b.mate_offset, d.mateOffset.p, sizeof(int64_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipMemcpyAsync(b.mate_length, d.mateLength.p, sizeof(int32_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(b.name_off, f.dNameOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(b.name_off, d.nameOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
       if (nCodes) HIP_CHECK(hipMemcpyAsync(b.codes, d.codes.p, nCodes, hipMemcpyDeviceToHost, s));
-      if (nNames) HIP_CHECK(hipMemcpyAsync(b.names, f.dNames.p, nNames, hipMemcpyDeviceToHost, s));
+      if (nNames) HIP_CHECK(hipMemcpyAsync(b.names, d.names.p, nNames, hipMemcpyDeviceToHost, s));
       if (keepQual) {
         HIP_CHECK(hipMemcpyAsync(b.qual_off, f.dQualOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(b.has_qual, f.dHasQual.p, (size_t)slots, hipMemcpyDeviceToHost, s));
@@ -174,6 +175,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     idx->ensureTablesFor(maxLen);  // (tables that grow wait for the launches that read them: DeviceTables::rw)
     d.maxLen = maxLen;
     d.h2dMs = up;
+    d.hasNames = true;
     d.nq = nq;
     *outBatch = &box->pub;
     return 0;

@@ -100,4 +100,74 @@ int xm_test_local_align(int32_t device, int32_t chain, int32_t mode, const xm_pa
   } catch (std::exception& e) { fail(std::string("xm_test_local_align: ") + e.what()); return -1; }
 }
 
+// Test-only entry (tests/test_gpu_sam.py): xm_sam_format_last's kernels over host-given batch arrays, names, contig names and result streams - no index and
+// no alignment.  The host checks what the kernels take on trust from the library's own stages: counts, mates inside codes, offsets that never fall.
+int xm_test_sam_format(int32_t device, const xm_test_sam_job* t, xm_sam_text** out) {
+  if (!t || !out) return fail("xm_test_sam_format: null argument");
+  *out = nullptr;
+  try {
+    const int64_t nq = t->num_queries;
+    if (nq < 0 || t->num_contigs < 0 || t->codes_length < 0) throw std::runtime_error("negative size");
+    if (!t->mate_count || !t->mate_offset || !t->mate_length || !t->names || !t->name_off || !t->contig_names || !t->int_off || !t->dbl_off) throw std::runtime_error("null array");
+    for (int64_t q = 0; q < nq; q++) {
+      if (t->mate_count[q] < 1 || t->mate_count[q] > 2) throw std::runtime_error("mate_count must be 1 or 2");
+      for (int m = 0; m < t->mate_count[q]; m++) {
+        const int32_t len = t->mate_length[2 * q + m];
+        if (len < 0 || t->mate_offset[2 * q + m] < 0 || t->mate_offset[2 * q + m] + len > t->codes_length) throw std::runtime_error("mate outside of codes");
+      }
+    }
+    if (t->int_off[0] != 0 || t->dbl_off[0] != 0) throw std::runtime_error("stream offsets must start at 0");
+    for (int64_t q = 0; q < nq; q++) if (t->int_off[q + 1] < t->int_off[q] || t->dbl_off[q + 1] < t->dbl_off[q]) throw std::runtime_error("stream offsets fall");
+    const size_t nInts = (size_t)t->int_off[nq], nDbls = (size_t)t->dbl_off[nq];
+    if ((nInts && !t->ints) || (nDbls && !t->dbls) || (t->codes_length && !t->codes)) throw std::runtime_error("null array");
+    if (device >= 0) HIP_CHECK(hipSetDevice(device));
+    SamStage g;
+    samUploadContigs(g, t->num_contigs, t->contig_names);
+    DevBuf<int32_t> dCount, dLength, dInts;
+    DevBuf<int64_t> dMateOff, dIntOff, dDblOff;
+    DevBuf<uint8_t> dCodes;
+    DevBuf<double> dDbls;
+    dCount.ensure((size_t)nq); dLength.ensure((size_t)nq * 2); dMateOff.ensure((size_t)nq * 2); dCodes.ensure((size_t)t->codes_length);
+    dInts.ensure(nInts); dDbls.ensure(nDbls); dIntOff.ensure((size_t)nq + 1); dDblOff.ensure((size_t)nq + 1);
+    if (nq) {
+      HIP_CHECK(hipMemcpy(dCount.p, t->mate_count, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dLength.p, t->mate_length, sizeof(int32_t) * (size_t)nq * 2, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dMateOff.p, t->mate_offset, sizeof(int64_t) * (size_t)nq * 2, hipMemcpyHostToDevice));
+    }
+    if (t->codes_length) HIP_CHECK(hipMemcpy(dCodes.p, t->codes, (size_t)t->codes_length, hipMemcpyHostToDevice));
+    if (nInts) HIP_CHECK(hipMemcpy(dInts.p, t->ints, sizeof(int32_t) * nInts, hipMemcpyHostToDevice));
+    if (nDbls) HIP_CHECK(hipMemcpy(dDbls.p, t->dbls, sizeof(double) * nDbls, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dIntOff.p, t->int_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dDblOff.p, t->dbl_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    SamJob job;
+    job.batch = xm::SamBatch{nq, dCount.p, dMateOff.p, dLength.p, dCodes.p, nullptr, nullptr};
+    job.streams = xm::SamStreams{dInts.p, dDbls.p, dIntOff.p, dDblOff.p};
+    job.contigs = xm::SamContigs{g.numContigs, g.dContigNames.p, g.dContigOff.p};
+    const xm_sam_names names{t->names, t->name_off};
+    SamBox* box = samFormat(g, job, &names, nullptr);
+    *out = &box->pub;
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_test_sam_format: ") + e.what()); }
+}
+
+// Test-only entry (tests/test_gpu_sam.py): Double.toString of xm_sam_rules.h run by the device on n values; out24 gets 24 bytes a value, len the lengths.
+int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len) {
+  if (n < 0 || (n > 0 && (!x || !out24 || !len))) return fail("xm_test_format_doubles: bad arguments");
+  try {
+    if (device >= 0) HIP_CHECK(hipSetDevice(device));
+    if (n == 0) return 0;
+    DevBuf<double> dX;
+    DevBuf<char> dOut;
+    DevBuf<int32_t> dLen;
+    dX.ensure((size_t)n); dOut.ensure((size_t)n * xm::XM_SAM_DOUBLE_BYTES); dLen.ensure((size_t)n);
+    HIP_CHECK(hipMemcpy(dX.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(xm_sam_doubles_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (long long)n, (const double*)dX.p, dOut.p, dLen.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(out24, dOut.p, (size_t)n * xm::XM_SAM_DOUBLE_BYTES, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(len, dLen.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_test_format_doubles: ") + e.what()); }
+}
+
 }  // extern "C"

@@ -144,11 +144,11 @@ struct ResultStage {
     if (usedI) HIP_CHECK(hipMemcpyAsync(res->ints, dFinalInts.p, sizeof(int32_t) * usedI, hipMemcpyDeviceToHost, s));
     if (usedD) HIP_CHECK(hipMemcpyAsync(res->dbls, dFinalDbls.p, sizeof(double) * usedD, hipMemcpyDeviceToHost, s));
   }
-  // the int stream of the last call where it lies in HBM, if it belongs to the resident batch of generation gen with nq queries (else: nq = -1)
-  struct LastStreams { int64_t nq; const int32_t* ints; const int64_t* intOff; size_t intsHeld; };
+  // the streams of the last call where they lie in HBM, if they belong to the resident batch of generation gen with nq queries (else: nq = -1)
+  struct LastStreams { int64_t nq; const int32_t* ints; const int64_t* intOff; size_t intsHeld; const double* dbls; const int64_t* dblOff; };
   LastStreams lastStreams(int64_t gen, int64_t nq) const {
-    if (lastAlignedNq < 0 || lastAlignedNq != nq || lastAlignedGen != gen) return LastStreams{-1, nullptr, nullptr, 0};
-    return LastStreams{lastAlignedNq, dFinalInts.p, dFinalIntOff.p, dFinalInts.n};
+    if (lastAlignedNq < 0 || lastAlignedNq != nq || lastAlignedGen != gen) return LastStreams{-1, nullptr, nullptr, 0, nullptr, nullptr};
+    return LastStreams{lastAlignedNq, dFinalInts.p, dFinalIntOff.p, dFinalInts.n, dFinalDbls.p, dFinalDblOff.p};
   }
 };
 

@@ -5,6 +5,7 @@ Java host keeps its own readers and writers (Mapper.java:699-732).  The per-obje
 reference for the formats; tests/test_hostio.py holds the two equal byte for byte."""
 import ctypes as C
 import os
+import time
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,6 +40,8 @@ def lib():
         L.xmio_write_batch.argtypes = [C.POINTER(XmioBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(XmioStats)]
         L.xmio_java_double.argtypes = [C.c_double, C.c_char_p, C.c_int32]
+        L.xmio_last_write_seconds.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.xmio_last_write_seconds.restype = None
         _lib = L
     return _lib
 
@@ -226,12 +229,23 @@ class Writer:
         self._sam, self._un = sam_file, unaligned_file
         self.stats = XmioStats()
         self.threads = int(threads or min(32, os.cpu_count() or 1))
+        self.seconds = {"format": 0.0, "write": 0.0}  # wall seconds of the write() calls so far: formatting on the host (and counting), and writing the files
 
-    def write(self, batch, result):
-        """result: anything with ints / dbls / int_off / dbl_off (api.BatchResult)."""
+    def write(self, batch, result, sam_text=None):
+        """result: anything with ints / dbls / int_off / dbl_off (api.BatchResult).  sam_text: the batch's SAM records as the GPU formatted them
+        (api.SamText, or any bytes-like object): they are written as they are, and the native call only counts the statistics and writes the unaligned queries."""
         for f in (self._sam, self._un):
             if f is not None:
                 f.flush()
+        sam_fd = self._sam.fileno() if self._sam is not None else -1
+        if sam_text is not None and sam_fd >= 0:
+            t0 = time.perf_counter()
+            view = sam_text.view() if hasattr(sam_text, "view") else memoryview(sam_text)
+            done = 0
+            while done < len(view):
+                done += os.write(sam_fd, view[done:])
+            self.seconds["write"] += time.perf_counter() - t0
+            sam_fd = -1
         ints = np.ascontiguousarray(result.ints, dtype=np.int32)
         dbls = np.ascontiguousarray(result.dbls, dtype=np.float64)
         io = np.ascontiguousarray(result.int_off, dtype=np.int64)
@@ -239,8 +253,12 @@ class Writer:
         if len(io) != batch.num_queries + 1:
             raise ValueError("result streams of %d queries for a batch of %d" % (len(io) - 1, batch.num_queries))
         if lib().xmio_write_batch(batch._ptr, ints.ctypes.data, dbls.ctypes.data, io.ctypes.data, do.ctypes.data, self._n, self._names,
-                                  self._sam.fileno() if self._sam is not None else -1, self._un.fileno() if self._un is not None else -1, self.threads, C.byref(self.stats)):
+                                  sam_fd, self._un.fileno() if self._un is not None else -1, self.threads, C.byref(self.stats)):
             raise RuntimeError(lib().xmio_last_error().decode())
+        fmt, wr = C.c_double(), C.c_double()
+        lib().xmio_last_write_seconds(C.byref(fmt), C.byref(wr))
+        self.seconds["format"] += fmt.value
+        self.seconds["write"] += wr.value
 
 
 def java_double(x):

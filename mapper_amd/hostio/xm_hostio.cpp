@@ -13,6 +13,7 @@
 #include <zlib.h>
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <charconv>
 #include <cstdio>
 #include <cstdlib>
@@ -689,6 +690,10 @@ bool formatRange(const FormatJob& J, int64_t q0, int64_t q1, std::string& sam, s
   return true;
 }
 
+// xmio_last_write_seconds: wall time of this thread's last xmio_write_batch call in formatting (and counting) and in write()
+thread_local double g_formatSeconds = 0, g_fileSeconds = 0;
+double nowSeconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
 bool writeAll(int fd, const std::string& s) {
   size_t done = 0;
   while (done < s.size()) {
@@ -717,6 +722,9 @@ int xmio_write_batch(const xmio_batch* b, const int32_t* ints, const double* dbl
   std::vector<std::string> sam((size_t)window), un((size_t)window);
   std::vector<Stats> st((size_t)nChunks);
   std::atomic<bool> bad(false);
+  const double tStart = nowSeconds();
+  double fileSeconds = 0;
+  g_formatSeconds = g_fileSeconds = 0;
   for (int64_t w0 = 0; w0 < nChunks; w0 += window) {
     const int64_t w1 = std::min(nChunks, w0 + window);
     std::atomic<int64_t> next(w0);
@@ -736,10 +744,12 @@ int xmio_write_batch(const xmio_batch* b, const int32_t* ints, const double* dbl
     work();
     for (auto& t : pool) t.join();
     if (bad) return fail("xmio_write_batch: malformed result streams");
+    const double tWrite = nowSeconds();
     for (int64_t c = w0; c < w1; c++) {
       if (sam_fd >= 0 && !writeAll(sam_fd, sam[(size_t)(c - w0)])) return fail("xmio_write_batch: write to the SAM file failed");
       if (unaligned_fd >= 0 && !writeAll(unaligned_fd, un[(size_t)(c - w0)])) return fail("xmio_write_batch: write to the unaligned-query file failed");
     }
+    fileSeconds += nowSeconds() - tWrite;
   }
   long long aligned = 0, totalLen = 0, indels = 0;
   for (auto& s : st) { aligned += s.aligned; totalLen += s.totalLen; indels += s.indels; }
@@ -765,7 +775,14 @@ int xmio_write_batch(const xmio_batch* b, const int32_t* ints, const double* dbl
   stats->total_aligned_length += totalLen;
   stats->num_indels += indels;
   stats->total_penalty = totalPenalty;
+  g_fileSeconds = fileSeconds;
+  g_formatSeconds = nowSeconds() - tStart - fileSeconds;
   return 0;
+}
+
+void xmio_last_write_seconds(double* format_seconds, double* file_seconds) {
+  if (format_seconds) *format_seconds = g_formatSeconds;
+  if (file_seconds) *file_seconds = g_fileSeconds;
 }
 
 // Double.toString of x as the SAM tags print it (tests)

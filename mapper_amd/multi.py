@@ -80,6 +80,15 @@ class MultiGpuDatabase:
     def info(self):
         return self.replicas[0].info()
 
+    def set_sam_contigs(self, names):
+        """ReferenceDatabase.set_sam_contigs for every replica."""
+        for r in self.replicas:
+            r.set_sam_contigs(names)
+
+    def format_sam_last(self, replica, batch=None):
+        """ReferenceDatabase.format_sam_last of replica `replica` (align_stream's on_aligned hook names it), on that replica's thread."""
+        return self.replicas[replica].format_sam_last(batch)
+
     def close(self):
         for r in self.replicas:
             r.close()
