@@ -26,12 +26,14 @@ namespace {
 __device__ unsigned long long* xm_read_times = nullptr;
 #endif
 // One lane aligns one read at a time (AlignerWorker.align, M/AlignerWorker.java:256-484) and loops until the batch is drained.
-__global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_align_kernel(IndexView ix, Params params, BatchView batch, const int64_t* todo, long long nTodo, int scale, int heavyAllowed, int lanesPerWave,
+__global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_align_kernel(const LaunchConst* launchConst, BatchView batch, const int64_t* todo, long long nTodo, int scale, int heavyAllowed, int lanesPerWave,
                                                        uint8_t* arenas, unsigned long long arenaBytes, OutView out, unsigned long long* nextItem, DevCounters* counters,
                                                        long long taperUnit, long long firstStride, PNode* waveNodes, HandOver ho, int pairLanes,
                                                        SearchPool searchPool, PassLists lists, int boundFilter) {
   // lanesPerWave < 64 (gapped pass): the extension chain diverges so much that a wave runs its reads nearly one after another, so
   // spreading them over more, partly filled waves shortens the critical path; the idle lanes own no scratch arena
+  // index view and parameters: one block in HBM for all lanes (LaunchConst, xm_defs.h) - the lanes hold its address and read it through scalar loads
+  const LaunchConstPtr lc = (LaunchConstPtr)launchConst;
   xmSetWaveNodes(waveNodes);
   xmSetPairMode(pairLanes);
   xmSetSearchPool(searchPool);
@@ -99,7 +101,7 @@ __global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_align_kernel(IndexV
     DevCounters before = local;
     if (ho.mode == 1) {
       uint8_t* region = ho.regions + (unsigned long long)myRegion * ho.regionBytes;
-      runReadRetaining(cx, &ix, params, in, scale, region, (size_t)ho.regionBytes, arena, (size_t)arenaBytes, &local, rr, heavyAllowed);
+      runReadRetaining(cx, lc, in, scale, region, (size_t)ho.regionBytes, arena, (size_t)arenaBytes, &local, rr, heavyAllowed);
       if (cx.status == XM_ST_NEED_HEAVY && savedReadOf(region, (size_t)ho.regionBytes)->valid) {
         // the read keeps this region; the lane needs a fresh one only if it will take another read (the list counter only grows, so a
         // lane that sees the list drained here finds it drained at its next fetch and leaves)
@@ -115,10 +117,10 @@ __global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_align_kernel(IndexV
       const int32_t rg = ho.regionOf[q];
       uint8_t* tmp = arena + ho.regionBytes;
       const size_t tmpBytes = (size_t)(arenaBytes - ho.regionBytes);
-      if (rg >= 0) runReadResumed(cx, savedReadOf(ho.regions + (unsigned long long)rg * ho.regionBytes, (size_t)ho.regionBytes), &ix, scale, tmp, tmpBytes, &local, rr);
-      else runReadRetaining(cx, &ix, params, in, ho.seedScale, arena, (size_t)ho.regionBytes, tmp, tmpBytes, &local, rr, 2, scale);
+      if (rg >= 0) runReadResumed(cx, savedReadOf(ho.regions + (unsigned long long)rg * ho.regionBytes, (size_t)ho.regionBytes), lc, scale, tmp, tmpBytes, &local, rr);
+      else runReadRetaining(cx, lc, in, ho.seedScale, arena, (size_t)ho.regionBytes, tmp, tmpBytes, &local, rr, 2, scale);
     } else {
-      runRead(cx, &ix, params, in, scale, arena, (size_t)arenaBytes, &local, rr, heavyAllowed);
+      runRead(cx, lc, in, scale, arena, (size_t)arenaBytes, &local, rr, heavyAllowed);
     }
     XM_PAIR_CHECK(0, cx.status);
     XM_PAIR_CHECK(1, ((long long)rr.nComponents << 40) ^ ((long long)rr.single[0] << 20) ^ (long long)rr.empty[0] ^ ((long long)local.pathAlignerNodes << 4));
@@ -220,7 +222,7 @@ __global__ void __launch_bounds__(256, XM_WAVES_PER_SIMD) xm_test_bound_kernel(P
 namespace xm {
 
 int xmAlignLaunch(const AlignLaunch& a, void* stream) {
-  hipLaunchKernelGGL(xm_align_kernel, dim3(a.grid), dim3(a.block), 0, (hipStream_t)stream, a.ix, a.params, a.batch, a.todo, a.nTodo, a.scale, a.heavyAllowed, a.lanesPerWave,
+  hipLaunchKernelGGL(xm_align_kernel, dim3(a.grid), dim3(a.block), 0, (hipStream_t)stream, a.launchConst, a.batch, a.todo, a.nTodo, a.scale, a.heavyAllowed, a.lanesPerWave,
                      a.arenas, a.arenaBytes, a.out, a.nextItem, a.counters, a.taperUnit, a.firstStride, a.waveNodes, a.ho, a.pairLanes, a.searchPool, a.lists, a.boundFilter);
   return (int)hipGetLastError();
 }

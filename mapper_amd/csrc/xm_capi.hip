@@ -285,6 +285,16 @@ struct PassBuffers {
   DevBuf<int32_t> dRegionOf;
   DevBuf<PNode> dWaveNodes;     // per wave: node payloads of its LDS-mode search
   DevBuf<uint8_t> dSearchPool;  // one buffer per wave for the arrays of HBM-mode searches (SearchPool, xm_extend.h)
+  DevBuf<LaunchConst> dLaunchConst;  // what every lane of a launch reads and none keeps (xm_defs.h); the context's own: contexts of one index run with different parameters
+
+  // The block of the next launch, written on s behind whatever launch of this context read the last one.  The view changes between the passes of a call (a
+  // confidence rerun: the table grew and moved), the parameters from call to call.  (params: as the lanes use them, StartingInsertionStartFree 0.)
+  const LaunchConst* launchConst(const IndexView& view, const Params& params, hipStream_t s) {
+    dLaunchConst.ensure(1);
+    const LaunchConst lc = launchConstOf(view, params);
+    HIP_CHECK(hipMemcpyAsync(dLaunchConst.p, &lc, sizeof(lc), hipMemcpyHostToDevice, s));
+    return dLaunchConst.p;
+  }
 
   // sized for a call of nq queries; counters and counts cleared, no query in error
   void prepare(int64_t nq, hipStream_t s) {
@@ -869,7 +879,7 @@ static float launchAlignPass(AlignCall& c, const BatchPolicy& pol, const PassSta
   pb.dWaveNodes.ensure((size_t)pl.grid * (pl.block / 64) * XM_PAL_NODES);
   AlignLaunch a{};
   a.grid = pl.grid; a.block = pl.block;
-  a.ix = c.view; a.params = c.params; a.batch = c.bv;
+  a.launchConst = pb.launchConst(c.view, c.params, s); a.batch = c.bv;
   a.todo = c.todo; a.nTodo = c.nTodo;
   a.scale = st.scale; a.heavyAllowed = st.heavy ? 2 : (int)pol.k.lightLevel; a.lanesPerWave = pl.lpw;
   a.arenas = pb.dArenas.p + pl.regionsTotal; a.arenaBytes = (unsigned long long)pl.arenaBytes;
@@ -936,7 +946,9 @@ static void runLanePasses(AlignCall& c, const BatchPolicy& pol) {
     // what the next pass needs besides its list: room to spare in the result arenas; the values its reads waited for; (profile builds) the gapped pass's timers alone
     if (np.kind == PassKind::OutRerun) idx->results.growAfterOverflow(s);
     if (np.kind == PassKind::ConfRerun) { idx->conf.absorbMisses(s); idx->conf.fillView(c.view); }
+#ifdef XM_HAVE_TICKS
     if (np.kind == PassKind::Gapped && pol.k.profGappedOnly) HIP_CHECK(hipMemsetAsync((char*)idx->passes.dCounters.p + offsetof(DevCounters, t), 0, sizeof(((DevCounters*)nullptr)->t), s));
+#endif
     c.todo = idx->passes.take(np, ctl, s);
     if (np.kind != PassKind::Gapped) c.rerun += c.nTodo;
   }
@@ -972,7 +984,11 @@ static void finishStreams(AlignCall& c) {
   res->extra[3] = c.boundFilterUsed ? 1 : 0;
   res->extra[6] = c.remembered;
   res->extra[7] = c.copies;
+#ifdef XM_HAVE_TICKS
   for (int i = 0; i < 16; i++) res->prof[i] = (int64_t)dc.t[i];
+#else
+  for (int i = 0; i < 16; i++) res->prof[i] = 0;  // (the phase timers exist in profile builds only)
+#endif
   res->kernel_ms = c.kernelMs;
   res->kernel_launches = c.launches;
 }

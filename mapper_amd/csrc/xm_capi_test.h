@@ -4,6 +4,13 @@
 
 extern "C" {
 
+// Test-only, not declared in the header (tests/test_launch_const_layout.py binds it by name): the layout of the launch block as the host side, which writes
+// it, was compiled (launchConstLayout, xm_defs.h).  out: XM_LAUNCH_CONST_LAYOUT_WORDS words.  Needs no GPU.
+int xm_test_launch_const_layout(int64_t* out, int32_t cap) {
+  if (!out || cap < XM_LAUNCH_CONST_LAYOUT_WORDS) return -1;
+  launchConstLayout(out);
+  return XM_LAUNCH_CONST_LAYOUT_WORDS;
+}
 // Test-only: what the rejection filter did in this thread's last xm_test_local_align call (searches taken, searches rejected, cells computed).
 static thread_local int64_t g_testBound[3] = {0, 0, 0};
 void xm_test_bound_counters(int64_t* out3) { for (int i = 0; i < 3; i++) out3[i] = g_testBound[i]; }

@@ -18,9 +18,11 @@
 #if defined(__HIP_DEVICE_COMPILE__)
 #define XM_GLOBAL(T) T __attribute__((address_space(1)))  // pointer known to address HBM: global_load/store instead of flat
 #define XM_LDS(T) T __attribute__((address_space(3)))     // pointer known to address the local data share: ds_read/ds_write instead of flat
+#define XM_CONST(T) T __attribute__((address_space(4)))   // pointer known to address memory no kernel writes while this one runs: with a uniform address, scalar loads (xmUniform)
 #else
 #define XM_GLOBAL(T) T
 #define XM_LDS(T) T
+#define XM_CONST(T) T
 #endif
 #define XM_INL __host__ __device__ __forceinline__
 #ifndef XM_NOINL_LINKAGE
@@ -32,6 +34,7 @@
 #define XM_HD
 #define XM_GLOBAL(T) T
 #define XM_LDS(T) T
+#define XM_CONST(T) T
 #define XM_INL inline
 #define XM_NOINL
 #define XM_NOINL_DECL
@@ -261,7 +264,9 @@ XM_INL void xmFillLine(W* line, uint32_t o0, uint32_t o1, const P* tablePosition
   for (uint32_t j = 0; j < (uint32_t)XM_LINE_SLOTS; j++) line[1 + j] = ((o0 & XM_OVERFULL) == 0 && j < count) ? (W)tablePositions[first + j] : (W)0;
 }
 
-XM_INL SeqView refView(const IndexView& ix, int contig, bool rc) {
+// (IX: IndexView in whichever address space the caller holds it - the launch's block, read through scalar loads, or a kernel's own copy)
+template <typename IX>
+XM_INL SeqView refView(const IX& ix, int contig, bool rc) {
   SeqView v;
   v.base = ix.refCodes + ix.contigStart[contig];
   v.len = ix.contigLen[contig];
@@ -307,6 +312,46 @@ XM_INL Caps makeCaps(int scale) {
   return c;
 }
 
+// ---------------------------------------------------------------- what is the same in every lane of a launch
+// One block per context in HBM (PassBuffers, xm_capi.hip), written on the context's stream in front of every launch of the lane-per-read kernel: the view
+// changes between the passes of a call (the confidence table grows and moves), the parameters from call to call.  A lane holds the block's ADDRESS
+// (ReadCtx, SeedEnv) and no copy: a copy in a structure whose address goes to an out-of-line function lives in the lane's private memory, and every
+// read of it is a memory access of 256 B per wave for a value all lanes share.  Through a uniform address in the constant address space
+// (xmUniform) the same read is one scalar load for the wave, served by the scalar cache.
+struct LaunchConst {
+  IndexView ix;
+  Params params;  // as the lanes use them: StartingInsertionStartFree 0 (runRead)
+};
+typedef XM_CONST(const LaunchConst)* LaunchConstPtr;
+// the block of a launch with this view and these parameters (host side; the host simulation makes one in front of every read it runs)
+inline LaunchConst launchConstOf(const IndexView& view, const Params& params) {
+  LaunchConst lc;
+  __builtin_memset(&lc, 0, sizeof(lc));
+  lc.ix = view;
+  lc.params = params;
+  lc.params.StartingInsertionStartFree = 0;
+  return lc;
+}
+// The block's layout as this translation unit sees it: size, then the offsets of the members and of the first and last field of each.  The host side of the
+// library reports it, and tests/test_launch_const_layout.py compiles this function from the header in the tree: the writer of the block and its readers are compiled apart.
+constexpr int XM_LAUNCH_CONST_LAYOUT_WORDS = 10;
+inline void launchConstLayout(int64_t* out) {
+  out[0] = (int64_t)sizeof(LaunchConst); out[1] = (int64_t)offsetof(LaunchConst, ix); out[2] = (int64_t)offsetof(LaunchConst, params);
+  out[3] = (int64_t)sizeof(IndexView); out[4] = (int64_t)offsetof(IndexView, contigStart); out[5] = (int64_t)offsetof(IndexView, lines32); out[6] = (int64_t)offsetof(IndexView, baLogStep);
+  out[7] = (int64_t)sizeof(Params); out[8] = (int64_t)offsetof(Params, Max_PenaltySpan); out[9] = (int64_t)offsetof(Params, StartingInsertionStartFree);
+}
+// The block's address as a function finds it in a structure in private memory or in its arguments (vector registers), made uniform: the loads through it become scalar loads.
+// (every lane of a launch holds the same address, so the first active lane's is everybody's)
+XM_INL LaunchConstPtr xmUniform(LaunchConstPtr p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint64_t v = (uint64_t)p;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return (LaunchConstPtr)(((uint64_t)hi << 32) | lo);
+#else
+  return p;
+#endif
+}
+
 // ---------------------------------------------------------------- bump arena
 #if defined(XM_ARENA_TRACE) && !defined(__HIPCC__)
 void xm_arena_trace(const void* base, size_t offset, size_t bytes);  // host simulation only (tests/hostsim): which structure lies where in an arena
@@ -337,7 +382,11 @@ struct DevCounters {
   unsigned long long reads, headerProbes, bucketFetches, hitsFetched, candidatesExtended, pathAlignerCalls, pathAlignerNodes,
       quickAccepts, blocksOut, alignmentsOut, refWindowBytes, readBytes;
   unsigned long long boundChecks, boundRejects, boundCells, boundPieceChecks, boundPieceRejects;  // (the last two: pieces the filter examined / proved unalignable before their chain ran)  // the rejection filter in front of PathAligner (xm_bound.h): searches it took, searches it proved null, cells it computed
-  unsigned long long t[16];  // XM_PROFILE builds only: shader-clock ticks per phase, summed over lanes
+#if defined(XM_PROFILE) || defined(XM_WAVE_PROFILE)
+#define XM_HAVE_TICKS 1
+  unsigned long long t[16];  // profile builds only: shader-clock ticks per phase, summed over lanes.  A product build has no such member: a lane keeps its counters
+                             // in private memory, and every read used to clear, save and restore these sixteen words with them
+#endif
 };
 
 #if defined(XM_PROFILE) && defined(__HIP_DEVICE_COMPILE__)

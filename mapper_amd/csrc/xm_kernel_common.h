@@ -38,8 +38,7 @@ struct PassLists {
 // One launch of xm_align_kernel (xm_align_kernel.hip): grid and block, then one member per kernel parameter, named as the parameter and in its order.
 struct AlignLaunch {
   int grid, block;
-  IndexView ix;
-  Params params;
+  const LaunchConst* launchConst;  // in HBM, written on the launch's stream in front of it: the index view and the parameters of this launch
   BatchView batch;
   const int64_t* todo;       // null: all reads
   long long nTodo;
@@ -98,7 +97,9 @@ __device__ __forceinline__ void addCounters(DevCounters* g, const DevCounters& l
   atomicAdd(&g->pathAlignerNodes, l.pathAlignerNodes); atomicAdd(&g->quickAccepts, l.quickAccepts); atomicAdd(&g->alignmentsOut, l.alignmentsOut);
   atomicAdd(&g->refWindowBytes, l.refWindowBytes); atomicAdd(&g->readBytes, l.readBytes);
   if (l.boundChecks | l.boundPieceChecks) { atomicAdd(&g->boundChecks, l.boundChecks); atomicAdd(&g->boundRejects, l.boundRejects); atomicAdd(&g->boundCells, l.boundCells); atomicAdd(&g->boundPieceChecks, l.boundPieceChecks); atomicAdd(&g->boundPieceRejects, l.boundPieceRejects); }
+#ifdef XM_HAVE_TICKS
   for (int i = 0; i < 16; i++) if (l.t[i]) atomicAdd(&g->t[i], l.t[i]);
+#endif
 }
 
 // what a lane does with a read it is done with: the result into the arenas, or the status the host's pass logic acts on

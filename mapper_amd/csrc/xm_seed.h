@@ -532,7 +532,9 @@ struct Pyramid {
 };
 
 // ---------------------------------------------------------------- database probes
-XM_INL const Table* containingMap(const IndexView& ix, int used, int32_t* status) {
+// (IX: IndexView in the address space the caller holds it in, as refView - the lane-per-read passes read the launch's block, the wave kernels their own copy)
+template <typename IX>
+XM_INL const Table* containingMap(const IX& ix, int used, int32_t* status) {
   if (used > ix.maxHashedLength) { *status = XM_ST_NEED_GROW; return nullptr; }  // M/Readable_HashBlock_Database.java:108-113
   return &ix.tables[used];
 }
@@ -542,7 +544,8 @@ XM_INL uint32_t packedKey(const Table* t, int32_t key) {  // M/PackedMap.java:21
   return (uint32_t)r;
 }
 // M/Readable_HashBlock_Database.java:72-80 + M/PackedMap.java:228-236: one 8-byte header probe (two adjacent CSR offsets)
-XM_INL int numMatchesLowerBound(const IndexView& ix, const QBlock& b, DevCounters* dc, int32_t* status) {
+template <typename IX>
+XM_INL int numMatchesLowerBound(const IX& ix, const QBlock& b, DevCounters* dc, int32_t* status) {
   if (b.used < ix.minInterestingSize) return INT32_MAX;
   const Table* t = containingMap(ix, b.used, status);
   if (!t) return INT32_MAX;
@@ -557,7 +560,8 @@ XM_INL int numMatchesLowerBound(const IndexView& ix, const QBlock& b, DevCounter
   if (o0 & XM_OVERFULL) return INT32_MAX;
   return (int)((o1 & ~XM_OVERFULL) - (o0 & ~XM_OVERFULL));
 }
-XM_INL int dbMaxNumMatchesAllowed(const IndexView& ix, const QBlock& b, int32_t* status) {  // :82-90
+template <typename IX>
+XM_INL int dbMaxNumMatchesAllowed(const IX& ix, const QBlock& b, int32_t* status) {  // :82-90
   if (b.used < ix.minInterestingSize) return -1;
   const Table* t = containingMap(ix, b.used, status);
   if (!t) return 0;
@@ -565,7 +569,8 @@ XM_INL int dbMaxNumMatchesAllowed(const IndexView& ix, const QBlock& b, int32_t*
 }
 // a decoded SequencePosition
 struct RefPos { int32_t contig; uint8_t rc; int32_t start; };
-XM_INL RefPos decodePosition(const IndexView& ix, int64_t enc) {
+template <typename IX>
+XM_INL RefPos decodePosition(const IX& ix, int64_t enc) {
   int lo = 0, hi = ix.numContigs * 2;  // last i with seqCumStart[i] <= enc
   while (hi - lo > 1) {
     int mid = (lo + hi) >> 1;
@@ -578,13 +583,15 @@ XM_INL RefPos decodePosition(const IndexView& ix, int64_t enc) {
   return p;
 }
 // position `idx` of the virtual positions array: a word of a bucket line (XM_LINE_FLAG) or an entry of the CSR positions
-XM_INL int64_t xmPositionAt(const IndexView& ix, int64_t idx) {
+template <typename IX>
+XM_INL int64_t xmPositionAt(const IX& ix, int64_t idx) {
   if (idx & XM_LINE_FLAG) { idx &= ~XM_LINE_FLAG; return ix.lines64 ? (int64_t)ix.lines64[idx] : (int64_t)ix.lines32[idx]; }
   return ix.posIs64 ? (int64_t)ix.positions64[idx] : (int64_t)ix.positions32[idx];
 }
 // M/Readable_HashBlock_Database.java:22-38 / M/PackedMap.java:160-172.  returns -1 for Java null, else the hit count and
 // (firstIndex into positions, invert flag)
-XM_INL int matchBlock(const IndexView& ix, const QBlock& b, int64_t& first, bool& invert, DevCounters* dc, int32_t* status) {
+template <typename IX>
+XM_INL int matchBlock(const IX& ix, const QBlock& b, int64_t& first, bool& invert, DevCounters* dc, int32_t* status) {
   if (b.used < ix.minInterestingSize) return -1;
   const Table* t = containingMap(ix, b.used, status);
   if (!t) return -1;
@@ -612,7 +619,8 @@ XM_INL int matchBlock(const IndexView& ix, const QBlock& b, int64_t& first, bool
   if (dc) dc->hitsFetched += (unsigned long long)count;
   return count;
 }
-XM_INL RefPos fetchHit(const IndexView& ix, int64_t idx, bool invert, int blockSpan) {
+template <typename IX>
+XM_INL RefPos fetchHit(const IX& ix, int64_t idx, bool invert, int blockSpan) {
   int64_t enc = xmPositionAt(ix, idx);
   RefPos p = decodePosition(ix, enc);
   if (invert) {  // Readable_HashBlock_Database.reverseComplement :55-59
@@ -677,7 +685,7 @@ struct Comp {  // one Counting_HashBlockPath (+ its HashBlockPath and pyramid)
 };
 
 struct SeedEnv {  // what the seed code needs from the surrounding read context
-  const IndexView* ix;
+  LaunchConstPtr lc;       // the launch's block (xm_defs.h): the index view is read through it, seIx
   const Caps* caps;
   DevCounters* dc;
   int32_t* status;
@@ -685,9 +693,13 @@ struct SeedEnv {  // what the seed code needs from the surrounding read context
   const int32_t* mateLen;  // [2]
 };
 
+// The index view of the launch, through a uniform address: its fields come by scalar loads.  An out-of-line function takes it once, at its entry, and hands it
+// to the inlined functions below it (the environment lies in private memory: fetching the address from it is the one private access left).
+typedef XM_CONST(const IndexView) LaunchIx;
+XM_INL LaunchIx& seIx(const SeedEnv& e) { return xmUniform(e.lc)->ix; }
 XM_INL int seqALen(const SeedEnv& e, uint8_t seqAId) { return e.mateLen[seqAId >> 1]; }
 XM_INL int smStartB(const SeqMatch& m) { return imax(0, m.offset); }
-XM_INL int smEndB(const SeedEnv& e, const SeqMatch& m) { return imin(m.offset + seqALen(e, m.seqAId), e.ix->contigLen[m.contig]); }
+XM_INL int smEndB(const SeedEnv& e, const SeqMatch& m) { return imin(m.offset + seqALen(e, m.seqAId), seIx(e).contigLen[m.contig]); }
 XM_INL bool smEquals(const SeqMatch& a, const SeqMatch& b) { return a.offset == b.offset && a.seqAId == b.seqAId && a.contig == b.contig; }
 
 XM_INL void pathInit(PathState& p) {  // M/HashBlockPath.java:15-24
@@ -724,8 +736,8 @@ XM_INL void pathMoveUpOrRight(Comp& c) {  // :111-122
   }
 }
 // :197-203.  returns false for null
-XM_INL bool pathWithGap(Comp& c, const SeedEnv& e, QBlock& out) {
-  if (!e.ix->enableGapmers) {
+XM_INL bool pathWithGap(Comp& c, LaunchIx& ix, QBlock& out) {
+  if (!ix.enableGapmers) {
     const PBlock& b = c.path.cur;
     out.start = b.start; out.len = b.len; out.used = b.len; out.fwd = b.fwd; out.rev = b.rev; out.flags = b.flags; out.id = -1;
     return true;
@@ -739,30 +751,30 @@ XM_INL bool pathWithGap(Comp& c, const SeedEnv& e, QBlock& out) {
   out = c.path.gap;
   return true;
 }
-XM_INL int pathMaxNumMatchesAllowed(Comp& c, const SeedEnv& e, const QBlock& b) {  // :205-219
-  if (b.len >= c.query.len / 6) return dbMaxNumMatchesAllowed(*e.ix, b, e.status);
+XM_INL int pathMaxNumMatchesAllowed(Comp& c, const SeedEnv& e, LaunchIx& ix, const QBlock& b) {  // :205-219
+  if (b.len >= c.query.len / 6) return dbMaxNumMatchesAllowed(ix, b, e.status);
   if (b.flags & F_RMR) return 5;
   return b.used + 1;
 }
 // :143-195.  returns false when the path is exhausted
-XM_NOINL_W1 bool pathAdvance(Comp& c, const SeedEnv& e) {
+XM_NOINL_W1 bool pathAdvance(Comp& c, const SeedEnv& e, LaunchIx& ix) {
   XM_TIC(t0);
   int singleLen = c.path.cur.len;
-  if (maxGapmerNumBasepairsUsed(singleLen) < e.ix->minInterestingSize && e.ix->enableGapmers) {
+  if (maxGapmerNumBasepairsUsed(singleLen) < ix.minInterestingSize && ix.enableGapmers) {
     pathMoveUpOrRight(c);
   } else {
     QBlock ext;
-    if (pathWithGap(c, e, ext)) {
-      int numMatches = numMatchesLowerBound(*e.ix, ext, e.dc, e.status);
+    if (pathWithGap(c, ix, ext)) {
+      int numMatches = numMatchesLowerBound(ix, ext, e.dc, e.status);
       if (numMatches < 6) {
         if (c.path.batchIndex > 0) pathMoveDown(c); else pathMoveRight(c);
       } else {
-        if (numMatches > pathMaxNumMatchesAllowed(c, e, ext)) pathMoveUpOrRight(c);
+        if (numMatches > pathMaxNumMatchesAllowed(c, e, ix, ext)) pathMoveUpOrRight(c);
         else pathMoveRight(c);
       }
     } else {
       int typical = singleLen * 3 / 2;
-      if (typical <= e.ix->minInterestingSize && e.ix->enableGapmers) pathMoveUpOrRight(c);
+      if (typical <= ix.minInterestingSize && ix.enableGapmers) pathMoveUpOrRight(c);
       else { if (c.path.batchIndex > 0) pathMoveDown(c); else pathMoveRight(c); }
     }
   }
@@ -774,15 +786,15 @@ XM_NOINL_W1 bool pathAdvance(Comp& c, const SeedEnv& e) {
   return c.path.curExists && *e.status == 0;
 }
 // getNextInterestingBlock :27-50 (+ getNextBlockWithGoodNumberOfMatches :68-96, recentlySeen :52-65)
-XM_NOINL_W1 bool pathNextInterestingBlock(Comp& c, const SeedEnv& e, QBlock& out) {
+XM_NOINL_W1 bool pathNextInterestingBlock(Comp& c, const SeedEnv& e, LaunchIx& ix, QBlock& out) {
   if (!c.path.curExists) return false;
   while (true) {
-    if (!pathAdvance(c, e)) return false;
+    if (!pathAdvance(c, e, ix)) return false;
     QBlock ext;
-    if (!pathWithGap(c, e, ext)) continue;
-    int n = numMatchesLowerBound(*e.ix, ext, e.dc, e.status);
+    if (!pathWithGap(c, ix, ext)) continue;
+    int n = numMatchesLowerBound(ix, ext, e.dc, e.status);
     if (*e.status) return false;
-    if (!(n <= pathMaxNumMatchesAllowed(c, e, ext))) continue;
+    if (!(n <= pathMaxNumMatchesAllowed(c, e, ix, ext))) continue;
     bool seen = false;
     if (c.path.havePrev1 && ext.fwd == c.path.prevFwd1) seen = true;
     else if (c.path.havePrev2 && ext.fwd == c.path.prevFwd2) seen = true;
@@ -798,12 +810,12 @@ XM_NOINL_W1 bool pathNextInterestingBlock(Comp& c, const SeedEnv& e, QBlock& out
 }
 
 // ---------------------------------------------------------------- Counting_HashBlockPath
-XM_INL void counterUpdate(Comp& c, const SeedEnv& e, Counter& k) {  // M/HashBlockMatch_Counter.java:41-46,74-88
+XM_INL void counterUpdate(Comp& c, LaunchIx& ix, Counter& k) {  // M/HashBlockMatch_Counter.java:41-46,74-88
   while (k.historyProcessedIndex < c.nHistory) {
     const QBlock& b = c.history[k.historyProcessedIndex];
     if (b.id != k.lastMatchedBlockId) {
       if (b.start >= k.lastMismatchedPosition) {
-        if (k.offset + b.end() <= e.ix->contigLen[k.contig]) {
+        if (k.offset + b.end() <= ix.contigLen[k.contig]) {
           k.numDistinctMismatches++;
           k.lastMismatchedPosition = b.end();
         }
@@ -812,35 +824,36 @@ XM_INL void counterUpdate(Comp& c, const SeedEnv& e, Counter& k) {  // M/HashBlo
     k.historyProcessedIndex++;
   }
 }
-XM_INL int counterNumDistinctMismatches(Comp& c, const SeedEnv& e, Counter& k) { counterUpdate(c, e, k); return k.numDistinctMismatches; }
-XM_INL void declareGood(Comp& c, const SeedEnv& e, int ci) {  // M/Counting_HashBlockPath.java:280-285
+XM_INL int counterNumDistinctMismatches(Comp& c, LaunchIx& ix, Counter& k) { counterUpdate(c, ix, k); return k.numDistinctMismatches; }
+XM_INL void declareGood(Comp& c, const SeedEnv& e, LaunchIx& ix, int ci) {  // M/Counting_HashBlockPath.java:280-285
   Counter& k = c.counters[ci];
   if (!k.good) {
     if (c.nGood >= e.caps->maxCounters) { *e.status = XM_ST_OVERFLOW; return; }
     c.good[c.nGood++] = (int16_t)ci;
     k.good = 1;
-    k.priority = counterNumDistinctMismatches(c, e, k);  // setGood
+    k.priority = counterNumDistinctMismatches(c, ix, k);  // setGood
   }
 }
-XM_INL void compAddMatch(Comp& c, const SeedEnv& e, int ci, const QBlock& qb, int queryBlockNumMatches, const SeqMatch& fullMatch) {  // :254-277
+XM_INL void compAddMatch(Comp& c, const SeedEnv& e, LaunchIx& ix, int ci, const QBlock& qb, int queryBlockNumMatches, const SeqMatch& fullMatch) {  // :254-277
   Counter& k = c.counters[ci];
   k.numMatches++;
   k.lastMatchedBlockId = qb.id;
-  counterUpdate(c, e, k);
+  counterUpdate(c, ix, k);
   if (k.numMatches <= 1) {
     if (k.numMatches == 1) {
       c.foundGood = true;
-      declareGood(c, e, ci);
+      declareGood(c, e, ix, ci);
     } else {
       if (queryBlockNumMatches <= qb.len) {
         int distanceFromStart = fullMatch.offset;
-        int distanceFromEnd = e.ix->contigLen[fullMatch.contig] - (fullMatch.offset + seqALen(e, fullMatch.seqAId));
-        if (imin(distanceFromStart, distanceFromEnd) < 0) declareGood(c, e, ci);
+        int distanceFromEnd = ix.contigLen[fullMatch.contig] - (fullMatch.offset + seqALen(e, fullMatch.seqAId));
+        if (imin(distanceFromStart, distanceFromEnd) < 0) declareGood(c, e, ix, ci);
       }
     }
   }
 }
 XM_NOINL_W3 void compUpdateMatches(Comp& c, const SeedEnv& e, const SeqMatch& m, const QBlock& qb, int queryBlockNumMatches) {  // :193-252
+  LaunchIx& ix = seIx(e);
   uint8_t mapSel = m.reversed() ? 0 : 1;
   int cur = -1, lower = -1, higher = -1;
   for (int i = 0; i < c.nCounters; i++) {
@@ -872,14 +885,14 @@ XM_NOINL_W3 void compUpdateMatches(Comp& c, const SeedEnv& e, const SeqMatch& m,
     }
   }
   int prev = c.counters[cur].prev;
-  if (prev >= 0) compAddMatch(c, e, prev, qb, queryBlockNumMatches, m);
+  if (prev >= 0) compAddMatch(c, e, ix, prev, qb, queryBlockNumMatches, m);
   int next = c.counters[cur].next;
-  if (next >= 0) compAddMatch(c, e, next, qb, queryBlockNumMatches, m);
+  if (next >= 0) compAddMatch(c, e, ix, next, qb, queryBlockNumMatches, m);
   bool updateThisOne = true;
   if ((prev >= 0 && c.counters[prev].good) || (next >= 0 && c.counters[next].good)) {
     if (!c.counters[cur].good) updateThisOne = false;
   }
-  if (updateThisOne) compAddMatch(c, e, cur, qb, queryBlockNumMatches, m);
+  if (updateThisOne) compAddMatch(c, e, ix, cur, qb, queryBlockNumMatches, m);
 }
 
 // iterate counters of one map in (contig, offset) order: returns the next index after (lastContig,lastOffset) or -1
@@ -893,7 +906,7 @@ XM_INL int nextCounterInOrder(const Comp& c, uint8_t mapSel, int lastContig, int
   }
   return best;
 }
-XM_NOINL_W2 void tryEnsureGoodMatchCounter(Comp& c, const SeedEnv& e) {  // :291-308
+XM_NOINL_W2 void tryEnsureGoodMatchCounter(Comp& c, const SeedEnv& e, LaunchIx& ix) {  // :291-308
   if (!c.foundGood && c.nCounters <= c.query.len) {
     for (int mapSel = 0; mapSel < 2; mapSel++) {
       int lc = 0, lo = 0;
@@ -902,7 +915,7 @@ XM_NOINL_W2 void tryEnsureGoodMatchCounter(Comp& c, const SeedEnv& e) {  // :291
         int i = nextCounterInOrder(c, (uint8_t)mapSel, lc, lo, first);
         if (i < 0) break;
         first = false; lc = c.counters[i].contig; lo = c.counters[i].offset;
-        declareGood(c, e, i);
+        declareGood(c, e, ix, i);
       }
     }
     c.foundGood = true;
@@ -910,11 +923,11 @@ XM_NOINL_W2 void tryEnsureGoodMatchCounter(Comp& c, const SeedEnv& e) {  // :291
 }
 
 // getNextInterestingBlock :344-368
-XM_NOINL_W2 bool compNextInterestingBlock(Comp& c, const SeedEnv& e, QBlock& out) {
+XM_NOINL_W2 bool compNextInterestingBlock(Comp& c, const SeedEnv& e, LaunchIx& ix, QBlock& out) {
   c.all.id = 0;  // previousAllPositions = null
   while (true) {
     QBlock b;
-    if (!pathNextInterestingBlock(c, e, b)) {
+    if (!pathNextInterestingBlock(c, e, ix, b)) {
       if (*e.status) return false;
       if (c.pendHead >= c.pendTail) return false;
       out = c.pending[c.pendHead++];
@@ -933,25 +946,25 @@ XM_NOINL_W2 bool compNextInterestingBlock(Comp& c, const SeedEnv& e, QBlock& out
 // step() :40-179
 XM_NOINL_W4 bool compStep(Comp& c, const SeedEnv& e) {
   if (c.done) return false;
+  LaunchIx& ix = seIx(e);
   QBlock qb;
   int64_t first = 0;
   bool invert = false;
   int nHits;
   while (true) {  // getNextInterestingMatch :371-384
-    if (!compNextInterestingBlock(c, e, qb)) {
+    if (!compNextInterestingBlock(c, e, ix, qb)) {
       if (*e.status) return false;
       c.done = true;
-      if (c.numBlocksMatchingAnywhere < 1) tryEnsureGoodMatchCounter(c, e);
+      if (c.numBlocksMatchingAnywhere < 1) tryEnsureGoodMatchCounter(c, e, ix);
       return false;
     }
-    nHits = matchBlock(*e.ix, qb, first, invert, e.dc, e.status);
+    nHits = matchBlock(ix, qb, first, invert, e.dc, e.status);
     if (*e.status) return false;
     if (nHits < 0) continue;
     break;
   }
   if (c.nHistory >= e.caps->maxHistory) { *e.status = XM_ST_OVERFLOW; return false; }
   c.history[c.nHistory++] = qb;
-  const IndexView& ix = *e.ix;
   XM_TIC(tHits);
   for (int h = 0; h < nHits; h++) {
     RefPos rp = fetchHit(ix, first + h, invert, qb.len);
@@ -1038,10 +1051,11 @@ XM_NOINL ListRef compGetBestMatches(Comp& c, const SeedEnv& e) {  // :471-493 (+
   c.best.id = ++(*e.listIdCounter);
   c.best.n = 0;
   if (c.numBlocksMatchingAnywhere < 1) return c.best;
+  LaunchIx& ix = seIx(e);
   if (c.minNumDistinctMismatches < 0) {
     int mn = c.numNonoverlappingBlocksVisited - 1;
     for (int i = 0; i < c.nGood; i++) {
-      int cnt = counterNumDistinctMismatches(c, e, c.counters[c.good[i]]);
+      int cnt = counterNumDistinctMismatches(c, ix, c.counters[c.good[i]]);
       if (mn >= cnt) mn = cnt;
     }
     c.minNumDistinctMismatches = mn;
@@ -1049,7 +1063,7 @@ XM_NOINL ListRef compGetBestMatches(Comp& c, const SeedEnv& e) {  // :471-493 (+
   int mn = c.minNumDistinctMismatches;
   int n = 0;
   for (int i = 0; i < c.nGood; i++) {
-    int cnt = counterNumDistinctMismatches(c, e, c.counters[c.good[i]]);
+    int cnt = counterNumDistinctMismatches(c, ix, c.counters[c.good[i]]);
     if (cnt <= mn) c.best.items[n++] = c.good[i];
   }
   c.best.n = n;
@@ -1131,7 +1145,7 @@ XM_NOINL void pcMatchWithoutCache(PathsCounter& pc, const SeedEnv& e, const List
       q.n = 2;
       q.c[0] = counterMatch(pc.comps[0].counters[c0]);
       q.c[1] = counterMatch(pc.comps[1].counters[c1]);
-      q.hint = counterNumDistinctMismatches(pc.comps[0], e, pc.comps[0].counters[c0]) < counterNumDistinctMismatches(pc.comps[1], e, pc.comps[1].counters[c1]) ? 1 : 0;
+      q.hint = counterNumDistinctMismatches(pc.comps[0], seIx(e), pc.comps[0].counters[c0]) < counterNumDistinctMismatches(pc.comps[1], seIx(e), pc.comps[1].counters[c1]) ? 1 : 0;
       q.priority = countPriority(pc, e, c0, c1);
     }
   }

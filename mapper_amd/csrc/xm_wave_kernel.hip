@@ -26,7 +26,9 @@ __device__ __forceinline__ void waveAddCounters(DevCounters* g, const DevCounter
   atomicAdd(&g->hitsFetched, l.hitsFetched); atomicAdd(&g->candidatesExtended, l.candidatesExtended); atomicAdd(&g->pathAlignerCalls, l.pathAlignerCalls);
   atomicAdd(&g->pathAlignerNodes, l.pathAlignerNodes); atomicAdd(&g->quickAccepts, l.quickAccepts); atomicAdd(&g->alignmentsOut, l.alignmentsOut);
   atomicAdd(&g->refWindowBytes, l.refWindowBytes); atomicAdd(&g->readBytes, l.readBytes);
+#ifdef XM_HAVE_TICKS
   for (int i = 0; i < 16; i++) if (l.t[i]) atomicAdd(&g->t[i], l.t[i]);
+#endif
 }
 #endif
 __device__ __forceinline__ void saveCounters(const DevCounters& l, unsigned long long* b) {
@@ -144,7 +146,9 @@ __global__ void __launch_bounds__(WV_SEARCH_WAVES * 64, WV_SEARCH_MINWAVES) xm_w
     const int mi = M->req.seqAId >> 1;
     wRunSearch(S, nodes, ix, params, batch.codes + batch.mateOffset[q * 2 + mi], batch.mateLength[q * 2 + mi], M, &local);
   }
+#ifdef XM_HAVE_TICKS
   if (lane == 0) for (int i = 0; i < 16; i++) if (local.t[i]) atomicAdd(&counters->t[i], local.t[i]);
+#endif
 }
 #endif
 #if WV_CONFIG == 100

@@ -55,13 +55,12 @@ struct AlignReadState {
 };
 
 struct ReadCtx {
-  const IndexView* ix;
+  LaunchConstPtr lc;  // the launch's block: index view and parameters, read through cxIx / cxParams (no copy of either in the lane's private memory)
   Caps caps;
   DevCounters* dc;
   int32_t status;
   int32_t listIdCounter;
   ReadIn in;
-  Params params;
   Arena persist;  // bottom part of the lane's arena
   Arena tmp;      // top part
   SeedEnv seed;
@@ -70,6 +69,21 @@ struct ReadCtx {
   float heavyHint;      // light pass: largest straight-alignment penalty among the candidates that needed the gapped chain
   AlignReadState ar;
 };
+
+// index view and parameters of the launch through a uniform address (scalar loads); an out-of-line function takes them once, at its entry
+typedef XM_CONST(const Params) LaunchParams;
+XM_INL LaunchIx& cxIx(const ReadCtx& cx) { return xmUniform(cx.lc)->ix; }
+XM_INL LaunchParams& cxParams(const ReadCtx& cx) { return xmUniform(cx.lc)->params; }
+// a copy a function may change, or call Params' member functions on (P: Params in whichever address space)
+template <typename P>
+XM_INL Params paramsCopy(const P& p) {
+  Params r;
+  r.MutationPenalty = p.MutationPenalty; r.InsertionStart_Penalty = p.InsertionStart_Penalty; r.InsertionExtension_Penalty = p.InsertionExtension_Penalty;
+  r.DeletionStart_Penalty = p.DeletionStart_Penalty; r.DeletionExtension_Penalty = p.DeletionExtension_Penalty; r.MaxErrorRate = p.MaxErrorRate;
+  r.UnalignedPenalty = p.UnalignedPenalty; r.AmbiguityPenalty = p.AmbiguityPenalty; r.Max_PenaltySpan = p.Max_PenaltySpan;
+  r.MaxNumMatches = p.MaxNumMatches; r.StartingInsertionStartFree = p.StartingInsertionStartFree;
+  return r;
+}
 
 XM_INL SeqView queryView(const ReadCtx& cx, uint8_t seqAId) {
   SeqView v;
@@ -87,7 +101,7 @@ XM_INL double divideRoundUp(double a, double b) {  // M/QueryMatch_Aligner.java:
 // goodCap: room for that many accepted alignments (the read's aligner: caps.maxGoodAlignments; the two aligners of getUnpairedAlignments half of it - the
 // seeding state of a pair must still fit the region beside them)
 XM_INL void qmaInit(ReadCtx& cx, QMAligner& a, int nMates, int queryLength, int goodCap) {
-  a.parameters = cx.params;
+  a.parameters = paramsCopy(cxParams(cx));  // (its own: qmaAlign lowers its MaxErrorRate as alignments are accepted)
   a.nMates = nMates;
   a.queryLength = queryLength;
   a.expectedInner = cx.in.expectedInner;
@@ -111,11 +125,12 @@ XM_INL void qmaInit(ReadCtx& cx, QMAligner& a, int nMates, int queryLength, int 
 XM_INL void makeExtEnv(ReadCtx& cx, ExtEnv& e, const SeqView& query, int contig) {
   e.caps = &cx.caps; e.dc = cx.dc; e.status = &cx.status; e.tmp = &cx.tmp;
   e.query = query;
-  e.reference = refView(*cx.ix, contig, false);
+  LaunchIx& ix = cxIx(cx);
+  e.reference = refView(ix, contig, false);
   e.contig = contig;
   e.slotA = e.slotB = e.slotT = nullptr;
   e.heavyHint = &cx.heavyHint;
-  e.baLogStep = cx.ix->baLogStep;
+  e.baLogStep = ix.baLogStep;
 }
 
 // alignMatch :412-462 (fromHashblockMatch is always true).  The matcher slots live in tmp for the duration of the call.
@@ -161,7 +176,7 @@ XM_NOINL bool qmaAlignMatch(ReadCtx& cx, const SeqView& seqA, int contig, int of
 // ---- helpers over finished SequenceAlignments
 XM_INL double saPenaltyInRange(ReadCtx& cx, const Params& p, const SeqAl& a, int startIndexB, int endIndexB) {  // M/AlignmentParameters.java:97-154
   SeqView q = queryView(cx, a.seqAId);
-  SeqView r = refView(*cx.ix, a.contig, false);
+  SeqView r = refView(cxIx(cx), a.contig, false);
   double total = 0;
   for (int k = 0; k < a.nb; k++) {
     const ABlock& b = a.blocks[k];
@@ -204,7 +219,7 @@ XM_INL int saLengthAAfter(const SeqAl& a, int refIndex) {
 XM_INL bool saHasIndel(const SeqAl& a) { for (int i = 0; i < a.nb; i++) if (a.blocks[i].lenA != a.blocks[i].lenB) return true; return false; }
 XM_INL bool saHasAmbiguous(ReadCtx& cx, const SeqAl& a) {
   SeqView q = queryView(cx, a.seqAId);
-  SeqView r = refView(*cx.ix, a.contig, false);
+  SeqView r = refView(cxIx(cx), a.contig, false);
   for (int k = 0; k < a.nb; k++) {
     const ABlock& b = a.blocks[k];
     if (b.lenA != b.lenB) continue;
@@ -448,7 +463,8 @@ XM_NOINL void qmaGetBestAlignments(QMAligner& a) {
 }
 
 // ---------------------------------------------------------------- duplication map (M/Readable_DuplicationDetector.java:28-47)
-XM_INL bool mayContainDuplicationInRange(const IndexView& ix, int contig, int startIndex, int endIndex) {
+template <typename IX>
+XM_INL bool mayContainDuplicationInRange(const IX& ix, int contig, int startIndex, int endIndex) {
   int w = ix.dupWindow;
   int windowStart = startIndex / w, windowEnd = endIndex / w;
   const int32_t* keys = ix.dupKeys + ix.dupKeyStart[contig];
@@ -488,9 +504,9 @@ XM_INL void writeQAl(OutWriter& w, const QAl& q) {
 }
 
 // what alignToAncestralReference returns: up to 2 components, each a list of alignments of one aligner
-XM_INL double penaltyLowerBound(const ReadCtx& cx, int numMismatchedHashblocks) {  // M/AlignerWorker.java:487-491
-  double mutationPenalty = numMismatchedHashblocks * cx.params.MutationPenalty;
-  double indelPenalty = cx.ix->minInterestingSize * numMismatchedHashblocks * cx.params.DeletionExtension_Penalty;
+XM_INL double penaltyLowerBound(LaunchConstPtr lc, int numMismatchedHashblocks) {  // M/AlignerWorker.java:487-491
+  double mutationPenalty = numMismatchedHashblocks * lc->params.MutationPenalty;
+  double indelPenalty = lc->ix.minInterestingSize * numMismatchedHashblocks * lc->params.DeletionExtension_Penalty;
   return dmin(mutationPenalty, indelPenalty);
 }
 
@@ -498,8 +514,9 @@ XM_INL double penaltyLowerBound(const ReadCtx& cx, int numMismatchedHashblocks) 
 // hold goes to the miss list and the read stops with XM_ST_NEED_CONF.  (Host simulation of the tests: evaluated in place, by the same host function.)
 XM_INL bool confidenceLength(ReadCtx& cx, double penalty, int queryTotalLength, double& value) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  if (confLookup(cx.ix->conf, cx.ix->confMask, penalty, queryTotalLength, value)) return true;
-  ConfMiss* miss = cx.ix->confMiss;
+  LaunchIx& ix = cxIx(cx);
+  if (confLookup(ix.conf, ix.confMask, penalty, queryTotalLength, value)) return true;
+  ConfMiss* miss = ix.confMiss;
   if (miss) {
     const unsigned long long at = atomicAdd(&miss->n, 1ull);
     if (at < miss->cap) { uint64_t bits; __builtin_memcpy(&bits, &penalty, 8); miss->keys[at].penaltyBits = bits; miss->keys[at].queryLength = queryTotalLength; miss->keys[at].pad = 0; }
@@ -507,7 +524,7 @@ XM_INL bool confidenceLength(ReadCtx& cx, double penalty, int queryTotalLength, 
   cx.status = XM_ST_NEED_CONF;
   return false;
 #else
-  value = confidenceLengthOnHost(penalty, queryTotalLength, cx.params.Max_PenaltySpan, cx.params.MutationPenalty, cx.ix->dupGranularity, cx.ix->totalForwardAndReverseSize);
+  value = confidenceLengthOnHost(penalty, queryTotalLength, cx.lc->params.Max_PenaltySpan, cx.lc->params.MutationPenalty, cx.lc->ix.dupGranularity, cx.lc->ix.totalForwardAndReverseSize);
   return true;
 #endif
 }
@@ -520,7 +537,11 @@ XM_NOINL bool quicklyConfidentInBestAlignment(ReadCtx& cx, QMAligner& a, int alI
   int contig = m.c[0].contig;
   int matchStart = qmStartIndexB(m), matchEnd = qmEndIndexB(m);
   double penalty = al.totalPenalty;
-  if (penalty <= 0 && cx.params.Max_PenaltySpan < cx.params.getMinPossibleNonzeroPenalty()) return true;
+  LaunchIx& ix = cxIx(cx);
+  if (penalty <= 0) {
+    const Params p = paramsCopy(cxParams(cx));
+    if (p.Max_PenaltySpan < p.getMinPossibleNonzeroPenalty()) return true;
+  }
   // :532-540: 1 - (1 - rate)^granularity, the two logarithms and their quotient are the host's (xm_confidence.h): table lookup by (penalty, length)
   double totalLengthForHighConfidence = 0;
   if (!confidenceLength(cx, penalty, qmQueryTotalLength(cx.seed, m), totalLengthForHighConfidence)) return false;  // (status set: the read runs again once the host has the value)
@@ -529,9 +550,9 @@ XM_NOINL bool quicklyConfidentInBestAlignment(ReadCtx& cx, QMAligner& a, int alI
   int windowStart = j2i(matchMiddle - interestingWindow);
   int windowEnd = j2i(matchMiddle + interestingWindow);
   bool hasNearbyDuplication = false;
-  if (mayContainDuplicationInRange(*cx.ix, contig, windowStart, windowEnd)) hasNearbyDuplication = true;
+  if (mayContainDuplicationInRange(ix, contig, windowStart, windowEnd)) hasNearbyDuplication = true;
   else if (matchStart <= interestingWindow) hasNearbyDuplication = true;
-  else if (matchEnd >= cx.ix->contigLen[contig] - interestingWindow) hasNearbyDuplication = true;
+  else if (matchEnd >= ix.contigLen[contig] - interestingWindow) hasNearbyDuplication = true;
   XM_TOC(cx.dc, T_CONFIDENT, t0);
   if (hasNearbyDuplication) return false;
   for (int k = 0; k < al.nSeq; k++) if (saHasAmbiguous(cx, al.seq[k])) return false;
@@ -592,20 +613,22 @@ XM_INL void compInit(ReadCtx& cx, Comp& c, const SeqView& query, const SeqView& 
   c.numBlocksMatchingAnywhere = 0; c.maxNonoverlappingBlockVisited = 0; c.numNonoverlappingBlocksVisited = 0; c.minNumDistinctMismatches = -1;
   c.nextBlockId = 0;
   c.hp.id = c.best.id = c.all.id = 0; c.hp.n = c.best.n = c.all.n = 0;
-  int maxPossibleIndel = j2i((query.len * cx.params.MaxErrorRate - cx.params.DeletionStart_Penalty) / cx.params.DeletionExtension_Penalty);
+  LaunchParams& params = cxParams(cx);
+  int maxPossibleIndel = j2i((query.len * params.MaxErrorRate - params.DeletionStart_Penalty) / params.DeletionExtension_Penalty);
   c.maxIndelLengthToConsider = maxPossibleIndel / 2;
 }
 
 // getUnpairedAlignments :602-644
 XM_NOINL void getUnpairedAlignments(ReadCtx& cx, ReadResult& rr) {
   rr.nComponents = 2;
+  LaunchConstPtr lc = xmUniform(cx.lc);
   double expectedInnerDistance = cx.in.expectedInner;
   for (int sequenceIndex = 0; sequenceIndex < 2; sequenceIndex++) {
     rr.single[sequenceIndex] = -1;
     rr.empty[sequenceIndex] = 0;
     int len = cx.in.mateLen[sequenceIndex];
-    double maxInterestingSubqueryPenalty = len * cx.params.MaxErrorRate;
-    int maxNumMismatches = j2i(maxInterestingSubqueryPenalty / cx.params.MutationPenalty);
+    double maxInterestingSubqueryPenalty = len * lc->params.MaxErrorRate;
+    int maxNumMismatches = j2i(maxInterestingSubqueryPenalty / lc->params.MutationPenalty);
     ListRef locs = compFindGoodPositionsHavingPriorityUpTo(cx.comps[sequenceIndex], cx.seed, maxNumMismatches);  // findGoodComponentMatches
     if (cx.status) return;
     QMAligner* sub = arenaArray<QMAligner>(cx.persist, 1);
@@ -618,7 +641,7 @@ XM_NOINL void getUnpairedAlignments(ReadCtx& cx, ReadResult& rr) {
       SeqMatch sm = counterMatch(k);
       int minInnerDistance;
       if (sequenceIndex % 2 == 1) minInnerDistance = smStartB(sm);
-      else minInnerDistance = cx.ix->contigLen[sm.contig] - smEndB(cx.seed, sm);
+      else minInnerDistance = lc->ix.contigLen[sm.contig] - smEndB(cx.seed, sm);
       double innerDistance = minInnerDistance;
       if (innerDistance < expectedInnerDistance) innerDistance = expectedInnerDistance;
       double spacingPenalty = innerDistance / cx.in.deviation;
@@ -642,6 +665,8 @@ XM_NOINL void alignRead(ReadCtx& cx, ReadResult& rr, bool resume = false) {
   const SeedEnv& se = cx.seed;
   QMAligner* aligner = nullptr;
   int al = -1;
+  const LaunchConstPtr lc = xmUniform(cx.lc);
+  const double maxPenaltySpan = lc->params.Max_PenaltySpan;
   if (resume) {
     rr = st.rr;
     aligner = st.aligner;
@@ -654,13 +679,13 @@ XM_NOINL void alignRead(ReadCtx& cx, ReadResult& rr, bool resume = false) {
   st.phase = 0;
   if (cx.dc) { cx.dc->reads++; for (int m = 0; m < in.nMates; m++) cx.dc->readBytes += (unsigned long long)((in.mateLen[m] + 1) / 2); }
   rr.nComponents = 1; rr.single[0] = -1; rr.empty[0] = 0; rr.aligner[0] = nullptr;
-  for (int m = 0; m < in.nMates; m++) if (in.mateLen[m] > cx.ix->maxHashedLength) { cx.status = XM_ST_NEED_GROW; return; }
+  for (int m = 0; m < in.nMates; m++) if (in.mateLen[m] > lc->ix.maxHashedLength) { cx.status = XM_ST_NEED_GROW; return; }
   st.queryLength = 0;
   for (int m = 0; m < in.nMates; m++) st.queryLength += in.mateLen[m];
-  st.maxInterestingPenalty = st.queryLength * cx.params.MaxErrorRate;
+  st.maxInterestingPenalty = st.queryLength * lc->params.MaxErrorRate;
   {
     int maxInnerDistance = j2i(st.maxInterestingPenalty * in.deviation + in.expectedInner);
-    cx.seed.ix = cx.ix; cx.seed.caps = &cx.caps; cx.seed.dc = cx.dc; cx.seed.status = &cx.status; cx.seed.listIdCounter = &cx.listIdCounter;
+    cx.seed.lc = cx.lc; cx.seed.caps = &cx.caps; cx.seed.dc = cx.dc; cx.seed.status = &cx.status; cx.seed.listIdCounter = &cx.listIdCounter;
     cx.seed.mateLen = cx.in.mateLen;
     cx.listIdCounter = 0;
     for (int i = 0; i < in.nMates; i++) {
@@ -707,8 +732,8 @@ resume_optimistic:
   st.phase = 2;
   if (st.optimisticBestAlignment >= 0) {
     while (true) {
-      double possiblePenalty = penaltyLowerBound(cx, st.numMismatches);
-      if (possiblePenalty > aligner->good[st.optimisticBestAlignment].totalPenalty + cx.params.Max_PenaltySpan) {
+      double possiblePenalty = penaltyLowerBound(lc, st.numMismatches);
+      if (possiblePenalty > aligner->good[st.optimisticBestAlignment].totalPenalty + maxPenaltySpan) {
         rr.single[0] = st.optimisticBestAlignment;
         return;
       }
@@ -723,8 +748,8 @@ resume_optimistic:
   st.bestPenalty = (double)INT32_MAX;
   st.candidateNumMismatches = 0;
   while (true) {
-    st.estimatedPenalty = penaltyLowerBound(cx, st.candidateNumMismatches);
-    if (st.estimatedPenalty > st.bestPenalty + cx.params.Max_PenaltySpan) break;
+    st.estimatedPenalty = penaltyLowerBound(lc, st.candidateNumMismatches);
+    if (st.estimatedPenalty > st.bestPenalty + maxPenaltySpan) break;
     if (st.candidateNumMismatches > pcGetNumBlocks(pc)) break;
     pcFindGoodPositionsHavingPriority(pc, se, st.candidateNumMismatches);
     if (cx.status) return;
@@ -775,7 +800,7 @@ resume_partial:
       getUnpairedAlignments(cx, rr);
       if (cx.status) return;
     }
-    if ((int64_t)numBest > (int64_t)cx.params.MaxNumMatches) {  // :476-481
+    if ((int64_t)numBest > (int64_t)lc->params.MaxNumMatches) {  // :476-481
       rr.nComponents = 1; rr.single[0] = -1; rr.empty[0] = 1;
     }
   }
@@ -857,12 +882,11 @@ XM_INL void applyChainCaps(Caps& c, int chainScale) {
 // A read whose persistent arena is a region of its own and whose temporaries are the lane's arena.  Light pass (heavyAllowed < 2): a read
 // that stops in front of the gapped chain leaves a SavedRead at the tail of the region.  Gapped pass, read without saved state
 // (heavyAllowed 2, chainScale = the gapped scale): seeded at `scale`, chain scratch of the gapped pass.
-XM_INL void runReadRetaining(ReadCtx& cx, const IndexView* ix, const Params& params, const ReadIn& in, int scale, void* region, size_t regionBytes, void* laneArena, size_t laneArenaBytes,
+XM_INL void runReadRetaining(ReadCtx& cx, LaunchConstPtr lc, const ReadIn& in, int scale, void* region, size_t regionBytes, void* laneArena, size_t laneArenaBytes,
                              DevCounters* dc, ReadResult& rr, int heavyAllowed, int chainScale = 0) {
-  cx.ix = ix; cx.caps = makeCaps(scale); cx.caps.heavyAllowed = heavyAllowed; cx.dc = dc; cx.status = XM_OK; cx.in = in; cx.params = params;
+  cx.lc = lc; cx.caps = makeCaps(scale); cx.caps.heavyAllowed = heavyAllowed; cx.dc = dc; cx.status = XM_OK; cx.in = in;
   if (chainScale > 0 && chainScale != scale) applyChainCaps(cx.caps, chainScale);
   cx.heavyHint = 0;
-  cx.params.StartingInsertionStartFree = 0;
   cx.persist.init(region, retainedPersistBytes(regionBytes));
   cx.tmp.init(laneArena, laneArenaBytes);
   SavedRead* sv = savedReadOf(region, regionBytes);
@@ -885,10 +909,10 @@ XM_INL void runReadRetaining(ReadCtx& cx, const IndexView* ix, const Params& par
 // gapped pass, a read the light pass handed over: the context back on this lane, pointers into the context re-seated, the chain's scratch
 // capacities of the gapped pass, temporaries in this lane's arena; then on from the candidate that needed the chain, to the read's end.  The saved
 // state is consumed (pyramid levels, hit lists and the aligner advance in place): a read is resumed once.
-XM_INL void runReadResumed(ReadCtx& cx, SavedRead* sv, const IndexView* ix, int chainScale, void* laneArena, size_t laneArenaBytes, DevCounters* dc, ReadResult& rr) {
+XM_INL void runReadResumed(ReadCtx& cx, SavedRead* sv, LaunchConstPtr lc, int chainScale, void* laneArena, size_t laneArenaBytes, DevCounters* dc, ReadResult& rr) {
   cx = sv->cx;
-  cx.ix = ix; cx.dc = dc; cx.status = XM_OK;
-  cx.seed.ix = ix; cx.seed.caps = &cx.caps; cx.seed.dc = dc; cx.seed.status = &cx.status; cx.seed.listIdCounter = &cx.listIdCounter; cx.seed.mateLen = cx.in.mateLen;
+  cx.lc = lc; cx.dc = dc; cx.status = XM_OK;  // (the block of THIS launch: the saved address was the light pass's)
+  cx.seed.lc = lc; cx.seed.caps = &cx.caps; cx.seed.dc = dc; cx.seed.status = &cx.status; cx.seed.listIdCounter = &cx.listIdCounter; cx.seed.mateLen = cx.in.mateLen;
   for (int m = 0; m < 2; m++) { cx.comps[m].pyr.status = &cx.status; cx.comps[m].pyr.dc = dc; }
   cx.pc.comps = cx.comps;
   cx.tmp.init(laneArena, laneArenaBytes);
@@ -902,10 +926,9 @@ XM_INL void runReadResumed(ReadCtx& cx, SavedRead* sv, const IndexView* ix, int 
 }
 
 // Carve a lane's arena and align one read.  `arena` must be 16-byte aligned.
-XM_INL void runRead(ReadCtx& cx, const IndexView* ix, const Params& params, const ReadIn& in, int scale, void* arena, size_t arenaBytes, DevCounters* dc, ReadResult& rr, int heavyAllowed = 2) {
-  cx.ix = ix; cx.caps = makeCaps(scale); cx.caps.heavyAllowed = heavyAllowed; cx.dc = dc; cx.status = XM_OK; cx.in = in; cx.params = params;
+XM_INL void runRead(ReadCtx& cx, LaunchConstPtr lc, const ReadIn& in, int scale, void* arena, size_t arenaBytes, DevCounters* dc, ReadResult& rr, int heavyAllowed = 2) {
+  cx.lc = lc; cx.caps = makeCaps(scale); cx.caps.heavyAllowed = heavyAllowed; cx.dc = dc; cx.status = XM_OK; cx.in = in;
   cx.heavyHint = 0;
-  cx.params.StartingInsertionStartFree = 0;
   const size_t persistBytes = arenaPersistBytes(arenaBytes);
   cx.persist.init(arena, persistBytes);
   cx.tmp.init((uint8_t*)arena + persistBytes, arenaBytes - persistBytes);
@@ -913,5 +936,27 @@ XM_INL void runRead(ReadCtx& cx, const IndexView* ix, const Params& params, cons
   alignRead(cx, rr);
   XM_TOC(dc, T_TOTAL, t0);
 }
+
+#if !defined(__HIPCC__)
+// Host simulation only (tests/hostsim): the entries as they were before the launch block, with the view and the parameters given directly.  The block a
+// read runs with is made here, in front of the read, as the product's host side makes it in front of a launch; it lives until the thread's next read.  A resumed
+// read takes its parameters from the block it was stopped under (the simulation resumes it on the same thread, under the same call's parameters).
+XM_INL void runReadRetaining(ReadCtx& cx, const IndexView* ix, const Params& params, const ReadIn& in, int scale, void* region, size_t regionBytes, void* laneArena, size_t laneArenaBytes,
+                             DevCounters* dc, ReadResult& rr, int heavyAllowed, int chainScale = 0) {
+  static thread_local LaunchConst block;
+  block = launchConstOf(*ix, params);
+  runReadRetaining(cx, &block, in, scale, region, regionBytes, laneArena, laneArenaBytes, dc, rr, heavyAllowed, chainScale);
+}
+XM_INL void runReadResumed(ReadCtx& cx, SavedRead* sv, const IndexView* ix, int chainScale, void* laneArena, size_t laneArenaBytes, DevCounters* dc, ReadResult& rr) {
+  static thread_local LaunchConst block;
+  block = launchConstOf(*ix, sv->cx.lc->params);
+  runReadResumed(cx, sv, &block, chainScale, laneArena, laneArenaBytes, dc, rr);
+}
+XM_INL void runRead(ReadCtx& cx, const IndexView* ix, const Params& params, const ReadIn& in, int scale, void* arena, size_t arenaBytes, DevCounters* dc, ReadResult& rr, int heavyAllowed = 2) {
+  static thread_local LaunchConst block;
+  block = launchConstOf(*ix, params);
+  runRead(cx, &block, in, scale, arena, arenaBytes, dc, rr, heavyAllowed);
+}
+#endif
 
 }  // namespace xm
