@@ -124,7 +124,7 @@ const char* xm_build_stamp(void);
 /* Version of this header's structs and entry points: 2 = xm_result.extra[] appended, xm_seed_probe_packed replaces xm_seed_probe; 3 = xm_context_set_collapse,
  * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6]; 5 = xm_memory_new, xm_context_attach_memory, xm_memory_info,
  * xm_memory_free, xm_result.reserved carries the wait for a memory; 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7 = xm_sam_set_contigs,
- * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles).  A binding checks it once
+ * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles); 8 = xm_batch_unstage.  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -228,7 +228,14 @@ int64_t xm_index_dup_keys(const xm_index* index, int32_t contig, int32_t* out, i
 
 /* Replaces the per-read loop of AlignerWorker.process() / Api.align (AlignerWorker.java:177-231,306-644): every query is
  * aligned on the GPU; *out is allocated by the library (its four streams are pinned host buffers from a pool the library keeps) and
- * released with xm_result_free.  Reads may contain IUPAC ambiguity codes (at most 128 ambiguous bases per mate). */
+ * released with xm_result_free.  Reads may contain IUPAC ambiguity codes (at most 128 ambiguous bases per mate).
+ * A call fails as a whole - "Failed to align query q: the reference implementation would have thrown here" - when the reference would have thrown for one of
+ * its queries: a mate contained in its partner (tryJoinQuerySequences asks for a range of negative length), a negative deviation, a deviation or expected
+ * inner distance so large that the mate window wraps in 32-bit arithmetic (TreeMap.subMap: fromKey > toKey); INTEGRATION.md section 2 states the conditions.
+ * q is the lowest failing query of the first pass that met one.  A call that fails leaves nothing behind: no result; nothing remembered
+ * (xm_context_set_memo, xm_memory_new); no streams of a last call - xm_sam_format_last and xm_pileup_add_last fail with "no longer resident" after it,
+ * whether or not an earlier call on the same resident batch had succeeded, until the next align call succeeds; the context's next call and the other
+ * contexts of the index align as if it had not happened. */
 int xm_align_batch(xm_index* index, const xm_params* params, const xm_query_batch* batch, xm_result** out);
 void xm_result_free(xm_result* result);
 /* The same in two steps, for callers that keep a batch in HBM (and for measuring the path without the PCIe copy):
@@ -238,9 +245,12 @@ int xm_align_resident(xm_index* index, const xm_params* params, xm_result** out)
 /* The reference's workers take the next batch of queries while the previous one is being aligned (AlignerWorker.run / requestMoreWork,
  * AlignerWorker.java:92-175).  Here: xm_batch_stage copies the NEXT batch into a second set of device buffers on its own stream and may
  * run (from another host thread) while xm_align_resident is aligning the resident batch; xm_batch_commit then makes the staged batch
- * the resident one (it waits for a running xm_align_resident).  xm_batch_upload = stage + commit without the overlap. */
+ * the resident one (it waits for a running xm_align_resident).  xm_batch_upload = stage + commit without the overlap.
+ * (ABI version 8) xm_batch_unstage drops a staged batch that will not be committed - the batch behind one whose align call failed - so that a later
+ * xm_batch_commit finds "no staged batch"; without a staged batch it does nothing.  The resident batch is untouched. */
 int xm_batch_stage(xm_index* index, const xm_query_batch* batch);
 int xm_batch_commit(xm_index* index);
+int xm_batch_unstage(xm_index* index);
 
 /* (ABI version 6) The batch staged from FASTQ text instead of from arrays: the host hands over a block of whole four-line records as it read them from the
  * file - one text for single reads, two texts of equally many records for pairs (record i of each is query i) - and kernels build the arrays of
@@ -275,7 +285,7 @@ int32_t xm_fastq_tile_bytes(void);
  * header.  The host is left with writing the bytes.  Not used by the Java host, which keeps its own writers.
  * xm_sam_set_contigs: the RNAME / RNEXT names, once per context, before the first format call; num_contigs must be the index's.
  * xm_sam_format_last has the contract of xm_pileup_add_last: it serialises with the context's other calls, runs on the context's stream, and fails with
- * "no longer resident" once another batch has been uploaded or committed.  names == NULL: the names that xm_batch_stage_fastq built, which belong to the
+ * "no longer resident" once another batch has been uploaded or committed, and after an align call that failed.  names == NULL: the names that xm_batch_stage_fastq built, which belong to the
  * batch in HBM (they change hands with it in xm_batch_commit); a batch that was staged from arrays has none, and the call fails.  Otherwise the mates'
  * names as xmio_batch holds them - name_off has 2 * num_queries + 1 entries, mate m of query q is names[name_off[2q + m] .. name_off[2q + m + 1]) - which
  * are copied up and may be pageable memory.  A slice that is not of the layout above (xmio_write_batch's "malformed result streams") fails the call with the

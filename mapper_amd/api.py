@@ -437,6 +437,10 @@ class ReferenceDatabase:
         """xm_batch_commit: the staged batch becomes the resident one."""
         _check(self._L.xm_batch_commit(self._h))
 
+    def unstage(self):
+        """xm_batch_unstage: a staged batch that will not be committed is dropped (none staged: nothing happens)."""
+        _check(self._L.xm_batch_unstage(self._h))
+
     def align_stream(self, batches, parameters, on_aligned=None):
         """Aligns a sequence of batches (each a tuple of upload_arrays' six arrays, or a hostio.TextBlock, which is staged with stage_fastq) and yields their BatchResults in order.  The copy of
         batch k+1 to HBM runs on a second host thread and a second stream while batch k is being aligned (the
@@ -492,6 +496,8 @@ class ReferenceDatabase:
             stop.set()
             aligned.release()
             t.join(timeout=60)
+            if not t.is_alive():  # (a stream that ends early - an align call failed, the caller went away - leaves no batch staged behind it)
+                self.unstage()
 
     def align_resident(self, parameters):
         return self._align(lambda p, res: self._L.xm_align_resident(self._h, p, res), parameters)

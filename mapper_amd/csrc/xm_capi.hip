@@ -1050,7 +1050,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 7; }
+int32_t xm_abi_version(void) { return 8; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();
@@ -1468,6 +1468,15 @@ int xm_batch_commit(xm_index* idx) {
   } catch (std::exception& e) { return fail(std::string("xm_batch_commit: ") + e.what()); }
 }
 
+int xm_batch_unstage(xm_index* idx) {
+  if (!idx) return fail("xm_batch_unstage: null argument");
+  try {
+    std::lock_guard<std::mutex> stageLock(idx->stageMu);
+    idx->staged.nq = -1;  // (its buffers stay: they are the staging set of the next xm_batch_stage)
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_batch_unstage: ") + e.what()); }
+}
+
 int xm_align_resident(xm_index* idx, const xm_params* p, xm_result** out) {
   if (!idx || !p || !out) return fail("xm_align_resident: null argument");
   try {
@@ -1496,6 +1505,7 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
   xm_result* res = &box->pub;
   try {
     const int64_t nq = idx->resident.nq;
+    idx->results.forgetLast();
     HIP_CHECK(hipSetDevice(idx->device));
     // the shared tables stay as they are while this call's kernels read them (another context that grows them waits; so does this one's next growth)
     std::shared_lock<std::shared_mutex> tablesInUse(idx->dt->rw);

@@ -62,6 +62,7 @@ enum : int32_t {
 
 // ---------------------------------------------------------------- Java arithmetic
 XM_INL int32_t jadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+XM_INL int32_t jsub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
 XM_INL int32_t jmul(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
 XM_INL int32_t jabs(int32_t v) { return v == INT32_MIN ? v : (v < 0 ? -v : v); }
 XM_INL int32_t j2i(double d) {  // (int)double: truncation, saturation, NaN -> 0

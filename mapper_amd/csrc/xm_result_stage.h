@@ -144,6 +144,8 @@ struct ResultStage {
     if (usedI) HIP_CHECK(hipMemcpyAsync(res->ints, dFinalInts.p, sizeof(int32_t) * usedI, hipMemcpyDeviceToHost, s));
     if (usedD) HIP_CHECK(hipMemcpyAsync(res->dbls, dFinalDbls.p, sizeof(double) * usedD, hipMemcpyDeviceToHost, s));
   }
+  // an align call begins: until it has succeeded (toHost) there are no streams of a last call - a call that fails leaves none behind
+  void forgetLast() { lastAlignedNq = -1; lastAlignedGen = -1; }
   // the streams of the last call where they lie in HBM, if they belong to the resident batch of generation gen with nq queries (else: nq = -1)
   struct LastStreams { int64_t nq; const int32_t* ints; const int64_t* intOff; size_t intsHeld; const double* dbls; const int64_t* dblOff; };
   LastStreams lastStreams(int64_t gen, int64_t nq) const {

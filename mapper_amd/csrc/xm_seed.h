@@ -1120,7 +1120,7 @@ XM_NOINL void pcMatchWithoutCache(PathsCounter& pc, const SeedEnv& e, const List
     int searchStart, searchEnd;
     bool otherSequenceExpectEarlier = (queryMatchReversed == lastComponentIsLargest);
     if (otherSequenceExpectEarlier) { searchStart = offset - maxReverseOffset; searchEnd = jadd(offset, pc.maxOffsetBetweenComponents); }
-    else { searchStart = offset - pc.maxOffsetBetweenComponents; searchEnd = offset + maxReverseOffset; }
+    else { searchStart = jsub(offset, pc.maxOffsetBetweenComponents); searchEnd = offset + maxReverseOffset; }
     if (searchStart > searchEnd) { *e.status = XM_ST_INTERNAL; return; }  // TreeMap.subMap would throw
     // entries of the first component filed under the same (direction, contig), offset in [searchStart, searchEnd], ascending
     int nn = 0;

@@ -942,7 +942,7 @@ WV_FN void wPcMatchWithoutCache(WL_T L, const WEnv& e, const int* which) {  // :
     int searchStart, searchEnd;
     const bool otherSequenceExpectEarlier = (queryMatchReversed == lastComponentIsLargest);
     if (otherSequenceExpectEarlier) { searchStart = offset - maxReverseOffset; searchEnd = jadd(offset, L->maxOffsetBetweenComponents); }
-    else { searchStart = offset - L->maxOffsetBetweenComponents; searchEnd = offset + maxReverseOffset; }
+    else { searchStart = jsub(offset, L->maxOffsetBetweenComponents); searchEnd = offset + maxReverseOffset; }
     if (searchStart > searchEnd) { L->status = XM_ST_INTERNAL; return; }  // TreeMap.subMap would throw
     // entries of the first component filed under the same (direction, contig) with offset in [searchStart, searchEnd], ascending
     int8_t nearby[LDS::kCounters];

@@ -565,7 +565,7 @@ struct HashBlockPaths_Counter {
           int searchStart, searchEnd;
           bool otherSequenceExpectEarlier = (queryMatchReversed == lastComponentIsLargest);
           if (otherSequenceExpectEarlier) { searchStart = offset - maxReverseOffset; searchEnd = jadd(offset, maxOffsetBetweenComponents); }
-          else { searchStart = offset - maxOffsetBetweenComponents; searchEnd = offset + maxReverseOffset; }
+          else { searchStart = jsub(offset, maxOffsetBetweenComponents); searchEnd = offset + maxReverseOffset; }
           std::vector<CounterP> nearby;
           if (searchStart <= searchEnd) {
             for (auto it = matchesOnThisSequence.lower_bound(searchStart); it != matchesOnThisSequence.end() && it->first <= searchEnd; ++it) nearby.push_back(it->second);

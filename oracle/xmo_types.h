@@ -24,6 +24,7 @@ namespace xmo {
 // ---------------------------------------------------------------- Java arithmetic helpers
 static inline int32_t jwrap(int64_t v) { return (int32_t)(uint32_t)(uint64_t)v; }
 static inline int32_t jadd(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
+static inline int32_t jsub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
 static inline int32_t jmul(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
 // (int)double in Java: truncation toward zero, saturating, NaN -> 0
 static inline int32_t j2i(double d) {
