@@ -124,7 +124,8 @@ const char* xm_build_stamp(void);
 /* Version of this header's structs and entry points: 2 = xm_result.extra[] appended, xm_seed_probe_packed replaces xm_seed_probe; 3 = xm_context_set_collapse,
  * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6]; 5 = xm_memory_new, xm_context_attach_memory, xm_memory_info,
  * xm_memory_free, xm_result.reserved carries the wait for a memory; 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7 = xm_sam_set_contigs,
- * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles); 8 = xm_batch_unstage.  A binding checks it once
+ * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles); 8 = xm_batch_unstage; 9 = xm_pileup_keep_insert_text, xm_pileup_event_text (and the test-only
+ * xm_test_pileup_text).  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -350,6 +351,20 @@ int xm_pileup_read_middle(xm_pileup* pileup, int32_t contig, int64_t first, int6
 int xm_pileup_add_last(xm_pileup* pileup, int64_t* num_events);
 int xm_pileup_read(xm_pileup* pileup, int32_t contig, int64_t first, int64_t n, uint64_t* depth, uint64_t* alt /* [4][n] */);
 int64_t xm_pileup_events(xm_pileup* pileup, int64_t first, int64_t n, int64_t* out /* [8 * n] */);
+/* (ABI version 9) The text of the insertion events kept with them.  When an event is made its bases are in HBM with the batch; with on != 0 every later
+ * xm_pileup_add_last also keeps them: kernels measure, place and write the letters of the call's insertions while the batch is resident, and the host copies
+ * them down with the events and carries them through the same ordering, so that a caller needs the queries of no batch to write an insertion (the mutations
+ * file: MutationsWriter_Test.java:18-134).  Off by default, and then xm_pileup_add_last launches and allocates what it did before; set before the first add.
+ * The text of an insertion event: byte i is the letter (the 16 of QuickVariants Basepairs: ?ACMGRSVTWYHKDBN by code) of base startA + i of the event's mate
+ * on the strand that was aligned - the complement of base readLen - 1 - (startA + i) of the mate as given when the reversed bit is set - for
+ * i < min(length, readLen - startA), which is all of `length` for every event the library makes; a deletion event has no text.  The mate is bit 0 of the
+ * flags word.  mapper_amd/csrc/xm_pileup_text_rules.h states this as code.
+ * xm_pileup_event_text has xm_pileup_events' paging contract over the same events: text_off[0 .. m] are offsets into `text`, relative to the first byte
+ * returned, event first + i owning [text_off[i], text_off[i + 1]); it returns m, the events served.  When text_cap bytes do not hold the text of all n
+ * events it serves fewer - as many as fit, at least one; -1 when the first event alone does not fit, when first is outside of the events, and when text
+ * was not kept.  Like the events the text is host memory: no live context and no GPU call are needed. */
+int xm_pileup_keep_insert_text(xm_pileup* pileup, int32_t on);
+int64_t xm_pileup_event_text(xm_pileup* pileup, int64_t first, int64_t n, int64_t* text_off /* [m + 1] */, char* text, int64_t text_cap);
 void xm_pileup_free(xm_pileup* pileup);
 
 /* TEST-ONLY entry (tests/test_gpu_kat.py; not part of the drop-in boundary): the reference's component-level known-answer tests run by the
@@ -379,6 +394,14 @@ typedef struct xm_test_sam_job {
   const int32_t* ints; const double* dbls; const int64_t* int_off; const int64_t* dbl_off;
 } xm_test_sam_job;
 int xm_test_sam_format(int32_t device, const xm_test_sam_job* job, xm_sam_text** out);
+/* Test-only (tests/test_gpu_pileup_text.py): the kernels that keep the insertion text (xm_pileup_keep_insert_text) over host-given events - eight int64 each,
+ * as xm_pileup_events returns them, holding anything - and the arrays of a batch, on `device`; no index and no alignment.  Query event[4] - query_base is the
+ * event's.  text_off[num_events + 1] and the text as xm_pileup_event_text pages them, in the order of `events`; launches (may be NULL): kernels launched. */
+typedef struct xm_test_pileup_job {
+  int64_t num_queries; const int64_t* mate_offset; const int32_t* mate_length; const uint8_t* codes; int64_t codes_length;
+  int64_t num_events; const int64_t* events; int64_t query_base;
+} xm_test_pileup_job;
+int xm_test_pileup_text(int32_t device, const xm_test_pileup_job* job, int64_t* text_off, char* text, int64_t text_cap, int32_t* launches);
 /* Test-only: Double.toString as the SAM tags print it, run by the device on n values: out24[24 * i ...] the string of x[i] (padded with NUL), len[i] its length. */
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len);
 

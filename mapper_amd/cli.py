@@ -17,10 +17,15 @@ outputs are the same, and one line on stderr says how many queries were served a
 it has aligned in that much HBM and serves byte-identical queries of its later batches from there: the same cache across batches; same outputs, one line on
 stderr), and --remember-queries-per-gpu <MiB> (one such memory per GPU, which all its contexts share and which keeps remembering when it is full; not
 together with --remember-queries), and --parse-on-gpu (the FASTQ files go to the GPU as text and are parsed there, api.ReferenceDatabase.stage_fastq: same outputs;
-four-line FASTQ records only, so a file the host reader takes may be refused with a message that says where; not with --per-object or a split size),
+four-line FASTQ records only, so a file the host reader takes may be refused with a message that says where; not with --per-object or a split size; a job
+whose output needs objects - --out-refs-map-count, needs_objects - parses on the host all the same),
 --format-on-gpu (the SAM records are formatted on the GPU while a batch and its results are resident, api.ReferenceDatabase.format_sam_last, and the host
 only writes the bytes: same outputs; --out-unaligned stays with the host; not with --per-object, --out-mutations or --out-refs-map-count; nothing to do
 without --out-sam), and --format-threads <n> (threads of the host's SAM formatter).
+
+--out-mutations streams like --out-sam: the device pile-up keeps the bases of every insertion with its event (pileup.MatchDatabase(keep_insert_text=True)), so
+the mutations file needs no object per read; with --per-object it is written the first way, from the Query objects of the whole job, which is the reference
+the streamed one is compared with.
 """
 import contextlib
 import gzip
@@ -220,7 +225,7 @@ def parse_args(argv):
         raise UsageError("--parse-on-gpu is not supported with --split-queries-past-size (the sections are cut by the host reader)")
     for other, key in (("--per-object", "per_object"), ("--out-mutations", "out_mutations"), ("--out-refs-map-count", "out_refs_map_count")):
         if o.get("format_on_gpu") and o.get(key):
-            raise UsageError("--format-on-gpu and %s exclude each other (that output goes through the per-object path, which formats on the host)" % other)
+            raise UsageError("--format-on-gpu and %s exclude each other (--per-object and --out-refs-map-count format on the host; the pile-up of --out-mutations has not been run beside the device formatter)" % other)
     if o.get("remember") and o.get("remember_per_gpu"):
         raise UsageError("--remember-queries (a memory per context) and --remember-queries-per-gpu (one per GPU) exclude each other")
     return o
@@ -292,6 +297,12 @@ def sam_header(contigs):
     lines += ["@SQ\tSN:%s\tLN:%d" % (name, len(text)) for name, text in contigs]
     lines.append("@PG\tID:xmapper-mi355x\tPN:xmapper-mi355x")
     return lines
+
+
+def needs_objects(o):
+    """Whether the job runs through the per-object path (object_source, ObjectSink): when it is asked for, and for the one output that is counted from
+    decoded alignments.  --out-mutations is not among them: its only use of the objects, the text of insertions, comes from the device pile-up."""
+    return bool(o.get("out_refs_map_count") or o.get("per_object"))
 
 
 def default_contexts(explicit_devices, batches, single_short):
@@ -544,7 +555,7 @@ def run(argv, out=sys.stdout, open_database=None):
     ordered = api.sort_reference(contigs)  # Mapper.sortAndComplementReference: alignment results refer to this order
     names = [n for n, _ in ordered]
     batch_size = o.get("batch_size") or 1_000_000
-    per_object = bool(o.get("out_mutations") or o.get("out_refs_map_count") or o.get("per_object"))  # (the outputs that need objects)
+    per_object = needs_objects(o)
     with contextlib.ExitStack() as job:  # what the job opens is closed here, last opened first, also when a step raises
         job.enter_context(strict_form_hint())
         batches, count, single_short, max_len = object_source(o, batch_size) if per_object else native_source(o, batch_size, job)
@@ -574,11 +585,12 @@ def run(argv, out=sys.stdout, open_database=None):
         match_db = on_aligned = None
         if o.get("out_mutations"):  # Mapper.java:700-708: the MatchDatabase listens to every batch; here it accumulates on the GPU while the batch is resident
             from . import pileup
-            match_db = pileup.MatchDatabase(db.replicas if hasattr(db, "replicas") else db, o.get("query_end_fraction", 0.1))  # (default 0.1: Mapper.java:76)
+            # (default 0.1: Mapper.java:76; streamed batches are closed once they are written, so the pile-up keeps the text of insertions itself)
+            match_db = pileup.MatchDatabase(db.replicas if hasattr(db, "replicas") else db, o.get("query_end_fraction", 0.1), keep_insert_text=not per_object)
             job.callback(match_db.close)
 
             def on_aligned(*at):  # ReferenceDatabase.align_stream calls it with (batch), MultiGpuDatabase's with (replica, batch), on the replica's thread
-                match_db.add_last(batches[at[-1]].queries, replica=at[0] if len(at) > 1 else 0)
+                match_db.add_last(batches[at[-1]].queries if per_object else None, replica=at[0] if len(at) > 1 else 0)
         t_stream = time.perf_counter()
         tally = {}
         copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned, tally, format_on_gpu=format_on_gpu)

@@ -1050,7 +1050,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 8; }
+int32_t xm_abi_version(void) { return 9; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();

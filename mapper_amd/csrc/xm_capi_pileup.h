@@ -1,5 +1,6 @@
 // The pile-up of the alignments on the reference (included once, by xm_capi.hip, behind xm_index): its kernel, its handle and its C entries.
 #pragma once
+#include "xm_pileup_text.h"
 
 namespace {
 
@@ -19,6 +20,7 @@ struct PileupView {
   long long queryBase;           // index of the batch's first query among all queries added so far
   unsigned long long* mid;       // [totalForwardSize] depth from query bases that are not near a query end (null: no query-end fraction set)
   double endFraction;            // MatchDatabase(queryEndFraction), --distinguish-query-ends (Mapper.java:76,351-353,700)
+  unsigned long long* textBytes; // the bytes of text the insertion events of this call keep, summed (null: no text is kept, xm_pileup_keep_insert_text)
 };
 // a query base "near the end of the query": within endFraction of the query's length of either end  [inferred: the rule lives in the un-vendored
 // MatchDatabase; pinned by MutationsWriter_Test.java:114-134 only for fraction 0.5 = every base]
@@ -85,6 +87,7 @@ __global__ void __launch_bounds__(256) xm_pileup_kernel(IndexView ix, BatchView 
               long long* e = pv.events + at * 8;
               e[0] = contig; e[1] = startB; e[2] = lenA > 0 ? 1 : 2; e[3] = lenA > 0 ? lenA : lenB; e[4] = pv.queryBase + q; e[5] = mate | (reversed << 1) | ((pv.mid && xmNearQueryEnd(startA, readLen, pv.endFraction)) ? 4 : 0); e[6] = startA;
               e[7] = (long long)((startB >= ovLo && startB < ovHi) ? (sq == 0 ? w / 2 : w - w / 2) : w);
+              if (pv.textBytes && lenA > 0) atomicAdd(pv.textBytes, (unsigned long long)pileupTextKept(1, lenA, startA, readLen));  // (the host sizes the text before the stages of xm_pileup_text.h have run)
             }
           }
         }
@@ -104,6 +107,10 @@ struct xm_pileup {
   DevBuf<long long> dEvents;
   long long total = 0, queriesAdded = 0;
   std::vector<long long> events;  // (host) 8 per event, in the order of the calls
+  bool keepText = false;          // xm_pileup_keep_insert_text: the bases of every insertion event are kept beside it
+  PileupTextStage textStage;      // (device) the stages' buffers
+  std::vector<int64_t> textOff;   // (host) with kept text: one entry per event, plus one ...
+  std::vector<char> text;         // ... into the letters of the insertions, parallel to events
 };
 
 extern "C" {
@@ -146,6 +153,17 @@ int xm_pileup_set_query_ends(xm_pileup* p, double fraction) {
   } catch (std::exception& e) { return fail(std::string("xm_pileup_set_query_ends: ") + e.what()); }
 }
 
+int xm_pileup_keep_insert_text(xm_pileup* p, int32_t on) {
+  if (!p) return fail("xm_pileup_keep_insert_text: null argument");
+  if (p->queriesAdded > 0) return fail("xm_pileup_keep_insert_text: alignments were already added");
+  try {
+    HIP_CHECK(hipSetDevice(p->device));
+    p->keepText = on != 0;
+    if (p->keepText) p->dEventCount.ensure(2);  // (the events of a call, the bytes of their text)
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_pileup_keep_insert_text: ") + e.what()); }
+}
+
 int xm_pileup_read_middle(xm_pileup* p, int32_t contig, int64_t first, int64_t n, uint64_t* depth) {
   if (!p || !p->hs || !depth) return fail("xm_pileup_read_middle: null argument");
   try {
@@ -174,29 +192,36 @@ int xm_pileup_add_last(xm_pileup* p, int64_t* num_events) {
     if (nq > 0) {
       const unsigned long long cap = (unsigned long long)last.intsHeld / 4 + 1;  // (an event is a block: at least four ints of the stream)
       p->dEvents.ensure((size_t)cap * 8);
-      HIP_CHECK(hipMemsetAsync(p->dEventCount.p, 0, sizeof(unsigned long long), s));
-      PileupView pv{p->dDepth.p, p->dAlt.p, p->total, p->dEvents.p, cap, p->dEventCount.p, p->queriesAdded, p->endFraction > 0 ? p->dMid.p : nullptr, p->endFraction};
+      const size_t words = p->keepText ? 2 : 1;  // (with kept text the kernel also sums the bytes of it: both are read in one copy)
+      HIP_CHECK(hipMemsetAsync(p->dEventCount.p, 0, sizeof(unsigned long long) * words, s));
+      PileupView pv{p->dDepth.p, p->dAlt.p, p->total, p->dEvents.p, cap, p->dEventCount.p, p->queriesAdded, p->endFraction > 0 ? p->dMid.p : nullptr, p->endFraction,
+                    p->keepText ? p->dEventCount.p + 1 : nullptr};
       std::shared_lock<std::shared_mutex> tablesInUse(idx->dt->rw);
       hipLaunchKernelGGL(xm_pileup_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, idx->dt->view, idx->resident.view(), last.ints, last.intOff, pv);
       HIP_CHECK(hipGetLastError());
-      unsigned long long n = 0;
-      HIP_CHECK(hipMemcpyAsync(&n, p->dEventCount.p, sizeof(n), hipMemcpyDeviceToHost, s));
+      unsigned long long counts[2] = {0, 0};
+      HIP_CHECK(hipMemcpyAsync(counts, p->dEventCount.p, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
+      const unsigned long long n = counts[0], textBytes = counts[1];
       if (n > cap) throw std::runtime_error("internal error: more indel events than blocks");
-      const size_t at = p->events.size();
-      p->events.resize(at + (size_t)n * 8);
-      if (n) HIP_CHECK(hipMemcpy(p->events.data() + at, p->dEvents.p, sizeof(long long) * (size_t)n * 8, hipMemcpyDeviceToHost));
-      // the order of the atomic appends is not fixed: events of a call are put in (query, position) order
-      std::vector<std::array<long long, 8>> ev((size_t)n);
-      for (size_t i = 0; i < (size_t)n; i++) for (int k = 0; k < 8; k++) ev[i][(size_t)k] = p->events[at + i * 8 + (size_t)k];
-      std::sort(ev.begin(), ev.end(), [](const std::array<long long, 8>& a, const std::array<long long, 8>& b) {
-        if (a[4] != b[4]) return a[4] < b[4];
-        if (a[0] != b[0]) return a[0] < b[0];
-        if (a[1] != b[1]) return a[1] < b[1];
-        if (a[5] != b[5]) return a[5] < b[5];
-        return a[6] < b[6];
-      });
-      for (size_t i = 0; i < (size_t)n; i++) for (int k = 0; k < 8; k++) p->events[at + i * 8 + (size_t)k] = ev[i][(size_t)k];
+      std::vector<long long> got((size_t)n * 8);
+      std::vector<int64_t> off;
+      std::vector<char> text;
+      if (p->keepText && n) {  // the stages of xm_pileup_text.h over the events where they lie; a call without insertions launches no gather and copies no text
+        const BatchView batch = idx->resident.view();
+        const PileupTextJob job{p->dEvents.p, (long long)n, p->queriesAdded, batch.nq, batch.mateOffset, batch.mateLength, batch.codes};
+        p->textStage.offsets(job, s);
+        if (textBytes) p->textStage.gather(job, (long long)textBytes, s);
+        off.resize((size_t)n + 1);
+        text.resize((size_t)textBytes);
+        HIP_CHECK(hipMemcpyAsync(off.data(), p->textStage.dOff.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, s));
+        if (textBytes) HIP_CHECK(hipMemcpyAsync(text.data(), p->textStage.dText.p, (size_t)textBytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (off[(size_t)n] != (int64_t)textBytes) throw std::runtime_error("internal error: the insertion text was measured twice with different results");
+      }
+      if (n) HIP_CHECK(hipMemcpy(got.data(), p->dEvents.p, sizeof(long long) * (size_t)n * 8, hipMemcpyDeviceToHost));
+      // the order of the atomic appends is not fixed: events of a call are put in (query, position) order, and each one's text goes with it
+      pileupAppendCall(got.data(), (size_t)n, p->keepText && n ? off.data() : nullptr, text.data(), p->events, &p->textOff, &p->text);
     }
     p->queriesAdded += nq;
     if (num_events) *num_events = (int64_t)(p->events.size() / 8);
@@ -226,6 +251,19 @@ int64_t xm_pileup_events(xm_pileup* p, int64_t first, int64_t n, int64_t* out) {
   if (first < 0 || first > have) return -1;
   const int64_t m = std::min<int64_t>(n, have - first);
   if (m > 0) memcpy(out, p->events.data() + (size_t)first * 8, sizeof(int64_t) * (size_t)m * 8);
+  return m;
+}
+
+int64_t xm_pileup_event_text(xm_pileup* p, int64_t first, int64_t n, int64_t* text_off, char* text, int64_t text_cap) {
+  if (!p || !p->keepText || !text_off) return -1;
+  const int64_t have = (int64_t)(p->events.size() / 8);
+  const int64_t m = pileupTextPage(p->textOff, have, first, n, text_cap);
+  if (m < 0) return -1;
+  const int64_t base = m > 0 ? p->textOff[(size_t)first] : 0;
+  for (int64_t i = 0; i <= m; i++) text_off[i] = m > 0 ? p->textOff[(size_t)(first + i)] - base : 0;
+  const int64_t bytes = text_off[m];
+  if (bytes > 0 && !text) return -1;
+  if (bytes > 0) memcpy(text, p->text.data() + (size_t)base, (size_t)bytes);
   return m;
 }
 

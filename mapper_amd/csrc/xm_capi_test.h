@@ -157,6 +157,51 @@ int xm_test_sam_format(int32_t device, const xm_test_sam_job* t, xm_sam_text** o
   } catch (std::exception& e) { return fail(std::string("xm_test_sam_format: ") + e.what()); }
 }
 
+// Test-only entry (tests/test_gpu_pileup_text.py): the three stages of xm_pileup_text.h - what xm_pileup_add_last runs with kept text - over host-given events
+// and batch arrays; no index, no alignment, no pile-up kernel (so the total is read from the offsets).  The host checks what the kernels take on trust from
+// the library's own stages: mates inside codes.  The events may hold anything.  launches: kernels launched (4 without text to gather, 5 with; 0 for no events).
+int xm_test_pileup_text(int32_t device, const xm_test_pileup_job* t, int64_t* text_off, char* text, int64_t text_cap, int32_t* launches) {
+  if (!t || !text_off) return fail("xm_test_pileup_text: null argument");
+  try {
+    const int64_t nq = t->num_queries, n = t->num_events;
+    if (nq < 0 || n < 0 || t->codes_length < 0 || text_cap < 0) throw std::runtime_error("negative size");
+    if ((nq && (!t->mate_offset || !t->mate_length)) || (t->codes_length && !t->codes) || (n && !t->events)) throw std::runtime_error("null array");
+    for (int64_t k = 0; k < 2 * nq; k++) {
+      const int32_t len = t->mate_length[k];
+      if (len < 0 || t->mate_offset[k] < 0 || t->mate_offset[k] + len > t->codes_length) throw std::runtime_error("mate outside of codes");
+    }
+    if (launches) *launches = 0;
+    text_off[0] = 0;
+    if (n == 0) return 0;
+    if (device >= 0) HIP_CHECK(hipSetDevice(device));
+    DevBuf<int32_t> dLength;
+    DevBuf<int64_t> dMateOff;
+    DevBuf<uint8_t> dCodes;
+    DevBuf<long long> dEvents;
+    dLength.ensure((size_t)nq * 2); dMateOff.ensure((size_t)nq * 2); dCodes.ensure((size_t)t->codes_length); dEvents.ensure((size_t)n * 8);
+    if (nq) {
+      HIP_CHECK(hipMemcpy(dLength.p, t->mate_length, sizeof(int32_t) * (size_t)nq * 2, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dMateOff.p, t->mate_offset, sizeof(int64_t) * (size_t)nq * 2, hipMemcpyHostToDevice));
+    }
+    if (t->codes_length) HIP_CHECK(hipMemcpy(dCodes.p, t->codes, (size_t)t->codes_length, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dEvents.p, t->events, sizeof(int64_t) * (size_t)n * 8, hipMemcpyHostToDevice));
+    PileupTextStage stage;
+    const PileupTextJob job{dEvents.p, (long long)n, (long long)t->query_base, (long long)nq, dMateOff.p, dLength.p, dCodes.p};
+    stage.offsets(job, nullptr);
+    HIP_CHECK(hipMemcpy(text_off, stage.dOff.p, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyDeviceToHost));
+    if (launches) *launches = 4;
+    const int64_t total = text_off[n];
+    if (total > text_cap) throw std::runtime_error("the text takes " + std::to_string(total) + " bytes");
+    if (total > 0) {
+      if (!text) throw std::runtime_error("null array");
+      stage.gather(job, total, nullptr);
+      if (launches) *launches = 5;
+      HIP_CHECK(hipMemcpy(text, stage.dText.p, (size_t)total, hipMemcpyDeviceToHost));
+    }
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_test_pileup_text: ") + e.what()); }
+}
+
 // Test-only entry (tests/test_gpu_sam.py): Double.toString of xm_sam_rules.h run by the device on n values; out24 gets 24 bytes a value, len the lengths.
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len) {
   if (n < 0 || (n > 0 && (!x || !out24 || !len))) return fail("xm_test_format_doubles: bad arguments");

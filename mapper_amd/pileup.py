@@ -17,7 +17,9 @@ alignments (taken as 1/n each), how ambiguous bases count (depth only), the orde
 (Mapper.java:208-230: taken as alt / total; an indel is cut where its continuation fails).
 
 The accumulation itself runs on the GPU (xm_pileup_kernel: one lane per query walks its result stream in HBM and adds to per-position
-integer counters, so the result does not depend on the order of the atomic adds); this module holds the host side."""
+integer counters, so the result does not depend on the order of the atomic adds); this module holds the host side.  The bases of an insertion come
+from the queries handed to add_last or, with keep_insert_text, from the device pile-up, which then keeps them beside the event (xm_pileup_text.h):
+a job that streams its batches needs no query after its batch is written."""
 import ctypes as C
 
 import numpy as np
@@ -63,11 +65,13 @@ def _number(x):
 
 class MatchDatabase:
     """MatchDatabase(queryEndFraction) + groupByPosition() for one ReferenceDatabase (or the replicas of a MultiGpuDatabase: one device pile-up
-    each, summed on the host in replica order)."""
+    each, summed on the host in replica order).  keep_insert_text: the device pile-ups keep the bases of every insertion with its event
+    (xm_pileup_keep_insert_text), so add_last needs no queries for the text of insertions and nothing of a batch has to outlive it."""
 
-    def __init__(self, databases, query_end_fraction=0.0):
+    def __init__(self, databases, query_end_fraction=0.0, keep_insert_text=False):
         self.dbs = list(databases) if isinstance(databases, (list, tuple)) else [databases]
         self.query_end_fraction = float(query_end_fraction)
+        self.keep_insert_text = bool(keep_insert_text)
         self._L = _capi.lib()
         self._h = []
         for db in self.dbs:
@@ -77,13 +81,16 @@ class MatchDatabase:
             self._h.append(h)
             if self._L.xm_pileup_set_query_ends(h, self.query_end_fraction):
                 raise RuntimeError(self._L.xm_last_error().decode())
+            if self.keep_insert_text and self._L.xm_pileup_keep_insert_text(h, 1):
+                raise RuntimeError(self._L.xm_last_error().decode())
         self.contigs = self.dbs[0].contigs
         self._reads = {}   # query ordinal (per replica) -> mates, kept only for queries with an insertion
         self._batches = [[] for _ in self.dbs]
 
     def add_last(self, queries=None, replica=0):
         """addAlignments(List<QueryAlignments>) for the batch replica `replica` aligned last (its streams are still in HBM).  `queries`: the
-        batch's Query objects or mate arrays, needed for the text of insertions (None: insertions are reported by length only)."""
+        batch's Query objects or mate arrays, needed for the text of insertions (None: the text the device kept, with keep_insert_text; without it
+        insertions are reported by length only)."""
         n = C.c_int64(0)
         if self._L.xm_pileup_add_last(self._h[replica], C.byref(n)):
             raise RuntimeError(self._L.xm_last_error().decode())
@@ -124,15 +131,29 @@ class MatchDatabase:
         return mid
 
     def _events(self):
-        """(replica, contig, startB, type, length, query ordinal, mate | reversed << 1, startA, weight) of every insertion / deletion block."""
+        """(replica, contig, startB, type, length, query ordinal, mate | reversed << 1, startA, weight) of every insertion / deletion block.  With
+        keep_insert_text the text is paged with the events: self._texts[(replica, k)] is the kept text of the replica's k-th event, for insertions."""
         out = []
         buf = np.zeros((1 << 16, 8), np.int64)
+        self._texts = {}
+        if self.keep_insert_text:
+            off = np.zeros(len(buf) + 1, np.int64)
+            text = np.zeros(1 << 20, np.uint8)
         for r, h in enumerate(self._h):
             first = 0
             while True:
                 m = self._L.xm_pileup_events(h, first, len(buf), buf.ctypes.data)
                 if m <= 0:
                     break
+                if self.keep_insert_text:
+                    # (a page of text may hold fewer events than asked for; an insertion longer than the page gets a page of its size)
+                    while (got := self._L.xm_pileup_event_text(h, first, m, off.ctypes.data, text.ctypes.data, len(text))) < 0:
+                        if len(text) >= 1 << 40:
+                            raise RuntimeError("xm_pileup_event_text failed for event %d of replica %d" % (first, r))
+                        text = np.zeros(2 * len(text), np.uint8)
+                    m = got
+                    for k in np.nonzero(buf[:m, 2] == 1)[0]:
+                        self._texts[(r, first + int(k))] = text[off[k]:off[k + 1]].tobytes().decode("ascii")
                 out += [(r,) + tuple(int(x) for x in row) for row in buf[:m]]
                 first += m
         return out
@@ -154,14 +175,18 @@ class MatchDatabase:
         f = parameters or MutationDetectionParameters.emptyFilter()
         rows = []
         indels = {}
-        for r, contig, pos, kind, length, ordinal, flags, start_a, weight in self._events():
+        events = self._events()
+        kept = getattr(self, "_texts", {})
+        seen = {}   # events of each replica so far: the index the kept text is filed under
+        for r, contig, pos, kind, length, ordinal, flags, start_a, weight in events:
+            at = seen[r] = seen.get(r, -1) + 1
             if flags & 4:   # near a query end: "when detecting indels, only consider the middle of each query" (Mapper.java:532)
                 continue
             ref = self.contigs[contig][1]
             if kind == 1:
                 mate = self._mate(r, ordinal, flags & 1)
-                if mate is None:
-                    text = "N" * length
+                if mate is None:   # no queries were handed in for its batch: what the device kept, if it kept text
+                    text = kept.get((r, at), "N" * length)
                 else:
                     oriented = reverse_complement(mate) if (flags >> 1) & 1 else mate
                     text = decode(oriented[start_a:start_a + length])
