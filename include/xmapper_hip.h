@@ -125,7 +125,7 @@ const char* xm_build_stamp(void);
  * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6]; 5 = xm_memory_new, xm_context_attach_memory, xm_memory_info,
  * xm_memory_free, xm_result.reserved carries the wait for a memory; 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7 = xm_sam_set_contigs,
  * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles); 8 = xm_batch_unstage; 9 = xm_pileup_keep_insert_text, xm_pileup_event_text (and the test-only
- * xm_test_pileup_text).  A binding checks it once
+ * xm_test_pileup_text); 10 = xm_context_set_result_copy, xm_summary_last, xm_summary_free (and the test-only xm_test_summary).  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -300,6 +300,31 @@ void xm_sam_text_free(xm_sam_text* text);
 /* Bytes of text per tile of the kernel that writes the records (test hook: tests/test_gpu_sam.py puts record ends on both sides of the multiples). */
 int32_t xm_sam_tile_bytes(void);
 
+/* (ABI version 10) The results left in HBM when only text and totals go to the host.  With xm_sam_format_last the host needs three small things of the four
+ * streams: the statistics of Mapper.run (Mapper.java:786-796), the unaligned queries, and their number.  xm_summary_last computes them on the GPU from the
+ * streams where they lie, and xm_context_set_result_copy(context, 0) then spares the copy of the streams altogether.  Not used by the Java host. */
+/* default 1.  0: every later align call of this context leaves its four streams where they lie in HBM and copies none of them: the xm_result has
+ * ints = dbls = int_off = dbl_off = NULL; num_queries, num_ints, num_dbls (the scan's totals: 16 bytes are read), counters, extra, the times and
+ * kernel_launches are what they are with the copy.  The scan and gather launches are the same.  Per context; may be changed between calls. */
+int xm_context_set_result_copy(xm_index* context, int32_t on);
+/* What xmio_write_batch (include/xmapper_hostio.h) counts of a batch's streams when it writes no SAM: queries with an alignment, alignments, the sum of
+ * lengthA over every block of every sequence, the blocks with lengthA != lengthB - and, because Mapper.run sums the penalties as doubles in query order and
+ * the order is part of the result, the totalPenalty of every alignment in stream order for the host to add up (xmio_write_summary).  The arrays are
+ * page-locked buffers of the library's pool (NULL where the count is 0); kernel_ms, d2h_ms: the kernels and the copy of the two arrays. */
+typedef struct xm_batch_summary {
+  int64_t num_queries, num_aligned, num_alignments, total_aligned_length, num_indels;
+  int64_t num_unaligned; int64_t* unaligned;   /* ascending query indices; NULL / 0 when not asked for */
+  double* penalties;                           /* [num_alignments]: totalPenalty of every alignment, stream order */
+  double kernel_ms, d2h_ms; void* store;
+} xm_batch_summary;
+/* xm_summary_last has the contract of xm_pileup_add_last and xm_sam_format_last: it serialises with the context's other calls, runs on the context's stream,
+ * and fails with "no longer resident" once another batch has been uploaded or committed, and after an align call that failed.  It works whether or not the
+ * copy of the streams is on.  A slice that is not of the layout above - where xmio_write_batch without a SAM file reports "malformed result streams", and
+ * also where a slice ends before the walk does - fails the call with the lowest such query in xm_last_error and no summary.  A batch of 0 queries launches
+ * nothing and gives zeros.  Released with xm_summary_free.  mapper_amd/csrc/xm_summary_rules.h states the walk as code. */
+int xm_summary_last(xm_index* context, int32_t want_unaligned, xm_batch_summary** out);
+void xm_summary_free(xm_batch_summary* summary);
+
 /* Bulk form of Readable_HashBlock_Database.getNumMatchesLowerBound + matchBlock / PackedMap.get (PackedMap.java:160-172,
  * 228-236) for n (used_length, lookup key) pairs: counts[i] = number of stored positions, -1 when the bucket is overfull or
  * holds more than the table's limit, -2 when used_length is not a hashed length.  Positions (at most max_per_probe <= 15 per probe, not reverse-complemented): the
@@ -402,6 +427,10 @@ typedef struct xm_test_pileup_job {
   int64_t num_events; const int64_t* events; int64_t query_base;
 } xm_test_pileup_job;
 int xm_test_pileup_text(int32_t device, const xm_test_pileup_job* job, int64_t* text_off, char* text, int64_t text_cap, int32_t* launches);
+/* Test-only (tests/test_gpu_summary.py), like xm_test_sam_format: the kernels of xm_summary_last over host-given streams on `device`; no index, no alignment.
+ * Same result, same errors. */
+int xm_test_summary(int32_t device, int64_t num_queries, int32_t num_contigs, const int32_t* ints, const double* dbls,
+                    const int64_t* int_off, const int64_t* dbl_off, int32_t want_unaligned, xm_batch_summary** out);
 /* Test-only: Double.toString as the SAM tags print it, run by the device on n values: out24[24 * i ...] the string of x[i] (padded with NUL), len[i] its length. */
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len);
 

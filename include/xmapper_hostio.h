@@ -50,7 +50,13 @@ void xmio_close(xmio_reader* reader);
  * they came with qualities, else FASTA) to unaligned_fd; either descriptor may be -1.  Query order; `threads` formatting threads.  Adds to *stats. */
 int xmio_write_batch(const xmio_batch* batch, const int32_t* ints, const double* dbls, const int64_t* int_off, const int64_t* dbl_off, int32_t num_contigs,
                      const char* const* contig_names, int32_t sam_fd, int32_t unaligned_fd, int32_t threads, xmio_stats* stats);
-/* Wall seconds of the calling thread's last xmio_write_batch call: formatting and counting, and the write() calls (either may be NULL). */
+/* xmio_write_batch with sam_fd = -1 for a caller that holds a summary of the streams instead of the streams (xm_batch_summary of include/xmapper_hip.h; the
+ * SAM text is made and written elsewhere): the queries of `unaligned` - num_unaligned indices into the batch, strictly ascending, else the call fails and
+ * writes nothing - go to unaligned_fd (-1: none) as xmio_write_batch writes them, and *stats grows by what xmio_write_batch would have added: the batch's
+ * queries, the three counts, and total_penalty continued from its value by one += per entry of penalties[0 .. num_alignments), in order. */
+int xmio_write_summary(const xmio_batch* batch, int64_t num_aligned, int64_t total_aligned_length, int64_t num_indels, int64_t num_alignments,
+                       const double* penalties, int64_t num_unaligned, const int64_t* unaligned, int32_t unaligned_fd, xmio_stats* stats);
+/* Wall seconds of the calling thread's last xmio_write_batch or xmio_write_summary call: formatting and counting, and the write() calls (either may be NULL). */
 void xmio_last_write_seconds(double* format_seconds, double* file_seconds);
 
 /* The query files cut into blocks of whole four-line FASTQ records, as text, for a parser that is not this library's (xm_batch_stage_fastq of

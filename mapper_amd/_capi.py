@@ -71,13 +71,20 @@ class XmTestSamJob(C.Structure):
                 ("ints", C.c_void_p), ("dbls", C.c_void_p), ("int_off", C.c_void_p), ("dbl_off", C.c_void_p)]
 
 
+class XmBatchSummary(C.Structure):
+    """xm_batch_summary: the statistics of a batch's result streams, the penalties of its alignments and its unaligned queries, in pinned buffers of the library."""
+    _fields_ = [("num_queries", C.c_int64), ("num_aligned", C.c_int64), ("num_alignments", C.c_int64), ("total_aligned_length", C.c_int64), ("num_indels", C.c_int64),
+                ("num_unaligned", C.c_int64), ("unaligned", C.POINTER(C.c_int64)), ("penalties", C.POINTER(C.c_double)),
+                ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("store", C.c_void_p)]
+
+
 class XmTestPileupJob(C.Structure):
     """xm_test_pileup_job (test-only): the mates of a batch and events of the pile-up, all on the host."""
     _fields_ = [("num_queries", C.c_int64), ("mate_offset", C.c_void_p), ("mate_length", C.c_void_p), ("codes", C.c_void_p), ("codes_length", C.c_int64),
                 ("num_events", C.c_int64), ("events", C.c_void_p), ("query_base", C.c_int64)]
 
 
-ABI_VERSION = 9  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text
+ABI_VERSION = 10  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary
 
 
 class XmIndexInfo(C.Structure):
@@ -88,7 +95,7 @@ class XmIndexInfo(C.Structure):
 
 
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
-           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free"]
+           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary"]
 
 
 def build_library(force=False):
@@ -201,6 +208,11 @@ def lib():
         L.xm_pileup_event_text.restype = C.c_int64
         L.xm_test_pileup_text.argtypes = [C.c_int32, C.POINTER(XmTestPileupJob), C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]
         L.xm_pileup_free.argtypes = [C.c_void_p]
+        L.xm_context_set_result_copy.argtypes = [C.c_void_p, C.c_int32]
+        L.xm_summary_last.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.POINTER(XmBatchSummary))]
+        L.xm_summary_free.argtypes = [C.POINTER(XmBatchSummary)]
+        L.xm_summary_free.restype = None
+        L.xm_test_summary.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.POINTER(XmBatchSummary))]
         _lib = L
     return _lib
 
@@ -256,6 +268,8 @@ def view_result(L, res):
     owner = _ResultOwner(L, res)
 
     def view(ptr, ctype, n):
+        if not ptr:  # (xm_context_set_result_copy(0): the streams stayed in HBM; with no view to hold it the owner frees the result when this returns)
+            return None
         buf = (ctype * max(int(n), 1)).from_address(C.addressof(ptr.contents))
         buf._xm_owner = owner
         return np.frombuffer(buf, dtype=np.dtype(ctype))[:int(n)]
@@ -263,7 +277,8 @@ def view_result(L, res):
     return dict(ints=view(r.ints, C.c_int32, r.num_ints), dbls=view(r.dbls, C.c_double, r.num_dbls), int_off=view(r.int_off, C.c_int64, r.num_queries + 1),
                 dbl_off=view(r.dbl_off, C.c_int64, r.num_queries + 1), counters=list(r.counters), kernel_ms=r.kernel_ms, h2d_ms=r.h2d_ms,
                 d2h_ms=r.d2h_ms, kernel_launches=r.kernel_launches, prof=list(r.prof), extra=list(r.extra),
-                memory_wait_us=int(r.reserved))  # (xm_result.reserved: host microseconds the call waited for its memory's mutex)
+                memory_wait_us=int(r.reserved),  # (xm_result.reserved: host microseconds the call waited for its memory's mutex)
+                num_queries=int(r.num_queries), num_ints=int(r.num_ints), num_dbls=int(r.num_dbls))
 
 
 def pinned_host_bytes():

@@ -138,7 +138,7 @@ class BatchResult:
         self.__dict__.update(d)
 
     def __len__(self):
-        return len(self.int_off) - 1
+        return self.num_queries if "num_queries" in self.__dict__ else len(self.int_off) - 1
 
     @property
     def copies(self):
@@ -153,7 +153,38 @@ class BatchResult:
         return int(self.extra[6])
 
     def query_alignments(self, q):
+        if self.int_off is None:
+            raise ValueError("this result has no streams: its context left them in HBM (ReferenceDatabase.set_result_copy(False)); use summary_last / format_sam_last, "
+                             "or set_result_copy(True) before the align call")
         return decode_streams(self.ints, self.dbls, self.int_off, self.dbl_off, q)
+
+
+class BatchSummary:
+    """What ReferenceDatabase.summary_last computed on the GPU from the result streams of one batch: the five counts (num_queries, num_aligned, num_alignments,
+    total_aligned_length, num_indels), `penalties` - every alignment's totalPenalty in stream order - and `unaligned` - the ascending indices of the queries
+    without an alignment (empty unless asked for) - as numpy views of page-locked buffers of the library, and the milliseconds of the kernels and of the copy.
+    close() gives the buffers back; the views must not be used after it."""
+
+    def __init__(self, L, ptr):
+        self._L, self._ptr = L, ptr
+        t = ptr.contents
+        self.num_queries, self.num_aligned, self.num_alignments = int(t.num_queries), int(t.num_aligned), int(t.num_alignments)
+        self.total_aligned_length, self.num_indels, self.num_unaligned = int(t.total_aligned_length), int(t.num_indels), int(t.num_unaligned)
+        self.kernel_ms, self.d2h_ms = t.kernel_ms, t.d2h_ms
+        self.penalties = np.ctypeslib.as_array(t.penalties, shape=(self.num_alignments,)) if self.num_alignments else np.zeros(0, np.float64)
+        self.unaligned = np.ctypeslib.as_array(t.unaligned, shape=(self.num_unaligned,)) if self.num_unaligned else np.zeros(0, np.int64)
+
+    def close(self):
+        if self._ptr is not None:
+            self.penalties = self.unaligned = None
+            self._L.xm_summary_free(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class SamText:
@@ -432,6 +463,22 @@ class ReferenceDatabase:
         _check(self._L.xm_sam_format_last(self._h, C.byref(names) if names is not None else None, C.byref(out)))
         self._tick("format", time.perf_counter() - t0)
         return SamText(self._L, out)
+
+    def set_result_copy(self, on):
+        """xm_context_set_result_copy: on=False - every later align call of this context leaves its four result streams in HBM and copies none of them to the
+        host; the BatchResult then has ints = dbls = int_off = dbl_off = None (len(), num_ints, num_dbls, the counters and the times are what they are with the
+        copy), and format_sam_last, summary_last and the pile-up read the streams where they lie.  True (the default) brings the copy back."""
+        _check(self._L.xm_context_set_result_copy(self._h, 1 if on else 0))
+
+    def summary_last(self, want_unaligned=False):
+        """xm_summary_last: the statistics of the last align call's result streams, its alignments' penalties and (want_unaligned) its unaligned queries,
+        computed on the GPU while the batch is still resident (align_stream's on_aligned hook is the place) -> BatchSummary.  hostio.Writer.write(batch, result,
+        summary=...) makes of it what it makes of the streams."""
+        t0 = time.perf_counter()
+        out = C.POINTER(_capi.XmBatchSummary)()
+        _check(self._L.xm_summary_last(self._h, 1 if want_unaligned else 0, C.byref(out)))
+        self._tick("format", time.perf_counter() - t0)
+        return BatchSummary(self._L, out)
 
     def commit_staged(self):
         """xm_batch_commit: the staged batch becomes the resident one."""

@@ -21,7 +21,11 @@ four-line FASTQ records only, so a file the host reader takes may be refused wit
 whose output needs objects - --out-refs-map-count, needs_objects - parses on the host all the same),
 --format-on-gpu (the SAM records are formatted on the GPU while a batch and its results are resident, api.ReferenceDatabase.format_sam_last, and the host
 only writes the bytes: same outputs; --out-unaligned stays with the host; not with --per-object, --out-mutations or --out-refs-map-count; nothing to do
-without --out-sam), and --format-threads <n> (threads of the host's SAM formatter).
+without --out-sam), --results-on-gpu (the align calls leave their result streams in HBM and copy none of them to the host,
+api.ReferenceDatabase.set_result_copy(False); what the host still needs of them - the statistics, every alignment's penalty, the unaligned queries - is computed
+on the GPU while the batch is resident, api.ReferenceDatabase.summary_last: same outputs; with --out-sam only together with --format-on-gpu, since the host
+formatter reads the streams; fine with --out-unaligned, --no-output and --out-mutations, whose pile-up reads the resident streams; not with --per-object or
+--out-refs-map-count, which decode the streams on the host), and --format-threads <n> (threads of the host's SAM formatter).
 
 --out-mutations streams like --out-sam: the device pile-up keeps the bases of every insertion with its event (pileup.MatchDatabase(keep_insert_text=True)), so
 the mutations file needs no object per read; with --per-object it is written the first way, from the Query objects of the whole job, which is the reference
@@ -204,6 +208,8 @@ def parse_args(argv):
             o["parse_on_gpu"] = True
         elif a == "--format-on-gpu":  # (not a Mapper flag) the SAM records are formatted on the GPU from the result streams while the batch is resident (api.ReferenceDatabase.format_sam_last)
             o["format_on_gpu"] = True
+        elif a == "--results-on-gpu":  # (not a Mapper flag) the result streams stay in HBM; the host gets the SAM text and a summary (api.ReferenceDatabase.set_result_copy, summary_last)
+            o["results_on_gpu"] = True
         elif a == "--format-threads":  # (not a Mapper flag) threads of the host's SAM formatter (hostio.Writer; default: the CPUs, 32 at the most)
             o["format_threads"] = int(argv[i + 1]); i += 1
             if o["format_threads"] < 1:
@@ -226,6 +232,13 @@ def parse_args(argv):
     for other, key in (("--per-object", "per_object"), ("--out-mutations", "out_mutations"), ("--out-refs-map-count", "out_refs_map_count")):
         if o.get("format_on_gpu") and o.get(key):
             raise UsageError("--format-on-gpu and %s exclude each other (--per-object and --out-refs-map-count format on the host; the pile-up of --out-mutations has not been run beside the device formatter)" % other)
+    if o.get("results_on_gpu"):
+        if o.get("per_object"):
+            raise UsageError("--results-on-gpu and --per-object exclude each other (the per-object path decodes the result streams on the host)")
+        if o.get("out_refs_map_count"):
+            raise UsageError("--results-on-gpu and --out-refs-map-count exclude each other (the count is made from alignments decoded on the host)")
+        if o["out_sam"] and not o.get("format_on_gpu"):
+            raise UsageError("--results-on-gpu with --out-sam needs --format-on-gpu (the host's SAM formatter reads the result streams, which stay on the GPU)")
     if o.get("remember") and o.get("remember_per_gpu"):
         raise UsageError("--remember-queries (a memory per context) and --remember-queries-per-gpu (one per GPU) exclude each other")
     return o
@@ -444,18 +457,21 @@ class ObjectSink:
                 f.write("%s\t%d\n" % (",".join(key), count))
 
 
-def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format_on_gpu=False):
+def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format_on_gpu=False, results_on_gpu=False, want_unaligned=False):
     """The job: the batches stream through the GPU contexts (align_stream: the copy of batch k + 1 overlaps the alignment of batch k; several contexts align
     side by side) and a writer thread hands each batch and its result streams to the sink while the next batches are being aligned; at most `depth` results
     wait for it.  Every batch taken from `batches` is closed, and the first exception - the reader's, the GPU's or the sink's - reaches the caller.
     -> the queries that were served as copies (BatchResult.copies); tally["remembered"], if given, grows by the ones served from the contexts' memories
     (BatchResult.remembered).  format_on_gpu: the context that aligned a batch formats its SAM records while the batch is resident (format_sam_last, in the
     on_aligned hook: between two align calls of that context), and the writer thread writes the text; tally["read"] grows by the seconds the feeder waited for
-    the reader."""
+    the reader.  results_on_gpu: the results carry no streams (set_result_copy(False) is the caller's); the same hook asks the context for the batch's summary
+    (summary_last, with the list of unaligned queries if want_unaligned) behind the text and before the caller's on_aligned, and the summary travels to the
+    writer thread with the text; both are closed there, also after a failure."""
     in_flight = queue.Queue()  # batches in the order they were dealt to the GPUs
     to_write = queue.Queue(maxsize=depth)
     failure = []
-    dealt, texts = {}, {}      # by batch number: the batch on its way to a context; the text its context made of it
+    dealt, texts = {}, {}      # by batch number: the batch on its way to a context; [the text, the summary] its context made of it
+    on_context = format_on_gpu or results_on_gpu
 
     def feed():
         it = iter(batches)
@@ -468,31 +484,37 @@ def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format
             if b is None:
                 return
             in_flight.put(b)
-            if format_on_gpu:
+            if on_context:
                 dealt[k] = b
             k += 1
             yield b if isinstance(b, hostio.TextBlock) else b.arrays()  # (a text block is staged by the context that gets it: align_stream)
 
     hook = on_aligned
-    if format_on_gpu:
+    if on_context:
         def hook(*at):  # ReferenceDatabase.align_stream calls it with (batch), MultiGpuDatabase's with (replica, batch), on the replica's thread
             b = dealt.pop(at[-1])
             context = db.replicas[at[0]] if len(at) > 1 else db
-            texts[at[-1]] = context.format_sam_last(None if isinstance(b, hostio.TextBlock) else b)  # (a text block's names are in HBM with the batch)
+            made = texts[at[-1]] = [None, None]  # (registered first: what a failing call leaves behind is closed with the rest)
+            if format_on_gpu:
+                made[0] = context.format_sam_last(None if isinstance(b, hostio.TextBlock) else b)  # (a text block's names are in HBM with the batch)
+            if results_on_gpu:
+                made[1] = context.summary_last(want_unaligned=want_unaligned)
             if on_aligned is not None:
                 on_aligned(*at)
 
     def write_loop():  # (after a failure it keeps taking what comes, unwritten, up to the end mark: the main thread never waits on a full queue for good)
-        for b, r, text in iter(to_write.get, None):
+        for b, r, made in iter(to_write.get, None):
+            text, summary = made or (None, None)
             try:
                 if not failure:
-                    sink.write(b, r, **({"sam_text": text} if text is not None else {}))
+                    sink.write(b, r, **({"sam_text": text} if text is not None else {}), **({"summary": summary} if summary is not None else {}))
             except BaseException as e:  # noqa: BLE001  (handed to the main thread)
                 failure.append(e)
             finally:
                 b.close()
-                if text is not None:
-                    text.close()
+                for held in (text, summary):
+                    if held is not None:
+                        held.close()
 
     wt = threading.Thread(target=write_loop, daemon=True)
     wt.start()
@@ -512,8 +534,10 @@ def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format
         results.close()  # (ends the threads that deal and upload: nothing takes from `batches` after this)
         while not in_flight.empty():
             in_flight.get().close()
-        for text in texts.values():
-            text.close()
+        for made in texts.values():
+            for held in made:
+                if held is not None:
+                    held.close()
     if failure:
         raise failure[0]
     return copies
@@ -570,11 +594,16 @@ def run(argv, out=sys.stdout, open_database=None):
         # some 60 bytes of fields; with the host's names, those are copied up as well)
         format_on_gpu = bool(o.get("format_on_gpu") and o["out_sam"]) and not per_object  # (without --out-sam there is nothing to format)
         sam_text = batch_size * (2 * (max_len + 200) + 24) if format_on_gpu else 0
+        # (--results-on-gpu: per query two counts and two offsets, and the penalties and the list, 8 bytes an alignment or an unaligned query)
+        results_on_gpu = bool(o.get("results_on_gpu"))
+        summary_arrays = batch_size * 64 if results_on_gpu else 0
         db = (open_database or open_gpu_database)(ordered, devices, max_len, enable_gapmers=o["enable_gapmers"], collapse=o.get("collapse", False),
-                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0) + sam_text, **memo)
+                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0) + sam_text + summary_arrays, **memo)
         job.callback(db.close)
         if format_on_gpu:
             db.set_sam_contigs(names)
+        if results_on_gpu:
+            db.set_result_copy(False)
         sam_out = un_out = None
         if o["out_sam"]:
             sam_out = sys.stdout if o["out_sam"] == "-" else job.enter_context(open(o["out_sam"], "w"))
@@ -593,7 +622,8 @@ def run(argv, out=sys.stdout, open_database=None):
                 match_db.add_last(batches[at[-1]].queries if per_object else None, replica=at[0] if len(at) > 1 else 0)
         t_stream = time.perf_counter()
         tally = {}
-        copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned, tally, format_on_gpu=format_on_gpu)
+        copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned, tally, format_on_gpu=format_on_gpu, results_on_gpu=results_on_gpu,
+                        want_unaligned=bool(o["out_unaligned"]))
         contexts = list(getattr(db, "replicas", [db]))
         spent = lambda key: sum(getattr(c, "seconds", {}).get(key, 0.0) for c in contexts)  # noqa: E731
         # seconds of the job by phase, summed over batches (and over contexts, which work side by side: the sum may exceed the wall time): the reader or cutter,

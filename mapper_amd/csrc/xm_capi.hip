@@ -9,7 +9,8 @@
 // Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_result_stage.h (ResultStage: the result arenas,
 // the scan and gather kernels, the canonical streams; throwFailedQuery), xm_conf_table.h (the host's confidence table), xm_capi_probe.h (seed-probe and
 // random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries), xm_capi_fastq.h (a batch staged from FASTQ text: the kernels of xm_fastq.h),
-// xm_capi_sam.h (SAM records formatted from the resident results: the kernels of xm_sam.h).
+// xm_capi_sam.h (SAM records formatted from the resident results: the kernels of xm_sam.h), xm_capi_summary.h (the statistics, the penalties and the unaligned
+// queries of the resident results: the kernels of xm_summary.h).
 // The big kernels are objects of their own, reached through launch functions: the lane-per-read align kernel is xm_align_kernel.hip (xmAlignLaunch,
 // xm_kernel_common.h), the wave-per-read kernels are xm_wave_kernel.hip (xmWaveLaunch, xm_kernel_args.h), the index build on the device is
 // xm_index_device.hip.  This unit uses the host-side pieces of the shared headers only (makeCaps, searchPoolBytes, the pass planner's sizes):
@@ -25,6 +26,7 @@
 #include "xm_collapse.h"
 #include "xm_fastq.h"
 #include "xm_sam.h"
+#include "xm_summary.h"
 #include "xm_memo.h"
 #include "xm_conf_table.h"
 #include "xm_device_rt.h"
@@ -274,6 +276,18 @@ struct SamStage {
   ~SamStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// What xm_summary_last works with (xm_summary.h; xm_capi_summary.h): alignments and the unaligned flag per query, the scan's block sums and both offset arrays;
+// the control word and the three counters; the penalties and the list of unaligned queries, which only grow; the call's events on the context's stream.
+struct SummaryStage {
+  DevBuf<int32_t> dAlignments, dUnalignedFlag;
+  DevBuf<long long> dBlockA, dBlockU;
+  DevBuf<int64_t> dOff, dUoff, dUnaligned;
+  DevBuf<unsigned long long> dCtl;
+  DevBuf<double> dPenalties;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // measure and offsets | (host sizes the arrays) | gather | arrays down
+  ~SummaryStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 // What the lane-per-read passes of a call work with besides the batch and the result stage: the work lists the lanes file unfinished reads into and the
 // counts of those lists (PassLists, PassCtl: xm_kernel_common.h), the device counters, and the scratch - the lanes' arenas behind the pool of saved
 // regions (HandOver), a wave's search nodes, the pool of search buffers (SearchPool).  Kept across calls; which list a pass reads is xm_pass_plan.h's.
@@ -507,6 +521,8 @@ struct xm_index {
   hipEvent_t cev0 = nullptr, cev1 = nullptr;  // this context's events on the GPU's staging stream (DeviceTables::copyStream)
   FastqStage fastq;            // xm_batch_stage_fastq's buffers (under stageMu)
   SamStage sam;                // xm_sam_format_last's buffers (under mu)
+  SummaryStage summary;        // xm_summary_last's buffers (under mu)
+  bool resultCopy = true;      // xm_context_set_result_copy: an align call copies its four streams to the host (false: they stay in HBM, and the result has none)
 
   void initContext() {  // stream and events of this context (the device tables exist)
     dt->contexts.fetch_add(1);
@@ -971,14 +987,14 @@ static void finishStreams(AlignCall& c) {
     c.dReadTimes.release();
   }
 #endif
-  idx->results.toHost(nq, c.copies, idx->residentGen, res, c.box, s);
+  idx->results.toHost(nq, c.copies, idx->residentGen, res, c.box, s, idx->resultCopy);
   DevCounters dc;
   HIP_CHECK(hipMemcpyAsync(&dc, idx->passes.dCounters.p, sizeof(dc), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipEventRecord(idx->ev1, s));
   HIP_CHECK(hipStreamSynchronize(s));
   HIP_CHECK(hipEventElapsedTime(&ms, idx->ev0, idx->ev1));
   res->d2h_ms = ms;
-  res->num_ints = res->int_off[nq]; res->num_dbls = res->dbl_off[nq];
+  if (idx->resultCopy) { res->num_ints = res->int_off[nq]; res->num_dbls = res->dbl_off[nq]; }  // (without the copy toHost read the two totals into them)
   countersToResult(dc, res);
   res->counters[11] = c.rerun;
   res->extra[3] = c.boundFilterUsed ? 1 : 0;
@@ -1050,7 +1066,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 9; }
+int32_t xm_abi_version(void) { return 10; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();
@@ -1127,6 +1143,13 @@ int xm_context_set_collapse(xm_index* idx, int32_t enable) {
   std::lock_guard<std::mutex> lock(idx->mu);
   idx->collapse = enable != 0;
   if (!idx->collapse && !idx->memoOn()) idx->collapseBufs = CollapseBuffers();
+  return 0;
+}
+
+int xm_context_set_result_copy(xm_index* idx, int32_t on) {
+  if (!idx) return fail("xm_context_set_result_copy: null argument");
+  std::lock_guard<std::mutex> lock(idx->mu);
+  idx->resultCopy = on != 0;
   return 0;
 }
 
@@ -1510,11 +1533,15 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
     // the shared tables stay as they are while this call's kernels read them (another context that grows them waits; so does this one's next growth)
     std::shared_lock<std::shared_mutex> tablesInUse(idx->dt->rw);
     res->num_queries = nq;
-    res->int_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(nq + 1), &box->bytesIntOff);
-    res->dbl_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(nq + 1), &box->bytesDblOff);
+    if (idx->resultCopy) {  // (xm_context_set_result_copy(0): the result has no streams, and no pinned buffer is taken for one)
+      res->int_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(nq + 1), &box->bytesIntOff);
+      res->dbl_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(nq + 1), &box->bytesDblOff);
+    }
     if (nq == 0) {
-      res->ints = (int32_t*)g_pinned->get(4, &box->bytesInts); res->dbls = (double*)g_pinned->get(8, &box->bytesDbls);
-      res->int_off[0] = res->dbl_off[0] = 0;
+      if (idx->resultCopy) {
+        res->ints = (int32_t*)g_pinned->get(4, &box->bytesInts); res->dbls = (double*)g_pinned->get(8, &box->bytesDbls);
+        res->int_off[0] = res->dbl_off[0] = 0;
+      }
       *out = res;
       return 0;
     }
@@ -1565,5 +1592,6 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 #include "xm_capi_probe.h"
 #include "xm_capi_pileup.h"
 #include "xm_capi_sam.h"
+#include "xm_capi_summary.h"
 #include "xm_capi_test.h"
 #include "xm_capi_fastq.h"

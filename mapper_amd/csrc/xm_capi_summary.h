@@ -1,0 +1,109 @@
+// xm_summary_last, xm_summary_free (included once, by xm_capi.hip): what the host still needs of the last align call's result streams when the SAM text is
+// made on the GPU - the four statistics, every alignment's penalty in stream order and the list of unaligned queries - computed by the kernels of xm_summary.h
+// from the streams where they lie in HBM - xm_pileup_add_last's contract (the context's mutex and stream, ResultStage::lastStreams) - and copied to pinned
+// buffers of the library's pool.  With xm_context_set_result_copy(0) these few bytes and the SAM text are all that crosses to the host of a batch's results.
+// summaryRun is the part that xm_test_summary runs over host-given arrays as well.
+#pragma once
+#include "xm_summary.h"
+
+namespace {
+
+// xm_batch_summary plus what xm_summary_free needs to know about its buffers
+struct SummaryBox {
+  xm_batch_summary pub;
+  size_t bytesPenalties, bytesUnaligned;
+};
+
+void freeSummaryBox(SummaryBox* box) {
+  g_pinned->put(box->pub.penalties, box->bytesPenalties);
+  g_pinned->put(box->pub.unaligned, box->bytesUnaligned);
+  free(box);
+}
+
+// The three stages on stream s over streams in HBM.  Returns the summary, its two arrays in pinned buffers (NULL where there is nothing to hold), or throws:
+// a malformed slice gives no summary.
+SummaryBox* summaryRun(SummaryStage& g, const xm::SummaryStreams& st, int64_t nq, bool wantUnaligned, hipStream_t s) {
+  SummaryBox* box = (SummaryBox*)calloc(1, sizeof(SummaryBox));
+  if (!box) throw std::runtime_error("out of host memory");
+  box->pub.store = box;
+  box->pub.num_queries = nq;
+  if (nq == 0) return box;  // (nothing is launched)
+  try {
+    for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+    // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
+    const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
+    g.dAlignments.ensure((size_t)nq); g.dUnalignedFlag.ensure((size_t)nq); g.dOff.ensure((size_t)nq + 1); g.dUoff.ensure((size_t)nq + 1);
+    g.dBlockA.ensure((size_t)nBlocks); g.dBlockU.ensure((size_t)nBlocks); g.dCtl.ensure(XM_SUMMARY_CTL_WORDS);
+    const unsigned grid = (unsigned)((nq + 255) / 256);
+    HIP_CHECK(hipEventRecord(g.ev[0], s));
+    HIP_CHECK(hipMemsetAsync(g.dCtl.p, 0xFF, sizeof(unsigned long long), s));                                               // XM_SUMMARY_NO_ERROR
+    HIP_CHECK(hipMemsetAsync(g.dCtl.p + 1, 0, sizeof(unsigned long long) * (XM_SUMMARY_CTL_WORDS - 1), s));                 // the three counters
+    hipLaunchKernelGGL(xm_summary_measure_kernel, dim3(grid), dim3(256), 0, s, st, (long long)nq, g.dAlignments.p, g.dUnalignedFlag.p, g.dCtl.p);
+    hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dAlignments.p, (const int32_t*)g.dUnalignedFlag.p, g.dBlockA.p, g.dBlockU.p);
+    hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, g.dBlockA.p, g.dBlockU.p, g.dOff.p, g.dUoff.p);
+    hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dAlignments.p, (const int32_t*)g.dUnalignedFlag.p,
+                       (const long long*)g.dBlockA.p, (const long long*)g.dBlockU.p, g.dOff.p, g.dUoff.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(g.ev[1], s));
+    unsigned long long ctl[XM_SUMMARY_CTL_WORDS] = {0, 0, 0, 0};
+    int64_t totals[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(ctl, g.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&totals[0], g.dOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&totals[1], g.dUoff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // (the one wait for the totals and the counters)
+    if (ctl[0] != XM_SUMMARY_NO_ERROR) throw std::runtime_error("malformed result streams: query " + std::to_string(ctl[0]));
+    const size_t nAl = (size_t)totals[0], nUn = wantUnaligned ? (size_t)totals[1] : 0;
+    box->pub.num_aligned = (int64_t)ctl[1]; box->pub.total_aligned_length = (int64_t)ctl[2]; box->pub.num_indels = (int64_t)ctl[3];
+    box->pub.num_alignments = (int64_t)nAl; box->pub.num_unaligned = (int64_t)nUn;
+    if (nAl) { g.dPenalties.ensure(nAl); box->pub.penalties = (double*)g_pinned->get(sizeof(double) * nAl, &box->bytesPenalties); }
+    if (nUn) { g.dUnaligned.ensure(nUn); box->pub.unaligned = (int64_t*)g_pinned->get(sizeof(int64_t) * nUn, &box->bytesUnaligned); }
+    HIP_CHECK(hipEventRecord(g.ev[2], s));
+    if (nAl || nUn) {
+      hipLaunchKernelGGL(xm_summary_gather_kernel, dim3(grid), dim3(256), 0, s, st, (long long)nq, (const int64_t*)g.dOff.p, (const int64_t*)g.dUoff.p,
+                         nAl ? g.dPenalties.p : nullptr, (long long)nAl, nUn ? g.dUnaligned.p : nullptr, (long long)nUn);
+      HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipEventRecord(g.ev[3], s));
+    if (nAl) HIP_CHECK(hipMemcpyAsync(box->pub.penalties, g.dPenalties.p, sizeof(double) * nAl, hipMemcpyDeviceToHost, s));
+    if (nUn) HIP_CHECK(hipMemcpyAsync(box->pub.unaligned, g.dUnaligned.p, sizeof(int64_t) * nUn, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipEventRecord(g.ev[4], s));
+    HIP_CHECK(hipEventSynchronize(g.ev[4]));
+    float measure = 0, gather = 0, down = 0;
+    HIP_CHECK(hipEventElapsedTime(&measure, g.ev[0], g.ev[1]));
+    HIP_CHECK(hipEventElapsedTime(&gather, g.ev[2], g.ev[3]));
+    HIP_CHECK(hipEventElapsedTime(&down, g.ev[3], g.ev[4]));
+    box->pub.kernel_ms = (double)measure + gather; box->pub.d2h_ms = down;
+    return box;
+  } catch (...) {
+    (void)hipStreamSynchronize(s);  // (nothing of this call is still in flight when its buffers go)
+    freeSummaryBox(box);
+    throw;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+void xm_summary_free(xm_batch_summary* summary) {
+  if (summary) freeSummaryBox((SummaryBox*)summary);  // pub is the first member
+}
+
+int xm_summary_last(xm_index* idx, int32_t want_unaligned, xm_batch_summary** out) {
+  if (!idx || !out) return fail("xm_summary_last: null argument");
+  *out = nullptr;
+  if (idx->hostOnly) return fail("xm_summary_last: index was built with host_only=1");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
+    if (last.nq < 0)
+      throw std::runtime_error("the batch of the last align call is no longer resident (call xm_summary_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
+    HIP_CHECK(hipSetDevice(idx->device));
+    const xm::SummaryStreams st{last.ints, last.dbls, last.intOff, last.dblOff, (int32_t)idx->host().numContigs()};
+    SummaryBox* box = summaryRun(idx->summary, st, last.nq, want_unaligned != 0, idx->stream);
+    *out = &box->pub;
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_summary_last: ") + e.what()); }
+}
+
+}  // extern "C"

@@ -115,7 +115,8 @@ struct ResultStage {
   }
   // Canonical streams in query order: offsets by prefix sum, slices gathered on the device, one copy per stream to pinned host memory (enqueued on s: the
   // caller waits for it).  copies: queries that share their representative's slice (collapseFanOut); gen: the resident batch these streams belong to.
-  void toHost(int64_t nq, int64_t copies, int64_t gen, xm_result* res, ResultBox* box, hipStream_t s) {
+  // copy = false (xm_context_set_result_copy(0)): the same launches, the streams stay where they lie, and only the scan's two totals are read, into res->num_ints / num_dbls.
+  void toHost(int64_t nq, int64_t copies, int64_t gen, xm_result* res, ResultBox* box, hipStream_t s, bool copy = true) {
     const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
     dBlockI.ensure((size_t)nBlocks); dBlockD.ensure((size_t)nBlocks);
     dFinalIntOff.ensure((size_t)nq + 1); dFinalDblOff.ensure((size_t)nq + 1);
@@ -135,6 +136,13 @@ struct ResultStage {
     hipLaunchKernelGGL(xm_gather_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, dIntOff.p, dDblOff.p, dIntLen.p, dDblLen.p,
                        dFinalIntOff.p, dFinalDblOff.p, dOutInts.p, dOutDbls.p, dFinalInts.p, dFinalDbls.p);
     HIP_CHECK(hipGetLastError());
+    if (!copy) {
+      lastAlignedNq = nq;
+      lastAlignedGen = gen;
+      HIP_CHECK(hipMemcpyAsync(&res->num_ints, dFinalIntOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(&res->num_dbls, dFinalDblOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+      return;
+    }
     res->ints = (int32_t*)g_pinned->get(sizeof(int32_t) * (usedI ? usedI : 1), &box->bytesInts);
     res->dbls = (double*)g_pinned->get(sizeof(double) * (usedD ? usedD : 1), &box->bytesDbls);
     lastAlignedNq = nq;

@@ -39,6 +39,7 @@ def lib():
         L.xmio_close.argtypes = [C.c_void_p]
         L.xmio_write_batch.argtypes = [C.POINTER(XmioBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(XmioStats)]
+        L.xmio_write_summary.argtypes = [C.POINTER(XmioBatch), C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(XmioStats)]
         L.xmio_java_double.argtypes = [C.c_double, C.c_char_p, C.c_int32]
         L.xmio_last_write_seconds.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.xmio_last_write_seconds.restype = None
@@ -231,9 +232,12 @@ class Writer:
         self.threads = int(threads or min(32, os.cpu_count() or 1))
         self.seconds = {"format": 0.0, "write": 0.0}  # wall seconds of the write() calls so far: formatting on the host (and counting), and writing the files
 
-    def write(self, batch, result, sam_text=None):
+    def write(self, batch, result, sam_text=None, summary=None):
         """result: anything with ints / dbls / int_off / dbl_off (api.BatchResult).  sam_text: the batch's SAM records as the GPU formatted them
-        (api.SamText, or any bytes-like object): they are written as they are, and the native call only counts the statistics and writes the unaligned queries."""
+        (api.SamText, or any bytes-like object): they are written as they are, and the native call only counts the statistics and writes the unaligned queries.
+        summary: what the GPU counted of the streams (api.BatchSummary, or anything with its fields): the statistics and the unaligned queries come from it
+        (xmio_write_summary) and none of result's streams is read - a result whose streams stayed in HBM has none.  A writer with a SAM file then needs the
+        text too, and one with an unaligned-query file a summary that was asked for the list."""
         for f in (self._sam, self._un):
             if f is not None:
                 f.flush()
@@ -246,6 +250,23 @@ class Writer:
                 done += os.write(sam_fd, view[done:])
             self.seconds["write"] += time.perf_counter() - t0
             sam_fd = -1
+        un_fd = self._un.fileno() if self._un is not None else -1
+        if summary is not None:
+            if sam_fd >= 0:
+                raise ValueError("a summary holds no alignments to format: with a SAM file the text must be given as well (sam_text)")
+            if summary.num_queries != batch.num_queries:
+                raise ValueError("the summary of %d queries for a batch of %d" % (summary.num_queries, batch.num_queries))
+            pen = np.ascontiguousarray(summary.penalties, dtype=np.float64)
+            un = np.ascontiguousarray(summary.unaligned, dtype=np.int64)
+            if len(pen) != summary.num_alignments:
+                raise ValueError("%d penalties for %d alignments" % (len(pen), summary.num_alignments))
+            if un_fd >= 0 and len(un) != batch.num_queries - summary.num_aligned:
+                raise ValueError("the summary lists %d unaligned queries of %d (ask for the list: summary_last(want_unaligned=True))" % (len(un), batch.num_queries - summary.num_aligned))
+            if lib().xmio_write_summary(batch._ptr, summary.num_aligned, summary.total_aligned_length, summary.num_indels, len(pen), pen.ctypes.data if len(pen) else None,
+                                        len(un), un.ctypes.data if len(un) else None, un_fd, C.byref(self.stats)):
+                raise RuntimeError(lib().xmio_last_error().decode())
+            self._tick_native()
+            return
         ints = np.ascontiguousarray(result.ints, dtype=np.int32)
         dbls = np.ascontiguousarray(result.dbls, dtype=np.float64)
         io = np.ascontiguousarray(result.int_off, dtype=np.int64)
@@ -253,8 +274,12 @@ class Writer:
         if len(io) != batch.num_queries + 1:
             raise ValueError("result streams of %d queries for a batch of %d" % (len(io) - 1, batch.num_queries))
         if lib().xmio_write_batch(batch._ptr, ints.ctypes.data, dbls.ctypes.data, io.ctypes.data, do.ctypes.data, self._n, self._names,
-                                  sam_fd, self._un.fileno() if self._un is not None else -1, self.threads, C.byref(self.stats)):
+                                  sam_fd, un_fd, self.threads, C.byref(self.stats)):
             raise RuntimeError(lib().xmio_last_error().decode())
+        self._tick_native()
+
+    def _tick_native(self):
+        """The seconds of this thread's last native write call into self.seconds."""
         fmt, wr = C.c_double(), C.c_double()
         lib().xmio_last_write_seconds(C.byref(fmt), C.byref(wr))
         self.seconds["format"] += fmt.value

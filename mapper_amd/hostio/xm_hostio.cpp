@@ -598,6 +598,21 @@ void appendSeq(std::string& out, const uint8_t* codes, int n, bool rev) {
   else for (int i = 0; i < n; i++) p[i] = g_decode[g_comp[codes[n - 1 - i] & 15]];
 }
 
+// query q as it came in, to the unaligned-query file's text: FASTQ when it had qualities, else FASTA [unpinned format]
+void appendUnaligned(std::string& un, const xmio_batch* b, int64_t q) {
+  const int nMates = b->mate_count[q];
+  for (int mate = 0; mate < nMates; mate++) {
+    const int64_t m = 2 * q + mate;
+    const bool fq = b->has_qual && b->has_qual[m];
+    un += fq ? '@' : '>';
+    un.append(b->names + b->name_off[m], (size_t)(b->name_off[m + 1] - b->name_off[m]));
+    un += '\n';
+    appendSeq(un, b->codes + b->mate_offset[m], b->mate_length[m], false);
+    un += '\n';
+    if (fq) { un += "+\n"; un.append(b->quals + b->qual_off[m], (size_t)(b->qual_off[m + 1] - b->qual_off[m])); un += '\n'; }
+  }
+}
+
 struct FormatJob {
   const xmio_batch* b;
   const int32_t* ints; const double* dbls; const int64_t* intOff; const int64_t* dblOff;
@@ -674,18 +689,7 @@ bool formatRange(const FormatJob& J, int64_t q0, int64_t q1, std::string& sam, s
       }
     }
     if (any) st.aligned++;
-    else if (J.wantUnaligned) {  // [unpinned format] the query as it came in: FASTQ when it had qualities, else FASTA
-      for (int mate = 0; mate < nMates; mate++) {
-        const int64_t m = 2 * q + mate;
-        const bool fq = b->has_qual && b->has_qual[m];
-        un += fq ? '@' : '>';
-        un.append(b->names + b->name_off[m], (size_t)(b->name_off[m + 1] - b->name_off[m]));
-        un += '\n';
-        appendSeq(un, b->codes + b->mate_offset[m], b->mate_length[m], false);
-        un += '\n';
-        if (fq) { un += "+\n"; un.append(b->quals + b->qual_off[m], (size_t)(b->qual_off[m + 1] - b->qual_off[m])); un += '\n'; }
-      }
-    }
+    else if (J.wantUnaligned) appendUnaligned(un, b, q);
   }
   return true;
 }
@@ -774,6 +778,44 @@ int xmio_write_batch(const xmio_batch* b, const int32_t* ints, const double* dbl
   stats->num_aligned += aligned;
   stats->total_aligned_length += totalLen;
   stats->num_indels += indels;
+  stats->total_penalty = totalPenalty;
+  g_fileSeconds = fileSeconds;
+  g_formatSeconds = nowSeconds() - tStart - fileSeconds;
+  return 0;
+}
+
+// What xmio_write_batch does with sam_fd = -1, from a summary of the streams instead of the streams (xm_summary_last of include/xmapper_hip.h): the unaligned
+// queries of the list to unaligned_fd, and the statistics.
+int xmio_write_summary(const xmio_batch* b, int64_t num_aligned, int64_t total_aligned_length, int64_t num_indels, int64_t num_alignments, const double* penalties,
+                       int64_t num_unaligned, const int64_t* unaligned, int32_t unaligned_fd, xmio_stats* stats) {
+  if (!b || !stats) return fail("xmio_write_summary: null argument");
+  if (num_alignments < 0 || num_unaligned < 0 || (num_alignments > 0 && !penalties) || (num_unaligned > 0 && !unaligned)) return fail("xmio_write_summary: a count without its array");
+  const int64_t nq = b->num_queries;
+  const double tStart = nowSeconds();
+  double fileSeconds = 0;
+  g_formatSeconds = g_fileSeconds = 0;
+  for (int64_t i = 0; i < num_unaligned; i++)
+    if (unaligned[i] < 0 || unaligned[i] >= nq || (i > 0 && unaligned[i] <= unaligned[i - 1]))
+      return fail("xmio_write_summary: the list of unaligned queries is not strictly ascending inside the batch (entry " + std::to_string(i) + ")");
+  if (unaligned_fd >= 0) {
+    std::string un;
+    for (int64_t i = 0; i < num_unaligned; i++) {
+      appendUnaligned(un, b, unaligned[i]);
+      if (un.size() >= (size_t)(8 << 20) || i + 1 == num_unaligned) {  // (memory stays bounded)
+        const double tWrite = nowSeconds();
+        if (!writeAll(unaligned_fd, un)) return fail("xmio_write_summary: write to the unaligned-query file failed");
+        fileSeconds += nowSeconds() - tWrite;
+        un.clear();
+      }
+    }
+  }
+  // the penalties in query order, as Mapper.run sums them (a double sum: the order is part of the result)
+  double totalPenalty = stats->total_penalty;
+  for (int64_t a = 0; a < num_alignments; a++) totalPenalty += penalties[a];
+  stats->num_queries += nq;
+  stats->num_aligned += num_aligned;
+  stats->total_aligned_length += total_aligned_length;
+  stats->num_indels += num_indels;
   stats->total_penalty = totalPenalty;
   g_fileSeconds = fileSeconds;
   g_formatSeconds = nowSeconds() - tStart - fileSeconds;

@@ -89,6 +89,15 @@ class MultiGpuDatabase:
         """ReferenceDatabase.format_sam_last of replica `replica` (align_stream's on_aligned hook names it), on that replica's thread."""
         return self.replicas[replica].format_sam_last(batch)
 
+    def set_result_copy(self, on):
+        """ReferenceDatabase.set_result_copy for every replica."""
+        for r in self.replicas:
+            r.set_result_copy(on)
+
+    def summary_last(self, replica, want_unaligned=False):
+        """ReferenceDatabase.summary_last of replica `replica` (align_stream's on_aligned hook names it), on that replica's thread."""
+        return self.replicas[replica].summary_last(want_unaligned)
+
     def close(self):
         for r in self.replicas:
             r.close()
