@@ -125,7 +125,8 @@ const char* xm_build_stamp(void);
  * xm_result.extra[7]; 4 = xm_context_set_memo, xm_context_memo_info, xm_result.extra[6]; 5 = xm_memory_new, xm_context_attach_memory, xm_memory_info,
  * xm_memory_free, xm_result.reserved carries the wait for a memory; 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7 = xm_sam_set_contigs,
  * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles); 8 = xm_batch_unstage; 9 = xm_pileup_keep_insert_text, xm_pileup_event_text (and the test-only
- * xm_test_pileup_text); 10 = xm_context_set_result_copy, xm_summary_last, xm_summary_free (and the test-only xm_test_summary).  A binding checks it once
+ * xm_test_pileup_text); 10 = xm_context_set_result_copy, xm_summary_last, xm_summary_free (and the test-only xm_test_summary);
+ * 11 = xm_refs_count_last, xm_refs_count_free (and the test-only xm_test_refs_count).  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -325,6 +326,36 @@ typedef struct xm_batch_summary {
 int xm_summary_last(xm_index* context, int32_t want_unaligned, xm_batch_summary** out);
 void xm_summary_free(xm_batch_summary* summary);
 
+/* (ABI version 11) The queries of the last align call counted per combination of contigs - what Mapper.run's --out-refs-map-count reports
+ * (Mapper.java:197, 747-756): for every query with an alignment, the set of contigs that the sequences of its alignments lie on, and per distinct set the
+ * number of such queries.  Kernels walk the resident streams, find equal sets through a table keyed by a fingerprint of the set, compare every query's set
+ * with its slot's first query, and count.  Between a few and a few thousand records cross to the host.  Not used by the Java host. */
+#define XM_REFS_RECORD_IDS 8
+typedef struct xm_refs_record {
+  int64_t count;                /* queries with exactly this set */
+  int32_t n;                    /* 1 .. XM_REFS_RECORD_IDS */
+  int32_t ids[XM_REFS_RECORD_IDS];  /* ids[0 .. n): contig indices (reference order of the index), ascending and distinct; 0 behind them */
+  int32_t reserved;
+} xm_refs_record;
+/* Every query with an alignment is either counted in one record or left over: a query on more than XM_REFS_RECORD_IDS contigs, or one whose set shares its
+ * fingerprint with a different set (with 64 bits: practically never).  Of a left-over query the host gets the contig of every sequence alignment, repeats
+ * included, in stream order: leftover_contigs[leftover_offsets[k] .. leftover_offsets[k + 1]) for the k-th of them in query order; the caller makes the set
+ * and adds one to it.  The sets of two records differ.  sum(count) + num_leftover_queries == num_aligned.  The arrays are page-locked buffers of the
+ * library's pool (NULL where the count is 0); kernel_ms, d2h_ms: the kernels and the copy of the arrays. */
+typedef struct xm_refs_count {
+  int64_t num_queries, num_aligned;
+  int64_t num_combinations; xm_refs_record* records;
+  int64_t num_leftover_queries; int64_t* leftover_offsets /* [num_leftover_queries + 1] */; int32_t* leftover_contigs;
+  double kernel_ms, d2h_ms; void* store;
+} xm_refs_count;
+/* xm_refs_count_last has xm_summary_last's contract: it serialises with the context's other calls, runs on the context's stream, fails with "no longer
+ * resident" once another batch has been uploaded or committed and after an align call that failed, works whether or not the copy of the streams is on, and
+ * fails with "malformed result streams: query N" for the lowest query whose slice is not of the layout (where xm_summary_last says so).  Nothing is launched
+ * or allocated for a context that never calls it, and a batch of 0 queries launches nothing.  Released with xm_refs_count_free.
+ * mapper_amd/csrc/xm_refs_rules.h states the walk, the set and the fingerprint as code. */
+int xm_refs_count_last(xm_index* context, xm_refs_count** out);
+void xm_refs_count_free(xm_refs_count* count);
+
 /* Bulk form of Readable_HashBlock_Database.getNumMatchesLowerBound + matchBlock / PackedMap.get (PackedMap.java:160-172,
  * 228-236) for n (used_length, lookup key) pairs: counts[i] = number of stored positions, -1 when the bucket is overfull or
  * holds more than the table's limit, -2 when used_length is not a hashed length.  Positions (at most max_per_probe <= 15 per probe, not reverse-complemented): the
@@ -431,6 +462,10 @@ int xm_test_pileup_text(int32_t device, const xm_test_pileup_job* job, int64_t* 
  * Same result, same errors. */
 int xm_test_summary(int32_t device, int64_t num_queries, int32_t num_contigs, const int32_t* ints, const double* dbls,
                     const int64_t* int_off, const int64_t* dbl_off, int32_t want_unaligned, xm_batch_summary** out);
+/* Test-only (tests/test_gpu_refs_count.py), like xm_test_summary: the kernels of xm_refs_count_last over host-given streams on `device`; no index, no
+ * alignment.  fingerprint_bits < 64 keeps only that many bits of the sets' fingerprints, so that different sets collide.  Same result, same errors. */
+int xm_test_refs_count(int32_t device, int64_t num_queries, int32_t num_contigs, const int32_t* ints, const double* dbls,
+                       const int64_t* int_off, const int64_t* dbl_off, int32_t fingerprint_bits, xm_refs_count** out);
 /* Test-only: Double.toString as the SAM tags print it, run by the device on n values: out24[24 * i ...] the string of x[i] (padded with NUL), len[i] its length. */
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len);
 

@@ -78,13 +78,25 @@ class XmBatchSummary(C.Structure):
                 ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("store", C.c_void_p)]
 
 
+class XmRefsRecord(C.Structure):
+    """xm_refs_record: one combination of contigs (ids[:n], ascending contig indices) and the queries of the batch with exactly that set."""
+    _fields_ = [("count", C.c_int64), ("n", C.c_int32), ("ids", C.c_int32 * 8), ("reserved", C.c_int32)]
+
+
+class XmRefsCount(C.Structure):
+    """xm_refs_count: the queries of a batch counted per combination of contigs, and the contigs of the queries left to the host, in pinned buffers of the library."""
+    _fields_ = [("num_queries", C.c_int64), ("num_aligned", C.c_int64), ("num_combinations", C.c_int64), ("records", C.POINTER(XmRefsRecord)),
+                ("num_leftover_queries", C.c_int64), ("leftover_offsets", C.POINTER(C.c_int64)), ("leftover_contigs", C.POINTER(C.c_int32)),
+                ("kernel_ms", C.c_double), ("d2h_ms", C.c_double), ("store", C.c_void_p)]
+
+
 class XmTestPileupJob(C.Structure):
     """xm_test_pileup_job (test-only): the mates of a batch and events of the pile-up, all on the host."""
     _fields_ = [("num_queries", C.c_int64), ("mate_offset", C.c_void_p), ("mate_length", C.c_void_p), ("codes", C.c_void_p), ("codes_length", C.c_int64),
                 ("num_events", C.c_int64), ("events", C.c_void_p), ("query_base", C.c_int64)]
 
 
-ABI_VERSION = 10  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary
+ABI_VERSION = 11  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count
 
 
 class XmIndexInfo(C.Structure):
@@ -95,7 +107,7 @@ class XmIndexInfo(C.Structure):
 
 
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
-           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary"]
+           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count"]
 
 
 def build_library(force=False):
@@ -213,6 +225,10 @@ def lib():
         L.xm_summary_free.argtypes = [C.POINTER(XmBatchSummary)]
         L.xm_summary_free.restype = None
         L.xm_test_summary.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.POINTER(XmBatchSummary))]
+        L.xm_refs_count_last.argtypes = [C.c_void_p, C.POINTER(C.POINTER(XmRefsCount))]
+        L.xm_refs_count_free.argtypes = [C.POINTER(XmRefsCount)]
+        L.xm_refs_count_free.restype = None
+        L.xm_test_refs_count.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.POINTER(XmRefsCount))]
         _lib = L
     return _lib
 

@@ -187,6 +187,53 @@ class BatchSummary:
             pass
 
 
+class RefsCount:
+    """What ReferenceDatabase.refs_count_last counted on the GPU from the result streams of one batch: num_queries, num_aligned, `records` - one per combination
+    of contigs, (tuple of ascending contig indices, queries with exactly that set) - and the queries the device left to the host (more than eight contigs, or
+    a set whose fingerprint another set had taken): num_leftover_queries, and the contigs of their sequence alignments in leftover_contigs[leftover_offsets[k]:
+    leftover_offsets[k + 1]].  counts() folds both into one dict.  Everything is copied out of the library's buffers here; close() gives them back."""
+
+    def __init__(self, L, ptr):
+        self._L, self._ptr = L, ptr
+        t = ptr.contents
+        self.num_queries, self.num_aligned = int(t.num_queries), int(t.num_aligned)
+        self.num_combinations, self.num_leftover_queries = int(t.num_combinations), int(t.num_leftover_queries)
+        self.kernel_ms, self.d2h_ms = t.kernel_ms, t.d2h_ms
+        self.records = []
+        if self.num_combinations:
+            raw = np.ctypeslib.as_array(C.cast(t.records, C.POINTER(C.c_int32)), shape=(self.num_combinations, 12))  # count (two ints), n, ids[8], reserved
+            count = raw[:, :2].copy().view(np.int64)[:, 0]
+            self.records = [(tuple(int(x) for x in raw[k, 3:3 + int(raw[k, 2])]), int(count[k])) for k in range(self.num_combinations)]
+        self.leftover_offsets, self.leftover_contigs = np.zeros(1, np.int64), np.zeros(0, np.int32)
+        if self.num_leftover_queries:
+            self.leftover_offsets = np.ctypeslib.as_array(t.leftover_offsets, shape=(self.num_leftover_queries + 1,)).copy()
+            total = int(self.leftover_offsets[-1])
+            self.leftover_contigs = np.ctypeslib.as_array(t.leftover_contigs, shape=(max(total, 1),))[:total].copy()
+        self.close()
+
+    def counts(self):
+        """-> {tuple of ascending contig indices: queries}: the records, and every left-over query added to the set of its contigs."""
+        out = {}
+        for ids, count in self.records:
+            out[ids] = out.get(ids, 0) + count
+        lo = self.leftover_offsets
+        for k in range(self.num_leftover_queries):
+            ids = tuple(sorted(set(int(c) for c in self.leftover_contigs[lo[k]:lo[k + 1]])))
+            out[ids] = out.get(ids, 0) + 1
+        return out
+
+    def close(self):
+        if self._ptr is not None:
+            self._L.xm_refs_count_free(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SamText:
     """The SAM records of one batch as ReferenceDatabase.format_sam_last built them: `bytes` of text (no header) in a page-locked buffer of the library, `records`
     lines, and the milliseconds of the call's three parts (names up, kernels, text down).  memoryview(text) / text.view() reads it without a copy, bytes(text)
@@ -479,6 +526,17 @@ class ReferenceDatabase:
         _check(self._L.xm_summary_last(self._h, 1 if want_unaligned else 0, C.byref(out)))
         self._tick("format", time.perf_counter() - t0)
         return BatchSummary(self._L, out)
+
+    def refs_count_last(self, raw=False):
+        """xm_refs_count_last: the queries of the last align call counted per combination of contigs - for every query with an alignment the set of contigs
+        its alignments lie on - on the GPU while the batch is still resident (align_stream's on_aligned hook is the place), with or without the copy of the
+        streams -> {tuple of ascending contig indices: queries}; raw=True: the RefsCount it is folded from."""
+        t0 = time.perf_counter()
+        out = C.POINTER(_capi.XmRefsCount)()
+        _check(self._L.xm_refs_count_last(self._h, C.byref(out)))
+        got = RefsCount(self._L, out)
+        self._tick("format", time.perf_counter() - t0)
+        return got if raw else got.counts()
 
     def commit_staged(self):
         """xm_batch_commit: the staged batch becomes the resident one."""

@@ -18,14 +18,18 @@ it has aligned in that much HBM and serves byte-identical queries of its later b
 stderr), and --remember-queries-per-gpu <MiB> (one such memory per GPU, which all its contexts share and which keeps remembering when it is full; not
 together with --remember-queries), and --parse-on-gpu (the FASTQ files go to the GPU as text and are parsed there, api.ReferenceDatabase.stage_fastq: same outputs;
 four-line FASTQ records only, so a file the host reader takes may be refused with a message that says where; not with --per-object or a split size; a job
-whose output needs objects - --out-refs-map-count, needs_objects - parses on the host all the same),
+whose output needs objects - --out-refs-map-count without --count-refs-on-gpu, needs_objects - parses on the host all the same),
 --format-on-gpu (the SAM records are formatted on the GPU while a batch and its results are resident, api.ReferenceDatabase.format_sam_last, and the host
 only writes the bytes: same outputs; --out-unaligned stays with the host; not with --per-object, --out-mutations or --out-refs-map-count; nothing to do
 without --out-sam), --results-on-gpu (the align calls leave their result streams in HBM and copy none of them to the host,
 api.ReferenceDatabase.set_result_copy(False); what the host still needs of them - the statistics, every alignment's penalty, the unaligned queries - is computed
 on the GPU while the batch is resident, api.ReferenceDatabase.summary_last: same outputs; with --out-sam only together with --format-on-gpu, since the host
 formatter reads the streams; fine with --out-unaligned, --no-output and --out-mutations, whose pile-up reads the resident streams; not with --per-object or
---out-refs-map-count, which decode the streams on the host), and --format-threads <n> (threads of the host's SAM formatter).
+--out-refs-map-count, which decode the streams on the host - unless the count is made on the GPU, next), --count-refs-on-gpu (the count behind
+--out-refs-map-count is made on the GPU while a batch and its results are resident, api.ReferenceDatabase.refs_count_last: per batch the queries per
+combination of contigs cross to the host, and the job needs no objects: it streams like any other, parses on the GPU if --parse-on-gpu says so, and
+--out-refs-map-count is then accepted beside --format-on-gpu and --results-on-gpu; same file; not with --per-object; nothing to do without
+--out-refs-map-count), and --format-threads <n> (threads of the host's SAM formatter).
 
 --out-mutations streams like --out-sam: the device pile-up keeps the bases of every insertion with its event (pileup.MatchDatabase(keep_insert_text=True)), so
 the mutations file needs no object per read; with --per-object it is written the first way, from the Query objects of the whole job, which is the reference
@@ -210,6 +214,8 @@ def parse_args(argv):
             o["format_on_gpu"] = True
         elif a == "--results-on-gpu":  # (not a Mapper flag) the result streams stay in HBM; the host gets the SAM text and a summary (api.ReferenceDatabase.set_result_copy, summary_last)
             o["results_on_gpu"] = True
+        elif a == "--count-refs-on-gpu":  # (not a Mapper flag) the count of --out-refs-map-count is made on the GPU from the resident result streams (api.ReferenceDatabase.refs_count_last)
+            o["count_refs_on_gpu"] = True
         elif a == "--format-threads":  # (not a Mapper flag) threads of the host's SAM formatter (hostio.Writer; default: the CPUs, 32 at the most)
             o["format_threads"] = int(argv[i + 1]); i += 1
             if o["format_threads"] < 1:
@@ -229,13 +235,19 @@ def parse_args(argv):
         raise UsageError("--parse-on-gpu and --per-object exclude each other (the per-object path reads the queries into Python objects)")
     if o.get("parse_on_gpu") and any(split > 0 for _, split in o["queries"]):
         raise UsageError("--parse-on-gpu is not supported with --split-queries-past-size (the sections are cut by the host reader)")
+    if o.get("count_refs_on_gpu"):
+        if o.get("per_object"):
+            raise UsageError("--count-refs-on-gpu and --per-object exclude each other (the per-object path counts from alignments decoded on the host)")
+        if not o.get("out_refs_map_count"):
+            raise UsageError("--count-refs-on-gpu has nothing to do without --out-refs-map-count")
+    refs_need_objects = bool(o.get("out_refs_map_count") and not o.get("count_refs_on_gpu"))
     for other, key in (("--per-object", "per_object"), ("--out-mutations", "out_mutations"), ("--out-refs-map-count", "out_refs_map_count")):
-        if o.get("format_on_gpu") and o.get(key):
+        if o.get("format_on_gpu") and o.get(key) and (key != "out_refs_map_count" or refs_need_objects):
             raise UsageError("--format-on-gpu and %s exclude each other (--per-object and --out-refs-map-count format on the host; the pile-up of --out-mutations has not been run beside the device formatter)" % other)
     if o.get("results_on_gpu"):
         if o.get("per_object"):
             raise UsageError("--results-on-gpu and --per-object exclude each other (the per-object path decodes the result streams on the host)")
-        if o.get("out_refs_map_count"):
+        if refs_need_objects:
             raise UsageError("--results-on-gpu and --out-refs-map-count exclude each other (the count is made from alignments decoded on the host)")
         if o["out_sam"] and not o.get("format_on_gpu"):
             raise UsageError("--results-on-gpu with --out-sam needs --format-on-gpu (the host's SAM formatter reads the result streams, which stay on the GPU)")
@@ -314,8 +326,9 @@ def sam_header(contigs):
 
 def needs_objects(o):
     """Whether the job runs through the per-object path (object_source, ObjectSink): when it is asked for, and for the one output that is counted from
-    decoded alignments.  --out-mutations is not among them: its only use of the objects, the text of insertions, comes from the device pile-up."""
-    return bool(o.get("out_refs_map_count") or o.get("per_object"))
+    decoded alignments, unless --count-refs-on-gpu has the GPU count it.  --out-mutations is not among them: its only use of the objects, the text of
+    insertions, comes from the device pile-up."""
+    return bool((o.get("out_refs_map_count") and not o.get("count_refs_on_gpu")) or o.get("per_object"))
 
 
 def default_contexts(explicit_devices, batches, single_short):
@@ -418,6 +431,33 @@ def object_source(o, batch_size):
     return batches, len(batches), all(len(q.sequences) == 1 for q, _ in pairs) and max_len <= 320, max_len
 
 
+def refs_map_key(indices, names):
+    """The key of --out-refs-map-count for a query whose alignments lie on the contigs `indices`: a set over names, so contigs of one name merge."""
+    return tuple(sorted({names[i] for i in indices}))
+
+
+def write_refs_map(path, counts):
+    """Mapper.java:747-756 (referenceAlignmentCounter.sumAlignments); [unpinned format]: one line per combination, most frequent first."""
+    with open(path, "w") as f:
+        for key, count in sorted(counts.items(), key=lambda kv: (-kv[1], kv[0])):
+            f.write("%s\t%d\n" % (",".join(key), count))
+
+
+class RefsTally:
+    """--count-refs-on-gpu: the job's count per combination of contig names, added up batch by batch from what each context counted on its GPU.  add() runs in
+    stream's on-context hook, on the replicas' threads: one counter, under a lock."""
+
+    def __init__(self, names):
+        self._names, self._lock, self.counts = names, threading.Lock(), {}
+
+    def add(self, context):
+        counted = context.refs_count_last()
+        with self._lock:
+            for indices, count in counted.items():
+                key = refs_map_key(indices, self._names)
+                self.counts[key] = self.counts.get(key, 0) + count
+
+
 class ObjectSink:
     """hostio.Writer's job with one Python object per alignment (sam.records), plus the count behind --out-refs-map-count."""
 
@@ -434,7 +474,7 @@ class ObjectSink:
             if any(len(c) > 0 for c in comps):
                 st.num_aligned += 1
                 if self.refs_map is not None:  # ReferenceAlignmentCounter [QuickVariants, inferred]: the set of contigs a query's alignments lie on
-                    key = tuple(sorted({self._names[sa.contig] for comp in comps for al in comp for sa in al.components}))
+                    key = refs_map_key((sa.contig for comp in comps for al in comp for sa in al.components), self._names)
                     self.refs_map[key] = self.refs_map.get(key, 0) + 1
                 for comp in comps:  # AlignmentCounter [QuickVariants, inferred]: every reported alignment's aligned length, penalty and indels
                     for al in comp:
@@ -451,13 +491,10 @@ class ObjectSink:
                     self._un.write("@%s\n%s\n+\n%s\n" % (name, text, qual) if qual is not None else ">%s\n%s\n" % (name, text))
 
     def write_refs_map(self, path):
-        """Mapper.java:747-756 (referenceAlignmentCounter.sumAlignments); [unpinned format]: one line per combination, most frequent first."""
-        with open(path, "w") as f:
-            for key, count in sorted(self.refs_map.items(), key=lambda kv: (-kv[1], kv[0])):
-                f.write("%s\t%d\n" % (",".join(key), count))
+        write_refs_map(path, self.refs_map)
 
 
-def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format_on_gpu=False, results_on_gpu=False, want_unaligned=False):
+def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format_on_gpu=False, results_on_gpu=False, want_unaligned=False, refs_tally=None):
     """The job: the batches stream through the GPU contexts (align_stream: the copy of batch k + 1 overlaps the alignment of batch k; several contexts align
     side by side) and a writer thread hands each batch and its result streams to the sink while the next batches are being aligned; at most `depth` results
     wait for it.  Every batch taken from `batches` is closed, and the first exception - the reader's, the GPU's or the sink's - reaches the caller.
@@ -466,12 +503,13 @@ def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format
     on_aligned hook: between two align calls of that context), and the writer thread writes the text; tally["read"] grows by the seconds the feeder waited for
     the reader.  results_on_gpu: the results carry no streams (set_result_copy(False) is the caller's); the same hook asks the context for the batch's summary
     (summary_last, with the list of unaligned queries if want_unaligned) behind the text and before the caller's on_aligned, and the summary travels to the
-    writer thread with the text; both are closed there, also after a failure."""
+    writer thread with the text; both are closed there, also after a failure.  refs_tally (a RefsTally): the same hook has the context count the batch's queries
+    per combination of contigs (refs_count_last) behind the text and the summary and before the caller's on_aligned."""
     in_flight = queue.Queue()  # batches in the order they were dealt to the GPUs
     to_write = queue.Queue(maxsize=depth)
     failure = []
     dealt, texts = {}, {}      # by batch number: the batch on its way to a context; [the text, the summary] its context made of it
-    on_context = format_on_gpu or results_on_gpu
+    on_context = format_on_gpu or results_on_gpu or refs_tally is not None
 
     def feed():
         it = iter(batches)
@@ -499,6 +537,8 @@ def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format
                 made[0] = context.format_sam_last(None if isinstance(b, hostio.TextBlock) else b)  # (a text block's names are in HBM with the batch)
             if results_on_gpu:
                 made[1] = context.summary_last(want_unaligned=want_unaligned)
+            if refs_tally is not None:
+                refs_tally.add(context)
             if on_aligned is not None:
                 on_aligned(*at)
 
@@ -597,8 +637,12 @@ def run(argv, out=sys.stdout, open_database=None):
         # (--results-on-gpu: per query two counts and two offsets, and the penalties and the list, 8 bytes an alignment or an unaligned query)
         results_on_gpu = bool(o.get("results_on_gpu"))
         summary_arrays = batch_size * 64 if results_on_gpu else 0
+        # (--count-refs-on-gpu: a table of two to four slots per query - key, first query and count, 24 bytes a slot - and per query a slot, three flags or
+        # lengths and four offsets)
+        refs_tally = RefsTally(names) if o.get("count_refs_on_gpu") else None
+        refs_arrays = batch_size * 144 if refs_tally is not None else 0
         db = (open_database or open_gpu_database)(ordered, devices, max_len, enable_gapmers=o["enable_gapmers"], collapse=o.get("collapse", False),
-                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0) + sam_text + summary_arrays, **memo)
+                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0) + sam_text + summary_arrays + refs_arrays, **memo)
         job.callback(db.close)
         if format_on_gpu:
             db.set_sam_contigs(names)
@@ -623,14 +667,16 @@ def run(argv, out=sys.stdout, open_database=None):
         t_stream = time.perf_counter()
         tally = {}
         copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned, tally, format_on_gpu=format_on_gpu, results_on_gpu=results_on_gpu,
-                        want_unaligned=bool(o["out_unaligned"]))
+                        want_unaligned=bool(o["out_unaligned"]), refs_tally=refs_tally)
         contexts = list(getattr(db, "replicas", [db]))
         spent = lambda key: sum(getattr(c, "seconds", {}).get(key, 0.0) for c in contexts)  # noqa: E731
         # seconds of the job by phase, summed over batches (and over contexts, which work side by side: the sum may exceed the wall time): the reader or cutter,
         # staging (copy up, and the parse with --parse-on-gpu), the align calls, formatting SAM (on the host, or the GPU call with --format-on-gpu), file writes
         phases = {"read": tally.get("read", 0.0), "stage": spent("stage"), "align": spent("align"),
                   "format": spent("format") + getattr(sink, "seconds", {}).get("format", 0.0), "write": getattr(sink, "seconds", {}).get("write", 0.0)}
-        if o.get("out_refs_map_count"):
+        if refs_tally is not None:
+            write_refs_map(o["out_refs_map_count"], refs_tally.counts)
+        elif o.get("out_refs_map_count"):
             sink.write_refs_map(o["out_refs_map_count"])
         if match_db is not None:  # Mapper.java:758-785
             with open(o["out_mutations"], "w") as f:

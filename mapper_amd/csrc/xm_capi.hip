@@ -10,7 +10,8 @@
 // the scan and gather kernels, the canonical streams; throwFailedQuery), xm_conf_table.h (the host's confidence table), xm_capi_probe.h (seed-probe and
 // random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries), xm_capi_fastq.h (a batch staged from FASTQ text: the kernels of xm_fastq.h),
 // xm_capi_sam.h (SAM records formatted from the resident results: the kernels of xm_sam.h), xm_capi_summary.h (the statistics, the penalties and the unaligned
-// queries of the resident results: the kernels of xm_summary.h).
+// queries of the resident results: the kernels of xm_summary.h), xm_capi_refs.h (the queries of the resident results counted per combination of contigs: the
+// kernels of xm_refs.h).
 // The big kernels are objects of their own, reached through launch functions: the lane-per-read align kernel is xm_align_kernel.hip (xmAlignLaunch,
 // xm_kernel_common.h), the wave-per-read kernels are xm_wave_kernel.hip (xmWaveLaunch, xm_kernel_args.h), the index build on the device is
 // xm_index_device.hip.  This unit uses the host-side pieces of the shared headers only (makeCaps, searchPoolBytes, the pass planner's sizes):
@@ -27,6 +28,7 @@
 #include "xm_fastq.h"
 #include "xm_sam.h"
 #include "xm_summary.h"
+#include "xm_refs.h"
 #include "xm_memo.h"
 #include "xm_conf_table.h"
 #include "xm_device_rt.h"
@@ -288,6 +290,20 @@ struct SummaryStage {
   ~SummaryStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
+// What xm_refs_count_last works with (xm_refs.h; xm_capi_refs.h): the table of the sets' fingerprints (keys, the lowest query and the count per slot); per query
+// its slot, whether it is its slot's representative, and what it leaves to the host (a flag and its sequence alignments); the scan's block sums and the three
+// offset arrays (dSpare: the scan's second output of the flags); the control words; the records and the left-over contigs with their starts, which only
+// grow; the call's events on the context's stream.  Nothing is allocated before the first call.
+struct RefsStage {
+  DevBuf<unsigned long long> dKeys, dReps, dCounts, dCtl;
+  DevBuf<int32_t> dSlotOf, dIsRep, dLeftLen, dLeftFlag, dLeft;
+  DevBuf<long long> dBlockA, dBlockB;
+  DevBuf<int64_t> dOff, dLoff, dLqoff, dSpare, dLeftStart;
+  DevBuf<RefsRecord> dRecords;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // claim, verify and offsets | (host sizes the arrays) | gather | arrays down
+  ~RefsStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 // What the lane-per-read passes of a call work with besides the batch and the result stage: the work lists the lanes file unfinished reads into and the
 // counts of those lists (PassLists, PassCtl: xm_kernel_common.h), the device counters, and the scratch - the lanes' arenas behind the pool of saved
 // regions (HandOver), a wave's search nodes, the pool of search buffers (SearchPool).  Kept across calls; which list a pass reads is xm_pass_plan.h's.
@@ -522,6 +538,7 @@ struct xm_index {
   FastqStage fastq;            // xm_batch_stage_fastq's buffers (under stageMu)
   SamStage sam;                // xm_sam_format_last's buffers (under mu)
   SummaryStage summary;        // xm_summary_last's buffers (under mu)
+  RefsStage refs;              // xm_refs_count_last's buffers (under mu)
   bool resultCopy = true;      // xm_context_set_result_copy: an align call copies its four streams to the host (false: they stay in HBM, and the result has none)
 
   void initContext() {  // stream and events of this context (the device tables exist)
@@ -1066,7 +1083,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 10; }
+int32_t xm_abi_version(void) { return 11; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();
@@ -1593,5 +1610,6 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 #include "xm_capi_pileup.h"
 #include "xm_capi_sam.h"
 #include "xm_capi_summary.h"
+#include "xm_capi_refs.h"
 #include "xm_capi_test.h"
 #include "xm_capi_fastq.h"

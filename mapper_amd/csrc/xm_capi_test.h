@@ -188,6 +188,39 @@ int xm_test_summary(int32_t device, int64_t num_queries, int32_t num_contigs, co
   } catch (std::exception& e) { return fail(std::string("xm_test_summary: ") + e.what()); }
 }
 
+// Test-only entry (tests/test_gpu_refs_count.py): xm_refs_count_last's kernels over host-given result streams - no index and no alignment -, with the sets'
+// fingerprints cut to fingerprint_bits bits (64 and more: whole).  The host checks what xm_test_summary checks.
+int xm_test_refs_count(int32_t device, int64_t num_queries, int32_t num_contigs, const int32_t* ints, const double* dbls, const int64_t* int_off, const int64_t* dbl_off,
+                       int32_t fingerprint_bits, xm_refs_count** out) {
+  if (!out) return fail("xm_test_refs_count: null argument");
+  *out = nullptr;
+  try {
+    const int64_t nq = num_queries;
+    if (nq < 0 || num_contigs < 0) throw std::runtime_error("negative size");
+    if (fingerprint_bits < 1) throw std::runtime_error("fingerprint_bits must be >= 1");
+    if (nq > 0 && (!int_off || !dbl_off)) throw std::runtime_error("null array");
+    if (nq > 0 && (int_off[0] != 0 || dbl_off[0] != 0)) throw std::runtime_error("stream offsets must start at 0");
+    for (int64_t q = 0; q < nq; q++) if (int_off[q + 1] < int_off[q] || dbl_off[q + 1] < dbl_off[q]) throw std::runtime_error("stream offsets fall");
+    const size_t nInts = nq ? (size_t)int_off[nq] : 0, nDbls = nq ? (size_t)dbl_off[nq] : 0;
+    if ((nInts && !ints) || (nDbls && !dbls)) throw std::runtime_error("null array");
+    const int bits = fingerprint_bits > 64 ? 64 : fingerprint_bits;
+    RefsStage g;
+    if (nq == 0) { *out = &refsRun(g, xm::SummaryStreams{nullptr, nullptr, nullptr, nullptr, num_contigs}, 0, bits, nullptr)->pub; return 0; }
+    if (device >= 0) HIP_CHECK(hipSetDevice(device));
+    DevBuf<int32_t> dInts;
+    DevBuf<double> dDbls;
+    DevBuf<int64_t> dIntOff, dDblOff;
+    dInts.ensure(nInts); dDbls.ensure(nDbls); dIntOff.ensure((size_t)nq + 1); dDblOff.ensure((size_t)nq + 1);
+    if (nInts) HIP_CHECK(hipMemcpy(dInts.p, ints, sizeof(int32_t) * nInts, hipMemcpyHostToDevice));
+    if (nDbls) HIP_CHECK(hipMemcpy(dDbls.p, dbls, sizeof(double) * nDbls, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dIntOff.p, int_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dDblOff.p, dbl_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    RefsBox* box = refsRun(g, xm::SummaryStreams{dInts.p, dDbls.p, dIntOff.p, dDblOff.p, num_contigs}, nq, bits, nullptr);
+    *out = &box->pub;
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_test_refs_count: ") + e.what()); }
+}
+
 // Test-only entry (tests/test_gpu_pileup_text.py): the three stages of xm_pileup_text.h - what xm_pileup_add_last runs with kept text - over host-given events
 // and batch arrays; no index, no alignment, no pile-up kernel (so the total is read from the offsets).  The host checks what the kernels take on trust from
 // the library's own stages: mates inside codes.  The events may hold anything.  launches: kernels launched (4 without text to gather, 5 with; 0 for no events).

@@ -98,6 +98,10 @@ class MultiGpuDatabase:
         """ReferenceDatabase.summary_last of replica `replica` (align_stream's on_aligned hook names it), on that replica's thread."""
         return self.replicas[replica].summary_last(want_unaligned)
 
+    def refs_count_last(self, replica, raw=False):
+        """ReferenceDatabase.refs_count_last of replica `replica` (align_stream's on_aligned hook names it), on that replica's thread."""
+        return self.replicas[replica].refs_count_last(raw)
+
     def close(self):
         for r in self.replicas:
             r.close()
