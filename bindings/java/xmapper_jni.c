@@ -19,12 +19,13 @@
 #include <string.h>
 #include "xmapper_hip.h"
 
-#define XMJ_ABI_VERSION 11 /* include/xmapper_hip.h: 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes (not used here: the Java host parses its own queries);
+#define XMJ_ABI_VERSION 12 /* include/xmapper_hip.h: 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes (not used here: the Java host parses its own queries);
                             * 7 = xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (not used here either: the Java host keeps its own writers);
                             * 8 = xm_batch_unstage (not used here: the shim aligns batch by batch);
                             * 9 = xm_pileup_keep_insert_text, xm_pileup_event_text (not used here: the Java host's MatchDatabase holds its own queries);
                             * 10 = xm_context_set_result_copy, xm_summary_last, xm_summary_free (not used here: the shim hands the four streams to the Java host, which counts its own statistics);
-                            * 11 = xm_refs_count_last, xm_refs_count_free (not used here: the Java host's ReferenceAlignmentCounter counts from its own alignments) */
+                            * 11 = xm_refs_count_last, xm_refs_count_free (not used here: the Java host's ReferenceAlignmentCounter counts from its own alignments);
+                            * 12 = xm_fastq_text.reserved becomes split_past_size (not used here: the Java host's SequenceSplitter cuts its own queries) */
 
 /* ---------------------------------------------------------------- part 1: marshalling on plain C arrays ---------------------------------------- */
 

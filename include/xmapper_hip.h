@@ -126,7 +126,8 @@ const char* xm_build_stamp(void);
  * xm_memory_free, xm_result.reserved carries the wait for a memory; 6 = xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7 = xm_sam_set_contigs,
  * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles); 8 = xm_batch_unstage; 9 = xm_pileup_keep_insert_text, xm_pileup_event_text (and the test-only
  * xm_test_pileup_text); 10 = xm_context_set_result_copy, xm_summary_last, xm_summary_free (and the test-only xm_test_summary);
- * 11 = xm_refs_count_last, xm_refs_count_free (and the test-only xm_test_refs_count).  A binding checks it once
+ * 11 = xm_refs_count_last, xm_refs_count_free (and the test-only xm_test_refs_count); 12 = xm_fastq_text.reserved becomes split_past_size (same layout; 0 is
+ * what every caller passed).  A binding checks it once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -262,7 +263,11 @@ typedef struct xm_fastq_text {
   const char* text1; int64_t bytes1; int64_t records1;
   const char* text2; int64_t bytes2; int64_t records2;   /* NULL / 0 / 0: single reads */
   double expected_inner, deviation;                       /* of every pair; single queries get 0 and 1 */
-  int32_t keep_qualities, reserved;
+  int32_t keep_qualities;
+  int32_t split_past_size;   /* (ABI version 12; was `reserved`, which callers set to 0)  0: a record is a query.  1 .. 30000: --split-queries-past-size on the GPU
+                              * (SequenceSplitter.java:9-38) - the trimmed sequence of `length` bases becomes (length - 1) / split_past_size + 1 queries, section k
+                              * being bases [length * k / n, length * (k + 1) / n) under the record's name, without quality (has_qual 0), its second slot
+                              * the padding mate; a record may then be longer than 30000 bases.  Single reads only. */
 } xm_fastq_text;
 /* Host copies of what was built, in page-locked buffers of the library's pool: the fields of xmio_batch (include/xmapper_hostio.h) up to `store`, in its
  * order and with its meaning, so that the harness's writers read it as they read a batch of the host reader; then the times of the call's three parts. */
@@ -275,7 +280,9 @@ typedef struct xm_fastq_batch {
 /* Does what xm_batch_stage does (same stream, same buffers; xm_batch_commit follows as usual) and returns the arrays.  The device takes the strict form only:
  * every record is four lines, the first starts with '@', the sequence has 1 .. 30000 bases, and records1 / records2 are the records the texts hold (a last
  * line without its newline is a line).  Anything else fails the call with nothing staged; xm_last_error names the file (1 or 2), the 0-based record and
- * the reason.  A text may hold up to 1 GiB. */
+ * the reason.  A text may hold up to 1 GiB.  With split_past_size > 0 xm_fastq_batch.num_queries is the number of sections (the call waits for it once more,
+ * to size what it builds per query), the 30000-base limit holds for a section instead of a record, errors still name the record, and text2 != NULL, a
+ * negative size and one above 30000 are refused in the same way. */
 int xm_batch_stage_fastq(xm_index* index, const xm_fastq_text* text, xm_fastq_batch** out);
 void xm_fastq_batch_free(xm_fastq_batch* batch);
 /* Bytes of text per workgroup of the kernels that find the line ends (test hook: tests/test_gpu_fastq.py puts newlines on both sides of the edges it gives). */

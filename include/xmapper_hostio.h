@@ -61,13 +61,15 @@ void xmio_last_write_seconds(double* format_seconds, double* file_seconds);
 
 /* The query files cut into blocks of whole four-line FASTQ records, as text, for a parser that is not this library's (xm_batch_stage_fastq of
  * include/xmapper_hip.h builds the batch arrays from such a block on the GPU).  The cutter looks for line ends only: no base is translated and nothing is
- * looked up per base.  FASTA, multi-line records and --split-queries-past-size stay with xmio_open. */
+ * looked up per base.  FASTA and multi-line records stay with xmio_open; so does --split-queries-past-size unless the reader is opened with
+ * xmio_text_open_split, whose blocks go to a parser that cuts the sections (xm_fastq_text.split_past_size). */
 typedef struct xmio_text_reader xmio_text_reader;
 typedef struct xmio_text_block {
   const char* text1; int64_t bytes1; int64_t records1;
   int64_t longest1;          /* length of the longest sequence line (lines 1, 5, 9, ...) of text1 as it stands in the file: an upper bound of the longest mate */
   const char* text2; int64_t bytes2; int64_t records2; int64_t longest2;   /* NULL / 0 / 0 / 0 for a single file */
   void* store;               /* owner of the texts (xmio_text_block_free) */
+  int64_t num_queries;       /* (appended) the queries the block gives: records1, or - xmio_text_open_split - the sections of its records, exactly */
 } xmio_text_block;
 /* path2 != NULL: paired files cut in step, a block holds the same number of records of each.  Files may be gzip-compressed. */
 xmio_text_reader* xmio_text_open(const char* path1, const char* path2);
@@ -75,6 +77,12 @@ xmio_text_reader* xmio_text_open(const char* path1, const char* path2);
  * trailing empty lines are dropped (the last block may lack its final newline).  Returns 0, or -1 (xmio_last_error names the file and the line) when a file
  * ends inside a record or the files of a pair hold different numbers of records. */
 int xmio_text_next(xmio_text_reader* reader, int64_t max_queries, xmio_text_block** out);
+/* One file whose records will be cut into sections of at most split_past_size (1 .. 30000) bases by the parser (SequenceSplitter.java:9-38, as xmio_open's
+ * split_past_size does on the host).  A block is still whole records, but max_queries counts sections: per record the sequence line is trimmed at its ends
+ * (fastqTrim of mapper_amd/csrc/xm_fastq_rules.h) and gives (length - 1) / split_past_size + 1 of them; the block stops in front of the record that would
+ * pass max_queries and always takes at least one record, so a record of more sections than that is a block of its own.  longest1 is at most split_past_size.
+ * Unlike xmio_next, no record's sections straddle two blocks. */
+xmio_text_reader* xmio_text_open_split(const char* path, int32_t split_past_size);
 void xmio_text_block_free(xmio_text_block* block);
 void xmio_text_close(xmio_text_reader* reader);
 

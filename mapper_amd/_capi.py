@@ -43,7 +43,7 @@ class XmResult(C.Structure):
 class XmFastqText(C.Structure):
     """xm_fastq_text: a block of whole four-line FASTQ records as read from the file(s)."""
     _fields_ = [("text1", C.c_void_p), ("bytes1", C.c_int64), ("records1", C.c_int64), ("text2", C.c_void_p), ("bytes2", C.c_int64), ("records2", C.c_int64),
-                ("expected_inner", C.c_double), ("deviation", C.c_double), ("keep_qualities", C.c_int32), ("reserved", C.c_int32)]
+                ("expected_inner", C.c_double), ("deviation", C.c_double), ("keep_qualities", C.c_int32), ("split_past_size", C.c_int32)]
 
 
 class XmFastqBatch(C.Structure):
@@ -96,7 +96,7 @@ class XmTestPileupJob(C.Structure):
                 ("num_events", C.c_int64), ("events", C.c_void_p), ("query_base", C.c_int64)]
 
 
-ABI_VERSION = 11  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count
+ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved)
 
 
 class XmIndexInfo(C.Structure):

@@ -480,14 +480,21 @@ class ReferenceDatabase:
     def stage_fastq(self, block):
         """xm_batch_stage_fastq: the NEXT batch from FASTQ text (a hostio.TextBlock) - the text is copied to HBM and parsed there by kernels; the block then
         offers the arrays hostio.Batch offers (names and qualities included, for the writers).  A text that is not of the strict form (four lines a record, '@'
-        headers, 1 .. 30000 bases) is a hostio.StrictFormError (a ValueError) that names file, record and reason, and nothing is staged."""
+        headers, 1 .. 30000 bases) is a hostio.StrictFormError (a ValueError) that names file, record and reason, and nothing is staged.  A block cut with a
+        split size (hostio.read_text_blocks(split=...)) is staged with it: the kernels cut every record into its sections, each a query, and a record may be
+        longer than 30000 bases; a query count that is not the cutter's is an internal error."""
         if block._text is None:
             raise ValueError("the block's text is gone: it has been staged or closed")
         t = block._text.contents
-        text = _capi.XmFastqText(t.text1, t.bytes1, t.records1, t.text2, t.bytes2, t.records2, block.pair_spacing[0], block.pair_spacing[1], 1 if block.keep_qualities else 0, 0)
+        text = _capi.XmFastqText(t.text1, t.bytes1, t.records1, t.text2, t.bytes2, t.records2, block.pair_spacing[0], block.pair_spacing[1], 1 if block.keep_qualities else 0, block.split)
         out = C.POINTER(_capi.XmFastqBatch)()
         if self._L.xm_batch_stage_fastq(self._h, C.byref(text), C.byref(out)):
             raise hostio.StrictFormError(self._L.xm_last_error().decode())
+        if int(out.contents.num_queries) != block.num_queries:  # (the cutter and the kernels count a split block's sections by the same rule)
+            n = int(out.contents.num_queries)
+            self._L.xm_fastq_batch_free(out)
+            self._L.xm_batch_unstage(self._h)
+            raise RuntimeError("xm_batch_stage_fastq: internal: the kernels built %d queries of a block the cutter counted %d in" % (n, block.num_queries))
         block.attach(out, self._L.xm_fastq_batch_free)
         return block
 

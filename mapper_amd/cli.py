@@ -17,8 +17,12 @@ outputs are the same, and one line on stderr says how many queries were served a
 it has aligned in that much HBM and serves byte-identical queries of its later batches from there: the same cache across batches; same outputs, one line on
 stderr), and --remember-queries-per-gpu <MiB> (one such memory per GPU, which all its contexts share and which keeps remembering when it is full; not
 together with --remember-queries), and --parse-on-gpu (the FASTQ files go to the GPU as text and are parsed there, api.ReferenceDatabase.stage_fastq: same outputs;
-four-line FASTQ records only, so a file the host reader takes may be refused with a message that says where; not with --per-object or a split size; a job
-whose output needs objects - --out-refs-map-count without --count-refs-on-gpu, needs_objects - parses on the host all the same),
+four-line FASTQ records only, so a file the host reader takes may be refused with a message that says where; not with --per-object, and with a split size
+only beside --split-on-gpu; a job whose output needs objects - --out-refs-map-count without --count-refs-on-gpu, needs_objects - parses on the host all the
+same), --split-on-gpu (with --parse-on-gpu and --split-queries-past-size: the kernels that parse the text also cut every record into its sections,
+hostio.read_text_blocks(split=...), so a long-read job goes from FASTQ text to SAM text without the host translating or cutting a base; a record's sections
+stay in one batch, where the host reader lets them straddle two; SAM, unaligned file, refs count and statistics are the same bytes at any --batch-size, the
+mutations file where both paths cut their batches at the same places),
 --format-on-gpu (the SAM records are formatted on the GPU while a batch and its results are resident, api.ReferenceDatabase.format_sam_last, and the host
 only writes the bytes: same outputs; --out-unaligned stays with the host; not with --per-object, --out-mutations or --out-refs-map-count; nothing to do
 without --out-sam), --results-on-gpu (the align calls leave their result streams in HBM and copy none of them to the host,
@@ -210,6 +214,8 @@ def parse_args(argv):
             o["per_object"] = True
         elif a == "--parse-on-gpu":  # (not a Mapper flag) the query files are cut into blocks of whole FASTQ records on the host and parsed on the GPU (api.ReferenceDatabase.stage_fastq)
             o["parse_on_gpu"] = True
+        elif a == "--split-on-gpu":  # (not a Mapper flag) with --parse-on-gpu, the sections of --split-queries-past-size are cut on the GPU too (xm_fastq_text.split_past_size)
+            o["split_on_gpu"] = True
         elif a == "--format-on-gpu":  # (not a Mapper flag) the SAM records are formatted on the GPU from the result streams while the batch is resident (api.ReferenceDatabase.format_sam_last)
             o["format_on_gpu"] = True
         elif a == "--results-on-gpu":  # (not a Mapper flag) the result streams stay in HBM; the host gets the SAM text and a summary (api.ReferenceDatabase.set_result_copy, summary_last)
@@ -233,8 +239,15 @@ def parse_args(argv):
         i += 1
     if o.get("parse_on_gpu") and o.get("per_object"):
         raise UsageError("--parse-on-gpu and --per-object exclude each other (the per-object path reads the queries into Python objects)")
-    if o.get("parse_on_gpu") and any(split > 0 for _, split in o["queries"]):
+    if o.get("parse_on_gpu") and any(split > 0 for _, split in o["queries"]) and not o.get("split_on_gpu"):
         raise UsageError("--parse-on-gpu is not supported with --split-queries-past-size (the sections are cut by the host reader)")
+    if o.get("split_on_gpu"):
+        if not o.get("parse_on_gpu"):
+            raise UsageError("--split-on-gpu needs --parse-on-gpu (the sections are cut by the kernels that parse the FASTQ text)")
+        if not any(split > 0 for _, split in o["queries"]):
+            raise UsageError("--split-on-gpu has nothing to do without --split-queries-past-size in front of --queries")
+        if any(split > 30000 for _, split in o["queries"]):
+            raise UsageError("--split-on-gpu takes a --split-queries-past-size of at most 30000 (a section is a mate)")
     if o.get("count_refs_on_gpu"):
         if o.get("per_object"):
             raise UsageError("--count-refs-on-gpu and --per-object exclude each other (the per-object path counts from alignments decoded on the host)")
@@ -375,8 +388,8 @@ def native_source(o, batch_size, job):
 
     def read():
         if on_gpu:
-            for path, _ in o["queries"]:
-                yield from hostio.read_text_blocks(path, None, batch_size, keep_qualities=keep_qual)
+            for path, split in o["queries"]:
+                yield from hostio.read_text_blocks(path, None, batch_size, keep_qualities=keep_qual, split=split)  # (a split size: --split-on-gpu, parse_args)
             for left, right, expected, deviation in o["paired"]:
                 yield from hostio.read_text_blocks(left, right, batch_size, keep_qualities=keep_qual, expected_inner=expected, deviation=deviation)
             return

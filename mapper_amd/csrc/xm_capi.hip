@@ -262,7 +262,12 @@ struct FastqStage {
   DevBuf<int64_t> dQualOff;
   DevBuf<uint8_t> dHasQual;
   DevBuf<char> dQuals;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // on the GPU's staging stream: text up | stages 1-3 | (host sizes the arrays) | stage 4 | arrays down
+  DevBuf<FastqMate> dRecs;        // the split form (split_past_size > 0): the fields of every record, its section count, its first query, the scan's block sums
+  DevBuf<int32_t> dRecCount;
+  DevBuf<int64_t> dRecFirst;
+  DevBuf<long long> dRecBlockSums;
+  // on the GPU's staging stream: text up | stages 1-3 | (host sizes the arrays) | stage 4 | arrays down; the split form also [6] behind stage 2b and [7] in front of 2c (the host sizes the slots between them)
+  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   ~FastqStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
@@ -1083,7 +1088,7 @@ const char* xm_last_error(void) { return g_error.c_str(); }
 #define XM_BUILD_STAMP "unstamped"
 #endif
 const char* xm_build_stamp(void) { return XM_BUILD_STAMP; }
-int32_t xm_abi_version(void) { return 11; }
+int32_t xm_abi_version(void) { return 12; }
 int64_t xm_pinned_host_bytes(int64_t* high_water) {
   if (high_water) *high_water = (int64_t)g_pinned->highWater.load();
   return (int64_t)g_pinned->allocatedBytes.load();

@@ -21,9 +21,8 @@ void freeFastqBox(FastqBox* box) {
 
 std::string fastqWhere(int file, long long record) { return "file " + std::to_string(file + 1) + " record " + std::to_string(record) + ": "; }
 
-// the stages of xm_fastq.h on stream s, up to the totals (queued; the caller waits for ev[2])
-void fastqParse(FastqStage& f, DeviceBatch& d, const xm_fastq_text* t, const FastqText texts[2], int64_t nq, bool paired, bool keepQual, hipStream_t s) {
-  const long long slots = 2 * nq;
+// the text up and stage 1 of xm_fastq.h (the line ends) on stream s
+void fastqLines(FastqStage& f, const xm_fastq_text* t, const FastqText texts[2], bool paired, hipStream_t s) {
   FastqCtl ctl0;
   memset(&ctl0, 0, sizeof(ctl0));
   ctl0.firstError = XM_FASTQ_NO_ERROR;
@@ -38,8 +37,10 @@ void fastqParse(FastqStage& f, DeviceBatch& d, const xm_fastq_text* t, const Fas
     hipLaunchKernelGGL(xm_fastq_tiles_kernel, dim3(1), dim3(256), 0, s, texts[k], nTiles, k, f.dCtl.p);
     hipLaunchKernelGGL(xm_fastq_ends_kernel, dim3((unsigned)nTiles), dim3(256), 0, s, texts[k]);
   }
-  FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, f.dHasQual.p, f.dCtl.p};
-  hipLaunchKernelGGL(xm_fastq_fields_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, texts[0], texts[1], (long long)nq, paired ? 1 : 0, t->expected_inner, t->deviation, out);
+}
+
+// stage 3 (the offsets of the mate slots, the totals) on stream s (queued; the caller waits for ev[2])
+void fastqOffsets(FastqStage& f, DeviceBatch& d, long long slots, bool keepQual, hipStream_t s) {
   const long long nBlocks = (slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
   int64_t* qualOff = keepQual ? f.dQualOff.p : nullptr;
   hipLaunchKernelGGL(xm_fastq_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, f.dBlockSums.p);
@@ -48,6 +49,46 @@ void fastqParse(FastqStage& f, DeviceBatch& d, const xm_fastq_text* t, const Fas
                      d.nameOff.p, qualOff);
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipEventRecord(f.ev[2], s));
+}
+
+// the stages of xm_fastq.h on stream s, up to the totals (queued; the caller waits for ev[2])
+void fastqParse(FastqStage& f, DeviceBatch& d, const xm_fastq_text* t, const FastqText texts[2], int64_t nq, bool paired, bool keepQual, hipStream_t s) {
+  const long long slots = 2 * nq;
+  fastqLines(f, t, texts, paired, s);
+  FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, f.dHasQual.p, f.dCtl.p};
+  hipLaunchKernelGGL(xm_fastq_fields_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, texts[0], texts[1], (long long)nq, paired ? 1 : 0, t->expected_inner, t->deviation, out);
+  fastqOffsets(f, d, slots, keepQual, s);
+}
+
+// the split form: the text up, stage 1, stages 2a and 2b (the records and their first queries) on stream s; the caller reads FastqCtl::sections behind ev[6]
+void fastqSplitRecords(FastqStage& f, const xm_fastq_text* t, const FastqText texts[2], hipStream_t s) {
+  const long long records = texts[0].records;
+  fastqLines(f, t, texts, false, s);
+  hipLaunchKernelGGL(xm_fastq_split_records_kernel, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, s, texts[0], (long long)t->split_past_size, f.dRecs.p, f.dRecCount.p, f.dCtl.p);
+  const long long nBlocks = (records + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
+  hipLaunchKernelGGL(xm_fastq_split_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, records, (const int32_t*)f.dRecCount.p, f.dRecBlockSums.p);
+  hipLaunchKernelGGL(xm_fastq_split_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, records, f.dRecBlockSums.p, f.dRecFirst.p, f.dCtl.p);
+  hipLaunchKernelGGL(xm_fastq_split_first_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, records, (const int32_t*)f.dRecCount.p, (const long long*)f.dRecBlockSums.p, f.dRecFirst.p);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(f.ev[6], s));
+}
+
+// the split form: stage 2c (a lane per section) and stage 3 over the section slots, which the caller has sized for nq queries
+void fastqSplitSections(FastqStage& f, DeviceBatch& d, long long records, int64_t nq, bool keepQual, hipStream_t s) {
+  HIP_CHECK(hipEventRecord(f.ev[7], s));
+  FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, f.dHasQual.p, f.dCtl.p};
+  hipLaunchKernelGGL(xm_fastq_split_sections_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, records, (const FastqMate*)f.dRecs.p, (const int64_t*)f.dRecFirst.p, out);
+  fastqOffsets(f, d, 2 * nq, keepQual, s);
+}
+
+// what the host reads of FastqCtl behind stage 2: a record that is not of the strict form comes first (an empty line between two records also makes the line count wrong)
+void fastqCheckText(const FastqCtl& ctl, const FastqText texts[2], bool paired) {
+  if (ctl.firstError != XM_FASTQ_NO_ERROR)
+    throw std::runtime_error(fastqWhere((int)(ctl.firstError >> 48), (long long)((ctl.firstError >> 8) & 0xFFFFFFFFFFull)) + fastqErrorText((int)(ctl.firstError & 0xFF)));
+  for (int k = 0; k < (paired ? 2 : 1); k++)
+    if (ctl.lines[k] != 4 * texts[k].records)
+      throw std::runtime_error(fastqWhere(k, std::min(ctl.lines[k] / 4, texts[k].records)) + fastqErrorText(XM_FQ_LINE_COUNT) + " (" + std::to_string(ctl.lines[k]) + " lines, " +
+                               std::to_string(texts[k].records) + " records announced)");
 }
 
 }  // namespace
@@ -75,13 +116,15 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
                 std::to_string(t->records2) + ")");
   }
   if (t->records1 > (1ll << 28)) return fail("xm_batch_stage_fastq: file 1 record 0: too many records for one text");
+  const int split = t->split_past_size;
+  if (split < 0) return fail("xm_batch_stage_fastq: file 1 record 0: split_past_size must be >= 0");
+  if (split > 0 && paired) return fail("xm_batch_stage_fastq: file 2 record 0: pairs are not cut into sections (split_past_size is for single reads, as --split-queries-past-size is)");
+  if (split > XM_FASTQ_MAX_MATE) return fail("xm_batch_stage_fastq: file 1 record 0: split_past_size out of range (0..30000: a section is a mate)");
   FastqBox* box = nullptr;
   try {
     std::lock_guard<std::mutex> stageLock(idx->stageMu);
     DeviceBatch& d = idx->staged;
     FastqStage& f = idx->fastq;
-    const int64_t nq = t->records1;
-    const long long slots = 2 * nq;
     d.nq = -1;
     d.h2dMs = 0;
     d.hasNames = false;
@@ -100,7 +143,27 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
       f.dTileCount[k].ensure((size_t)((bytes + XM_FASTQ_TILE_BYTES - 1) / XM_FASTQ_TILE_BYTES));
       texts[k] = FastqText{f.dText[k].p, bytes, records, f.dLineEnd[k].p, f.dTileCount[k].p};
     }
-    f.dMates.ensure((size_t)slots); f.dHasQual.ensure((size_t)slots); f.dCtl.ensure(1);
+    f.dCtl.ensure(1);
+    FastqCtl ctl;
+    int64_t nq = t->records1;
+    if (split > 0) {
+      // the split form: the records' fields and the scan of their section counts first - the query count sizes everything per slot, so the host waits for it
+      // (one wait more than without a split: three in the call)
+      const long long records = t->records1;
+      f.dRecs.ensure((size_t)records); f.dRecCount.ensure((size_t)records); f.dRecFirst.ensure((size_t)records + 1);
+      f.dRecBlockSums.ensure((size_t)((records + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK));
+      idx->dt->onStagingStream([&](hipStream_t s) {
+        fastqSplitRecords(f, t, texts, s);
+        HIP_CHECK(hipMemcpyAsync(&ctl, f.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+      });
+      fastqCheckText(ctl, texts, false);
+      nq = ctl.sections;
+      if (nq < records || nq > t->bytes1) throw std::runtime_error("internal: " + std::to_string(nq) + " sections of " + std::to_string(records) + " records");
+      if (nq > (1ll << 28)) throw std::runtime_error(fastqWhere(0, 0) + "too many sections for one text (" + std::to_string(nq) + ")");
+    }
+    const long long slots = 2 * nq;
+    f.dMates.ensure((size_t)slots); f.dHasQual.ensure((size_t)slots);
     f.dBlockSums.ensure((size_t)(3 * ((slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK)));
     d.nameOff.ensure((size_t)slots + 1);
     if (keepQual) f.dQualOff.ensure((size_t)slots + 1);
@@ -115,20 +178,15 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
       b.qual_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[7]);
       b.has_qual = (uint8_t*)g_pinned->get((size_t)slots, &box->bytes[8]);
     }
-    // text up, stages 1 to 3, the control words down
-    FastqCtl ctl;
+    // text up, stages 1 to 3 (with a split: stages 2c and 3), the control words down
     idx->dt->onStagingStream([&](hipStream_t s) {
-      fastqParse(f, d, t, texts, nq, paired, keepQual, s);
+      if (split > 0) fastqSplitSections(f, d, t->records1, nq, keepQual, s);
+      else fastqParse(f, d, t, texts, nq, paired, keepQual, s);
       HIP_CHECK(hipMemcpyAsync(&ctl, f.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));  // (under the stream's lock: the copy lands in this frame)
     });
-    // (a record that is not of the strict form comes first: an empty line between two records also makes the line count wrong)
-    if (ctl.firstError != XM_FASTQ_NO_ERROR)
-      throw std::runtime_error(fastqWhere((int)(ctl.firstError >> 48), (long long)((ctl.firstError >> 8) & 0xFFFFFFFFFFull)) + fastqErrorText((int)(ctl.firstError & 0xFF)));
-    for (int k = 0; k < (paired ? 2 : 1); k++)
-      if (ctl.lines[k] != 4 * texts[k].records)
-        throw std::runtime_error(fastqWhere(k, std::min(ctl.lines[k] / 4, texts[k].records)) + fastqErrorText(XM_FQ_LINE_COUNT) + " (" + std::to_string(ctl.lines[k]) + " lines, " +
-                                 std::to_string(texts[k].records) + " records announced)");
+    if (split == 0) fastqCheckText(ctl, texts, paired);
+    else if (ctl.sections != nq) throw std::runtime_error("internal: the section count changed between two launches");
     // the arrays the totals size, stage 4, everything down
     const size_t nCodes = (size_t)ctl.totals[0], nNames = (size_t)ctl.totals[1], nQuals = (size_t)ctl.totals[2];
     d.codes.ensure(nCodes);
@@ -161,7 +219,12 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     HIP_CHECK(hipEventSynchronize(f.ev[5]));
     float up = 0, parse = 0, gather = 0, down = 0;
     HIP_CHECK(hipEventElapsedTime(&up, f.ev[0], f.ev[1]));
-    HIP_CHECK(hipEventElapsedTime(&parse, f.ev[1], f.ev[2]));
+    if (split > 0) {  // (not the time the host took between the two to size the slots)
+      float records = 0;
+      HIP_CHECK(hipEventElapsedTime(&records, f.ev[1], f.ev[6]));
+      HIP_CHECK(hipEventElapsedTime(&parse, f.ev[7], f.ev[2]));
+      parse += records;
+    } else HIP_CHECK(hipEventElapsedTime(&parse, f.ev[1], f.ev[2]));
     HIP_CHECK(hipEventElapsedTime(&gather, f.ev[3], f.ev[4]));
     HIP_CHECK(hipEventElapsedTime(&down, f.ev[4], f.ev[5]));
     b.h2d_ms = up; b.kernel_ms = (double)parse + gather; b.d2h_ms = down;

@@ -8,6 +8,7 @@
 //                 xm_fastq_ends_kernel     the tile's lanes again: every newline writes its position to lineEnd[its line index]
 //   2 fields      xm_fastq_fields_kernel   a lane per mate slot: the four line bounds of its record -> name, sequence, quality (fastqRecord); the first
 //                                          record that is not of the strict form is kept with atomicMin on (file, record)
+//                 (with a split size: 2a-2c below - records, the scan of their section counts, a lane per section; stages 3 and 4 then see section slots)
 //   3 offsets     xm_fastq_sums_kernel, xm_fastq_blocks_kernel, xm_fastq_offsets_kernel
 //                                          exclusive scans of the sequence, name and quality lengths in batch order (the three-kernel scan of
 //                                          xm_result_stage.h with three values); the host reads the totals to size codes, names, quals
@@ -32,6 +33,7 @@ struct FastqCtl {
   unsigned long long firstError;  // XM_FASTQ_NO_ERROR, or (file << 48) | (record << 8) | FastqError of the lowest (file, record) that is not of the strict form
   long long lines[2];             // lines found in each text
   long long totals[3];            // bases, name bytes, quality bytes of the batch
+  long long sections;             // the split form: queries of the batch (the sections of all its records), read by the host in front of stage 2c
 };
 
 struct FastqText {
@@ -186,6 +188,111 @@ __global__ void __launch_bounds__(256) xm_fastq_fields_kernel(FastqText t0, Fast
   out.mates[slot] = m;
   out.mateLength[slot] = m.seqLen;
   out.hasQual[slot] = padding ? 0 : 1;
+}
+
+// ---- the split form of stage 2 (split_past_size > 0, single reads): a record becomes its SequenceSplitter sections, each a query.  Three steps
+// in the place of xm_fastq_fields_kernel, each its own launch(es); the host reads the query count between the second and the third to size the slot arrays.
+//   2a records    xm_fastq_split_records_kernel   a lane per record: fastqRecordSplit -> the record's fields and how many sections it gives
+//   2b first      xm_fastq_split_sums_kernel, xm_fastq_split_blocks_kernel, xm_fastq_split_first_kernel
+//                                                 exclusive scan of the section counts: first[r] = the first query of record r, first[records] = ctl->sections
+//   2c sections   xm_fastq_split_sections_kernel  a lane per query: its record by binary search over first[], its section by fastqSectionMate -> both mate slots
+__global__ void __launch_bounds__(256) xm_fastq_split_records_kernel(FastqText t, long long split, FastqMate* recs, int32_t* counts, FastqCtl* ctl) {
+  const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= t.records) return;
+  FastqMate m;
+  m.nameAt = m.seqAt = m.qualAt = 0;
+  m.nameLen = m.seqLen = m.qualLen = 0;
+  m.file = 0;
+  int32_t count = 0;
+  const long long l = 4 * r;
+  const long long found = ctl->lines[0], kept = 4 * t.records + 1;  // (as xm_fastq_fields_kernel: only records whose four line ends were found and kept)
+  if (l + 3 < (found < kept ? found : kept)) {
+    const long long s0 = l == 0 ? 0 : (long long)t.lineEnd[l - 1] + 1;
+    const long long e0 = t.lineEnd[l], e1 = t.lineEnd[l + 1], e2 = t.lineEnd[l + 2], e3 = t.lineEnd[l + 3];
+    FastqFields f;
+    const int err = fastqRecordSplit(t.text, s0, e0, e0 + 1, e1, e2 + 1, e3, f);
+    if (err != XM_FQ_OK) atomicMin(&ctl->firstError, ((unsigned long long)r << 8) | (unsigned long long)err);
+    else {
+      m.nameAt = f.nameAt; m.seqAt = f.seqAt;
+      m.nameLen = (int32_t)f.nameLen; m.seqLen = (int32_t)f.seqLen;  // (a text holds at most 2^30 bytes)
+      count = (int32_t)fastqSectionCount(f.seqLen, split);
+    }
+  }
+  recs[r] = m;
+  counts[r] = count;
+}
+
+__global__ void __launch_bounds__(256) xm_fastq_split_sums_kernel(long long records, const int32_t* counts, long long* blockSums) {
+  __shared__ long long sh[256];
+  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
+  long long a = 0;
+  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < records) a += counts[base + k];
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int d = 128; d > 0; d >>= 1) {
+    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) blockSums[blockIdx.x] = sh[0];
+}
+
+__global__ void xm_fastq_split_blocks_kernel(long long nBlocks, long long records, long long* blockSums, int64_t* first, FastqCtl* ctl) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  long long run = 0;
+  for (long long i = 0; i < nBlocks; i++) { const long long x = blockSums[i]; blockSums[i] = run; run += x; }
+  first[records] = run;
+  ctl->sections = run;
+}
+
+__global__ void __launch_bounds__(256) xm_fastq_split_first_kernel(long long records, const int32_t* counts, const long long* blockSums, int64_t* first) {
+  __shared__ long long sh[256];
+  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
+  long long a = 0;
+  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < records) a += counts[base + k];
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int d = 1; d < 256; d <<= 1) {
+    long long x = 0;
+    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
+    __syncthreads();
+    sh[threadIdx.x] += x;
+    __syncthreads();
+  }
+  long long at = blockSums[blockIdx.x] + sh[threadIdx.x] - a;
+  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < records) { first[base + k] = at; at += counts[base + k]; }
+}
+
+// nq = first[records] as the host read it, which sized out's arrays: no lane writes behind them
+__global__ void __launch_bounds__(256) xm_fastq_split_sections_kernel(long long nq, long long records, const FastqMate* recs, const int64_t* first, FastqFieldsOut out) {
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq || records < 1 || first[records] != nq) return;
+  long long lo = 0, hi = records;  // first[lo] <= q < first[hi]: the last record that starts at or in front of q is the one that holds it (its count is > 0)
+  while (hi - lo > 1) {
+    const long long mid = (lo + hi) >> 1;
+    if (first[mid] <= q) lo = mid; else hi = mid;
+  }
+  const FastqMate rec = recs[lo];
+  FastqFields rf, sf;
+  rf.nameAt = rec.nameAt; rf.seqAt = rec.seqAt; rf.qualAt = rec.qualAt;
+  rf.nameLen = rec.nameLen; rf.seqLen = rec.seqLen; rf.qualLen = rec.qualLen;
+  fastqSectionMate(rf, first[lo + 1] - first[lo], q - first[lo], sf);
+  FastqMate m;
+  m.nameAt = sf.nameAt; m.seqAt = sf.seqAt; m.qualAt = sf.qualAt;
+  m.nameLen = (int32_t)sf.nameLen; m.seqLen = (int32_t)sf.seqLen; m.qualLen = 0;
+  m.file = 0;
+  FastqMate pad;
+  pad.nameAt = pad.seqAt = pad.qualAt = 0;
+  pad.nameLen = pad.seqLen = pad.qualLen = 0;
+  pad.file = 0;
+  out.mates[2 * q] = m;
+  out.mates[2 * q + 1] = pad;
+  out.mateCount[q] = 1;
+  out.expected[q] = 0.0;
+  out.deviation[q] = 1.0;
+  out.mateLength[2 * q] = m.seqLen;
+  out.mateLength[2 * q + 1] = 0;
+  out.hasQual[2 * q] = 0;
+  out.hasQual[2 * q + 1] = 0;
 }
 
 // ---- stage 3: the scans (xm_result_stage.h's, over three values; without qualities the third is 0)

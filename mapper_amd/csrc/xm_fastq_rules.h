@@ -107,6 +107,38 @@ XM_FASTQ_FN int fastqRecord(const char* text, long long s0, long long e0, long l
   return XM_FQ_OK;
 }
 
+// ---- the split form (--split-queries-past-size): a record of a single file becomes the sections SequenceSplitter.java:9-38 cuts it into, each a
+// query of its own.  The definitions are the split branch of xmio_next (xm_hostio.cpp) and cli.split_sections.
+// sections of a sequence of `length` >= 1 bases cut past `split` >= 1 bases
+XM_FASTQ_FN long long fastqSectionCount(long long length, long long split) { return (length - 1) / split + 1; }
+// section k of `count`: [length * k / count, length * (k + 1) / count) in 64-bit integers (length and count below 2^31: no product overflows)
+XM_FASTQ_FN void fastqSection(long long length, long long count, long long k, long long& start, long long& end) {
+  start = length * k / count;
+  end = length * (k + 1) / count;
+}
+// fastqRecord for a record that will be cut: its sequence - trimmed first, as the host reader trims it - may be as long as the text allows; every other
+// refusal stays.  What it leaves in f.qual* is not used: a section has no quality.
+XM_FASTQ_FN int fastqRecordSplit(const char* text, long long s0, long long e0, long long s1, long long e1, long long s3, long long e3, FastqFields& f) {
+  const int err = fastqRecord(text, s0, e0, s1, e1, s3, e3, f);  // (the length is the last thing it looks at: the fields of a record that is too long are complete)
+  return err == XM_FQ_TOO_LONG ? XM_FQ_OK : err;
+}
+// section k of the `count` of record `rec` as the mate of its query's first slot: the record's name, its slice of the sequence, no quality (has_qual 0);
+// the query's second slot is the padding mate
+XM_FASTQ_FN void fastqSectionMate(const FastqFields& rec, long long count, long long k, FastqFields& m) {
+  long long start, end;
+  fastqSection(rec.seqLen, count, k, start, end);
+  m.nameAt = rec.nameAt; m.nameLen = rec.nameLen;
+  m.seqAt = rec.seqAt + start; m.seqLen = end - start;
+  m.qualAt = rec.seqAt; m.qualLen = 0;
+}
+// the sequence line [start, end) of a record (end: the position of its '\n', or the text's size) -> its sections; 0 for a line that trims to nothing (the
+// parser refuses the record).  The cutter of libxm_hostio.so counts a block's queries with this: it looks at the ends of the line only.
+XM_FASTQ_FN long long fastqLineSections(const char* text, long long start, long long end, long long split) {
+  end = fastqLineEnd(text, start, end);
+  fastqTrim(text, start, end);
+  return end > start ? fastqSectionCount(end - start, split) : 0;
+}
+
 // Batch order: query i is record i of file 1 and, for pairs, record i of file 2 as its second mate; a query has two mate slots, 2i and 2i + 1.  The second
 // slot of a single query is the padding mate: offset 0, length 0, no name, no quality, has_qual 0.  Every real mate has has_qual 1.
 XM_FASTQ_FN long long fastqMateSlot(long long record, int file) { return 2 * record + file; }

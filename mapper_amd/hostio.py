@@ -106,7 +106,8 @@ class StrictFormError(ValueError):
 
 class XmioTextBlock(C.Structure):
     _fields_ = [("text1", C.c_void_p), ("bytes1", C.c_int64), ("records1", C.c_int64), ("longest1", C.c_int64),
-                ("text2", C.c_void_p), ("bytes2", C.c_int64), ("records2", C.c_int64), ("longest2", C.c_int64), ("store", C.c_void_p)]
+                ("text2", C.c_void_p), ("bytes2", C.c_int64), ("records2", C.c_int64), ("longest2", C.c_int64), ("store", C.c_void_p),
+                ("num_queries", C.c_int64)]
 
 
 def _text_lib():
@@ -114,6 +115,8 @@ def _text_lib():
     if not hasattr(L, "_xm_text_ready"):
         L.xmio_text_open.restype = C.c_void_p
         L.xmio_text_open.argtypes = [C.c_char_p, C.c_char_p]
+        L.xmio_text_open_split.restype = C.c_void_p
+        L.xmio_text_open_split.argtypes = [C.c_char_p, C.c_int32]
         L.xmio_text_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.POINTER(XmioTextBlock))]
         L.xmio_text_block_free.argtypes = [C.POINTER(XmioTextBlock)]
         L.xmio_text_block_free.restype = None
@@ -127,12 +130,14 @@ class TextBlock:
     """A block of whole four-line FASTQ records as text (one file's, or a pair's in step), for api.ReferenceDatabase.stage_fastq: the GPU parses it.  Before it
     is staged it offers num_queries and longest_line (an upper bound of the longest mate); once staged - the text is released then - it offers what Batch
     does: the six arrays(), mate_count / mate_offset / mate_length / codes, and a _ptr that Writer.write takes (an XmioBatch over the arrays the library
-    returned, store NULL).  block[k] is the mates of query k, as pileup.MatchDatabase.add_last(queries=block) reads them."""
+    returned, store NULL).  block[k] is the mates of query k, as pileup.MatchDatabase.add_last(queries=block) reads them.  split > 0: the block was cut
+    for a parser that cuts every record into sections of at most that many bases (read_text_blocks(split=...)); num_queries counts the sections."""
 
-    def __init__(self, ptr, keep_qualities, expected_inner, deviation):
+    def __init__(self, ptr, keep_qualities, expected_inner, deviation, split=0):
         self._text = ptr
         t = ptr.contents
-        self.num_queries = int(t.records1)
+        self.split = int(split)
+        self.num_queries = int(t.num_queries)
         self.paired = bool(t.text2)
         self.longest_line = int(max(t.longest1, t.longest2))
         self.keep_qualities = bool(keep_qualities)
@@ -153,7 +158,7 @@ class TextBlock:
         """stage_fastq's result: `staged` points to the library's xm_fastq_batch, free(staged) gives it back."""
         self._release_staged()
         f = staged.contents
-        n = self.num_queries
+        n = self.num_queries = int(f.num_queries)  # (with a split size: the sections the kernels cut; stage_fastq has held it against the cutter's count)
         self._staged, self._free = staged, free
         self._batch = XmioBatch(n, f.mate_count, f.mate_offset, f.mate_length, f.codes, f.codes_length, f.names, f.name_off, f.quals, f.qual_off, f.has_qual, None)
         self._ptr = C.pointer(self._batch)
@@ -202,10 +207,17 @@ class TextBlock:
             pass
 
 
-def read_text_blocks(path1, path2=None, batch_size=1_000_000, keep_qualities=False, expected_inner=0.0, deviation=1.0):
-    """Generator of TextBlock objects over a four-line FASTQ file (or a pair of them, cut in step): whole records as text, at most batch_size of them."""
+def read_text_blocks(path1, path2=None, batch_size=1_000_000, keep_qualities=False, expected_inner=0.0, deviation=1.0, split=0):
+    """Generator of TextBlock objects over a four-line FASTQ file (or a pair of them, cut in step): whole records as text, at most batch_size of them.
+    split > 0 (a single file): the records will be cut into sections of at most `split` bases by the parser, batch_size counts the sections, and a record
+    of more sections than that is a block of its own."""
     L = _text_lib()
-    r = L.xmio_text_open(os.fsencode(path1), os.fsencode(path2) if path2 else None)
+    if split and path2:
+        raise ValueError("a split size is for single reads (--paired-queries is not supported with --split-queries-past-size)")
+    if split:
+        r = L.xmio_text_open_split(os.fsencode(path1), int(split))
+    else:
+        r = L.xmio_text_open(os.fsencode(path1), os.fsencode(path2) if path2 else None)
     if not r:
         raise OSError(L.xmio_last_error().decode())
     r = C.c_void_p(r)
@@ -216,7 +228,7 @@ def read_text_blocks(path1, path2=None, batch_size=1_000_000, keep_qualities=Fal
                 raise StrictFormError(L.xmio_last_error().decode())
             if not ptr:
                 return
-            yield TextBlock(ptr, keep_qualities, expected_inner, deviation)
+            yield TextBlock(ptr, keep_qualities, expected_inner, deviation, split)
     finally:
         L.xmio_text_close(r)
 

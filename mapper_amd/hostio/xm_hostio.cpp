@@ -363,20 +363,23 @@ void giveBuffer(std::vector<char>& b) {
 // What the next block takes of a source: found without taking anything (the pair's other file may allow fewer records, then this is done again).
 struct Cut {
   int64_t records = 0, bytes = 0, longest = 0;
+  int64_t sections = 0;  // the queries the records give: `records`, or with a split size the sections of their sequence lines (xm::fastqLineSections)
   size_t consume = 0;   // bytes the source gives up: `bytes`, and at the end of the input the empty lines behind them
   bool atEnd = false;   // the source ended within this scan
 };
 
 // Whole records from src.pos on: line ends are found with memchr, every fourth ends a record.  Records of nothing but empty lines at the end of the
 // block are left for the next one, which drops them if the input ends there.  false: the file ends inside a record, or a record is larger than a block.
-bool scanBlock(Source& src, int64_t maxRecords, Cut& c) {
+// split > 0: maxRecords counts sections; the block stops in front of the record that would pass it, but takes at least one record with text.
+bool scanBlock(Source& src, int64_t maxRecords, Cut& c, int64_t split = 0) {
   c = Cut();
   size_t off = 0, lineAt[4] = {0, 0, 0, 0}, lineTo[4] = {0, 0, 0, 0};  // (relative to src.pos: fill() moves the buffer)
   int inRecord = 0;  // complete lines of the record in progress
   bool someText = false;
   int64_t records = 0, bytes = 0, longest = 0, fullRecords = 0, fullBytes = 0;  // all records so far | up to the last one that is more than empty lines
   int64_t bytesAtMax = 0;
-  while (records < maxRecords || fullRecords == 0) {  // (records of nothing but empty lines: on to the text behind them, or to the end, where they are dropped)
+  int64_t sections = 0, fullSections = 0;  // (without a split size: the records)
+  while (sections < maxRecords || fullRecords == 0) {  // (records of nothing but empty lines: on to the text behind them, or to the end, where they are dropped)
     const char* base = src.buf.data() + src.pos;
     const size_t avail = src.end - src.pos;
     const char* nl = off < avail ? (const char*)memchr(base + off, '\n', avail - off) : nullptr;
@@ -406,10 +409,12 @@ bool scanBlock(Source& src, int64_t maxRecords, Cut& c) {
       g_error = src.path + ": a FASTQ record of more than 1 GiB at line " + std::to_string(src.line + 1);
       return false;
     }
-    records++; bytes = (int64_t)off;
+    const int64_t ns = split > 0 ? (int64_t)xm::fastqLineSections(base, (long long)lineAt[1], (long long)lineTo[1], (long long)split) : 1;
+    if (split > 0 && fullRecords > 0 && sections + ns > maxRecords) break;  // (the record stays for the next block)
+    records++; bytes = (int64_t)off; sections += ns;
     if (records == maxRecords) bytesAtMax = bytes;
     longest = std::max(longest, (int64_t)(lineTo[1] - lineAt[1]));
-    if (someText) { fullRecords = records; fullBytes = bytes; }
+    if (someText) { fullRecords = records; fullBytes = bytes; fullSections = sections; }
     inRecord = 0; someText = false;
   }
   if (c.atEnd) {
@@ -419,16 +424,23 @@ bool scanBlock(Source& src, int64_t maxRecords, Cut& c) {
     if (inRecord < 4 && off < avail) { lineAt[n] = off; lineTo[n] = avail; n++; }  // a last line without its newline
     while (n > 0 && xm::fastqEmptyLine(base, (long long)lineAt[n - 1], (long long)lineTo[n - 1])) n--;  // trailing empty lines are dropped
     if (n == 4) {  // (three lines and the one without newline)
+      const int64_t ns = split > 0 ? (int64_t)xm::fastqLineSections(base, (long long)lineAt[1], (long long)lineTo[1], (long long)split) : 1;
       if ((int64_t)avail > kTextBlockLimit && records > 0) { c.atEnd = false; }
-      else { records++; bytes = (int64_t)avail; longest = std::max(longest, (int64_t)(lineTo[1] - lineAt[1])); fullRecords = records; fullBytes = bytes; }
+      else if (split > 0 && fullRecords > 0 && sections + ns > maxRecords) { c.atEnd = false; }  // (the next block takes it)
+      else {
+        records++; bytes = (int64_t)avail; sections += ns; longest = std::max(longest, (int64_t)(lineTo[1] - lineAt[1]));
+        fullRecords = records; fullBytes = bytes; fullSections = sections;
+      }
     } else if (n > 0) {
       g_error = src.path + ": the file ends after " + std::to_string(n) + " of the 4 lines of a FASTQ record, at line " + std::to_string(src.line + 4 * records + n);
       return false;
     }
-    if (c.atEnd) { c.records = fullRecords; c.bytes = fullBytes; c.longest = longest; c.consume = avail; return true; }
+    if (split > 0) longest = std::min(longest, split);  // (an upper bound of the longest mate: no section is longer than the split size)
+    if (c.atEnd) { c.records = fullRecords; c.bytes = fullBytes; c.sections = fullSections; c.longest = longest; c.consume = avail; return true; }
   }
-  if (fullRecords > maxRecords) { fullRecords = maxRecords; fullBytes = bytesAtMax; }  // (a block of empty lines with text behind them: the parser will name them)
-  c.records = fullRecords; c.bytes = fullBytes; c.longest = longest; c.consume = (size_t)fullBytes;
+  if (split == 0 && fullRecords > maxRecords) { fullRecords = fullSections = maxRecords; fullBytes = bytesAtMax; }  // (a block of empty lines with text behind them: the parser will name them)
+  if (split > 0) longest = std::min(longest, split);
+  c.records = fullRecords; c.bytes = fullBytes; c.sections = fullSections; c.longest = longest; c.consume = (size_t)fullBytes;
   return true;
 }
 
@@ -439,6 +451,7 @@ struct TextStore { std::vector<char> a, b; };
 struct xmio_text_reader {
   Source a, b;
   bool paired = false;
+  int64_t split = 0;  // xmio_text_open_split
 };
 
 extern "C" {
@@ -457,6 +470,13 @@ xmio_text_reader* xmio_text_open(const char* path1, const char* path2) {
   };
   adopt(r->a);
   if (r->paired) adopt(r->b);
+  return r;
+}
+
+xmio_text_reader* xmio_text_open_split(const char* path, int32_t split_past_size) {
+  if (split_past_size < 1 || split_past_size > xm::XM_FASTQ_MAX_MATE) { g_error = "xmio_text_open_split: split_past_size must be 1 .. 30000 (a section is a mate)"; return nullptr; }
+  xmio_text_reader* r = xmio_text_open(path, nullptr);
+  if (r) r->split = split_past_size;
   return r;
 }
 
@@ -479,7 +499,7 @@ int xmio_text_next(xmio_text_reader* r, int64_t max_queries, xmio_text_block** o
   *out = nullptr;
   if (max_queries < 1) return fail("xmio_text_next: max_queries must be >= 1");
   Cut a, b;
-  if (!scanBlock(r->a, max_queries, a)) return -1;
+  if (!scanBlock(r->a, max_queries, a, r->split)) return -1;
   if (r->paired) {
     if (!scanBlock(r->b, a.records > 0 ? a.records : 1, b)) return -1;
     if ((a.records == 0) != (b.records == 0) || (b.records < a.records && b.atEnd))
@@ -516,6 +536,7 @@ int xmio_text_next(xmio_text_reader* r, int64_t max_queries, xmio_text_block** o
   blk->store = st;
   blk->text1 = text1; blk->bytes1 = a.bytes; blk->records1 = a.records; blk->longest1 = a.longest;
   blk->text2 = text2; blk->bytes2 = r->paired ? b.bytes : 0; blk->records2 = r->paired ? b.records : 0; blk->longest2 = r->paired ? b.longest : 0;
+  blk->num_queries = a.sections;
   *out = blk;
   return 0;
 }
