@@ -127,7 +127,8 @@ const char* xm_build_stamp(void);
  * xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes (and the test-only xm_test_sam_format, xm_test_format_doubles); 8 = xm_batch_unstage; 9 = xm_pileup_keep_insert_text, xm_pileup_event_text (and the test-only
  * xm_test_pileup_text); 10 = xm_context_set_result_copy, xm_summary_last, xm_summary_free (and the test-only xm_test_summary);
  * 11 = xm_refs_count_last, xm_refs_count_free (and the test-only xm_test_refs_count); 12 = xm_fastq_text.reserved becomes split_past_size (same layout; 0 is
- * what every caller passed).  A binding checks it once
+ * what every caller passed).  xm_batch_stage_fasta was added without a new version: it changes no struct and no entry, so the version stays 12 and a
+ * caller that wants it looks the symbol up (a library of version 12 built before it does not export it).  A binding checks the version once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -287,6 +288,25 @@ int xm_batch_stage_fastq(xm_index* index, const xm_fastq_text* text, xm_fastq_ba
 void xm_fastq_batch_free(xm_fastq_batch* batch);
 /* Bytes of text per workgroup of the kernels that find the line ends (test hook: tests/test_gpu_fastq.py puts newlines on both sides of the edges it gives). */
 int32_t xm_fastq_tile_bytes(void);
+
+/* (ABI version 12, added without a new version: look the symbol up)  The batch staged from FASTA text: what xm_batch_stage_fastq does for '>' records of any
+ * number of lines.  A line is a header exactly when its first byte is '>'; every other line up to the next header belongs to the record, is trimmed of
+ * blanks and tabs at both ends on its own and appended to the record's bases (so lines that start with '@', '+' or a blank are bases, as the host reader of
+ * libxm_hostio.so has them).  The name is what stands behind '>' up to the first blank or tab.  records1 / lines1 (and records2 / lines2) are the headers and
+ * the lines the texts hold, a last line without its newline being a line; a text holds at most 1 GiB and 2^26 lines.  A FASTA mate has no quality:
+ * keep_qualities only sizes qual_off / has_qual as the host reader does (has_qual 0, quals empty).  split_past_size is xm_fastq_text's, for single reads. */
+typedef struct xm_fasta_text {
+  const char* text1; int64_t bytes1, records1, lines1;
+  const char* text2; int64_t bytes2, records2, lines2;   /* NULL / 0 / 0 / 0: single reads */
+  double expected_inner, deviation;                       /* of every pair; single queries get 0 and 1 */
+  int32_t keep_qualities;
+  int32_t split_past_size;
+} xm_fasta_text;
+/* The contract of xm_batch_stage_fastq, and its result (freed by xm_fastq_batch_free; the names belong to the staged batch, so xm_sam_format_last takes
+ * names == NULL).  The strict form: the text's first byte is '>', the headers and lines found are the ones announced, every record has at least one base
+ * and - without a split size - at most 30000; with one the limit holds for a section.  Anything else fails the call with nothing staged; xm_last_error
+ * names the file (1 or 2), the 0-based record and the reason, the lowest (file, record) first. */
+int xm_batch_stage_fasta(xm_index* index, const xm_fasta_text* text, xm_fastq_batch** out);
 
 /* (ABI version 7) The SAM records of the last align call formatted on the GPU: the output-side counterpart of xm_batch_stage_fastq.  When an align call
  * returns, its four streams and its batch are still in HBM; kernels walk them there and build the text that the harness's host formatter

@@ -61,15 +61,19 @@ void xmio_last_write_seconds(double* format_seconds, double* file_seconds);
 
 /* The query files cut into blocks of whole four-line FASTQ records, as text, for a parser that is not this library's (xm_batch_stage_fastq of
  * include/xmapper_hip.h builds the batch arrays from such a block on the GPU).  The cutter looks for line ends only: no base is translated and nothing is
- * looked up per base.  FASTA and multi-line records stay with xmio_open; so does --split-queries-past-size unless the reader is opened with
- * xmio_text_open_split, whose blocks go to a parser that cuts the sections (xm_fastq_text.split_past_size). */
+ * looked up per base.  Multi-line FASTQ records stay with xmio_open; FASTA records of any number of lines are cut by a reader opened with
+ * xmio_text_open_fasta (for xm_batch_stage_fasta); --split-queries-past-size stays with xmio_open unless the reader is opened with xmio_text_open_split or
+ * with xmio_text_open_fasta's split size, whose blocks go to a parser that cuts the sections (xm_fastq_text.split_past_size, xm_fasta_text.split_past_size). */
+enum { XMIO_TEXT_FASTQ = 0, XMIO_TEXT_FASTA = 1 };
 typedef struct xmio_text_reader xmio_text_reader;
 typedef struct xmio_text_block {
   const char* text1; int64_t bytes1; int64_t records1;
   int64_t longest1;          /* length of the longest sequence line (lines 1, 5, 9, ...) of text1 as it stands in the file: an upper bound of the longest mate */
   const char* text2; int64_t bytes2; int64_t records2; int64_t longest2;   /* NULL / 0 / 0 / 0 for a single file */
   void* store;               /* owner of the texts (xmio_text_block_free) */
-  int64_t num_queries;       /* (appended) the queries the block gives: records1, or - xmio_text_open_split - the sections of its records, exactly */
+  int64_t num_queries;       /* (appended) the queries the block gives: records1, or - with a split size - the sections of its records, exactly */
+  int64_t lines1, lines2;    /* (appended) the lines of each text, a last line without its newline included: 4 * records for FASTQ text */
+  int32_t format;            /* (appended) XMIO_TEXT_FASTQ or XMIO_TEXT_FASTA: which parser the block is cut for */
 } xmio_text_block;
 /* path2 != NULL: paired files cut in step, a block holds the same number of records of each.  Files may be gzip-compressed. */
 xmio_text_reader* xmio_text_open(const char* path1, const char* path2);
@@ -83,6 +87,17 @@ int xmio_text_next(xmio_text_reader* reader, int64_t max_queries, xmio_text_bloc
  * pass max_queries and always takes at least one record, so a record of more sections than that is a block of its own.  longest1 is at most split_past_size.
  * Unlike xmio_next, no record's sections straddle two blocks. */
 xmio_text_reader* xmio_text_open_split(const char* path, int32_t split_past_size);
+/* One FASTA file, or two cut in step, for xm_batch_stage_fasta (the rules: mapper_amd/csrc/xm_fasta_rules.h).  A block is whole records: a record starts at a
+ * line whose first byte is '>' and ends in front of the next such line or at the end of the input, so empty lines and lines that start with '@', '+' or a
+ * blank belong to the record they stand in.  A file's leading empty lines are dropped; a first line that starts with neither '>' nor '@' is refused in the
+ * host reader's words, and one that starts with '@' is refused as well.  max_queries counts records; with split_past_size (1 .. 30000, single file only; 0:
+ * none) it counts sections, from the sum of the record's trimmed line lengths.  The block stops in front of the record that would pass max_queries, 1 GiB or
+ * 2^26 lines, and always takes at least one record; a single record beyond 1 GiB or 2^26 lines is refused with its line.  longest1 / longest2 are the bases
+ * of the longest record, capped at the split size.  Read through xmio_text_next; the blocks carry lines1 / lines2 and XMIO_TEXT_FASTA. */
+xmio_text_reader* xmio_text_open_fasta(const char* path1, const char* path2, int32_t split_past_size);
+/* The first byte of a query file's first line that is not empty ('>' or '@'; gzip is read through), 0 for a file of nothing but empty lines, -1 (xmio_last_error)
+ * for a file that cannot be opened or whose first line starts with anything else: which cutter the file is for, without reading it twice. */
+int xmio_first_header_byte(const char* path);
 void xmio_text_block_free(xmio_text_block* block);
 void xmio_text_close(xmio_text_reader* reader);
 

@@ -46,6 +46,12 @@ class XmFastqText(C.Structure):
                 ("expected_inner", C.c_double), ("deviation", C.c_double), ("keep_qualities", C.c_int32), ("split_past_size", C.c_int32)]
 
 
+class XmFastaText(C.Structure):
+    """xm_fasta_text: a block of whole FASTA records ('>' header, any number of body lines) as read from the file(s), with its line counts."""
+    _fields_ = [("text1", C.c_void_p), ("bytes1", C.c_int64), ("records1", C.c_int64), ("lines1", C.c_int64), ("text2", C.c_void_p), ("bytes2", C.c_int64), ("records2", C.c_int64),
+                ("lines2", C.c_int64), ("expected_inner", C.c_double), ("deviation", C.c_double), ("keep_qualities", C.c_int32), ("split_past_size", C.c_int32)]
+
+
 class XmFastqBatch(C.Structure):
     """xm_fastq_batch: hostio.XmioBatch's fields (pinned host copies of what the kernels built), then the times of the call's three parts."""
     _fields_ = [("num_queries", C.c_int64), ("mate_count", C.POINTER(C.c_int32)), ("mate_offset", C.POINTER(C.c_int64)), ("mate_length", C.POINTER(C.c_int32)),
@@ -96,7 +102,7 @@ class XmTestPileupJob(C.Structure):
                 ("num_events", C.c_int64), ("events", C.c_void_p), ("query_base", C.c_int64)]
 
 
-ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved)
+ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved); xm_batch_stage_fasta came without a new version (no struct or entry changed)
 
 
 class XmIndexInfo(C.Structure):
@@ -107,7 +113,7 @@ class XmIndexInfo(C.Structure):
 
 
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
-           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count"]
+           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_batch_stage_fasta", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count"]
 
 
 def build_library(force=False):
@@ -191,6 +197,7 @@ def lib():
         L.xm_batch_commit.argtypes = [C.c_void_p]
         L.xm_batch_unstage.argtypes = [C.c_void_p]
         L.xm_batch_stage_fastq.argtypes = [C.c_void_p, C.POINTER(XmFastqText), C.POINTER(C.POINTER(XmFastqBatch))]
+        L.xm_batch_stage_fasta.argtypes = [C.c_void_p, C.POINTER(XmFastaText), C.POINTER(C.POINTER(XmFastqBatch))]  # (added without a new ABI version: include/xmapper_hip.h)
         L.xm_fastq_batch_free.argtypes = [C.POINTER(XmFastqBatch)]
         L.xm_fastq_batch_free.restype = None
         L.xm_sam_set_contigs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p)]

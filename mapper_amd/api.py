@@ -482,19 +482,26 @@ class ReferenceDatabase:
         offers the arrays hostio.Batch offers (names and qualities included, for the writers).  A text that is not of the strict form (four lines a record, '@'
         headers, 1 .. 30000 bases) is a hostio.StrictFormError (a ValueError) that names file, record and reason, and nothing is staged.  A block cut with a
         split size (hostio.read_text_blocks(split=...)) is staged with it: the kernels cut every record into its sections, each a query, and a record may be
-        longer than 30000 bases; a query count that is not the cutter's is an internal error."""
+        longer than 30000 bases; a query count that is not the cutter's is an internal error.  A block of FASTA text (hostio.read_text_blocks(fasta=True)) goes to
+        xm_batch_stage_fasta with its line counts: records of any number of lines, the same arrays, no qualities."""
         if block._text is None:
             raise ValueError("the block's text is gone: it has been staged or closed")
         t = block._text.contents
-        text = _capi.XmFastqText(t.text1, t.bytes1, t.records1, t.text2, t.bytes2, t.records2, block.pair_spacing[0], block.pair_spacing[1], 1 if block.keep_qualities else 0, block.split)
         out = C.POINTER(_capi.XmFastqBatch)()
-        if self._L.xm_batch_stage_fastq(self._h, C.byref(text), C.byref(out)):
+        keep = 1 if block.keep_qualities else 0
+        if block.fasta:
+            text = _capi.XmFastaText(t.text1, t.bytes1, t.records1, t.lines1, t.text2, t.bytes2, t.records2, t.lines2, block.pair_spacing[0], block.pair_spacing[1], keep, block.split)
+            rc = self._L.xm_batch_stage_fasta(self._h, C.byref(text), C.byref(out))
+        else:
+            text = _capi.XmFastqText(t.text1, t.bytes1, t.records1, t.text2, t.bytes2, t.records2, block.pair_spacing[0], block.pair_spacing[1], keep, block.split)
+            rc = self._L.xm_batch_stage_fastq(self._h, C.byref(text), C.byref(out))
+        if rc:
             raise hostio.StrictFormError(self._L.xm_last_error().decode())
         if int(out.contents.num_queries) != block.num_queries:  # (the cutter and the kernels count a split block's sections by the same rule)
             n = int(out.contents.num_queries)
             self._L.xm_fastq_batch_free(out)
             self._L.xm_batch_unstage(self._h)
-            raise RuntimeError("xm_batch_stage_fastq: internal: the kernels built %d queries of a block the cutter counted %d in" % (n, block.num_queries))
+            raise RuntimeError("%s: internal: the kernels built %d queries of a block the cutter counted %d in" % ("xm_batch_stage_fasta" if block.fasta else "xm_batch_stage_fastq", n, block.num_queries))
         block.attach(out, self._L.xm_fastq_batch_free)
         return block
 

@@ -22,7 +22,10 @@ only beside --split-on-gpu; a job whose output needs objects - --out-refs-map-co
 same), --split-on-gpu (with --parse-on-gpu and --split-queries-past-size: the kernels that parse the text also cut every record into its sections,
 hostio.read_text_blocks(split=...), so a long-read job goes from FASTQ text to SAM text without the host translating or cutting a base; a record's sections
 stay in one batch, where the host reader lets them straddle two; SAM, unaligned file, refs count and statistics are the same bytes at any --batch-size, the
-mutations file where both paths cut their batches at the same places),
+mutations file where both paths cut their batches at the same places), --fasta-on-gpu (with --parse-on-gpu: a query file whose first record is FASTA -
+'>', records of any number of lines - is parsed on the GPU too, hostio.read_text_blocks(fasta=True) and xm_batch_stage_fasta; same outputs, the unaligned
+file being FASTA as the host writes it for mates without quality; without the flag such a file is refused as before; the two files of a pair must be of
+one format; works beside --split-on-gpu and the other device stages),
 --format-on-gpu (the SAM records are formatted on the GPU while a batch and its results are resident, api.ReferenceDatabase.format_sam_last, and the host
 only writes the bytes: same outputs; --out-unaligned stays with the host; not with --per-object, --out-mutations or --out-refs-map-count; nothing to do
 without --out-sam), --results-on-gpu (the align calls leave their result streams in HBM and copy none of them to the host,
@@ -216,6 +219,8 @@ def parse_args(argv):
             o["parse_on_gpu"] = True
         elif a == "--split-on-gpu":  # (not a Mapper flag) with --parse-on-gpu, the sections of --split-queries-past-size are cut on the GPU too (xm_fastq_text.split_past_size)
             o["split_on_gpu"] = True
+        elif a == "--fasta-on-gpu":  # (not a Mapper flag) with --parse-on-gpu, query files whose first record is FASTA are parsed on the GPU as well (xm_batch_stage_fasta)
+            o["fasta_on_gpu"] = True
         elif a == "--format-on-gpu":  # (not a Mapper flag) the SAM records are formatted on the GPU from the result streams while the batch is resident (api.ReferenceDatabase.format_sam_last)
             o["format_on_gpu"] = True
         elif a == "--results-on-gpu":  # (not a Mapper flag) the result streams stay in HBM; the host gets the SAM text and a summary (api.ReferenceDatabase.set_result_copy, summary_last)
@@ -248,6 +253,8 @@ def parse_args(argv):
             raise UsageError("--split-on-gpu has nothing to do without --split-queries-past-size in front of --queries")
         if any(split > 30000 for _, split in o["queries"]):
             raise UsageError("--split-on-gpu takes a --split-queries-past-size of at most 30000 (a section is a mate)")
+    if o.get("fasta_on_gpu") and not o.get("parse_on_gpu"):
+        raise UsageError("--fasta-on-gpu needs --parse-on-gpu (it lets the kernels that parse the query text take FASTA records too)")
     if o.get("count_refs_on_gpu"):
         if o.get("per_object"):
             raise UsageError("--count-refs-on-gpu and --per-object exclude each other (the per-object path counts from alignments decoded on the host)")
@@ -386,12 +393,22 @@ def native_source(o, batch_size, job):
     keep_qual = bool(o["out_unaligned"])
     on_gpu = bool(o.get("parse_on_gpu"))  # the blocks are text (hostio.TextBlock) until a context stages them: the first one speaks through its longest line
 
+    def is_fasta(*paths):
+        """--fasta-on-gpu: do the files start with a FASTA record?  (Without the flag nothing is looked at: a '>' file is the FASTQ parser's to refuse, as before.)"""
+        if not o.get("fasta_on_gpu"):
+            return False
+        first = [hostio.first_header_byte(p) for p in paths]
+        if len(set(first) - {b""}) > 1:
+            raise hostio.StrictFormError("paired query files are of different formats: %s" % ", ".join(
+                "%s starts with a %s record" % (p, "FASTA" if c == b">" else "FASTQ") for p, c in zip(paths, first)))
+        return b">" in first
+
     def read():
         if on_gpu:
             for path, split in o["queries"]:
-                yield from hostio.read_text_blocks(path, None, batch_size, keep_qualities=keep_qual, split=split)  # (a split size: --split-on-gpu, parse_args)
+                yield from hostio.read_text_blocks(path, None, batch_size, keep_qualities=keep_qual, split=split, fasta=is_fasta(path))  # (a split size: --split-on-gpu, parse_args)
             for left, right, expected, deviation in o["paired"]:
-                yield from hostio.read_text_blocks(left, right, batch_size, keep_qualities=keep_qual, expected_inner=expected, deviation=deviation)
+                yield from hostio.read_text_blocks(left, right, batch_size, keep_qualities=keep_qual, expected_inner=expected, deviation=deviation, fasta=is_fasta(left, right))
             return
         for path, split in o["queries"]:
             yield from hostio.read_batches(path, None, batch_size, split=split, keep_qualities=keep_qual)

@@ -9,6 +9,7 @@
 // Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_result_stage.h (ResultStage: the result arenas,
 // the scan and gather kernels, the canonical streams; throwFailedQuery), xm_conf_table.h (the host's confidence table), xm_capi_probe.h (seed-probe and
 // random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries), xm_capi_fastq.h (a batch staged from FASTQ text: the kernels of xm_fastq.h),
+// xm_capi_fasta.h (the same from FASTA text of any number of lines a record: the kernels of xm_fasta.h),
 // xm_capi_sam.h (SAM records formatted from the resident results: the kernels of xm_sam.h), xm_capi_summary.h (the statistics, the penalties and the unaligned
 // queries of the resident results: the kernels of xm_summary.h), xm_capi_refs.h (the queries of the resident results counted per combination of contigs: the
 // kernels of xm_refs.h).
@@ -26,6 +27,7 @@
 #include "xm_pass_plan.h"
 #include "xm_collapse.h"
 #include "xm_fastq.h"
+#include "xm_fasta.h"
 #include "xm_sam.h"
 #include "xm_summary.h"
 #include "xm_refs.h"
@@ -266,6 +268,9 @@ struct FastqStage {
   DevBuf<int32_t> dRecCount;
   DevBuf<int64_t> dRecFirst;
   DevBuf<long long> dRecBlockSums;
+  DevBuf<int32_t> dLineStart[2], dLineBases[2], dBaseBefore[2], dRecLine[2];  // FASTA text (xm_batch_stage_fasta; xm_fasta.h): the per-line arrays of each text, its records' header lines,
+  DevBuf<uint8_t> dLineHeader[2];                                             // the line scans' block sums
+  DevBuf<long long> dLineBlockSums[2];
   // on the GPU's staging stream: text up | stages 1-3 | (host sizes the arrays) | stage 4 | arrays down; the split form also [6] behind stage 2b and [7] in front of 2c (the host sizes the slots between them)
   hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   ~FastqStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
@@ -1618,3 +1623,4 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 #include "xm_capi_refs.h"
 #include "xm_capi_test.h"
 #include "xm_capi_fastq.h"
+#include "xm_capi_fasta.h"

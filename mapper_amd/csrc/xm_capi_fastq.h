@@ -91,6 +91,68 @@ void fastqCheckText(const FastqCtl& ctl, const FastqText texts[2], bool paired) 
                                std::to_string(texts[k].records) + " records announced)");
 }
 
+// What the entries that stage a batch from text do behind stage 3 (xm_batch_stage_fastq, and xm_batch_stage_fasta of xm_capi_fasta.h): the arrays the totals size, stage 4
+// (launchGather queues it on the stream it is given), everything down into the box's pinned buffers, the times of the call's parts, and the host's facts of the batch.
+// splitWaits: the call waited for the section count between ev[6] and ev[7].
+template <class LaunchGather>
+void fastqFinish(xm_index* idx, FastqBox* box, const FastqCtl& ctl, int64_t nq, bool keepQual, bool splitWaits, LaunchGather&& launchGather) {
+  DeviceBatch& d = idx->staged;
+  FastqStage& f = idx->fastq;
+  xm_fastq_batch& b = box->pub;
+  const long long slots = 2 * nq;
+  // the arrays the totals size, stage 4, everything down
+  const size_t nCodes = (size_t)ctl.totals[0], nNames = (size_t)ctl.totals[1], nQuals = (size_t)ctl.totals[2];
+  d.codes.ensure(nCodes);
+  d.names.ensure(nNames);
+  if (keepQual) f.dQuals.ensure(nQuals);
+  b.codes_length = (int64_t)nCodes;
+  b.codes = (uint8_t*)g_pinned->get(nCodes, &box->bytes[3]);
+  b.names = (char*)g_pinned->get(nNames, &box->bytes[4]);
+  if (keepQual) b.quals = (char*)g_pinned->get(nQuals, &box->bytes[6]);
+  idx->dt->onStagingStream([&](hipStream_t s) {
+    HIP_CHECK(hipEventRecord(f.ev[3], s));
+    launchGather(s);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(f.ev[4], s));
+    HIP_CHECK(hipMemcpyAsync(b.mate_count, d.mateCount.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(b.mate_offset, d.mateOffset.p, sizeof(int64_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(b.mate_length, d.mateLength.p, sizeof(int32_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(b.name_off, d.nameOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
+    if (nCodes) HIP_CHECK(hipMemcpyAsync(b.codes, d.codes.p, nCodes, hipMemcpyDeviceToHost, s));
+    if (nNames) HIP_CHECK(hipMemcpyAsync(b.names, d.names.p, nNames, hipMemcpyDeviceToHost, s));
+    if (keepQual) {
+      HIP_CHECK(hipMemcpyAsync(b.qual_off, f.dQualOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(b.has_qual, f.dHasQual.p, (size_t)slots, hipMemcpyDeviceToHost, s));
+      if (nQuals) HIP_CHECK(hipMemcpyAsync(b.quals, f.dQuals.p, nQuals, hipMemcpyDeviceToHost, s));
+    }
+    HIP_CHECK(hipEventRecord(f.ev[5], s));
+  });
+  HIP_CHECK(hipEventSynchronize(f.ev[5]));
+  float up = 0, parse = 0, gather = 0, down = 0;
+  HIP_CHECK(hipEventElapsedTime(&up, f.ev[0], f.ev[1]));
+  if (splitWaits) {  // (not the time the host took between the two to size the slots)
+    float records = 0;
+    HIP_CHECK(hipEventElapsedTime(&records, f.ev[1], f.ev[6]));
+    HIP_CHECK(hipEventElapsedTime(&parse, f.ev[7], f.ev[2]));
+    parse += records;
+  } else HIP_CHECK(hipEventElapsedTime(&parse, f.ev[1], f.ev[2]));
+  HIP_CHECK(hipEventElapsedTime(&gather, f.ev[3], f.ev[4]));
+  HIP_CHECK(hipEventElapsedTime(&down, f.ev[4], f.ev[5]));
+  b.h2d_ms = up; b.kernel_ms = (double)parse + gather; b.d2h_ms = down;
+  // the host's facts of the batch, from the returned mate lengths
+  xm_query_batch view;
+  memset(&view, 0, sizeof(view));
+  view.num_queries = nq; view.mate_count = b.mate_count; view.mate_offset = b.mate_offset; view.mate_length = b.mate_length; view.codes = b.codes; view.codes_length = b.codes_length;
+  bool anyPaired = false;
+  const int maxLen = validateBatch(&view, &anyPaired, &d.lens);
+  d.anyPaired = anyPaired;
+  idx->ensureTablesFor(maxLen);  // (tables that grow wait for the launches that read them: DeviceTables::rw)
+  d.maxLen = maxLen;
+  d.h2dMs = up;
+  d.hasNames = true;
+  d.nq = nq;
+}
+
 }  // namespace
 
 extern "C" {
@@ -141,7 +203,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
       f.dText[k].ensure((size_t)((bytes + 15) & ~15ll));
       f.dLineEnd[k].ensure((size_t)(4 * records + 1));
       f.dTileCount[k].ensure((size_t)((bytes + XM_FASTQ_TILE_BYTES - 1) / XM_FASTQ_TILE_BYTES));
-      texts[k] = FastqText{f.dText[k].p, bytes, records, f.dLineEnd[k].p, f.dTileCount[k].p};
+      texts[k] = FastqText{f.dText[k].p, bytes, records, f.dLineEnd[k].p, f.dTileCount[k].p, 4 * records + 1};
     }
     f.dCtl.ensure(1);
     FastqCtl ctl;
@@ -187,59 +249,11 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     });
     if (split == 0) fastqCheckText(ctl, texts, paired);
     else if (ctl.sections != nq) throw std::runtime_error("internal: the section count changed between two launches");
-    // the arrays the totals size, stage 4, everything down
-    const size_t nCodes = (size_t)ctl.totals[0], nNames = (size_t)ctl.totals[1], nQuals = (size_t)ctl.totals[2];
-    d.codes.ensure(nCodes);
-    d.names.ensure(nNames);
-    if (keepQual) f.dQuals.ensure(nQuals);
-    b.codes_length = (int64_t)nCodes;
-    b.codes = (uint8_t*)g_pinned->get(nCodes, &box->bytes[3]);
-    b.names = (char*)g_pinned->get(nNames, &box->bytes[4]);
-    if (keepQual) b.quals = (char*)g_pinned->get(nQuals, &box->bytes[6]);
-    idx->dt->onStagingStream([&](hipStream_t s) {
-      HIP_CHECK(hipEventRecord(f.ev[3], s));
+    fastqFinish(idx, box, ctl, nq, keepQual, split > 0, [&](hipStream_t s) {
       hipLaunchKernelGGL(xm_fastq_gather_kernel, dim3((unsigned)((slots + 3) / 4)), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, (const char*)f.dText[0].p, (const char*)f.dText[1].p,
                          (const int64_t*)d.mateOffset.p, (const int64_t*)d.nameOff.p, (const int64_t*)(keepQual ? f.dQualOff.p : nullptr), d.codes.p, d.names.p,
                          keepQual ? f.dQuals.p : nullptr);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(f.ev[4], s));
-      HIP_CHECK(hipMemcpyAsync(b.mate_count, d.mateCount.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(b.mate_offset, d.mateOffset.p, sizeof(int64_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(b.mate_length, d.mateLength.p, sizeof(int32_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(b.name_off, d.nameOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
-      if (nCodes) HIP_CHECK(hipMemcpyAsync(b.codes, d.codes.p, nCodes, hipMemcpyDeviceToHost, s));
-      if (nNames) HIP_CHECK(hipMemcpyAsync(b.names, d.names.p, nNames, hipMemcpyDeviceToHost, s));
-      if (keepQual) {
-        HIP_CHECK(hipMemcpyAsync(b.qual_off, f.dQualOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(b.has_qual, f.dHasQual.p, (size_t)slots, hipMemcpyDeviceToHost, s));
-        if (nQuals) HIP_CHECK(hipMemcpyAsync(b.quals, f.dQuals.p, nQuals, hipMemcpyDeviceToHost, s));
-      }
-      HIP_CHECK(hipEventRecord(f.ev[5], s));
     });
-    HIP_CHECK(hipEventSynchronize(f.ev[5]));
-    float up = 0, parse = 0, gather = 0, down = 0;
-    HIP_CHECK(hipEventElapsedTime(&up, f.ev[0], f.ev[1]));
-    if (split > 0) {  // (not the time the host took between the two to size the slots)
-      float records = 0;
-      HIP_CHECK(hipEventElapsedTime(&records, f.ev[1], f.ev[6]));
-      HIP_CHECK(hipEventElapsedTime(&parse, f.ev[7], f.ev[2]));
-      parse += records;
-    } else HIP_CHECK(hipEventElapsedTime(&parse, f.ev[1], f.ev[2]));
-    HIP_CHECK(hipEventElapsedTime(&gather, f.ev[3], f.ev[4]));
-    HIP_CHECK(hipEventElapsedTime(&down, f.ev[4], f.ev[5]));
-    b.h2d_ms = up; b.kernel_ms = (double)parse + gather; b.d2h_ms = down;
-    // the host's facts of the batch, from the returned mate lengths
-    xm_query_batch view;
-    memset(&view, 0, sizeof(view));
-    view.num_queries = nq; view.mate_count = b.mate_count; view.mate_offset = b.mate_offset; view.mate_length = b.mate_length; view.codes = b.codes; view.codes_length = b.codes_length;
-    bool anyPaired = false;
-    const int maxLen = validateBatch(&view, &anyPaired, &d.lens);
-    d.anyPaired = anyPaired;
-    idx->ensureTablesFor(maxLen);  // (tables that grow wait for the launches that read them: DeviceTables::rw)
-    d.maxLen = maxLen;
-    d.h2dMs = up;
-    d.hasNames = true;
-    d.nq = nq;
     *outBatch = &box->pub;
     return 0;
   } catch (std::exception& e) {

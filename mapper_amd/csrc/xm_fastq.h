@@ -13,7 +13,7 @@
 //                                          exclusive scans of the sequence, name and quality lengths in batch order (the three-kernel scan of
 //                                          xm_result_stage.h with three values); the host reads the totals to size codes, names, quals
 //   4 gather      xm_fastq_gather_kernel   a wave per mate, the code table in LDS: bases translated into codes, name and quality bytes copied, 64 bytes a round
-// Plain HIP.  Everything is sized by the host from `records` and `bytes`: lineEnd holds 4 * records + 1 entries, stage 1 writes no entry behind them and
+// Plain HIP.  Everything is sized by the host from `records` and `bytes`: lineEnd holds 4 * records + 1 entries (FastqText::lineCap), stage 1 writes no entry behind them and
 // stage 2 reads none that was not written, whatever the text holds; a text whose line count is not 4 * records is an error the host sees in FastqCtl.
 #pragma once
 #include "xm_fastq_rules.h"
@@ -34,13 +34,15 @@ struct FastqCtl {
   long long lines[2];             // lines found in each text
   long long totals[3];            // bases, name bytes, quality bytes of the batch
   long long sections;             // the split form: queries of the batch (the sections of all its records), read by the host in front of stage 2c
+  long long headers[2];           // FASTA text (xm_fasta.h): the header lines found in each text
 };
 
 struct FastqText {
   const char* text;     // allocated up to the next multiple of 16 bytes
   long long bytes, records;
-  int32_t* lineEnd;     // [4 * records + 1]
+  int32_t* lineEnd;     // [lineCap]
   int32_t* tileCount;   // [tiles] newlines of each tile, then (xm_fastq_tiles_kernel) the line index of its first one
+  long long lineCap;    // entries of lineEnd: 4 * records + 1 for FASTQ text; the lines announced + 1 for FASTA text (xm_fasta.h), whose `records` says nothing about its lines
 };
 
 // a mate slot's fields as stage 2 leaves them for stages 3 and 4: positions in its file's text
@@ -109,7 +111,7 @@ __global__ void __launch_bounds__(256) xm_fastq_tiles_kernel(FastqText t, long l
   if (threadIdx.x == 0) {
     long long lines = sh[255];
     if (t.bytes > 0 && t.text[t.bytes - 1] != '\n') {  // the last block of a file may lack the final newline
-      if (lines < 4 * t.records + 1) t.lineEnd[lines] = (int32_t)t.bytes;
+      if (lines < t.lineCap) t.lineEnd[lines] = (int32_t)t.bytes;
       lines++;
     }
     ctl->lines[file] = lines;
@@ -131,7 +133,7 @@ __global__ void __launch_bounds__(256) xm_fastq_ends_kernel(FastqText t) {
     __syncthreads();
   }
   long long line = (long long)t.tileCount[blockIdx.x] + sh[threadIdx.x] - mine;
-  const long long cap = 4 * t.records + 1;
+  const long long cap = t.lineCap;
   for (int k = 0; k < 4; k++) {
     uint32_t b = bits[k];
     while (b) {

@@ -107,7 +107,10 @@ class StrictFormError(ValueError):
 class XmioTextBlock(C.Structure):
     _fields_ = [("text1", C.c_void_p), ("bytes1", C.c_int64), ("records1", C.c_int64), ("longest1", C.c_int64),
                 ("text2", C.c_void_p), ("bytes2", C.c_int64), ("records2", C.c_int64), ("longest2", C.c_int64), ("store", C.c_void_p),
-                ("num_queries", C.c_int64)]
+                ("num_queries", C.c_int64), ("lines1", C.c_int64), ("lines2", C.c_int64), ("format", C.c_int32)]
+
+
+TEXT_FASTQ, TEXT_FASTA = 0, 1  # XmioTextBlock.format (include/xmapper_hostio.h)
 
 
 def _text_lib():
@@ -117,6 +120,9 @@ def _text_lib():
         L.xmio_text_open.argtypes = [C.c_char_p, C.c_char_p]
         L.xmio_text_open_split.restype = C.c_void_p
         L.xmio_text_open_split.argtypes = [C.c_char_p, C.c_int32]
+        L.xmio_text_open_fasta.restype = C.c_void_p
+        L.xmio_text_open_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_int32]
+        L.xmio_first_header_byte.argtypes = [C.c_char_p]
         L.xmio_text_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.POINTER(XmioTextBlock))]
         L.xmio_text_block_free.argtypes = [C.POINTER(XmioTextBlock)]
         L.xmio_text_block_free.restype = None
@@ -127,7 +133,8 @@ def _text_lib():
 
 
 class TextBlock:
-    """A block of whole four-line FASTQ records as text (one file's, or a pair's in step), for api.ReferenceDatabase.stage_fastq: the GPU parses it.  Before it
+    """A block of whole records as text (one file's, or a pair's in step) - four-line FASTQ records, or with fasta = True FASTA records of any number of
+    lines, whose line counts lines(which) then go to the parser too - for api.ReferenceDatabase.stage_fastq: the GPU parses it.  Before it
     is staged it offers num_queries and longest_line (an upper bound of the longest mate); once staged - the text is released then - it offers what Batch
     does: the six arrays(), mate_count / mate_offset / mate_length / codes, and a _ptr that Writer.write takes (an XmioBatch over the arrays the library
     returned, store NULL).  block[k] is the mates of query k, as pileup.MatchDatabase.add_last(queries=block) reads them.  split > 0: the block was cut
@@ -137,6 +144,7 @@ class TextBlock:
         self._text = ptr
         t = ptr.contents
         self.split = int(split)
+        self.fasta = int(t.format) == TEXT_FASTA
         self.num_queries = int(t.num_queries)
         self.paired = bool(t.text2)
         self.longest_line = int(max(t.longest1, t.longest2))
@@ -153,6 +161,10 @@ class TextBlock:
     def records(self, which=0):
         t = self._text.contents
         return int(t.records2 if which else t.records1)
+
+    def lines(self, which=0):
+        t = self._text.contents
+        return int(t.lines2 if which else t.lines1)
 
     def attach(self, staged, free):
         """stage_fastq's result: `staged` points to the library's xm_fastq_batch, free(staged) gives it back."""
@@ -207,14 +219,28 @@ class TextBlock:
             pass
 
 
-def read_text_blocks(path1, path2=None, batch_size=1_000_000, keep_qualities=False, expected_inner=0.0, deviation=1.0, split=0):
+def first_header_byte(path):
+    """b">" or b"@": the first byte of the file's first line that is not empty (gzip is read through), i.e. which cutter of read_text_blocks the file is
+    for; b"" for a file of nothing but empty lines.  Any other first byte is a StrictFormError in the host reader's words."""
+    L = _text_lib()
+    c = L.xmio_first_header_byte(os.fsencode(path))
+    if c < 0:
+        message = L.xmio_last_error().decode()
+        raise OSError(message) if message.startswith("cannot open") else StrictFormError(message)
+    return bytes([c]) if c else b""
+
+
+def read_text_blocks(path1, path2=None, batch_size=1_000_000, keep_qualities=False, expected_inner=0.0, deviation=1.0, split=0, fasta=False):
     """Generator of TextBlock objects over a four-line FASTQ file (or a pair of them, cut in step): whole records as text, at most batch_size of them.
     split > 0 (a single file): the records will be cut into sections of at most `split` bases by the parser, batch_size counts the sections, and a record
-    of more sections than that is a block of its own."""
+    of more sections than that is a block of its own.  fasta = True: the files hold FASTA records of any number of lines ('>' headers); the blocks carry
+    their line counts and block.fasta, and stage_fastq hands them to the FASTA parser."""
     L = _text_lib()
     if split and path2:
         raise ValueError("a split size is for single reads (--paired-queries is not supported with --split-queries-past-size)")
-    if split:
+    if fasta:
+        r = L.xmio_text_open_fasta(os.fsencode(path1), os.fsencode(path2) if path2 else None, int(split))
+    elif split:
         r = L.xmio_text_open_split(os.fsencode(path1), int(split))
     else:
         r = L.xmio_text_open(os.fsencode(path1), os.fsencode(path2) if path2 else None)

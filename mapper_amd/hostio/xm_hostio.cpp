@@ -10,6 +10,7 @@
 // mapper_amd/sam.py, whose records() this formatter reproduces byte for byte (tests/test_hostio.py compares the two on random result streams).
 #include "../../include/xmapper_hostio.h"
 #include "../csrc/xm_fastq_rules.h"
+#include "../csrc/xm_fasta_rules.h"
 #include <zlib.h>
 #include <algorithm>
 #include <atomic>
@@ -333,7 +334,8 @@ int xmio_next(xmio_reader* r, int64_t max_queries, xmio_batch** out) {
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- cutting (text blocks for the device parser: the rules are ../csrc/xm_fastq_rules.h)
+// ---------------------------------------------------------------- cutting (text blocks for the device parsers: the rules are ../csrc/xm_fastq_rules.h for four-line
+// FASTQ records - scanBlock - and ../csrc/xm_fasta_rules.h for FASTA records of any number of lines - scanFastaBlock; multi-line FASTQ stays with xmio_open)
 namespace {
 
 constexpr int64_t kTextBlockLimit = 1ll << 30;  // bytes of one file in one block
@@ -364,9 +366,23 @@ void giveBuffer(std::vector<char>& b) {
 struct Cut {
   int64_t records = 0, bytes = 0, longest = 0;
   int64_t sections = 0;  // the queries the records give: `records`, or with a split size the sections of their sequence lines (xm::fastqLineSections)
+  int64_t lines = 0;    // FASTA text (scanFastaBlock): the lines of the records; FASTQ text has four a record
   size_t consume = 0;   // bytes the source gives up: `bytes`, and at the end of the input the empty lines behind them
   bool atEnd = false;   // the source ended within this scan
 };
+
+// A full buffer grows at once to what the block will need, as far as the records so far (`bytes` of text) and the rest of a plain file tell (else fill()
+// doubles it, and every doubling copies what is there).
+void growAhead(Source& src, int64_t records, int64_t bytes, int64_t maxRecords) {
+  if (src.pos != 0 || src.end != src.buf.size() || records < 256 || src.fd < 0) return;
+  struct stat st;
+  const off_t at = lseek(src.fd, 0, SEEK_CUR);
+  if (fstat(src.fd, &st) != 0 || at < 0) return;
+  const double perRecord = (double)bytes / (double)records;
+  size_t want = (size_t)std::min<double>(perRecord * 1.125 * (double)maxRecords, (double)kTextBlockLimit) + 2 * kTextFillBytes;
+  want = std::min<size_t>(want, src.end + (size_t)std::max<off_t>(st.st_size - at, 0) + kTextFillBytes);
+  if (want > 2 * src.buf.size()) src.buf.resize(want);
+}
 
 // Whole records from src.pos on: line ends are found with memchr, every fourth ends a record.  Records of nothing but empty lines at the end of the
 // block are left for the next one, which drops them if the input ends there.  false: the file ends inside a record, or a record is larger than a block.
@@ -384,18 +400,7 @@ bool scanBlock(Source& src, int64_t maxRecords, Cut& c, int64_t split = 0) {
     const size_t avail = src.end - src.pos;
     const char* nl = off < avail ? (const char*)memchr(base + off, '\n', avail - off) : nullptr;
     if (!nl) {
-      // a full buffer grows at once to what the block will need, as far as the records so far and the rest of a plain file tell (else fill() doubles it,
-      // and every doubling copies what is there)
-      if (src.pos == 0 && src.end == src.buf.size() && records >= 256 && src.fd >= 0) {
-        struct stat st;
-        const off_t at = lseek(src.fd, 0, SEEK_CUR);
-        if (fstat(src.fd, &st) == 0 && at >= 0) {
-          const double perRecord = (double)bytes / (double)records;
-          size_t want = (size_t)std::min<double>(perRecord * 1.125 * (double)maxRecords, (double)kTextBlockLimit) + 2 * kTextFillBytes;
-          want = std::min<size_t>(want, src.end + (size_t)std::max<off_t>(st.st_size - at, 0) + kTextFillBytes);
-          if (want > 2 * src.buf.size()) src.buf.resize(want);
-        }
-      }
+      growAhead(src, records, bytes, maxRecords);
       if (!src.fill(kTextFillBytes)) { c.atEnd = true; break; }  // (a few MiB at a time: the lines are looked for while they are in the cache)
       continue;
     }
@@ -444,6 +449,79 @@ bool scanBlock(Source& src, int64_t maxRecords, Cut& c, int64_t split = 0) {
   return true;
 }
 
+// A file's leading empty lines are dropped (the reader skips them in front of a header); then its first byte is the first header's.  -> that byte ('>' or
+// '@'), 0 at the end of the input, -1 for any other byte, in the reader's words.  Nothing but the empty lines is taken from the source.
+int firstHeaderByte(Source& src) {
+  while (true) {
+    const char* base = src.buf.data() + src.pos;
+    const size_t avail = src.end - src.pos;
+    const char* nl = avail ? (const char*)memchr(base, '\n', avail) : nullptr;
+    if (!nl && src.fill(kTextFillBytes)) continue;
+    const size_t e = nl ? (size_t)(nl - base) : avail;
+    if (!nl && avail == 0) return 0;
+    if (xm::fastqEmptyLine(base, 0, (long long)e)) {
+      src.pos += nl ? e + 1 : e;
+      src.line++;
+      continue;
+    }
+    if (base[0] == '>' || base[0] == '@') return (unsigned char)base[0];
+    g_error = src.path + ": line " + std::to_string(src.line + 1) + " is neither a FASTA nor a FASTQ header";
+    return -1;
+  }
+}
+
+// scanBlock for FASTA text (the rules are ../csrc/xm_fasta_rules.h): whole records from src.pos on, a record ending in front of the next line whose first byte
+// is '>' or at the end of the input.  maxRecords counts records, or with a split size the sections of their bases - the sum of the trimmed lengths of their
+// body lines: the cutter looks at line ends and at the bytes at a line's two ends, never at a base.  The block stops in front of the record that would pass
+// maxRecords, 1 GiB or 2^26 lines, but takes at least one record; a single record beyond either limit is refused with its line.
+bool scanFastaBlock(Source& src, int64_t maxRecords, Cut& c, int64_t split = 0) {
+  c = Cut();
+  const int first = firstHeaderByte(src);  // (only a file's first block has empty lines in front, or stands at another byte than '>')
+  if (first < 0) return false;
+  if (first == 0) { c.atEnd = true; return true; }
+  if (first != '>') { g_error = src.path + ": line " + std::to_string(src.line + 1) + " is a FASTQ header where FASTA records were announced"; return false; }
+  size_t off = 0;                         // (relative to src.pos: fill() moves the buffer)
+  int64_t recLines = 0, recBases = 0;     // the record in progress
+  // the record in progress ends at `to`: into the block if it fits; false: the block is full in front of it
+  auto close = [&](size_t to) {
+    const int64_t ns = split > 0 && recBases > 0 ? (int64_t)xm::fastqSectionCount(recBases, split) : 1;  // (a record of no bases: the parser names it)
+    if (c.records > 0 && ((int64_t)to > kTextBlockLimit || c.lines + recLines > xm::XM_FASTA_MAX_LINES || c.sections + ns > maxRecords)) return false;
+    c.records++; c.bytes = (int64_t)to; c.lines += recLines; c.sections += ns;
+    c.longest = std::max(c.longest, recBases);
+    recLines = recBases = 0;
+    return true;
+  };
+  while (true) {
+    const char* base = src.buf.data() + src.pos;
+    const size_t avail = src.end - src.pos;
+    if (off >= avail) {
+      growAhead(src, c.records, c.bytes, maxRecords);
+      if (src.fill(kTextFillBytes)) continue;
+      c.atEnd = true;
+      break;
+    }
+    if (base[off] == '>' && recLines > 0) {  // the next record's header
+      if (!close(off) || c.sections >= maxRecords) break;
+    }
+    const char* nl = (const char*)memchr(base + off, '\n', avail - off);
+    if (!nl) growAhead(src, c.records, c.bytes, maxRecords);
+    if (!nl && src.fill(kTextFillBytes)) continue;
+    const size_t e = nl ? (size_t)(nl - base) : avail;  // (a last line without its newline)
+    recLines++;
+    recBases += (int64_t)xm::fastaLineBases(base, (long long)off, (long long)e);
+    off = nl ? e + 1 : e;
+    if ((int64_t)off > kTextBlockLimit || recLines > xm::XM_FASTA_MAX_LINES) {
+      if (c.records > 0) break;  // the block is full; the record in progress is the next block's
+      g_error = src.path + ": a FASTA record of more than 1 GiB or 2^26 lines at line " + std::to_string(src.line + 1);
+      return false;
+    }
+  }
+  if (c.atEnd && recLines > 0 && !close(off)) c.atEnd = false;  // (the next block takes the last record)
+  if (split > 0) c.longest = std::min(c.longest, split);
+  c.consume = (size_t)c.bytes;
+  return true;
+}
+
 struct TextStore { std::vector<char> a, b; };
 
 }  // namespace
@@ -452,6 +530,7 @@ struct xmio_text_reader {
   Source a, b;
   bool paired = false;
   int64_t split = 0;  // xmio_text_open_split
+  bool fasta = false;  // xmio_text_open_fasta
 };
 
 extern "C" {
@@ -480,6 +559,22 @@ xmio_text_reader* xmio_text_open_split(const char* path, int32_t split_past_size
   return r;
 }
 
+xmio_text_reader* xmio_text_open_fasta(const char* path1, const char* path2, int32_t split_past_size) {
+  if (split_past_size < 0 || split_past_size > xm::XM_FASTQ_MAX_MATE) { g_error = "xmio_text_open_fasta: split_past_size must be 0 .. 30000 (a section is a mate)"; return nullptr; }
+  if (split_past_size > 0 && path2) { g_error = "xmio_text_open_fasta: pairs are not cut into sections (a split size is for single reads)"; return nullptr; }
+  xmio_text_reader* r = xmio_text_open(path1, path2);
+  if (r) { r->fasta = true; r->split = split_past_size; }
+  return r;
+}
+
+int xmio_first_header_byte(const char* path) {
+  Source src;
+  if (!path || !src.open(path)) return fail(std::string("cannot open ") + (path ? path : "(null)"));
+  const int c = firstHeaderByte(src);
+  src.close();
+  return c;
+}
+
 void xmio_text_close(xmio_text_reader* r) {
   if (!r) return;
   r->a.close(); r->b.close();
@@ -499,19 +594,26 @@ int xmio_text_next(xmio_text_reader* r, int64_t max_queries, xmio_text_block** o
   *out = nullptr;
   if (max_queries < 1) return fail("xmio_text_next: max_queries must be >= 1");
   Cut a, b;
-  if (!scanBlock(r->a, max_queries, a, r->split)) return -1;
+  auto scan = [r](Source& src, int64_t most, Cut& c, int64_t split) { return r->fasta ? scanFastaBlock(src, most, c, split) : scanBlock(src, most, c, split); };
+  if (!scan(r->a, max_queries, a, r->split)) return -1;
   if (r->paired) {
-    if (!scanBlock(r->b, a.records > 0 ? a.records : 1, b)) return -1;
-    if ((a.records == 0) != (b.records == 0) || (b.records < a.records && b.atEnd))
-      return fail("paired query files have different numbers of reads: " + r->a.path + ", " + r->b.path);
-    if (b.records < a.records && !scanBlock(r->a, b.records, a)) return -1;  // (the second file's block was full first)
+    if (!scan(r->b, a.records > 0 ? a.records : 1, b, 0)) return -1;
+    if ((a.records == 0) != (b.records == 0) || (b.records < a.records && b.atEnd)) {
+      std::string where;  // (FASTA text: the line the shorter file ends at)
+      if (r->fasta) {
+        const bool firstEnds = a.records == 0;
+        where = " (" + (firstEnds ? r->a.path : r->b.path) + " ends at line " + std::to_string((firstEnds ? r->a.line + a.lines : r->b.line + b.lines)) + ")";
+      }
+      return fail("paired query files have different numbers of reads: " + r->a.path + ", " + r->b.path + where);
+    }
+    if (b.records < a.records && !scan(r->a, b.records, a, 0)) return -1;  // (the second file's block was full first)
     if (a.records != b.records) return fail("paired query files cannot be cut in step: " + r->a.path + ", " + r->b.path);
   }
   // -> where the block's text lies: in the source's buffer, which the block then owns (the source gets another one with what is left), or in a copy
   auto take = [](Source& src, const Cut& c, std::vector<char>& hold) -> const char* {
     const char* text = src.buf.data() + src.pos;
     const size_t avail = src.end - src.pos, rest = avail - c.consume;
-    src.line += 4 * c.records;
+    src.line += c.lines ? c.lines : 4 * c.records;
     if ((size_t)c.bytes < kTextBufferBytes / 2 || rest > (size_t)c.bytes / 4) {  // a small block, or one of several in the buffer
       hold.assign(text, text + c.bytes);
       src.pos += c.consume;
@@ -537,6 +639,8 @@ int xmio_text_next(xmio_text_reader* r, int64_t max_queries, xmio_text_block** o
   blk->text1 = text1; blk->bytes1 = a.bytes; blk->records1 = a.records; blk->longest1 = a.longest;
   blk->text2 = text2; blk->bytes2 = r->paired ? b.bytes : 0; blk->records2 = r->paired ? b.records : 0; blk->longest2 = r->paired ? b.longest : 0;
   blk->num_queries = a.sections;
+  blk->lines1 = r->fasta ? a.lines : 4 * a.records; blk->lines2 = !r->paired ? 0 : r->fasta ? b.lines : 4 * b.records;
+  blk->format = r->fasta ? XMIO_TEXT_FASTA : XMIO_TEXT_FASTQ;
   *out = blk;
   return 0;
 }
