@@ -353,6 +353,28 @@ typedef struct xm_batch_summary {
 int xm_summary_last(xm_index* context, int32_t want_unaligned, xm_batch_summary** out);
 void xm_summary_free(xm_batch_summary* summary);
 
+/* (no new ABI version: no struct or entry changed; a caller looks the two entries up by name, as xm_batch_stage_fasta)  The unaligned-query file written on
+ * the GPU, and the staged batch kept in HBM.  A batch that xm_batch_stage_fastq / xm_batch_stage_fasta built from text comes back to the host whole - about as
+ * many bytes as the text - and with xm_sam_format_last and xm_summary_last one reader of that copy is left: the harness's --out-unaligned, which rebuilds each
+ * unaligned query's record from codes, names and qualities (xmio_write_summary).  xm_unaligned_format_last builds that text from the resident batch, and
+ * xm_context_set_batch_copy(context, 0) then spares the copy.  Not used by the Java host.
+ * xm_unaligned_format_last has xm_summary_last's contract: it serialises with the context's other calls, runs on the context's stream, fails with "no longer
+ * resident" once another batch has been uploaded or committed and after an align call that failed, works whether or not the copy of the streams is on, and
+ * fails with "malformed result streams: query N" for the lowest query whose slice is not of the layout (where xm_summary_last says so).  It fails for a batch
+ * that was staged from arrays, which has no names in HBM.  The text: for every query without an alignment, in query order, each mate m < mate_count[q] as
+ * xmio_write_batch writes it - '@' if the mate came as FASTQ and the batch was staged with keep_qualities, else '>'; the name; '\n'; the bases by code & 15
+ * through ?ACMGRSVTWYHKDBN; '\n'; and for a FASTQ mate "+\n", the quality bytes, '\n' (mapper_amd/csrc/xm_unaligned_rules.h states it as code).  The
+ * qualities belong to the batch in HBM as the names do: they change hands with it in xm_batch_commit, so staging the next block does not touch them.
+ * *out: an xm_sam_text released with xm_sam_text_free - the text in a page-locked buffer (not NUL-terminated), its bytes, records = the mates written,
+ * h2d_ms = 0, kernel_ms and d2h_ms the call's kernels and copy.  A batch of 0 queries launches nothing; a batch without an unaligned query gives bytes == 0
+ * and launches nothing behind the totals.  Nothing is launched or allocated for a context that never calls it. */
+int xm_unaligned_format_last(xm_index* context, xm_sam_text** out);
+/* default 1.  0: every later xm_batch_stage_fastq / xm_batch_stage_fasta call of this context copies down only mate_count, mate_offset and mate_length (what
+ * the host needs to know of the batch: the longest mate, any pair, the lengths); the returned xm_fastq_batch has codes = names = name_off = quals = qual_off =
+ * has_qual = NULL and no pinned buffer is taken for them; num_queries, codes_length and the times are what they are.  keep_qualities still decides whether
+ * the qualities are kept in HBM.  Per context; may be changed between calls. */
+int xm_context_set_batch_copy(xm_index* context, int32_t on);
+
 /* (ABI version 11) The queries of the last align call counted per combination of contigs - what Mapper.run's --out-refs-map-count reports
  * (Mapper.java:197, 747-756): for every query with an alignment, the set of contigs that the sequences of its alignments lie on, and per distinct set the
  * number of such queries.  Kernels walk the resident streams, find equal sets through a table keyed by a fingerprint of the set, compare every query's set
@@ -489,6 +511,17 @@ int xm_test_pileup_text(int32_t device, const xm_test_pileup_job* job, int64_t* 
  * Same result, same errors. */
 int xm_test_summary(int32_t device, int64_t num_queries, int32_t num_contigs, const int32_t* ints, const double* dbls,
                     const int64_t* int_off, const int64_t* dbl_off, int32_t want_unaligned, xm_batch_summary** out);
+/* Test-only (tests/test_gpu_unaligned.py), like xm_test_sam_format: the kernels of xm_unaligned_format_last over host-given arrays - a batch with its names,
+ * its qualities (quals, qual_off and has_qual may all be NULL: a batch without them) and the four result streams - on `device`; no index and no alignment.
+ * Same result, same errors.  The write kernel's tile is xm_sam_tile_bytes(). */
+typedef struct xm_test_unaligned_job {
+  int64_t num_queries; const int32_t* mate_count; const int64_t* mate_offset; const int32_t* mate_length; const uint8_t* codes; int64_t codes_length;
+  const char* names; const int64_t* name_off;
+  const char* quals; const int64_t* qual_off; const uint8_t* has_qual;
+  int32_t num_contigs, reserved;
+  const int32_t* ints; const double* dbls; const int64_t* int_off; const int64_t* dbl_off;
+} xm_test_unaligned_job;
+int xm_test_unaligned_format(int32_t device, const xm_test_unaligned_job* job, xm_sam_text** out);
 /* Test-only (tests/test_gpu_refs_count.py), like xm_test_summary: the kernels of xm_refs_count_last over host-given streams on `device`; no index, no
  * alignment.  fingerprint_bits < 64 keeps only that many bits of the sets' fingerprints, so that different sets collide.  Same result, same errors. */
 int xm_test_refs_count(int32_t device, int64_t num_queries, int32_t num_contigs, const int32_t* ints, const double* dbls,

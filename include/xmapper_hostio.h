@@ -53,7 +53,9 @@ int xmio_write_batch(const xmio_batch* batch, const int32_t* ints, const double*
 /* xmio_write_batch with sam_fd = -1 for a caller that holds a summary of the streams instead of the streams (xm_batch_summary of include/xmapper_hip.h; the
  * SAM text is made and written elsewhere): the queries of `unaligned` - num_unaligned indices into the batch, strictly ascending, else the call fails and
  * writes nothing - go to unaligned_fd (-1: none) as xmio_write_batch writes them, and *stats grows by what xmio_write_batch would have added: the batch's
- * queries, the three counts, and total_penalty continued from its value by one += per entry of penalties[0 .. num_alignments), in order. */
+ * queries, the three counts, and total_penalty continued from its value by one += per entry of penalties[0 .. num_alignments), in order.  A batch whose
+ * names or codes are NULL (it stayed in HBM: xm_context_set_batch_copy(0) of include/xmapper_hip.h) fails the call with a message when unaligned_fd >= 0 and
+ * the list is not empty: the caller writes the text of xm_unaligned_format_last itself and passes unaligned_fd = -1. */
 int xmio_write_summary(const xmio_batch* batch, int64_t num_aligned, int64_t total_aligned_length, int64_t num_indels, int64_t num_alignments,
                        const double* penalties, int64_t num_unaligned, const int64_t* unaligned, int32_t unaligned_fd, xmio_stats* stats);
 /* Wall seconds of the calling thread's last xmio_write_batch or xmio_write_summary call: formatting and counting, and the write() calls (either may be NULL). */

@@ -77,6 +77,13 @@ class XmTestSamJob(C.Structure):
                 ("ints", C.c_void_p), ("dbls", C.c_void_p), ("int_off", C.c_void_p), ("dbl_off", C.c_void_p)]
 
 
+class XmTestUnalignedJob(C.Structure):
+    """xm_test_unaligned_job (test-only): a batch with its names and qualities and the four result streams, all on the host."""
+    _fields_ = [("num_queries", C.c_int64), ("mate_count", C.c_void_p), ("mate_offset", C.c_void_p), ("mate_length", C.c_void_p), ("codes", C.c_void_p), ("codes_length", C.c_int64),
+                ("names", C.c_void_p), ("name_off", C.c_void_p), ("quals", C.c_void_p), ("qual_off", C.c_void_p), ("has_qual", C.c_void_p), ("num_contigs", C.c_int32), ("reserved", C.c_int32),
+                ("ints", C.c_void_p), ("dbls", C.c_void_p), ("int_off", C.c_void_p), ("dbl_off", C.c_void_p)]
+
+
 class XmBatchSummary(C.Structure):
     """xm_batch_summary: the statistics of a batch's result streams, the penalties of its alignments and its unaligned queries, in pinned buffers of the library."""
     _fields_ = [("num_queries", C.c_int64), ("num_aligned", C.c_int64), ("num_alignments", C.c_int64), ("total_aligned_length", C.c_int64), ("num_indels", C.c_int64),
@@ -102,7 +109,7 @@ class XmTestPileupJob(C.Structure):
                 ("num_events", C.c_int64), ("events", C.c_void_p), ("query_base", C.c_int64)]
 
 
-ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved); xm_batch_stage_fasta came without a new version (no struct or entry changed)
+ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved); xm_batch_stage_fasta came without a new version (no struct or entry changed), and so did xm_unaligned_format_last, xm_context_set_batch_copy and xm_test_unaligned_format
 
 
 class XmIndexInfo(C.Structure):
@@ -113,7 +120,7 @@ class XmIndexInfo(C.Structure):
 
 
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
-           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_batch_stage_fasta", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count"]
+           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_batch_stage_fasta", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count", "xm_unaligned_format_last", "xm_context_set_batch_copy", "xm_test_unaligned_format"]
 
 
 def build_library(force=False):
@@ -236,6 +243,9 @@ def lib():
         L.xm_refs_count_free.argtypes = [C.POINTER(XmRefsCount)]
         L.xm_refs_count_free.restype = None
         L.xm_test_refs_count.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.POINTER(XmRefsCount))]
+        L.xm_unaligned_format_last.argtypes = [C.c_void_p, C.POINTER(C.POINTER(XmSamText))]  # (added without a new ABI version, as xm_batch_stage_fasta)
+        L.xm_context_set_batch_copy.argtypes = [C.c_void_p, C.c_int32]
+        L.xm_test_unaligned_format.argtypes = [C.c_int32, C.POINTER(XmTestUnalignedJob), C.POINTER(C.POINTER(XmSamText))]
         _lib = L
     return _lib
 

@@ -541,6 +541,24 @@ class ReferenceDatabase:
         self._tick("format", time.perf_counter() - t0)
         return BatchSummary(self._L, out)
 
+    def unaligned_format_last(self):
+        """xm_unaligned_format_last: the unaligned-query file's text of the last align call - every query without an alignment as it came in, FASTQ where it
+        came with qualities, else FASTA - made on the GPU from the batch and the result streams where they lie in HBM, while the batch is still resident
+        (align_stream's on_aligned hook is the place) -> SamText, whose `records` counts the mates written.  The batch must have been staged from text
+        (stage_fastq): a batch staged from arrays has no names in HBM.  The bytes equal hostio.Writer's for the same batch and streams;
+        hostio.Writer.write(batch, result, summary=..., unaligned_text=...) writes them."""
+        t0 = time.perf_counter()
+        out = C.POINTER(_capi.XmSamText)()
+        _check(self._L.xm_unaligned_format_last(self._h, C.byref(out)))
+        self._tick("format", time.perf_counter() - t0)
+        return SamText(self._L, out)
+
+    def set_batch_copy(self, on):
+        """xm_context_set_batch_copy: on=False - every later stage_fastq of this context leaves the batch it builds in HBM and copies down only the mate counts,
+        offsets and lengths; the block then has codes = None, block[k] raises, and its _ptr holds no names, codes or qualities.  format_sam_last(None),
+        summary_last, unaligned_format_last and the pile-up read the batch where it lies.  True (the default) brings the copy back."""
+        _check(self._L.xm_context_set_batch_copy(self._h, 1 if on else 0))
+
     def refs_count_last(self, raw=False):
         """xm_refs_count_last: the queries of the last align call counted per combination of contigs - for every query with an alignment the set of contigs
         its alignments lie on - on the GPU while the batch is still resident (align_stream's on_aligned hook is the place), with or without the copy of the

@@ -36,7 +36,12 @@ formatter reads the streams; fine with --out-unaligned, --no-output and --out-mu
 --out-refs-map-count is made on the GPU while a batch and its results are resident, api.ReferenceDatabase.refs_count_last: per batch the queries per
 combination of contigs cross to the host, and the job needs no objects: it streams like any other, parses on the GPU if --parse-on-gpu says so, and
 --out-refs-map-count is then accepted beside --format-on-gpu and --results-on-gpu; same file; not with --per-object; nothing to do without
---out-refs-map-count), and --format-threads <n> (threads of the host's SAM formatter).
+--out-refs-map-count), --unaligned-on-gpu (the unaligned-query file's text is made on the GPU while a batch and its results are resident,
+api.ReferenceDatabase.unaligned_format_last, and the host only writes the bytes: same file; needs --out-unaligned, --parse-on-gpu - the names and qualities
+are then in HBM with the batch - and --results-on-gpu, whose summary the statistics come from), --batch-on-gpu (a batch parsed on the GPU stays there: of
+what the kernels build only the mate counts, offsets and lengths are copied to the host, api.ReferenceDatabase.set_batch_copy(False); same outputs; needs
+--parse-on-gpu and --results-on-gpu, since the host's formatter and writers read the batch, and with --out-unaligned also --unaligned-on-gpu; not with
+--per-object), and --format-threads <n> (threads of the host's SAM formatter).
 
 --out-mutations streams like --out-sam: the device pile-up keeps the bases of every insertion with its event (pileup.MatchDatabase(keep_insert_text=True)), so
 the mutations file needs no object per read; with --per-object it is written the first way, from the Query objects of the whole job, which is the reference
@@ -227,6 +232,10 @@ def parse_args(argv):
             o["results_on_gpu"] = True
         elif a == "--count-refs-on-gpu":  # (not a Mapper flag) the count of --out-refs-map-count is made on the GPU from the resident result streams (api.ReferenceDatabase.refs_count_last)
             o["count_refs_on_gpu"] = True
+        elif a == "--unaligned-on-gpu":  # (not a Mapper flag) the unaligned-query file's text is made on the GPU from the resident batch and streams (api.ReferenceDatabase.unaligned_format_last)
+            o["unaligned_on_gpu"] = True
+        elif a == "--batch-on-gpu":  # (not a Mapper flag) a batch parsed on the GPU stays in HBM: only the mate counts, offsets and lengths come down (api.ReferenceDatabase.set_batch_copy)
+            o["batch_on_gpu"] = True
         elif a == "--format-threads":  # (not a Mapper flag) threads of the host's SAM formatter (hostio.Writer; default: the CPUs, 32 at the most)
             o["format_threads"] = int(argv[i + 1]); i += 1
             if o["format_threads"] < 1:
@@ -271,6 +280,24 @@ def parse_args(argv):
             raise UsageError("--results-on-gpu and --out-refs-map-count exclude each other (the count is made from alignments decoded on the host)")
         if o["out_sam"] and not o.get("format_on_gpu"):
             raise UsageError("--results-on-gpu with --out-sam needs --format-on-gpu (the host's SAM formatter reads the result streams, which stay on the GPU)")
+    if o.get("unaligned_on_gpu"):
+        if o.get("per_object"):
+            raise UsageError("--unaligned-on-gpu and --per-object exclude each other (the per-object path writes the unaligned queries from Python objects)")
+        if not o["out_unaligned"]:
+            raise UsageError("--unaligned-on-gpu has nothing to do without --out-unaligned")
+        if not o.get("parse_on_gpu"):
+            raise UsageError("--unaligned-on-gpu needs --parse-on-gpu (the text is made from the names and qualities that the parser leaves in HBM with the batch)")
+        if not o.get("results_on_gpu"):
+            raise UsageError("--unaligned-on-gpu needs --results-on-gpu (the statistics then come from the summary, not from the host's walk that writes the unaligned queries)")
+    if o.get("batch_on_gpu"):
+        if o.get("per_object"):
+            raise UsageError("--batch-on-gpu and --per-object exclude each other (the per-object path reads the queries into Python objects)")
+        if not o.get("parse_on_gpu"):
+            raise UsageError("--batch-on-gpu needs --parse-on-gpu (only a batch that the GPU parsed from text is there without a host copy)")
+        if not o.get("results_on_gpu"):
+            raise UsageError("--batch-on-gpu needs --results-on-gpu (the host's formatter walks the streams over the batch's arrays, which stay on the GPU)")
+        if o["out_unaligned"] and not o.get("unaligned_on_gpu"):
+            raise UsageError("--batch-on-gpu with --out-unaligned needs --unaligned-on-gpu (the host writes the unaligned queries from the batch's arrays, which stay on the GPU)")
     if o.get("remember") and o.get("remember_per_gpu"):
         raise UsageError("--remember-queries (a memory per context) and --remember-queries-per-gpu (one per GPU) exclude each other")
     return o
@@ -524,7 +551,7 @@ class ObjectSink:
         write_refs_map(path, self.refs_map)
 
 
-def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format_on_gpu=False, results_on_gpu=False, want_unaligned=False, refs_tally=None):
+def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format_on_gpu=False, results_on_gpu=False, want_unaligned=False, refs_tally=None, unaligned_on_gpu=False):
     """The job: the batches stream through the GPU contexts (align_stream: the copy of batch k + 1 overlaps the alignment of batch k; several contexts align
     side by side) and a writer thread hands each batch and its result streams to the sink while the next batches are being aligned; at most `depth` results
     wait for it.  Every batch taken from `batches` is closed, and the first exception - the reader's, the GPU's or the sink's - reaches the caller.
@@ -534,11 +561,13 @@ def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format
     the reader.  results_on_gpu: the results carry no streams (set_result_copy(False) is the caller's); the same hook asks the context for the batch's summary
     (summary_last, with the list of unaligned queries if want_unaligned) behind the text and before the caller's on_aligned, and the summary travels to the
     writer thread with the text; both are closed there, also after a failure.  refs_tally (a RefsTally): the same hook has the context count the batch's queries
-    per combination of contigs (refs_count_last) behind the text and the summary and before the caller's on_aligned."""
+    per combination of contigs (refs_count_last) behind the text and the summary and before the caller's on_aligned.  unaligned_on_gpu (with results_on_gpu):
+    the same hook asks the context for the text of the batch's unaligned queries (unaligned_format_last) behind the summary - which is then asked without the
+    list - and before the caller's on_aligned; the text travels to the writer thread with the SAM text and the summary and is closed there, also after a failure."""
     in_flight = queue.Queue()  # batches in the order they were dealt to the GPUs
     to_write = queue.Queue(maxsize=depth)
     failure = []
-    dealt, texts = {}, {}      # by batch number: the batch on its way to a context; [the text, the summary] its context made of it
+    dealt, texts = {}, {}      # by batch number: the batch on its way to a context; [the text, the summary, the unaligned queries' text] its context made of it
     on_context = format_on_gpu or results_on_gpu or refs_tally is not None
 
     def feed():
@@ -562,11 +591,13 @@ def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format
         def hook(*at):  # ReferenceDatabase.align_stream calls it with (batch), MultiGpuDatabase's with (replica, batch), on the replica's thread
             b = dealt.pop(at[-1])
             context = db.replicas[at[0]] if len(at) > 1 else db
-            made = texts[at[-1]] = [None, None]  # (registered first: what a failing call leaves behind is closed with the rest)
+            made = texts[at[-1]] = [None, None, None]  # (registered first: what a failing call leaves behind is closed with the rest)
             if format_on_gpu:
                 made[0] = context.format_sam_last(None if isinstance(b, hostio.TextBlock) else b)  # (a text block's names are in HBM with the batch)
             if results_on_gpu:
-                made[1] = context.summary_last(want_unaligned=want_unaligned)
+                made[1] = context.summary_last(want_unaligned=want_unaligned and not unaligned_on_gpu)
+            if unaligned_on_gpu:
+                made[2] = context.unaligned_format_last()
             if refs_tally is not None:
                 refs_tally.add(context)
             if on_aligned is not None:
@@ -574,15 +605,16 @@ def stream(db, batches, params, sink, depth, on_aligned=None, tally=None, format
 
     def write_loop():  # (after a failure it keeps taking what comes, unwritten, up to the end mark: the main thread never waits on a full queue for good)
         for b, r, made in iter(to_write.get, None):
-            text, summary = made or (None, None)
+            text, summary, unaligned = made or (None, None, None)
             try:
                 if not failure:
-                    sink.write(b, r, **({"sam_text": text} if text is not None else {}), **({"summary": summary} if summary is not None else {}))
+                    sink.write(b, r, **({"sam_text": text} if text is not None else {}), **({"summary": summary} if summary is not None else {}),
+                               **({"unaligned_text": unaligned} if unaligned is not None else {}))
             except BaseException as e:  # noqa: BLE001  (handed to the main thread)
                 failure.append(e)
             finally:
                 b.close()
-                for held in (text, summary):
+                for held in (text, summary, unaligned):
                     if held is not None:
                         held.close()
 
@@ -671,13 +703,19 @@ def run(argv, out=sys.stdout, open_database=None):
         # lengths and four offsets)
         refs_tally = RefsTally(names) if o.get("count_refs_on_gpu") else None
         refs_arrays = batch_size * 144 if refs_tally is not None else 0
+        # (--unaligned-on-gpu: every context keeps the text of a batch's unaligned queries in HBM - at the most every mate's bases, qualities and name and six
+        # bytes around them - and per query two counts, two offsets and an entry of the list)
+        unaligned_on_gpu = bool(o.get("unaligned_on_gpu"))
+        unaligned_text = batch_size * (2 * (2 * max_len + 200) + 32) if unaligned_on_gpu else 0
         db = (open_database or open_gpu_database)(ordered, devices, max_len, enable_gapmers=o["enable_gapmers"], collapse=o.get("collapse", False),
-                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0) + sam_text + summary_arrays + refs_arrays, **memo)
+                                                  cache_dir=o.get("cache_dir"), per_context_extra=pile_up + o.get("remember", 0) + sam_text + summary_arrays + refs_arrays + unaligned_text, **memo)
         job.callback(db.close)
         if format_on_gpu:
             db.set_sam_contigs(names)
         if results_on_gpu:
             db.set_result_copy(False)
+        if o.get("batch_on_gpu"):
+            db.set_batch_copy(False)
         sam_out = un_out = None
         if o["out_sam"]:
             sam_out = sys.stdout if o["out_sam"] == "-" else job.enter_context(open(o["out_sam"], "w"))
@@ -697,7 +735,7 @@ def run(argv, out=sys.stdout, open_database=None):
         t_stream = time.perf_counter()
         tally = {}
         copies = stream(db, batches, params, sink, 2 * len(devices), on_aligned, tally, format_on_gpu=format_on_gpu, results_on_gpu=results_on_gpu,
-                        want_unaligned=bool(o["out_unaligned"]), refs_tally=refs_tally)
+                        want_unaligned=bool(o["out_unaligned"]), refs_tally=refs_tally, unaligned_on_gpu=unaligned_on_gpu)
         contexts = list(getattr(db, "replicas", [db]))
         spent = lambda key: sum(getattr(c, "seconds", {}).get(key, 0.0) for c in contexts)  # noqa: E731
         # seconds of the job by phase, summed over batches (and over contexts, which work side by side: the sum may exceed the wall time): the reader or cutter,

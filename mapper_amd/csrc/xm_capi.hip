@@ -12,7 +12,8 @@
 // xm_capi_fasta.h (the same from FASTA text of any number of lines a record: the kernels of xm_fasta.h),
 // xm_capi_sam.h (SAM records formatted from the resident results: the kernels of xm_sam.h), xm_capi_summary.h (the statistics, the penalties and the unaligned
 // queries of the resident results: the kernels of xm_summary.h), xm_capi_refs.h (the queries of the resident results counted per combination of contigs: the
-// kernels of xm_refs.h).
+// kernels of xm_refs.h), xm_capi_unaligned.h (the unaligned-query file's text made from the resident batch and results: the kernels of xm_unaligned.h; and
+// the switch that keeps a batch staged from text in HBM).
 // The big kernels are objects of their own, reached through launch functions: the lane-per-read align kernel is xm_align_kernel.hip (xmAlignLaunch,
 // xm_kernel_common.h), the wave-per-read kernels are xm_wave_kernel.hip (xmWaveLaunch, xm_kernel_args.h), the index build on the device is
 // xm_index_device.hip.  This unit uses the host-side pieces of the shared headers only (makeCaps, searchPoolBytes, the pass planner's sizes):
@@ -30,6 +31,7 @@
 #include "xm_fasta.h"
 #include "xm_sam.h"
 #include "xm_summary.h"
+#include "xm_unaligned.h"
 #include "xm_refs.h"
 #include "xm_memo.h"
 #include "xm_conf_table.h"
@@ -216,6 +218,11 @@ struct DeviceBatch {
   DevBuf<char> names;         // the mates' names as xm_batch_stage_fastq built them (xmio_batch's layout: nameOff has 2 * nq + 1 entries), for xm_sam_format_last;
   DevBuf<int64_t> nameOff;    // they belong to the batch, so that they swap with it in xm_batch_commit while the next block is staged
   bool hasNames = false;      // false: a batch copied in from arrays, which have no names
+  DevBuf<char> quals;         // the mates' quality strings the same way (xm_fastq_text.keep_qualities), for xm_unaligned_format_last: staging block k + 1 must not
+  DevBuf<int64_t> qualOff;    // overwrite them while batch k is resident, so they change hands in xm_batch_commit as the names do; hasQual[2 * nq]: the mate
+  DevBuf<uint8_t> hasQual;    // came as FASTQ (written by every parse, with or without kept qualities)
+  bool hasQuals = false;      // true: quals, qualOff and hasQual hold this batch's qualities
+  int64_t codesLength = 0, namesLength = 0, qualsLength = 0;  // the bytes of codes, names and quals that are this batch's (a batch staged from text)
   int64_t nq = -1;            // -1: no batch
   int maxLen = 0;             // longest mate
   bool anyPaired = false;
@@ -230,6 +237,7 @@ struct DeviceBatch {
     nq = -1;
     h2dMs = 0;
     hasNames = false;
+    hasQuals = false;
     if (n > 0) {
       mateCount.ensure((size_t)n); mateOffset.ensure((size_t)n * 2); mateLength.ensure((size_t)n * 2);
       codes.ensure((size_t)b->codes_length); expected.ensure((size_t)n); deviation.ensure((size_t)n);
@@ -254,16 +262,13 @@ struct DeviceBatch {
 };
 
 // What xm_batch_stage_fastq works with besides the staged batch (xm_fastq.h; xm_capi_fastq.h): the text of a block in HBM, the line ends and the fields of its
-// records, the scans' block sums, and the qualities built for the host (the names are the batch's: DeviceBatch).  Empty until the first such call of the context.
+// records, the scans' block sums (the names and the qualities are the batch's: DeviceBatch).  Empty until the first such call of the context.
 struct FastqStage {
   DevBuf<char> dText[2];
   DevBuf<int32_t> dLineEnd[2], dTileCount[2];
   DevBuf<FastqMate> dMates;
   DevBuf<long long> dBlockSums;
   DevBuf<FastqCtl> dCtl;
-  DevBuf<int64_t> dQualOff;
-  DevBuf<uint8_t> dHasQual;
-  DevBuf<char> dQuals;
   DevBuf<FastqMate> dRecs;        // the split form (split_past_size > 0): the fields of every record, its section count, its first query, the scan's block sums
   DevBuf<int32_t> dRecCount;
   DevBuf<int64_t> dRecFirst;
@@ -298,6 +303,19 @@ struct SummaryStage {
   DevBuf<double> dPenalties;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // measure and offsets | (host sizes the arrays) | gather | arrays down
   ~SummaryStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+// What xm_unaligned_format_last works with (xm_unaligned.h; xm_capi_unaligned.h): the record bytes and the unaligned flag per query, the scan's block sums and
+// both offset arrays; the control words; the list of unaligned queries and the text, which only grow; the call's events on the context's stream.  Nothing is
+// allocated before the first call.
+struct UnalignedStage {
+  DevBuf<int32_t> dBytes, dFlag;
+  DevBuf<long long> dBlockB, dBlockU;
+  DevBuf<int64_t> dOff, dUoff, dList;
+  DevBuf<unsigned long long> dCtl;
+  DevBuf<char> dText;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // measure and offsets | (host sizes the list and the text) | compact and write | text down
+  ~UnalignedStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 // What xm_refs_count_last works with (xm_refs.h; xm_capi_refs.h): the table of the sets' fingerprints (keys, the lowest query and the count per slot); per query
@@ -550,6 +568,8 @@ struct xm_index {
   SummaryStage summary;        // xm_summary_last's buffers (under mu)
   RefsStage refs;              // xm_refs_count_last's buffers (under mu)
   bool resultCopy = true;      // xm_context_set_result_copy: an align call copies its four streams to the host (false: they stay in HBM, and the result has none)
+  UnalignedStage unaligned;    // xm_unaligned_format_last's buffers (under mu)
+  bool batchCopy = true;       // xm_context_set_batch_copy: a batch staged from text is copied to the host whole (false: only the mate counts, offsets and lengths; under stageMu)
 
   void initContext() {  // stream and events of this context (the device tables exist)
     dt->contexts.fetch_add(1);
@@ -1621,6 +1641,7 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 #include "xm_capi_sam.h"
 #include "xm_capi_summary.h"
 #include "xm_capi_refs.h"
+#include "xm_capi_unaligned.h"
 #include "xm_capi_test.h"
 #include "xm_capi_fastq.h"
 #include "xm_capi_fasta.h"

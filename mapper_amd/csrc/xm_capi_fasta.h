@@ -68,6 +68,7 @@ int xm_batch_stage_fasta(xm_index* idx, const xm_fasta_text* t, xm_fastq_batch**
     d.nq = -1;
     d.h2dMs = 0;
     d.hasNames = false;
+    d.hasQuals = false;
     HIP_CHECK(hipSetDevice(idx->device));
     for (hipEvent_t& e : f.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
     box = (FastqBox*)calloc(1, sizeof(FastqBox));
@@ -125,18 +126,19 @@ int xm_batch_stage_fasta(xm_index* idx, const xm_fasta_text* t, xm_fastq_batch**
     }
     if (nq > (1ll << 28)) throw std::runtime_error(fastqWhere(0, 0) + "too many records for one text");
     const long long slots = 2 * nq;
-    f.dMates.ensure((size_t)slots); f.dHasQual.ensure((size_t)slots);
+    f.dMates.ensure((size_t)slots); d.hasQual.ensure((size_t)slots);
     f.dBlockSums.ensure((size_t)(3 * ((slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK)));
     d.nameOff.ensure((size_t)slots + 1);
-    if (keepQual) f.dQualOff.ensure((size_t)slots + 1);
+    if (keepQual) d.qualOff.ensure((size_t)slots + 1);
     d.mateCount.ensure((size_t)nq); d.mateOffset.ensure((size_t)slots); d.mateLength.ensure((size_t)slots);
     d.expected.ensure((size_t)nq); d.deviation.ensure((size_t)nq);
     b.num_queries = nq;
     b.mate_count = (int32_t*)g_pinned->get(sizeof(int32_t) * (size_t)nq, &box->bytes[0]);
     b.mate_offset = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)slots, &box->bytes[1]);
     b.mate_length = (int32_t*)g_pinned->get(sizeof(int32_t) * (size_t)slots, &box->bytes[2]);
-    b.name_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[5]);
-    if (keepQual) {
+    const bool copyBatch = idx->batchCopy;  // (xm_context_set_batch_copy(0): the six arrays below and in fastqFinish stay in HBM, and no pinned buffer is taken for them)
+    if (copyBatch) b.name_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[5]);
+    if (keepQual && copyBatch) {
       b.qual_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[7]);
       b.has_qual = (uint8_t*)g_pinned->get((size_t)slots, &box->bytes[8]);
     }
@@ -145,7 +147,7 @@ int xm_batch_stage_fasta(xm_index* idx, const xm_fasta_text* t, xm_fastq_batch**
       if (split > 0) fastqSplitSections(f, d, t->records1, nq, keepQual, s);
       else {
         fastaLines(f, &up, texts, lines, paired, s);
-        FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, f.dHasQual.p, f.dCtl.p};
+        FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, d.hasQual.p, f.dCtl.p};
         hipLaunchKernelGGL(xm_fasta_records_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, texts[0], texts[1], lines[0], lines[1], (long long)nq, paired ? 1 : 0,
                            t->expected_inner, t->deviation, out);
         fastqOffsets(f, d, slots, keepQual, s);
@@ -155,7 +157,7 @@ int xm_batch_stage_fasta(xm_index* idx, const xm_fasta_text* t, xm_fastq_batch**
     });
     if (split == 0) fastaCheckText(ctl, texts, lines, paired);
     else if (ctl.sections != nq) throw std::runtime_error("internal: the section count changed between two launches");
-    fastqFinish(idx, box, ctl, nq, keepQual, split > 0, [&](hipStream_t s) {
+    fastqFinish(idx, box, ctl, nq, keepQual, copyBatch, split > 0, [&](hipStream_t s) {
       hipLaunchKernelGGL(xm_fasta_gather_kernel, dim3((unsigned)((slots + 3) / 4)), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, gather[0], gather[1], (const int64_t*)d.mateOffset.p,
                          (const int64_t*)d.nameOff.p, d.codes.p, d.names.p);
     });

@@ -42,7 +42,7 @@ void fastqLines(FastqStage& f, const xm_fastq_text* t, const FastqText texts[2],
 // stage 3 (the offsets of the mate slots, the totals) on stream s (queued; the caller waits for ev[2])
 void fastqOffsets(FastqStage& f, DeviceBatch& d, long long slots, bool keepQual, hipStream_t s) {
   const long long nBlocks = (slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
-  int64_t* qualOff = keepQual ? f.dQualOff.p : nullptr;
+  int64_t* qualOff = keepQual ? d.qualOff.p : nullptr;
   hipLaunchKernelGGL(xm_fastq_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, f.dBlockSums.p);
   hipLaunchKernelGGL(xm_fastq_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, slots, f.dBlockSums.p, d.nameOff.p, qualOff, f.dCtl.p);
   hipLaunchKernelGGL(xm_fastq_offsets_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, (const long long*)f.dBlockSums.p, d.mateOffset.p,
@@ -55,7 +55,7 @@ void fastqOffsets(FastqStage& f, DeviceBatch& d, long long slots, bool keepQual,
 void fastqParse(FastqStage& f, DeviceBatch& d, const xm_fastq_text* t, const FastqText texts[2], int64_t nq, bool paired, bool keepQual, hipStream_t s) {
   const long long slots = 2 * nq;
   fastqLines(f, t, texts, paired, s);
-  FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, f.dHasQual.p, f.dCtl.p};
+  FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, d.hasQual.p, f.dCtl.p};
   hipLaunchKernelGGL(xm_fastq_fields_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, texts[0], texts[1], (long long)nq, paired ? 1 : 0, t->expected_inner, t->deviation, out);
   fastqOffsets(f, d, slots, keepQual, s);
 }
@@ -76,7 +76,7 @@ void fastqSplitRecords(FastqStage& f, const xm_fastq_text* t, const FastqText te
 // the split form: stage 2c (a lane per section) and stage 3 over the section slots, which the caller has sized for nq queries
 void fastqSplitSections(FastqStage& f, DeviceBatch& d, long long records, int64_t nq, bool keepQual, hipStream_t s) {
   HIP_CHECK(hipEventRecord(f.ev[7], s));
-  FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, f.dHasQual.p, f.dCtl.p};
+  FastqFieldsOut out{f.dMates.p, d.mateCount.p, d.mateLength.p, d.expected.p, d.deviation.p, d.hasQual.p, f.dCtl.p};
   hipLaunchKernelGGL(xm_fastq_split_sections_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, records, (const FastqMate*)f.dRecs.p, (const int64_t*)f.dRecFirst.p, out);
   fastqOffsets(f, d, 2 * nq, keepQual, s);
 }
@@ -92,10 +92,10 @@ void fastqCheckText(const FastqCtl& ctl, const FastqText texts[2], bool paired) 
 }
 
 // What the entries that stage a batch from text do behind stage 3 (xm_batch_stage_fastq, and xm_batch_stage_fasta of xm_capi_fasta.h): the arrays the totals size, stage 4
-// (launchGather queues it on the stream it is given), everything down into the box's pinned buffers, the times of the call's parts, and the host's facts of the batch.
+// (launchGather queues it on the stream it is given), everything down into the box's pinned buffers (copyBatch off: the mate counts, offsets and lengths only), the times of the call's parts, and the host's facts of the batch.
 // splitWaits: the call waited for the section count between ev[6] and ev[7].
 template <class LaunchGather>
-void fastqFinish(xm_index* idx, FastqBox* box, const FastqCtl& ctl, int64_t nq, bool keepQual, bool splitWaits, LaunchGather&& launchGather) {
+void fastqFinish(xm_index* idx, FastqBox* box, const FastqCtl& ctl, int64_t nq, bool keepQual, bool copyBatch, bool splitWaits, LaunchGather&& launchGather) {
   DeviceBatch& d = idx->staged;
   FastqStage& f = idx->fastq;
   xm_fastq_batch& b = box->pub;
@@ -104,11 +104,13 @@ void fastqFinish(xm_index* idx, FastqBox* box, const FastqCtl& ctl, int64_t nq, 
   const size_t nCodes = (size_t)ctl.totals[0], nNames = (size_t)ctl.totals[1], nQuals = (size_t)ctl.totals[2];
   d.codes.ensure(nCodes);
   d.names.ensure(nNames);
-  if (keepQual) f.dQuals.ensure(nQuals);
+  if (keepQual) d.quals.ensure(nQuals);
   b.codes_length = (int64_t)nCodes;
-  b.codes = (uint8_t*)g_pinned->get(nCodes, &box->bytes[3]);
-  b.names = (char*)g_pinned->get(nNames, &box->bytes[4]);
-  if (keepQual) b.quals = (char*)g_pinned->get(nQuals, &box->bytes[6]);
+  if (copyBatch) {
+    b.codes = (uint8_t*)g_pinned->get(nCodes, &box->bytes[3]);
+    b.names = (char*)g_pinned->get(nNames, &box->bytes[4]);
+    if (keepQual) b.quals = (char*)g_pinned->get(nQuals, &box->bytes[6]);
+  }
   idx->dt->onStagingStream([&](hipStream_t s) {
     HIP_CHECK(hipEventRecord(f.ev[3], s));
     launchGather(s);
@@ -117,13 +119,15 @@ void fastqFinish(xm_index* idx, FastqBox* box, const FastqCtl& ctl, int64_t nq, 
     HIP_CHECK(hipMemcpyAsync(b.mate_count, d.mateCount.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(b.mate_offset, d.mateOffset.p, sizeof(int64_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(b.mate_length, d.mateLength.p, sizeof(int32_t) * (size_t)slots, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(b.name_off, d.nameOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
-    if (nCodes) HIP_CHECK(hipMemcpyAsync(b.codes, d.codes.p, nCodes, hipMemcpyDeviceToHost, s));
-    if (nNames) HIP_CHECK(hipMemcpyAsync(b.names, d.names.p, nNames, hipMemcpyDeviceToHost, s));
-    if (keepQual) {
-      HIP_CHECK(hipMemcpyAsync(b.qual_off, f.dQualOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(b.has_qual, f.dHasQual.p, (size_t)slots, hipMemcpyDeviceToHost, s));
-      if (nQuals) HIP_CHECK(hipMemcpyAsync(b.quals, f.dQuals.p, nQuals, hipMemcpyDeviceToHost, s));
+    if (copyBatch) {
+      HIP_CHECK(hipMemcpyAsync(b.name_off, d.nameOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
+      if (nCodes) HIP_CHECK(hipMemcpyAsync(b.codes, d.codes.p, nCodes, hipMemcpyDeviceToHost, s));
+      if (nNames) HIP_CHECK(hipMemcpyAsync(b.names, d.names.p, nNames, hipMemcpyDeviceToHost, s));
+    }
+    if (keepQual && copyBatch) {
+      HIP_CHECK(hipMemcpyAsync(b.qual_off, d.qualOff.p, sizeof(int64_t) * (size_t)(slots + 1), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(b.has_qual, d.hasQual.p, (size_t)slots, hipMemcpyDeviceToHost, s));
+      if (nQuals) HIP_CHECK(hipMemcpyAsync(b.quals, d.quals.p, nQuals, hipMemcpyDeviceToHost, s));
     }
     HIP_CHECK(hipEventRecord(f.ev[5], s));
   });
@@ -150,6 +154,8 @@ void fastqFinish(xm_index* idx, FastqBox* box, const FastqCtl& ctl, int64_t nq, 
   d.maxLen = maxLen;
   d.h2dMs = up;
   d.hasNames = true;
+  d.hasQuals = keepQual;
+  d.codesLength = (int64_t)nCodes; d.namesLength = (int64_t)nNames; d.qualsLength = keepQual ? (int64_t)nQuals : 0;
   d.nq = nq;
 }
 
@@ -190,6 +196,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     d.nq = -1;
     d.h2dMs = 0;
     d.hasNames = false;
+    d.hasQuals = false;
     HIP_CHECK(hipSetDevice(idx->device));
     for (hipEvent_t& e : f.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
     box = (FastqBox*)calloc(1, sizeof(FastqBox));
@@ -225,18 +232,19 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
       if (nq > (1ll << 28)) throw std::runtime_error(fastqWhere(0, 0) + "too many sections for one text (" + std::to_string(nq) + ")");
     }
     const long long slots = 2 * nq;
-    f.dMates.ensure((size_t)slots); f.dHasQual.ensure((size_t)slots);
+    f.dMates.ensure((size_t)slots); d.hasQual.ensure((size_t)slots);
     f.dBlockSums.ensure((size_t)(3 * ((slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK)));
     d.nameOff.ensure((size_t)slots + 1);
-    if (keepQual) f.dQualOff.ensure((size_t)slots + 1);
+    if (keepQual) d.qualOff.ensure((size_t)slots + 1);
     d.mateCount.ensure((size_t)nq); d.mateOffset.ensure((size_t)slots); d.mateLength.ensure((size_t)slots);
     d.expected.ensure((size_t)nq); d.deviation.ensure((size_t)nq);
     b.num_queries = nq;
     b.mate_count = (int32_t*)g_pinned->get(sizeof(int32_t) * (size_t)nq, &box->bytes[0]);
     b.mate_offset = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)slots, &box->bytes[1]);
     b.mate_length = (int32_t*)g_pinned->get(sizeof(int32_t) * (size_t)slots, &box->bytes[2]);
-    b.name_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[5]);
-    if (keepQual) {
+    const bool copyBatch = idx->batchCopy;  // (xm_context_set_batch_copy(0): the six arrays below and in fastqFinish stay in HBM, and no pinned buffer is taken for them)
+    if (copyBatch) b.name_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[5]);
+    if (keepQual && copyBatch) {
       b.qual_off = (int64_t*)g_pinned->get(sizeof(int64_t) * (size_t)(slots + 1), &box->bytes[7]);
       b.has_qual = (uint8_t*)g_pinned->get((size_t)slots, &box->bytes[8]);
     }
@@ -249,10 +257,10 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     });
     if (split == 0) fastqCheckText(ctl, texts, paired);
     else if (ctl.sections != nq) throw std::runtime_error("internal: the section count changed between two launches");
-    fastqFinish(idx, box, ctl, nq, keepQual, split > 0, [&](hipStream_t s) {
+    fastqFinish(idx, box, ctl, nq, keepQual, copyBatch, split > 0, [&](hipStream_t s) {
       hipLaunchKernelGGL(xm_fastq_gather_kernel, dim3((unsigned)((slots + 3) / 4)), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, (const char*)f.dText[0].p, (const char*)f.dText[1].p,
-                         (const int64_t*)d.mateOffset.p, (const int64_t*)d.nameOff.p, (const int64_t*)(keepQual ? f.dQualOff.p : nullptr), d.codes.p, d.names.p,
-                         keepQual ? f.dQuals.p : nullptr);
+                         (const int64_t*)d.mateOffset.p, (const int64_t*)d.nameOff.p, (const int64_t*)(keepQual ? d.qualOff.p : nullptr), d.codes.p, d.names.p,
+                         keepQual ? d.quals.p : nullptr);
     });
     *outBatch = &box->pub;
     return 0;

@@ -188,6 +188,70 @@ int xm_test_summary(int32_t device, int64_t num_queries, int32_t num_contigs, co
   } catch (std::exception& e) { return fail(std::string("xm_test_summary: ") + e.what()); }
 }
 
+// Test-only entry (tests/test_gpu_unaligned.py): xm_unaligned_format_last's kernels over host-given batch arrays, names, qualities, has_qual and the four
+// result streams - no index and no alignment.  The host checks what the kernels take on trust from the library's own stages: counts, and offsets that start
+// at 0 and never fall.  What lies inside a slice may be anything, and a mate may lie anywhere: the kernels clip their loads to the arrays.
+int xm_test_unaligned_format(int32_t device, const xm_test_unaligned_job* t, xm_sam_text** out) {
+  if (!t || !out) return fail("xm_test_unaligned_format: null argument");
+  *out = nullptr;
+  try {
+    const int64_t nq = t->num_queries;
+    if (nq < 0 || t->num_contigs < 0 || t->codes_length < 0) throw std::runtime_error("negative size");
+    UnalignedStage g;
+    if (nq == 0) {
+      xm::UnalignedBatch none;
+      memset(&none, 0, sizeof(none));
+      *out = &unalignedFormat(g, none, xm::SummaryStreams{nullptr, nullptr, nullptr, nullptr, t->num_contigs}, nullptr)->pub;
+      return 0;
+    }
+    if (!t->mate_count || !t->mate_offset || !t->mate_length || !t->names || !t->name_off || !t->int_off || !t->dbl_off) throw std::runtime_error("null array");
+    const bool withQual = t->has_qual != nullptr;
+    if (withQual && (!t->quals || !t->qual_off)) throw std::runtime_error("has_qual without quals and qual_off");
+    for (int64_t q = 0; q < nq; q++) if (t->mate_count[q] < 1 || t->mate_count[q] > 2) throw std::runtime_error("mate_count must be 1 or 2");
+    const int64_t nameBytes = samCheckNameOffsets(t->name_off, nq);
+    int64_t qualBytes = 0;
+    if (withQual) {
+      if (t->qual_off[0] != 0) throw std::runtime_error("qual_off must start at 0");
+      for (int64_t i = 0; i < 2 * nq; i++) if (t->qual_off[i + 1] < t->qual_off[i]) throw std::runtime_error("qual_off falls at entry " + std::to_string(i + 1));
+      qualBytes = t->qual_off[2 * nq];
+    }
+    if (t->int_off[0] != 0 || t->dbl_off[0] != 0) throw std::runtime_error("stream offsets must start at 0");
+    for (int64_t q = 0; q < nq; q++) if (t->int_off[q + 1] < t->int_off[q] || t->dbl_off[q + 1] < t->dbl_off[q]) throw std::runtime_error("stream offsets fall");
+    const size_t nInts = (size_t)t->int_off[nq], nDbls = (size_t)t->dbl_off[nq];
+    if ((nInts && !t->ints) || (nDbls && !t->dbls) || (t->codes_length && !t->codes)) throw std::runtime_error("null array");
+    if (device >= 0) HIP_CHECK(hipSetDevice(device));
+    DevBuf<int32_t> dCount, dLength, dInts;
+    DevBuf<int64_t> dMateOff, dIntOff, dDblOff, dNameOff, dQualOff;
+    DevBuf<uint8_t> dCodes, dHasQual;
+    DevBuf<char> dNames, dQuals;
+    DevBuf<double> dDbls;
+    const size_t slots = (size_t)nq * 2;
+    dCount.ensure((size_t)nq); dLength.ensure(slots); dMateOff.ensure(slots); dCodes.ensure((size_t)t->codes_length); dNames.ensure((size_t)nameBytes); dNameOff.ensure(slots + 1);
+    dInts.ensure(nInts); dDbls.ensure(nDbls); dIntOff.ensure((size_t)nq + 1); dDblOff.ensure((size_t)nq + 1);
+    HIP_CHECK(hipMemcpy(dCount.p, t->mate_count, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dLength.p, t->mate_length, sizeof(int32_t) * slots, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dMateOff.p, t->mate_offset, sizeof(int64_t) * slots, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dNameOff.p, t->name_off, sizeof(int64_t) * (slots + 1), hipMemcpyHostToDevice));
+    if (nameBytes) HIP_CHECK(hipMemcpy(dNames.p, t->names, (size_t)nameBytes, hipMemcpyHostToDevice));
+    if (t->codes_length) HIP_CHECK(hipMemcpy(dCodes.p, t->codes, (size_t)t->codes_length, hipMemcpyHostToDevice));
+    if (withQual) {
+      dQuals.ensure((size_t)qualBytes); dQualOff.ensure(slots + 1); dHasQual.ensure(slots);
+      HIP_CHECK(hipMemcpy(dQualOff.p, t->qual_off, sizeof(int64_t) * (slots + 1), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dHasQual.p, t->has_qual, slots, hipMemcpyHostToDevice));
+      if (qualBytes) HIP_CHECK(hipMemcpy(dQuals.p, t->quals, (size_t)qualBytes, hipMemcpyHostToDevice));
+    }
+    if (nInts) HIP_CHECK(hipMemcpy(dInts.p, t->ints, sizeof(int32_t) * nInts, hipMemcpyHostToDevice));
+    if (nDbls) HIP_CHECK(hipMemcpy(dDbls.p, t->dbls, sizeof(double) * nDbls, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dIntOff.p, t->int_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dDblOff.p, t->dbl_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    const xm::UnalignedBatch b{nq, dCount.p, dMateOff.p, dLength.p, dCodes.p, t->codes_length, dNames.p, dNameOff.p, nameBytes,
+                               withQual ? dQuals.p : nullptr, withQual ? dQualOff.p : nullptr, withQual ? dHasQual.p : nullptr, qualBytes};
+    SamBox* box = unalignedFormat(g, b, xm::SummaryStreams{dInts.p, dDbls.p, dIntOff.p, dDblOff.p, t->num_contigs}, nullptr);
+    *out = &box->pub;
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_test_unaligned_format: ") + e.what()); }
+}
+
 // Test-only entry (tests/test_gpu_refs_count.py): xm_refs_count_last's kernels over host-given result streams - no index and no alignment -, with the sets'
 // fingerprints cut to fingerprint_bits bits (64 and more: whole).  The host checks what xm_test_summary checks.
 int xm_test_refs_count(int32_t device, int64_t num_queries, int32_t num_contigs, const int32_t* ints, const double* dbls, const int64_t* int_off, const int64_t* dbl_off,

@@ -1,0 +1,109 @@
+// xm_unaligned_format_last, xm_context_set_batch_copy (included once, by xm_capi.hip, behind xm_capi_sam.h and xm_capi_summary.h): the unaligned-query file's
+// text of the last align call made by the kernels of xm_unaligned.h from the batch and the streams where they lie in HBM - xm_summary_last's contract (the
+// context's mutex and stream, ResultStage::lastStreams) - and copied to a pinned buffer of the library's pool; and the switch that then lets a batch staged
+// from text stay in HBM.  unalignedFormat is the part that xm_test_unaligned_format (xm_capi_test.h) runs over host-given arrays as well.
+#pragma once
+
+namespace {
+
+// The four stages on stream s over a batch and streams in HBM.  Returns the text in a pinned buffer (an xm_sam_text: records = the mates written, h2d_ms = 0), or
+// throws: a malformed slice gives no text.  Nothing is launched for a batch of 0 queries, and nothing behind the totals for one without an unaligned query.
+SamBox* unalignedFormat(UnalignedStage& g, const xm::UnalignedBatch& b, const xm::SummaryStreams& st, hipStream_t s) {
+  const int64_t nq = b.nq;
+  SamBox* box = (SamBox*)calloc(1, sizeof(SamBox));
+  if (!box) throw std::runtime_error("out of host memory");
+  box->pub.store = box;
+  try {
+    if (nq == 0) {  // (a text of 0 bytes still has a buffer to give back, as xm_sam_format_last's has)
+      box->pub.text = (char*)g_pinned->get(1, &box->bytesText);
+      return box;
+    }
+    for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+    // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
+    const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
+    g.dBytes.ensure((size_t)nq); g.dFlag.ensure((size_t)nq); g.dOff.ensure((size_t)nq + 1); g.dUoff.ensure((size_t)nq + 1);
+    g.dBlockB.ensure((size_t)nBlocks); g.dBlockU.ensure((size_t)nBlocks); g.dCtl.ensure(XM_UNALIGNED_CTL_WORDS);
+    const unsigned grid = (unsigned)((nq + 255) / 256);
+    unsigned long long ctl[XM_UNALIGNED_CTL_WORDS] = {XM_UNALIGNED_NO_ERROR, 0, XM_UNALIGNED_NO_ERROR, 0};
+    int64_t totals[2] = {0, 0};
+    HIP_CHECK(hipEventRecord(g.ev[0], s));
+    HIP_CHECK(hipMemcpyAsync(g.dCtl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(xm_unaligned_measure_kernel, dim3(grid), dim3(256), 0, s, b, st, g.dBytes.p, g.dFlag.p, g.dCtl.p);
+    hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dBytes.p, (const int32_t*)g.dFlag.p, g.dBlockB.p, g.dBlockU.p);
+    hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, g.dBlockB.p, g.dBlockU.p, g.dOff.p, g.dUoff.p);
+    hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dBytes.p, (const int32_t*)g.dFlag.p,
+                       (const long long*)g.dBlockB.p, (const long long*)g.dBlockU.p, g.dOff.p, g.dUoff.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(g.ev[1], s));
+    HIP_CHECK(hipMemcpyAsync(ctl, g.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&totals[0], g.dOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&totals[1], g.dUoff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));  // (the one wait for the totals and the control words)
+    if (ctl[0] != XM_UNALIGNED_NO_ERROR) throw std::runtime_error("malformed result streams: query " + std::to_string(ctl[0]));
+    if (ctl[2] != XM_UNALIGNED_NO_ERROR) throw std::runtime_error("the record of query " + std::to_string(ctl[2]) + " is longer than 2^31 - 1 bytes");
+    const size_t total = (size_t)totals[0], nUn = (size_t)totals[1];
+    float measure = 0, write = 0, down = 0;
+    HIP_CHECK(hipEventElapsedTime(&measure, g.ev[0], g.ev[1]));
+    box->pub.records = (int64_t)ctl[1];
+    box->pub.text = (char*)g_pinned->get(total ? total : 1, &box->bytesText);
+    box->pub.bytes = (int64_t)total;
+    if (total && nUn) {
+      g.dList.ensure(nUn); g.dText.ensure(total);
+      HIP_CHECK(hipEventRecord(g.ev[2], s));
+      hipLaunchKernelGGL(xm_unaligned_compact_kernel, dim3(grid), dim3(256), 0, s, (long long)nq, (const int64_t*)g.dUoff.p, g.dList.p, (long long)nUn);
+      const unsigned waves = (unsigned)std::min<size_t>(nUn, 16384);  // (a wavefront takes every waves-th entry of the list)
+      hipLaunchKernelGGL(xm_unaligned_write_kernel, dim3(waves), dim3(64), 0, s, b, (const int64_t*)g.dList.p, (long long)nUn, (const int64_t*)g.dOff.p, g.dText.p, (long long)total, g.dCtl.p);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(g.ev[3], s));
+      HIP_CHECK(hipMemcpyAsync(box->pub.text, g.dText.p, total, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(ctl, g.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipEventRecord(g.ev[4], s));
+      HIP_CHECK(hipEventSynchronize(g.ev[4]));
+      if (ctl[3] != 0) throw std::runtime_error("internal error: the records of " + std::to_string(ctl[3]) + " queries did not end where they were measured to");
+      HIP_CHECK(hipEventElapsedTime(&write, g.ev[2], g.ev[3]));
+      HIP_CHECK(hipEventElapsedTime(&down, g.ev[3], g.ev[4]));
+    }
+    box->pub.kernel_ms = (double)measure + write; box->pub.d2h_ms = down;
+    return box;
+  } catch (...) {
+    (void)hipStreamSynchronize(s);  // (nothing of this call is still in flight when its buffers go)
+    if (box->pub.text) freeSamBox(box); else free(box);
+    throw;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int xm_unaligned_format_last(xm_index* idx, xm_sam_text** out) {
+  if (!idx || !out) return fail("xm_unaligned_format_last: null argument");
+  *out = nullptr;
+  if (idx->hostOnly) return fail("xm_unaligned_format_last: index was built with host_only=1");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
+    if (last.nq < 0)
+      throw std::runtime_error("the batch of the last align call is no longer resident (call xm_unaligned_format_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
+    const DeviceBatch& d = idx->resident;
+    if (!d.hasNames)
+      throw std::runtime_error("the resident batch has no names in HBM (it was staged from arrays, not by xm_batch_stage_fastq or xm_batch_stage_fasta)");
+    HIP_CHECK(hipSetDevice(idx->device));
+    const bool q = d.hasQuals;
+    const xm::UnalignedBatch b{last.nq, d.mateCount.p, d.mateOffset.p, d.mateLength.p, d.codes.p, d.codesLength, d.names.p, d.nameOff.p, d.namesLength,
+                               q ? d.quals.p : nullptr, q ? d.qualOff.p : nullptr, q ? d.hasQual.p : nullptr, q ? d.qualsLength : 0};
+    const xm::SummaryStreams st{last.ints, last.dbls, last.intOff, last.dblOff, (int32_t)idx->host().numContigs()};
+    SamBox* box = unalignedFormat(idx->unaligned, b, st, idx->stream);
+    *out = &box->pub;
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_unaligned_format_last: ") + e.what()); }
+}
+
+int xm_context_set_batch_copy(xm_index* idx, int32_t on) {
+  if (!idx) return fail("xm_context_set_batch_copy: null argument");
+  std::lock_guard<std::mutex> stageLock(idx->stageMu);  // (the staging calls read it under this lock)
+  idx->batchCopy = on != 0;
+  return 0;
+}
+
+}  // extern "C"

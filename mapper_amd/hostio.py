@@ -137,7 +137,8 @@ class TextBlock:
     lines, whose line counts lines(which) then go to the parser too - for api.ReferenceDatabase.stage_fastq: the GPU parses it.  Before it
     is staged it offers num_queries and longest_line (an upper bound of the longest mate); once staged - the text is released then - it offers what Batch
     does: the six arrays(), mate_count / mate_offset / mate_length / codes, and a _ptr that Writer.write takes (an XmioBatch over the arrays the library
-    returned, store NULL).  block[k] is the mates of query k, as pileup.MatchDatabase.add_last(queries=block) reads them.  split > 0: the block was cut
+    returned, store NULL).  block[k] is the mates of query k, as pileup.MatchDatabase.add_last(queries=block) reads them.  Staged by a context with
+    set_batch_copy(False) the batch stays in HBM: codes is None, on_host False, block[k] raises a ValueError, and _ptr holds no names, codes or qualities.  split > 0: the block was cut
     for a parser that cuts every record into sections of at most that many bases (read_text_blocks(split=...)); num_queries counts the sections."""
 
     def __init__(self, ptr, keep_qualities, expected_inner, deviation, split=0):
@@ -177,7 +178,9 @@ class TextBlock:
         self.mate_count = np.ctypeslib.as_array(f.mate_count, shape=(n,))
         self.mate_offset = np.ctypeslib.as_array(f.mate_offset, shape=(2 * n,))
         self.mate_length = np.ctypeslib.as_array(f.mate_length, shape=(2 * n,))
-        self.codes = np.ctypeslib.as_array(f.codes, shape=(max(int(f.codes_length), 1),))
+        # (a context with set_batch_copy(False) leaves codes, names and qualities in HBM: the library returns NULL for them)
+        self.codes = np.ctypeslib.as_array(f.codes, shape=(max(int(f.codes_length), 1),)) if f.codes else None
+        self.on_host = bool(f.codes) and bool(f.names)
         paired = self.mate_count > 1
         self.expected_inner = np.where(paired, self.pair_spacing[0], 0.0)
         self.deviation = np.where(paired, self.pair_spacing[1], 1.0)
@@ -194,6 +197,8 @@ class TextBlock:
 
     def __getitem__(self, k):
         self.arrays()
+        if self.codes is None:
+            raise ValueError("the batch stayed in HBM (ReferenceDatabase.set_batch_copy(False)): its bases are not on the host")
         return [self.codes[self.mate_offset[2 * k + m]:self.mate_offset[2 * k + m] + self.mate_length[2 * k + m]] for m in range(int(self.mate_count[k]))]
 
     def _release_text(self):
@@ -270,12 +275,21 @@ class Writer:
         self.threads = int(threads or min(32, os.cpu_count() or 1))
         self.seconds = {"format": 0.0, "write": 0.0}  # wall seconds of the write() calls so far: formatting on the host (and counting), and writing the files
 
-    def write(self, batch, result, sam_text=None, summary=None):
+    def write(self, batch, result, sam_text=None, summary=None, unaligned_text=None):
         """result: anything with ints / dbls / int_off / dbl_off (api.BatchResult).  sam_text: the batch's SAM records as the GPU formatted them
         (api.SamText, or any bytes-like object): they are written as they are, and the native call only counts the statistics and writes the unaligned queries.
         summary: what the GPU counted of the streams (api.BatchSummary, or anything with its fields): the statistics and the unaligned queries come from it
         (xmio_write_summary) and none of result's streams is read - a result whose streams stayed in HBM has none.  A writer with a SAM file then needs the
-        text too, and one with an unaligned-query file a summary that was asked for the list."""
+        text too, and one with an unaligned-query file a summary that was asked for the list.  unaligned_text: the batch's unaligned queries as the GPU wrote
+        them (api.ReferenceDatabase.unaligned_format_last, or any bytes-like object): they are written as they are to the unaligned-query file, and the native
+        call gets unaligned_fd = -1; it needs a summary, which the statistics come from (the list is not needed).  A batch that stayed in HBM
+        (set_batch_copy(False)) has no arrays on the host to write its unaligned queries from: with an unaligned-query file it needs the text."""
+        if unaligned_text is not None and summary is None:
+            raise ValueError("the text of the unaligned queries comes with a summary, which the statistics are made of (summary=)")
+        if self._un is not None and unaligned_text is None and not getattr(batch, "on_host", True):
+            raise ValueError("the batch stayed in HBM (set_batch_copy(False)) and has no arrays on the host: with an unaligned-query file the text must be given (unaligned_text)")
+        if summary is None and not getattr(batch, "on_host", True):
+            raise ValueError("the batch stayed in HBM (set_batch_copy(False)) and has no arrays on the host for the host's formatter to read: give a summary (and the texts)")
         for f in (self._sam, self._un):
             if f is not None:
                 f.flush()
@@ -289,6 +303,15 @@ class Writer:
             self.seconds["write"] += time.perf_counter() - t0
             sam_fd = -1
         un_fd = self._un.fileno() if self._un is not None else -1
+        if unaligned_text is not None and un_fd >= 0:
+            t0 = time.perf_counter()
+            view = unaligned_text.view() if hasattr(unaligned_text, "view") else memoryview(unaligned_text)
+            done = 0
+            while done < len(view):
+                done += os.write(un_fd, view[done:])
+            self.seconds["write"] += time.perf_counter() - t0
+        if unaligned_text is not None:
+            un_fd = -1
         if summary is not None:
             if sam_fd >= 0:
                 raise ValueError("a summary holds no alignments to format: with a SAM file the text must be given as well (sam_text)")

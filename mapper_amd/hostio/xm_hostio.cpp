@@ -922,6 +922,9 @@ int xmio_write_summary(const xmio_batch* b, int64_t num_aligned, int64_t total_a
   for (int64_t i = 0; i < num_unaligned; i++)
     if (unaligned[i] < 0 || unaligned[i] >= nq || (i > 0 && unaligned[i] <= unaligned[i - 1]))
       return fail("xmio_write_summary: the list of unaligned queries is not strictly ascending inside the batch (entry " + std::to_string(i) + ")");
+  if (unaligned_fd >= 0 && num_unaligned > 0 && (!b->names || !b->codes || !b->name_off || !b->mate_count || !b->mate_offset || !b->mate_length))
+    return fail("xmio_write_summary: the batch has no names or codes on the host (it stayed in HBM: xm_context_set_batch_copy(0)), so its unaligned queries cannot be written from it "
+                "(write the text of xm_unaligned_format_last and pass unaligned_fd = -1)");
   if (unaligned_fd >= 0) {
     std::string un;
     for (int64_t i = 0; i < num_unaligned; i++) {

@@ -98,6 +98,15 @@ class MultiGpuDatabase:
         """ReferenceDatabase.summary_last of replica `replica` (align_stream's on_aligned hook names it), on that replica's thread."""
         return self.replicas[replica].summary_last(want_unaligned)
 
+    def unaligned_format_last(self, replica):
+        """ReferenceDatabase.unaligned_format_last of replica `replica` (align_stream's on_aligned hook names it), on that replica's thread."""
+        return self.replicas[replica].unaligned_format_last()
+
+    def set_batch_copy(self, on):
+        """ReferenceDatabase.set_batch_copy for every replica."""
+        for r in self.replicas:
+            r.set_batch_copy(on)
+
     def refs_count_last(self, replica, raw=False):
         """ReferenceDatabase.refs_count_last of replica `replica` (align_stream's on_aligned hook names it), on that replica's thread."""
         return self.replicas[replica].refs_count_last(raw)
