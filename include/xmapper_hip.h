@@ -128,7 +128,8 @@ const char* xm_build_stamp(void);
  * xm_test_pileup_text); 10 = xm_context_set_result_copy, xm_summary_last, xm_summary_free (and the test-only xm_test_summary);
  * 11 = xm_refs_count_last, xm_refs_count_free (and the test-only xm_test_refs_count); 12 = xm_fastq_text.reserved becomes split_past_size (same layout; 0 is
  * what every caller passed).  xm_batch_stage_fasta was added without a new version: it changes no struct and no entry, so the version stays 12 and a
- * caller that wants it looks the symbol up (a library of version 12 built before it does not export it).  A binding checks the version once
+ * caller that wants it looks the symbol up (a library of version 12 built before it does not export it); xm_pileup_absorb, xm_pileup_call_snps,
+ * xm_snp_calls_free, xm_pileup_judge_indels and xm_mutations_block_positions (and the test-only xm_test_pileup_call) came the same way.  A binding checks the version once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -471,6 +472,50 @@ int64_t xm_pileup_events(xm_pileup* pileup, int64_t first, int64_t n, int64_t* o
 int xm_pileup_keep_insert_text(xm_pileup* pileup, int32_t on);
 int64_t xm_pileup_event_text(xm_pileup* pileup, int64_t first, int64_t n, int64_t* text_off /* [m + 1] */, char* text, int64_t text_cap);
 void xm_pileup_free(xm_pileup* pileup);
+/* (added without a new ABI version, as xm_unaligned_format_last was: no struct or entry changed; look them up by name)  The end of the mutations file on
+ * the device: the counts stay where they are and only the answer crosses to the host - the SNP rows and, per indel candidate, a verdict.  The host path
+ * (xm_pileup_read, xm_pileup_read_middle and the thresholds of mapper_amd/pileup.py) is the definition; mapper_amd/csrc/xm_mutations_rules.h states the rules as
+ * the code the kernels run.  Not used by the Java host.  All three calls have xm_pileup_read's contract: they synchronise the device first, no
+ * xm_pileup_add_last may run on the pile-up(s) meanwhile, and they need no live context.
+ * The thresholds (MutationDetectionParameters [QuickVariants], Mapper.java:208-230): a pair (total depth, fraction) drops what it judges when the total depth
+ * at the position is below the first, or when (float)support < (float)fraction * (float)total with the product taken in float32. */
+typedef struct xm_mutation_filter {
+  double min_snp_total_depth, min_indel_total_start_depth, min_indel_continuation_total_depth;
+  float min_snp_depth_fraction, min_indel_start_depth_fraction, min_indel_continuation_depth_fraction;
+  int32_t reserved;
+} xm_mutation_filter;
+/* xm_pileup_absorb moves the counts of `from` into `into`: into += from, from = 0, over depth, the four alt planes and the middle depth; the sum over both is
+ * what it was, so xm_pileup_read over all pile-ups of a run gives the same sums before and after.  Events and kept insertion text stay with the pile-up that
+ * collected them.  On one GPU it is one kernel; from another GPU, chunks come by peer copy into a buffer on into's GPU, are added there and cleared at the
+ * source.  A `from` whose counts an earlier call moved away, and that no xm_pileup_add_last has added to since, holds zeros and is skipped.  Fails for a
+ * null argument, the same handle twice, pile-ups of different indexes, different query-end fractions, and a `from` on a GPU that into's
+ * GPU cannot reach by peer copy. */
+int xm_pileup_absorb(xm_pileup* into, xm_pileup* from);
+/* The SNP rows of the pile-up: one per (forward position, letter A, C, G, T by index 0..3) whose alt count is not 0 and passes the SNP pair over the depth at
+ * the position; ordered by contig, position, letter.  Two passes over the counts and a scan over one count per XM_MUTATIONS_BLOCK positions
+ * (xm_mutations_block_positions()); the rows come in a pinned buffer of the library (rows NULL when there are none - nothing is launched behind the total
+ * then).  bytes_to_host: what the call copied to the host. */
+typedef struct xm_snp_row {
+  int32_t contig, position;              /* position: 0-based in the contig */
+  uint8_t letter, reference_code, reserved[6];
+  uint64_t support_units, total_units;   /* in units of 1 / XM_PILEUP_UNIT */
+} xm_snp_row;
+typedef struct xm_snp_calls {
+  int64_t num_rows; xm_snp_row* rows;
+  int64_t positions, bytes_to_host;
+  double kernel_ms, d2h_ms;
+  void* store;
+} xm_snp_calls;
+int xm_pileup_call_snps(xm_pileup* pileup, const xm_mutation_filter* filter, xm_snp_calls** out);
+void xm_snp_calls_free(xm_snp_calls* calls);
+int64_t xm_mutations_block_positions(void);
+/* Indel candidates judged over the middle depth (the depth itself without a query-end fraction): candidate i = (contig, kind 1 insertion / 2 deletion, 1-based
+ * pos1, length, support in units) gets verdicts[i] = (middle depth in units where it starts, keep), keep 0 when the start pair drops it, else 1 .. length: it
+ * is cut in front of the first further base that the continuation pair drops (a deletion's bases where they lie, an insertion's all at its one position; no
+ * position leaves the candidate's contig).  n = 0 launches nothing.  Fails for a contig outside of the reference or without bases, a kind other than 1 or 2. */
+typedef struct xm_indel_candidate { int32_t contig, kind; int64_t pos1, length; uint64_t support_units; } xm_indel_candidate;
+typedef struct xm_indel_verdict { uint64_t total_units; int64_t keep; } xm_indel_verdict;
+int xm_pileup_judge_indels(xm_pileup* pileup, const xm_mutation_filter* filter, const xm_indel_candidate* candidates, int64_t n, xm_indel_verdict* verdicts);
 
 /* TEST-ONLY entry (tests/test_gpu_kat.py; not part of the drop-in boundary): the reference's component-level known-answer tests run by the
  * device code of the align kernels over two given texts.  chain 0 = PathAligner alone (PathAligner_Test.java:10-39): mode 0 the lane-per-read
@@ -526,6 +571,19 @@ int xm_test_unaligned_format(int32_t device, const xm_test_unaligned_job* job, x
  * alignment.  fingerprint_bits < 64 keeps only that many bits of the sets' fingerprints, so that different sets collide.  Same result, same errors. */
 int xm_test_refs_count(int32_t device, int64_t num_queries, int32_t num_contigs, const int32_t* ints, const double* dbls,
                        const int64_t* int_off, const int64_t* dbl_off, int32_t fingerprint_bits, xm_refs_count** out);
+/* Test-only (tests/test_gpu_mutations.py): the kernels of xm_pileup_absorb, xm_pileup_call_snps and xm_pileup_judge_indels over host-given counts on `device`; no
+ * index, no alignment and no pile-up.  contig_lengths[num_contigs] (every one >= 1); one or two sets of counts in units - depth[total], alt[4][total] and
+ * middle[total] (NULL in every set: the middle depth is the depth) -; with two sets the second is first absorbed into the first.  The rows (their
+ * reference_code is 0: there is no reference) and the verdicts are those of set 0 afterwards; read_back[s] (may be NULL) receives set s as it then lies in HBM:
+ * depth, the four alt planes and, when given, the middle depth, total entries each.  Same results, same errors. */
+typedef struct xm_test_mutations_job {
+  int32_t num_contigs, num_sets; const int32_t* contig_lengths;
+  const uint64_t* depth[2]; const uint64_t* alt[2]; const uint64_t* middle[2];
+  const xm_mutation_filter* filter;
+  int64_t num_candidates; const xm_indel_candidate* candidates; xm_indel_verdict* verdicts;
+  uint64_t* read_back[2];
+} xm_test_mutations_job;
+int xm_test_pileup_call(int32_t device, const xm_test_mutations_job* job, xm_snp_calls** out);
 /* Test-only: Double.toString as the SAM tags print it, run by the device on n values: out24[24 * i ...] the string of x[i] (padded with NUL), len[i] its length. */
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len);
 

@@ -109,7 +109,37 @@ class XmTestPileupJob(C.Structure):
                 ("num_events", C.c_int64), ("events", C.c_void_p), ("query_base", C.c_int64)]
 
 
-ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved); xm_batch_stage_fasta came without a new version (no struct or entry changed), and so did xm_unaligned_format_last, xm_context_set_batch_copy and xm_test_unaligned_format
+class XmMutationFilter(C.Structure):
+    """xm_mutation_filter: MutationDetectionParameters - the total-depth thresholds as doubles, the fractions as floats."""
+    _fields_ = [("min_snp_total_depth", C.c_double), ("min_indel_total_start_depth", C.c_double), ("min_indel_continuation_total_depth", C.c_double),
+                ("min_snp_depth_fraction", C.c_float), ("min_indel_start_depth_fraction", C.c_float), ("min_indel_continuation_depth_fraction", C.c_float), ("reserved", C.c_int32)]
+
+
+class XmSnpRow(C.Structure):
+    """xm_snp_row: a SNP row of the device pile-up (position 0-based in the contig, letter the index into ACGT, the depths in units)."""
+    _fields_ = [("contig", C.c_int32), ("position", C.c_int32), ("letter", C.c_uint8), ("reference_code", C.c_uint8), ("reserved", C.c_uint8 * 6),
+                ("support_units", C.c_uint64), ("total_units", C.c_uint64)]
+
+
+SNP_ROW = np.dtype({"names": ["contig", "position", "letter", "reference_code", "support_units", "total_units"], "formats": [np.int32, np.int32, np.uint8, np.uint8, np.uint64, np.uint64],
+                    "offsets": [0, 4, 8, 9, 16, 24], "itemsize": 32})  # XmSnpRow as a numpy record
+INDEL_CANDIDATE = np.dtype([("contig", np.int32), ("kind", np.int32), ("pos1", np.int64), ("length", np.int64), ("support_units", np.uint64)])  # xm_indel_candidate
+INDEL_VERDICT = np.dtype([("total_units", np.uint64), ("keep", np.int64)])  # xm_indel_verdict
+
+
+class XmSnpCalls(C.Structure):
+    """xm_snp_calls: the SNP rows of a pile-up in a pinned buffer of the library, what crossed to the host and the times of the call's two parts."""
+    _fields_ = [("num_rows", C.c_int64), ("rows", C.POINTER(XmSnpRow)), ("positions", C.c_int64), ("bytes_to_host", C.c_int64), ("kernel_ms", C.c_double), ("d2h_ms", C.c_double),
+                ("store", C.c_void_p)]
+
+
+class XmTestMutationsJob(C.Structure):
+    """xm_test_mutations_job (test-only): contig lengths, one or two sets of counts, a filter and indel candidates, all on the host."""
+    _fields_ = [("num_contigs", C.c_int32), ("num_sets", C.c_int32), ("contig_lengths", C.c_void_p), ("depth", C.c_void_p * 2), ("alt", C.c_void_p * 2), ("middle", C.c_void_p * 2),
+                ("filter", C.POINTER(XmMutationFilter)), ("num_candidates", C.c_int64), ("candidates", C.c_void_p), ("verdicts", C.c_void_p), ("read_back", C.c_void_p * 2)]
+
+
+ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved); xm_batch_stage_fasta came without a new version (no struct or entry changed), and so did xm_unaligned_format_last, xm_context_set_batch_copy and xm_test_unaligned_format, and xm_pileup_absorb, xm_pileup_call_snps, xm_snp_calls_free, xm_pileup_judge_indels, xm_mutations_block_positions and xm_test_pileup_call
 
 
 class XmIndexInfo(C.Structure):
@@ -120,7 +150,8 @@ class XmIndexInfo(C.Structure):
 
 
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
-           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_batch_stage_fasta", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count", "xm_unaligned_format_last", "xm_context_set_batch_copy", "xm_test_unaligned_format"]
+           "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_batch_stage_fasta", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count", "xm_unaligned_format_last", "xm_context_set_batch_copy", "xm_test_unaligned_format",
+           "xm_pileup_absorb", "xm_pileup_call_snps", "xm_snp_calls_free", "xm_pileup_judge_indels", "xm_mutations_block_positions", "xm_test_pileup_call"]
 
 
 def build_library(force=False):
@@ -246,6 +277,13 @@ def lib():
         L.xm_unaligned_format_last.argtypes = [C.c_void_p, C.POINTER(C.POINTER(XmSamText))]  # (added without a new ABI version, as xm_batch_stage_fasta)
         L.xm_context_set_batch_copy.argtypes = [C.c_void_p, C.c_int32]
         L.xm_test_unaligned_format.argtypes = [C.c_int32, C.POINTER(XmTestUnalignedJob), C.POINTER(C.POINTER(XmSamText))]
+        L.xm_pileup_absorb.argtypes = [C.c_void_p, C.c_void_p]  # (these six, too, came without a new ABI version)
+        L.xm_pileup_call_snps.argtypes = [C.c_void_p, C.POINTER(XmMutationFilter), C.POINTER(C.POINTER(XmSnpCalls))]
+        L.xm_snp_calls_free.argtypes = [C.POINTER(XmSnpCalls)]
+        L.xm_snp_calls_free.restype = None
+        L.xm_pileup_judge_indels.argtypes = [C.c_void_p, C.POINTER(XmMutationFilter), C.c_void_p, C.c_int64, C.c_void_p]
+        L.xm_mutations_block_positions.restype = C.c_int64
+        L.xm_test_pileup_call.argtypes = [C.c_int32, C.POINTER(XmTestMutationsJob), C.POINTER(C.POINTER(XmSnpCalls))]
         _lib = L
     return _lib
 

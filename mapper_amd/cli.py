@@ -41,7 +41,10 @@ api.ReferenceDatabase.unaligned_format_last, and the host only writes the bytes:
 are then in HBM with the batch - and --results-on-gpu, whose summary the statistics come from), --batch-on-gpu (a batch parsed on the GPU stays there: of
 what the kernels build only the mate counts, offsets and lengths are copied to the host, api.ReferenceDatabase.set_batch_copy(False); same outputs; needs
 --parse-on-gpu and --results-on-gpu, since the host's formatter and writers read the batch, and with --out-unaligned also --unaligned-on-gpu; not with
---per-object), and --format-threads <n> (threads of the host's SAM formatter).
+--per-object), --call-mutations-on-gpu (the end of --out-mutations runs where the pile-up lies: the replicas' counts are summed on the GPU, the SNP rows are
+picked there and the indel candidates judged there, pileup.MatchDatabase.mutations(on_gpu=True), so that only the rows cross to the host and not 40 to 48 bytes
+per reference base and context; same file; needs --out-mutations; not with --per-object; beside it --format-on-gpu is accepted with --out-mutations),
+and --format-threads <n> (threads of the host's SAM formatter).
 
 --out-mutations streams like --out-sam: the device pile-up keeps the bases of every insertion with its event (pileup.MatchDatabase(keep_insert_text=True)), so
 the mutations file needs no object per read; with --per-object it is written the first way, from the Query objects of the whole job, which is the reference
@@ -236,6 +239,8 @@ def parse_args(argv):
             o["unaligned_on_gpu"] = True
         elif a == "--batch-on-gpu":  # (not a Mapper flag) a batch parsed on the GPU stays in HBM: only the mate counts, offsets and lengths come down (api.ReferenceDatabase.set_batch_copy)
             o["batch_on_gpu"] = True
+        elif a == "--call-mutations-on-gpu":  # (not a Mapper flag) the thresholds of --out-mutations are applied on the GPU, where the pile-up lies (pileup.MatchDatabase.mutations(on_gpu=True))
+            o["call_mutations_on_gpu"] = True
         elif a == "--format-threads":  # (not a Mapper flag) threads of the host's SAM formatter (hostio.Writer; default: the CPUs, 32 at the most)
             o["format_threads"] = int(argv[i + 1]); i += 1
             if o["format_threads"] < 1:
@@ -269,8 +274,15 @@ def parse_args(argv):
             raise UsageError("--count-refs-on-gpu and --per-object exclude each other (the per-object path counts from alignments decoded on the host)")
         if not o.get("out_refs_map_count"):
             raise UsageError("--count-refs-on-gpu has nothing to do without --out-refs-map-count")
+    if o.get("call_mutations_on_gpu"):
+        if not o.get("out_mutations"):
+            raise UsageError("--call-mutations-on-gpu has nothing to do without --out-mutations")
+        if o.get("per_object"):
+            raise UsageError("--call-mutations-on-gpu and --per-object exclude each other (the per-object path takes the text of insertions from Python objects; it is the reference the device path is compared with)")
     refs_need_objects = bool(o.get("out_refs_map_count") and not o.get("count_refs_on_gpu"))
     for other, key in (("--per-object", "per_object"), ("--out-mutations", "out_mutations"), ("--out-refs-map-count", "out_refs_map_count")):
+        if key == "out_mutations" and o.get("call_mutations_on_gpu"):
+            continue  # (with the mutations called on the GPU the pile-up has been run beside the device formatter: tests/test_gpu_mutations.py)
         if o.get("format_on_gpu") and o.get(key) and (key != "out_refs_map_count" or refs_need_objects):
             raise UsageError("--format-on-gpu and %s exclude each other (--per-object and --out-refs-map-count format on the host; the pile-up of --out-mutations has not been run beside the device formatter)" % other)
     if o.get("results_on_gpu"):
@@ -751,7 +763,7 @@ def run(argv, out=sys.stdout, open_database=None):
                 filt = pileup.MutationDetectionParameters.defaultFilter()  # Mapper.java:56; --snp-threshold etc. override it
                 for k, v in o.get("mutation_filter", {}).items():
                     setattr(filt, k, v)
-                match_db.write_mutations(f, filt)
+                match_db.write_mutations(f, filt, on_gpu=bool(o.get("call_mutations_on_gpu")))
     n = int(sink.stats.num_queries)
     global last_timing
     last_timing = {"queries": n, "stream_seconds": time.perf_counter() - t_stream, "contexts": len(devices), "phases": phases}  # first batch to the GPUs .. last byte of the outputs (bench.py's end_to_end leg)

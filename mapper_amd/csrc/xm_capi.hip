@@ -1638,6 +1638,7 @@ static int alignResidentLocked(xm_index* idx, const xm_params* p, xm_result** ou
 
 #include "xm_capi_probe.h"
 #include "xm_capi_pileup.h"
+#include "xm_capi_mutations.h"
 #include "xm_capi_sam.h"
 #include "xm_capi_summary.h"
 #include "xm_capi_refs.h"

@@ -1,6 +1,7 @@
 // The pile-up of the alignments on the reference (included once, by xm_capi.hip, behind xm_index): its kernel, its handle and its C entries.
 #pragma once
 #include "xm_pileup_text.h"
+#include "xm_mutations.h"
 
 namespace {
 
@@ -111,6 +112,8 @@ struct xm_pileup {
   PileupTextStage textStage;      // (device) the stages' buffers
   std::vector<int64_t> textOff;   // (host) with kept text: one entry per event, plus one ...
   std::vector<char> text;         // ... into the letters of the insertions, parallel to events
+  long long absorbedAt = -1;      // queriesAdded when xm_pileup_absorb last moved these counts away (-1: never, or counts came in since): nothing to move again
+  MutationsStage mutations;       // (device) what xm_pileup_absorb, xm_pileup_call_snps and xm_pileup_judge_indels work with: empty until one of them is called
 };
 
 extern "C" {

@@ -285,6 +285,61 @@ int xm_test_refs_count(int32_t device, int64_t num_queries, int32_t num_contigs,
   } catch (std::exception& e) { return fail(std::string("xm_test_refs_count: ") + e.what()); }
 }
 
+// Test-only entry (tests/test_gpu_mutations.py): the kernels of xm_pileup_absorb, xm_pileup_call_snps and xm_pileup_judge_indels over host-given counts - no
+// index, no alignment and no pile-up; the contigs are their lengths.  With two sets the second is absorbed into the first; rows and verdicts are the first's.
+int xm_test_pileup_call(int32_t device, const xm_test_mutations_job* t, xm_snp_calls** out) {
+  if (!t || !out) return fail("xm_test_pileup_call: null argument");
+  *out = nullptr;
+  try {
+    if (t->num_contigs < 1 || !t->contig_lengths) throw std::runtime_error("at least one contig is needed");
+    if (t->num_sets < 1 || t->num_sets > 2) throw std::runtime_error("num_sets must be 1 or 2");
+    if (!t->filter) throw std::runtime_error("null filter");
+    if (t->num_candidates < 0 || (t->num_candidates > 0 && (!t->candidates || !t->verdicts))) throw std::runtime_error("candidates without arrays");
+    std::vector<int64_t> start((size_t)t->num_contigs);
+    long long total = 0;
+    for (int c = 0; c < t->num_contigs; c++) {
+      if (t->contig_lengths[c] < 1) throw std::runtime_error("a contig without bases");
+      start[(size_t)c] = total;
+      total += t->contig_lengths[c];
+    }
+    const bool withMiddle = t->middle[0] != nullptr;
+    for (int s = 0; s < t->num_sets; s++) {
+      if (!t->depth[s] || !t->alt[s]) throw std::runtime_error("null array");
+      if ((t->middle[s] != nullptr) != withMiddle) throw std::runtime_error("every set has a middle depth or none has");
+    }
+    mutationsCheckCandidates(t->candidates, t->num_candidates, t->contig_lengths, t->num_contigs);
+    if (device >= 0) HIP_CHECK(hipSetDevice(device));
+    const size_t bytes = sizeof(unsigned long long) * (size_t)total;
+    DevBuf<unsigned long long> dDepth[2], dAlt[2], dMid[2];
+    MutationsCounts counts[2];
+    for (int s = 0; s < t->num_sets; s++) {
+      dDepth[s].ensure((size_t)total); dAlt[s].ensure((size_t)total * 4);
+      HIP_CHECK(hipMemcpy(dDepth[s].p, t->depth[s], bytes, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(dAlt[s].p, t->alt[s], bytes * 4, hipMemcpyHostToDevice));
+      if (withMiddle) { dMid[s].ensure((size_t)total); HIP_CHECK(hipMemcpy(dMid[s].p, t->middle[s], bytes, hipMemcpyHostToDevice)); }
+      counts[s] = MutationsCounts{dDepth[s].p, dAlt[s].p, withMiddle ? dMid[s].p : nullptr, total};
+    }
+    MutationsStage g;
+    if (t->num_sets == 2) { mutationsAbsorb(counts[0], counts[1], nullptr); HIP_CHECK(hipDeviceSynchronize()); }
+    const xm::MutationFilter f = mutationsFilter(t->filter);
+    SnpBox* box = mutationsSelect(g, counts[0], start.data(), t->contig_lengths, t->num_contigs, f, nullptr);
+    try {
+      if (t->num_candidates > 0) mutationsJudge(g, counts[0], start.data(), t->contig_lengths, t->num_contigs, f, t->candidates, t->num_candidates, t->verdicts, nullptr);
+      for (int s = 0; s < t->num_sets; s++) {
+        if (!t->read_back[s]) continue;
+        HIP_CHECK(hipMemcpy(t->read_back[s], dDepth[s].p, bytes, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(t->read_back[s] + total, dAlt[s].p, bytes * 4, hipMemcpyDeviceToHost));
+        if (withMiddle) HIP_CHECK(hipMemcpy(t->read_back[s] + total * 5, dMid[s].p, bytes, hipMemcpyDeviceToHost));
+      }
+    } catch (...) {
+      freeSnpBox(box);
+      throw;
+    }
+    *out = &box->pub;
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_test_pileup_call: ") + e.what()); }
+}
+
 // Test-only entry (tests/test_gpu_pileup_text.py): the three stages of xm_pileup_text.h - what xm_pileup_add_last runs with kept text - over host-given events
 // and batch arrays; no index, no alignment, no pile-up kernel (so the total is read from the offsets).  The host checks what the kernels take on trust from
 // the library's own stages: mates inside codes.  The events may hold anything.  launches: kernels launched (4 without text to gather, 5 with; 0 for no events).

@@ -21,6 +21,7 @@ integer counters, so the result does not depend on the order of the atomic adds)
 from the queries handed to add_last or, with keep_insert_text, from the device pile-up, which then keeps them beside the event (xm_pileup_text.h):
 a job that streams its batches needs no query after its batch is written."""
 import ctypes as C
+import heapq
 
 import numpy as np
 
@@ -170,10 +171,9 @@ class MatchDatabase:
             at += len(qs)
         return None
 
-    def mutations(self, parameters=None):
-        """-> list of (contig index, 1-based position, reference allele, query allele, allele depth, total depth), in contig and position order."""
-        f = parameters or MutationDetectionParameters.emptyFilter()
-        rows = []
+    def _indels(self):
+        """The insertion / deletion events away from the query ends, grouped: (contig, 1-based position, kind 1 insertion / 2 deletion, reference allele, query
+        allele) -> summed weight in units, in the order the events first name them."""
         indels = {}
         events = self._events()
         kept = getattr(self, "_texts", {})
@@ -194,6 +194,16 @@ class MatchDatabase:
             else:
                 key = (contig, pos + 1, 2, decode(ref[pos:pos + length]), "-" * length)
             indels[key] = indels.get(key, 0) + weight
+        return indels
+
+    def mutations(self, parameters=None, on_gpu=False):
+        """-> list of (contig index, 1-based position, reference allele, query allele, allele depth, total depth), in contig and position order.
+        on_gpu: the thresholds are applied where the counts lie (_mutations_on_gpu); the path below is the definition of what that returns."""
+        f = parameters or MutationDetectionParameters.emptyFilter()
+        if on_gpu:
+            return self._mutations_on_gpu(f)
+        rows = []
+        indels = self._indels()
         for c in range(len(self.contigs)):
             depth, alt = self._sum(c)
             mid = self._middle(c) if indels else depth
@@ -227,12 +237,64 @@ class MatchDatabase:
         rows.sort(key=lambda t: (t[0], t[1], t[2], t[3], t[4]))
         return [(c, pos1, ra, qa, w, total) for c, pos1, _, ra, qa, w, total in rows]
 
-    def write_mutations(self, out, parameters=None):
+    def _mutations_on_gpu(self, f):
+        """mutations(f) without reading the pile-up back: every replica's counts are moved into the first pile-up (xm_pileup_absorb: the sums over
+        the replicas stay what they were, so the host path still gives the same rows afterwards), the SNP rows come from the device in contig, position and
+        letter order (xm_pileup_call_snps), and the indel candidates of all contigs - the events are host memory already and are grouped as ever - are judged
+        in one call (xm_pileup_judge_indels).  What crosses to the host is the rows and a verdict per candidate.  self.last_on_gpu: the figures of the call."""
+        if not self._h:
+            raise RuntimeError("mutations(on_gpu=True) needs a device pile-up")
+        L, first = self._L, self._h[0]
+        for h in self._h[1:]:
+            if L.xm_pileup_absorb(first, h):
+                raise RuntimeError(L.xm_last_error().decode())
+        filt = _capi.XmMutationFilter(f.minSNPTotalDepth, f.minIndelTotalStartDepth, f.minIndelContinuationTotalDepth,
+                                      f.minSNPDepthFraction, f.minIndelStartDepthFraction, f.minIndelContinuationDepthFraction, 0)
+        calls = C.POINTER(_capi.XmSnpCalls)()
+        if L.xm_pileup_call_snps(first, C.byref(filt), C.byref(calls)):
+            raise RuntimeError(L.xm_last_error().decode())
+        try:
+            got = calls.contents
+            n = int(got.num_rows)
+            self.last_on_gpu = {"snp_rows": n, "bytes_to_host": int(got.bytes_to_host), "select_ms": got.kernel_ms, "d2h_ms": got.d2h_ms}
+            snps = np.frombuffer((_capi.XmSnpRow * n).from_address(C.addressof(got.rows.contents)), dtype=_capi.SNP_ROW).copy() if n else np.zeros(0, _capi.SNP_ROW)
+        finally:
+            L.xm_snp_calls_free(calls)
+        indels = list(self._indels().items())
+        candidates = indel_candidates(indels)
+        verdicts = np.zeros(len(indels), _capi.INDEL_VERDICT)
+        if L.xm_pileup_judge_indels(first, C.byref(filt), candidates.ctypes.data, len(indels), verdicts.ctypes.data):
+            raise RuntimeError(L.xm_last_error().decode())
+        self.last_on_gpu.update(candidates=len(indels), bytes_to_host=self.last_on_gpu["bytes_to_host"] + verdicts.nbytes)
+        return merged_rows(snps, indels, verdicts, lambda contig, position, code: decode((code,)))
+
+    def write_mutations(self, out, parameters=None, on_gpu=False):
         """MutationsWriter.write: one line per mutation.  The two header lines are [unpinned] (the reference's test drops '#' and 'CHR' lines)."""
         out.write("# mutations of the aligned queries against the reference\n")
         out.write("CHR\tPOS\tREF\tALT\tALT DEPTH\tTOTAL DEPTH\n")
-        for c, pos1, ra, qa, w, total in self.mutations(parameters):
+        for c, pos1, ra, qa, w, total in self.mutations(parameters, on_gpu=on_gpu):
             out.write("%s\t%d\t%s\t%s\t%s\t%s\n" % (self.contigs[c][0], pos1, ra, qa, _number(w), _number(total)))
+
+
+def indel_candidates(indels):
+    """The groups of MatchDatabase._indels(), as a list of items -> xm_indel_candidate records, one per group in its order."""
+    candidates = np.zeros(len(indels), _capi.INDEL_CANDIDATE)
+    for i, ((c, pos1, kind, ra, qa), w) in enumerate(indels):
+        candidates[i] = (c, kind, pos1, max(len(ra), len(qa)), w)
+    return candidates
+
+
+def merged_rows(snps, indels, verdicts, reference_allele):
+    """The rows of mutations() from what the device (or the rules' test program) answered: snps, xm_snp_row records in contig, position and letter order;
+    indels, the candidates' groups with verdicts, one xm_indel_verdict each.  reference_allele(contig, 0-based position, the row's reference code) -> text.
+    The two sorted sets are merged by the key the host path sorts with."""
+    rows = [(c, p + 1, 0, reference_allele(c, p, code), "ACGT"[b], s / UNIT, t / UNIT) for c, p, b, code, s, t in
+            zip(snps["contig"].tolist(), snps["position"].tolist(), snps["letter"].tolist(), snps["reference_code"].tolist(), snps["support_units"], snps["total_units"])]
+    judged = [(c, pos1, kind, ra[:keep], qa[:keep], w / UNIT, total / UNIT)
+              for ((c, pos1, kind, ra, qa), w), total, keep in zip(indels, verdicts["total_units"], verdicts["keep"].tolist()) if keep > 0]
+    key = lambda t: (t[0], t[1], t[2], t[3], t[4])  # noqa: E731
+    judged.sort(key=key)
+    return [(c, pos1, ra, qa, w, total) for c, pos1, _, ra, qa, w, total in heapq.merge(rows, judged, key=key)]
 
 
 class CountedMatchDatabase(MatchDatabase):
