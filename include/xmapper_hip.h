@@ -129,7 +129,8 @@ const char* xm_build_stamp(void);
  * 11 = xm_refs_count_last, xm_refs_count_free (and the test-only xm_test_refs_count); 12 = xm_fastq_text.reserved becomes split_past_size (same layout; 0 is
  * what every caller passed).  xm_batch_stage_fasta was added without a new version: it changes no struct and no entry, so the version stays 12 and a
  * caller that wants it looks the symbol up (a library of version 12 built before it does not export it); xm_pileup_absorb, xm_pileup_call_snps,
- * xm_snp_calls_free, xm_pileup_judge_indels and xm_mutations_block_positions (and the test-only xm_test_pileup_call) came the same way.  A binding checks the version once
+ * xm_snp_calls_free, xm_pileup_judge_indels and xm_mutations_block_positions (and the test-only xm_test_pileup_call) came the same way, and so did
+ * xm_pileup_group_events, xm_pileup_call_indels and xm_indel_calls_free (and the test-only xm_test_pileup_group).  A binding checks the version once
  * after loading the library (mapper_amd/_capi.py, bindings/java/xmapper_jni.c). */
 int32_t xm_abi_version(void);
 /* Page-locked host memory this process holds through the library's pool of result buffers (in use + kept for reuse; at most 4 GiB are kept idle), and - through
@@ -516,6 +517,36 @@ int64_t xm_mutations_block_positions(void);
 typedef struct xm_indel_candidate { int32_t contig, kind; int64_t pos1, length; uint64_t support_units; } xm_indel_candidate;
 typedef struct xm_indel_verdict { uint64_t total_units; int64_t keep; } xm_indel_verdict;
 int xm_pileup_judge_indels(xm_pileup* pileup, const xm_mutation_filter* filter, const xm_indel_candidate* candidates, int64_t n, xm_indel_verdict* verdicts);
+/* (added without a new ABI version, like the entries above: look them up by name)  The insertion / deletion events grouped on the device as the batches come
+ * in (mapper_amd/csrc/xm_indel_groups.h; the rules as code: xm_indel_groups_rules.h; the definition: MatchDatabase._indels() of mapper_amd/pileup.py).
+ * xm_pileup_group_events(pileup, 1), before the first xm_pileup_add_last (it fails afterwards), makes every add fold the call's events into a table in HBM
+ * that belongs to the pile-up and grows with it: a group is (contig, 1-based pos1, kind 1 insertion / 2 deletion, length, the insertion's letters) and its
+ * support the sum of its events' weights; an insertion has pos1 = the event's position, a deletion pos1 = position + 1; events with bit 2 of their flags word
+ * (near a query end) are in no group.  It implies xm_pileup_keep_insert_text - grouping needs the letters -, but neither events nor letters are copied to the
+ * host any more, except those of LEFT-OVERS: events whose key met another key with the same 64-bit fingerprint in the table.  With grouping on,
+ * xm_pileup_events, xm_pileup_event_text and xm_pileup_add_last's num_events speak of the left-overs only - in every run seen so far there are none -, and
+ * the groups of the left-overs (the host makes them as ever) and the groups of the device's table of one pile-up are disjoint.
+ * xm_pileup_call_indels judges the groups where they lie - xm_pileup_judge_indels' rule, over the middle depth - and returns those with keep > 0, each with
+ * its letters at letters[letters_at .. letters_at + num_letters), in pinned buffers of the library; filter NULL: every group comes down unjudged, keep =
+ * length, total_units as judged.  The order of the rows is not part of the contract.  xm_pileup_read's contract: it synchronises the device first and needs
+ * no live context.  events: the events all adds made so far; groups: the groups of the table; left_over: the events the host holds; table_bytes: HBM of
+ * the table, the records and the arena.  xm_pileup_absorb between two pile-ups that both group also folds from's groups into into's table and empties
+ * from's; what that fold leaves over becomes events of `into` (query -1); it fails when only one of the two groups. */
+typedef struct xm_indel_call {
+  int32_t contig, kind;
+  int64_t pos1, length, keep;
+  uint64_t support_units, total_units;   /* in units of 1 / XM_PILEUP_UNIT */
+  int64_t letters_at, num_letters;
+} xm_indel_call;
+typedef struct xm_indel_calls {
+  int64_t num_rows; xm_indel_call* rows;
+  int64_t num_letters; char* letters;
+  int64_t groups, events, left_over, table_bytes, bytes_to_host;
+  void* store;
+} xm_indel_calls;
+int xm_pileup_group_events(xm_pileup* pileup, int32_t on);
+int xm_pileup_call_indels(xm_pileup* pileup, const xm_mutation_filter* filter, xm_indel_calls** out);
+void xm_indel_calls_free(xm_indel_calls* calls);
 
 /* TEST-ONLY entry (tests/test_gpu_kat.py; not part of the drop-in boundary): the reference's component-level known-answer tests run by the
  * device code of the align kernels over two given texts.  chain 0 = PathAligner alone (PathAligner_Test.java:10-39): mode 0 the lane-per-read
@@ -584,6 +615,24 @@ typedef struct xm_test_mutations_job {
   uint64_t* read_back[2];
 } xm_test_mutations_job;
 int xm_test_pileup_call(int32_t device, const xm_test_mutations_job* job, xm_snp_calls** out);
+/* Test-only (tests/test_gpu_indel_groups.py): the kernels of xm_pileup_group_events over host-given events on `device`; no index, no alignment and no pile-up.
+ * One or two sets of calls; a call is num_events events (eight int64 each, holding anything) with text_off[num_events + 1] into text, the letters of event i
+ * at text[text_off[i] .. text_off[i + 1]).  Every set has a table of its own that starts with initial_capacity slots (rounded up to a power of two, at least
+ * 4) and keeps fingerprint_bits bits of the fingerprints (64 and more: whole); with two sets the second is absorbed into the first after their calls.  out:
+ * the groups of set 0 as xm_pileup_call_indels returns them with filter NULL (total_units 0: there are no counts).  The left-over events, at most left_cap
+ * with at most left_text_cap letters, in the order the host holds them: left_events (eight int64 each), left_call (the call that left the event over: set 0's
+ * calls count from 0, set 1's follow, the absorb comes last), left_text_off[num_left + 1] and left_text.  grows: how often the table, the records and the
+ * arena of set 0 grew beyond their first allocation. */
+typedef struct xm_test_group_call { int64_t num_events; const int64_t* events; const int64_t* text_off; const char* text; } xm_test_group_call;
+typedef struct xm_test_group_job {
+  int32_t fingerprint_bits, initial_capacity;
+  int32_t num_calls[2]; const xm_test_group_call* calls[2];
+  int64_t left_cap, left_text_cap;
+  int64_t* left_events; int32_t* left_call; int64_t* left_text_off; char* left_text;
+  int64_t num_left;
+  int64_t grows[3];
+} xm_test_group_job;
+int xm_test_pileup_group(int32_t device, xm_test_group_job* job, xm_indel_calls** out);
 /* Test-only: Double.toString as the SAM tags print it, run by the device on n values: out24[24 * i ...] the string of x[i] (padded with NUL), len[i] its length. */
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len);
 

@@ -139,7 +139,44 @@ class XmTestMutationsJob(C.Structure):
                 ("filter", C.POINTER(XmMutationFilter)), ("num_candidates", C.c_int64), ("candidates", C.c_void_p), ("verdicts", C.c_void_p), ("read_back", C.c_void_p * 2)]
 
 
-ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved); xm_batch_stage_fasta came without a new version (no struct or entry changed), and so did xm_unaligned_format_last, xm_context_set_batch_copy and xm_test_unaligned_format, and xm_pileup_absorb, xm_pileup_call_snps, xm_snp_calls_free, xm_pileup_judge_indels, xm_mutations_block_positions and xm_test_pileup_call
+class XmIndelCall(C.Structure):
+    """xm_indel_call: a group of insertion / deletion events as xm_pileup_call_indels returns it."""
+    _fields_ = [("contig", C.c_int32), ("kind", C.c_int32), ("pos1", C.c_int64), ("length", C.c_int64), ("keep", C.c_int64), ("support_units", C.c_uint64), ("total_units", C.c_uint64),
+                ("letters_at", C.c_int64), ("num_letters", C.c_int64)]
+
+
+INDEL_CALL = np.dtype([("contig", np.int32), ("kind", np.int32), ("pos1", np.int64), ("length", np.int64), ("keep", np.int64), ("support_units", np.uint64), ("total_units", np.uint64),
+                       ("letters_at", np.int64), ("num_letters", np.int64)])  # xm_indel_call as a numpy record
+
+
+class XmIndelCalls(C.Structure):
+    """xm_indel_calls: the kept groups of a pile-up and their letters in pinned buffers of the library, and the figures of the table."""
+    _fields_ = [("num_rows", C.c_int64), ("rows", C.POINTER(XmIndelCall)), ("num_letters", C.c_int64), ("letters", C.c_void_p), ("groups", C.c_int64), ("events", C.c_int64),
+                ("left_over", C.c_int64), ("table_bytes", C.c_int64), ("bytes_to_host", C.c_int64), ("store", C.c_void_p)]
+
+
+class XmTestGroupCall(C.Structure):
+    """xm_test_group_call (test-only): the events of one call with the offsets of their letters and the letters."""
+    _fields_ = [("num_events", C.c_int64), ("events", C.c_void_p), ("text_off", C.c_void_p), ("text", C.c_void_p)]
+
+
+class XmTestGroupJob(C.Structure):
+    """xm_test_group_job (test-only): one or two sets of calls, the knobs of the table, and where the left-over events go."""
+    _fields_ = [("fingerprint_bits", C.c_int32), ("initial_capacity", C.c_int32), ("num_calls", C.c_int32 * 2), ("calls", C.POINTER(XmTestGroupCall) * 2), ("left_cap", C.c_int64),
+                ("left_text_cap", C.c_int64), ("left_events", C.c_void_p), ("left_call", C.c_void_p), ("left_text_off", C.c_void_p), ("left_text", C.c_void_p), ("num_left", C.c_int64),
+                ("grows", C.c_int64 * 3)]
+
+
+def indel_calls(calls):
+    """POINTER(XmIndelCalls) -> (xm_indel_call records, their letters as bytes, the figures), copied: the C result can be freed afterwards."""
+    got = calls.contents
+    n, nl = int(got.num_rows), int(got.num_letters)
+    rows = np.frombuffer((XmIndelCall * n).from_address(C.addressof(got.rows.contents)), dtype=INDEL_CALL).copy() if n else np.zeros(0, INDEL_CALL)
+    letters = C.string_at(got.letters, nl) if nl else b""
+    return rows, letters, {"groups": int(got.groups), "events": int(got.events), "left_over": int(got.left_over), "table_bytes": int(got.table_bytes), "bytes_to_host": int(got.bytes_to_host)}
+
+
+ABI_VERSION = 12  # include/xmapper_hip.h, xm_abi_version(): xm_result.extra[] appended; xm_seed_probe_packed (the packed output layout under its own name); 3: xm_context_set_collapse, extra[7]; 4: xm_context_set_memo, xm_context_memo_info, extra[6]; 5: xm_memory_new, xm_context_attach_memory, xm_memory_info, xm_memory_free; 6: xm_batch_stage_fastq, xm_fastq_batch_free, xm_fastq_tile_bytes; 7: xm_sam_set_contigs, xm_sam_format_last, xm_sam_text_free, xm_sam_tile_bytes, xm_test_sam_format, xm_test_format_doubles; 8: xm_batch_unstage; 9: xm_pileup_keep_insert_text, xm_pileup_event_text, xm_test_pileup_text; 10: xm_context_set_result_copy, xm_summary_last, xm_summary_free, xm_test_summary; 11: xm_refs_count_last, xm_refs_count_free, xm_test_refs_count; 12: xm_fastq_text.split_past_size (was reserved); xm_batch_stage_fasta came without a new version (no struct or entry changed), and so did xm_unaligned_format_last, xm_context_set_batch_copy and xm_test_unaligned_format, and xm_pileup_absorb, xm_pileup_call_snps, xm_snp_calls_free, xm_pileup_judge_indels, xm_mutations_block_positions and xm_test_pileup_call, and xm_pileup_group_events, xm_pileup_call_indels, xm_indel_calls_free and xm_test_pileup_group
 
 
 class XmIndexInfo(C.Structure):
@@ -151,7 +188,8 @@ class XmIndexInfo(C.Structure):
 
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
            "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_batch_stage_fasta", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count", "xm_unaligned_format_last", "xm_context_set_batch_copy", "xm_test_unaligned_format",
-           "xm_pileup_absorb", "xm_pileup_call_snps", "xm_snp_calls_free", "xm_pileup_judge_indels", "xm_mutations_block_positions", "xm_test_pileup_call"]
+           "xm_pileup_absorb", "xm_pileup_call_snps", "xm_snp_calls_free", "xm_pileup_judge_indels", "xm_mutations_block_positions", "xm_test_pileup_call",
+           "xm_pileup_group_events", "xm_pileup_call_indels", "xm_indel_calls_free", "xm_test_pileup_group"]
 
 
 def build_library(force=False):
@@ -284,6 +322,11 @@ def lib():
         L.xm_pileup_judge_indels.argtypes = [C.c_void_p, C.POINTER(XmMutationFilter), C.c_void_p, C.c_int64, C.c_void_p]
         L.xm_mutations_block_positions.restype = C.c_int64
         L.xm_test_pileup_call.argtypes = [C.c_int32, C.POINTER(XmTestMutationsJob), C.POINTER(C.POINTER(XmSnpCalls))]
+        L.xm_pileup_group_events.argtypes = [C.c_void_p, C.c_int32]  # (these four, too, came without a new ABI version)
+        L.xm_pileup_call_indels.argtypes = [C.c_void_p, C.POINTER(XmMutationFilter), C.POINTER(C.POINTER(XmIndelCalls))]
+        L.xm_indel_calls_free.argtypes = [C.POINTER(XmIndelCalls)]
+        L.xm_indel_calls_free.restype = None
+        L.xm_test_pileup_group.argtypes = [C.c_int32, C.POINTER(XmTestGroupJob), C.POINTER(C.POINTER(XmIndelCalls))]
         _lib = L
     return _lib
 

@@ -43,7 +43,10 @@ what the kernels build only the mate counts, offsets and lengths are copied to t
 --parse-on-gpu and --results-on-gpu, since the host's formatter and writers read the batch, and with --out-unaligned also --unaligned-on-gpu; not with
 --per-object), --call-mutations-on-gpu (the end of --out-mutations runs where the pile-up lies: the replicas' counts are summed on the GPU, the SNP rows are
 picked there and the indel candidates judged there, pileup.MatchDatabase.mutations(on_gpu=True), so that only the rows cross to the host and not 40 to 48 bytes
-per reference base and context; same file; needs --out-mutations; not with --per-object; beside it --format-on-gpu is accepted with --out-mutations),
+per reference base and context; same file; needs --out-mutations; not with --per-object; beside it --format-on-gpu is accepted with --out-mutations), --group-indels-on-gpu (the
+pile-up's insertion / deletion events are grouped on the GPU as the batches come in, pileup.MatchDatabase(group_on_gpu=True): a table of groups per context in
+HBM takes the place of the events that every batch copied to the host and that the host held to the end of the job and grouped one by one; same file; needs
+--out-mutations; not with --per-object; independent of --call-mutations-on-gpu, beside which only the groups that pass the thresholds cross to the host),
 and --format-threads <n> (threads of the host's SAM formatter).
 
 --out-mutations streams like --out-sam: the device pile-up keeps the bases of every insertion with its event (pileup.MatchDatabase(keep_insert_text=True)), so
@@ -241,6 +244,8 @@ def parse_args(argv):
             o["batch_on_gpu"] = True
         elif a == "--call-mutations-on-gpu":  # (not a Mapper flag) the thresholds of --out-mutations are applied on the GPU, where the pile-up lies (pileup.MatchDatabase.mutations(on_gpu=True))
             o["call_mutations_on_gpu"] = True
+        elif a == "--group-indels-on-gpu":  # (not a Mapper flag) the pile-up's insertion / deletion events are grouped on the GPU as the batches come in (pileup.MatchDatabase(group_on_gpu=True))
+            o["group_indels_on_gpu"] = True
         elif a == "--format-threads":  # (not a Mapper flag) threads of the host's SAM formatter (hostio.Writer; default: the CPUs, 32 at the most)
             o["format_threads"] = int(argv[i + 1]); i += 1
             if o["format_threads"] < 1:
@@ -279,6 +284,13 @@ def parse_args(argv):
             raise UsageError("--call-mutations-on-gpu has nothing to do without --out-mutations")
         if o.get("per_object"):
             raise UsageError("--call-mutations-on-gpu and --per-object exclude each other (the per-object path takes the text of insertions from Python objects; it is the reference the device path is compared with)")
+    if o.get("group_indels_on_gpu"):
+        if not o.get("out_mutations"):
+            raise UsageError("--group-indels-on-gpu has nothing to do without --out-mutations")
+        if o.get("out_refs_map_count") and not o.get("count_refs_on_gpu"):
+            raise UsageError("--group-indels-on-gpu and --out-refs-map-count exclude each other without --count-refs-on-gpu (the count then runs the job through the per-object path)")
+        if o.get("per_object"):
+            raise UsageError("--group-indels-on-gpu and --per-object exclude each other (the per-object path takes the text of insertions from Python objects; the device groups the events with the text it keeps)")
     refs_need_objects = bool(o.get("out_refs_map_count") and not o.get("count_refs_on_gpu"))
     for other, key in (("--per-object", "per_object"), ("--out-mutations", "out_mutations"), ("--out-refs-map-count", "out_refs_map_count")):
         if key == "out_mutations" and o.get("call_mutations_on_gpu"):
@@ -701,6 +713,10 @@ def run(argv, out=sys.stdout, open_database=None):
         # (--out-mutations: every context accumulates its own pile-up on its GPU - depth 8 B, four alternative counts 32 B and, with a query-end fraction, the
         # middle depth 8 B per reference base: 149 GB for a 3.1 Gb reference - so the contexts of a GPU are counted with it)
         pile_up = (48 if o.get("query_end_fraction", 0.1) > 0 else 40) * sum(len(t) for _, t in ordered) + (64 << 20) if o.get("out_mutations") else 0
+        # (--group-indels-on-gpu: the first allocation of a pile-up's table of groups, taken as an event per read - two to four slots of 16 bytes, a record
+        # of 48, eight bytes of letters - and the arrays of a fold, a slot, four flags or lengths and two offsets per event; the table grows with the groups)
+        if o.get("group_indels_on_gpu"):
+            pile_up += batch_size * 192
         memo = {"memo_bytes": o["remember"]} if o.get("remember") else {}  # (--remember-queries: every context's memory, counted beside its scratch)
         if o.get("remember_per_gpu"):  # (--remember-queries-per-gpu: one memory per GPU, counted once per GPU when its contexts divide the scratch)
             memo = {"shared_memo_bytes": o["remember_per_gpu"]}
@@ -739,7 +755,8 @@ def run(argv, out=sys.stdout, open_database=None):
         if o.get("out_mutations"):  # Mapper.java:700-708: the MatchDatabase listens to every batch; here it accumulates on the GPU while the batch is resident
             from . import pileup
             # (default 0.1: Mapper.java:76; streamed batches are closed once they are written, so the pile-up keeps the text of insertions itself)
-            match_db = pileup.MatchDatabase(db.replicas if hasattr(db, "replicas") else db, o.get("query_end_fraction", 0.1), keep_insert_text=not per_object)
+            grouping = {"group_on_gpu": True} if o.get("group_indels_on_gpu") else {}  # (--group-indels-on-gpu: the events are grouped where they lie)
+            match_db = pileup.MatchDatabase(db.replicas if hasattr(db, "replicas") else db, o.get("query_end_fraction", 0.1), keep_insert_text=not per_object, **grouping)
             job.callback(match_db.close)
 
             def on_aligned(*at):  # ReferenceDatabase.align_stream calls it with (batch), MultiGpuDatabase's with (replica, batch), on the replica's thread

@@ -169,6 +169,106 @@ void mutationsCheckCandidates(const xm_indel_candidate* candidates, int64_t n, c
 
 MutationsCounts mutationsCountsOf(xm_pileup* p) { return MutationsCounts{p->dDepth.p, p->dAlt.p, p->endFraction > 0 ? p->dMid.p : nullptr, p->total}; }
 
+// ---------------------------------------------------------------- the groups of xm_indel_groups.h at the end
+static_assert(sizeof(xm_indel_call) == sizeof(IGroupsCall), "the layouts of include/xmapper_hip.h");
+
+// xm_indel_calls plus what xm_indel_calls_free needs to know about its buffers
+struct IndelBox {
+  xm_indel_calls pub;
+  size_t bytesRows, bytesLetters;
+};
+
+void freeIndelBox(IndelBox* box) {
+  if (box->pub.rows) g_pinned->put(box->pub.rows, box->bytesRows);
+  if (box->pub.letters) g_pinned->put(box->pub.letters, box->bytesLetters);
+  free(box);
+}
+
+// The groups of g judged over `middle` (null: no counts - every group comes down whole with a total of 0) on stream s: a lane per group, two scans over the
+// kept ones and their letters, and the records and letters gathered into pinned buffers.  f null: unjudged.  Two waits: the totals, then the records.
+IndelBox* igroupsCall(IGroupsStage& g, MutationsStage& m, const unsigned long long* middle, const int64_t* contigStart, const int32_t* contigLen, int numContigs, const xm::MutationFilter* f,
+                      hipStream_t s) {
+  IndelBox* box = (IndelBox*)calloc(1, sizeof(IndelBox));
+  if (!box) throw std::runtime_error("out of host memory");
+  box->pub.store = box;
+  box->pub.groups = g.groups;
+  const long long n = g.groups;
+  if (n <= 0) return box;  // (nothing is launched)
+  try {
+    const long long nBlocks = (n + XM_PTEXT_SCAN_PER_BLOCK - 1) / XM_PTEXT_SCAN_PER_BLOCK;
+    g.dKeep.ensure((size_t)n); g.dTotal.ensure((size_t)n); g.dFlag.ensure((size_t)n); g.dLen.ensure((size_t)n); g.dBlocks.ensure((size_t)nBlocks);
+    g.dOffA.ensure((size_t)n + 1); g.dOffB.ensure((size_t)n + 1);
+    if (middle) mutationsContigs(m, contigStart, contigLen, numContigs, s);
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(xm_igroups_judge_kernel, dim3(grid), dim3(256), 0, s, (const xm::IndelGroup*)g.dGroups.p, n, middle, (const int64_t*)m.dContigStart.p, (const int32_t*)m.dContigLen.p,
+                       middle ? numContigs : 0, f ? *f : xm::MutationFilter{0, 0, 0, 0, 0, 0, 0}, f ? 1 : 0, g.dKeep.p, g.dTotal.p, g.dFlag.p, g.dLen.p);
+    HIP_CHECK(hipGetLastError());
+    igroupsScan(n, g.dFlag.p, g.dBlocks, g.dOffA.p, s);
+    igroupsScan(n, g.dLen.p, g.dBlocks, g.dOffB.p, s);
+    int64_t totals[2] = {0, 0};
+    HIP_CHECK(hipMemcpyAsync(&totals[0], g.dOffA.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&totals[1], g.dOffB.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const size_t kept = (size_t)totals[0], letters = (size_t)totals[1];
+    box->pub.num_rows = (int64_t)kept;
+    box->pub.num_letters = (int64_t)letters;
+    box->pub.bytes_to_host = (int64_t)sizeof(totals);
+    if (kept) {
+      g.dCalls.ensure(kept); g.dLeftText.ensure(letters + 1);
+      box->pub.rows = (xm_indel_call*)g_pinned->get(sizeof(xm_indel_call) * kept, &box->bytesRows);
+      if (letters) box->pub.letters = (char*)g_pinned->get(letters, &box->bytesLetters);
+      hipLaunchKernelGGL(xm_igroups_gather_kernel, dim3(grid), dim3(256), 0, s, (const xm::IndelGroup*)g.dGroups.p, (const char*)g.dArena.p, n, (const long long*)g.dKeep.p,
+                         (const unsigned long long*)g.dTotal.p, (const long long*)g.dFlag.p, (const int64_t*)g.dOffA.p, (const int64_t*)g.dOffB.p, g.dCalls.p, (long long)kept, g.dLeftText.p,
+                         (long long)letters);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(box->pub.rows, g.dCalls.p, sizeof(IGroupsCall) * kept, hipMemcpyDeviceToHost, s));
+      if (letters) HIP_CHECK(hipMemcpyAsync(box->pub.letters, g.dLeftText.p, letters, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      box->pub.bytes_to_host += (int64_t)(sizeof(IGroupsCall) * kept + letters);
+    }
+    return box;
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    freeIndelBox(box);
+    throw;
+  }
+}
+
+// The groups of `from` folded into `into`'s table as items, and `from`'s table emptied; what the fold leaves over goes to `left` as events.  Both branches
+// are "compact, (copy,) fold": the records and the used part of the arena are compacted into staging buffers on from's GPU, brought to into's GPU by peer copy
+// when that is another one, and folded there by the kernels every add runs.  The current GPU is into's, before and after.
+void igroupsAbsorb(IGroupsStage& into, int intoDevice, IGroupsStage& from, int fromDevice, const IGroupsLeft& left) {
+  const long long n = from.groups;
+  if (n <= 0) return;
+  const long long bytes = from.arenaUsed;
+  HIP_CHECK(hipSetDevice(fromDevice));
+  DevBuf<xm::IndelGroup> staged;
+  DevBuf<char> stagedArena;
+  staged.ensure((size_t)n); stagedArena.ensure((size_t)bytes + 8);
+  HIP_CHECK(hipMemcpy(staged.p, from.dGroups.p, sizeof(xm::IndelGroup) * (size_t)n, hipMemcpyDeviceToDevice));
+  if (bytes) HIP_CHECK(hipMemcpy(stagedArena.p, from.dArena.p, (size_t)bytes, hipMemcpyDeviceToDevice));
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipSetDevice(intoDevice));
+  DevBuf<xm::IndelGroup> here;
+  DevBuf<char> hereArena;
+  const xm::IndelGroup* records = staged.p;
+  const char* arena = stagedArena.p;
+  if (intoDevice != fromDevice) {
+    here.ensure((size_t)n); hereArena.ensure((size_t)bytes + 8);
+    HIP_CHECK(hipMemcpyPeer(here.p, intoDevice, staged.p, fromDevice, sizeof(xm::IndelGroup) * (size_t)n));
+    if (bytes) HIP_CHECK(hipMemcpyPeer(hereArena.p, intoDevice, stagedArena.p, fromDevice, (size_t)bytes));
+    records = here.p; arena = hereArena.p;
+  }
+  into.reserve(n, bytes, nullptr);
+  into.fold(IGroupsItems{nullptr, nullptr, nullptr, records, arena, n}, nullptr, left);
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipSetDevice(fromDevice));
+  from.clear(nullptr);
+  HIP_CHECK(hipDeviceSynchronize());
+  staged = DevBuf<xm::IndelGroup>(); stagedArena = DevBuf<char>();  // (freed on the GPU they were made on)
+  HIP_CHECK(hipSetDevice(intoDevice));
+}
+
 }  // namespace
 
 extern "C" {
@@ -180,6 +280,7 @@ int xm_pileup_absorb(xm_pileup* into, xm_pileup* from) {
   if (into == from) return fail("xm_pileup_absorb: the same pile-up was given twice");
   if (!into->hs || into->hs != from->hs || into->total != from->total) return fail("xm_pileup_absorb: the pile-ups belong to different indexes");
   if (into->endFraction != from->endFraction) return fail("xm_pileup_absorb: the pile-ups have different query-end fractions");
+  if (into->groupEvents != from->groupEvents) return fail("xm_pileup_absorb: one pile-up groups its events on the device (xm_pileup_group_events) and the other does not");
   if (from->absorbedAt == from->queriesAdded) return 0;  // (its counts were moved away and none came since: every count is 0)
   try {
     if (into->device != from->device) {
@@ -197,6 +298,7 @@ int xm_pileup_absorb(xm_pileup* into, xm_pileup* from) {
     } else {
       mutationsAbsorbPeer(into->mutations, mutationsCountsOf(into), into->device, mutationsCountsOf(from), from->device);
     }
+    if (into->groupEvents) igroupsAbsorb(into->groups, into->device, from->groups, from->device, IGroupsLeft{&into->events, &into->textOff, &into->text});
     from->absorbedAt = from->queriesAdded;
     into->absorbedAt = -1;
     return 0;
@@ -225,6 +327,30 @@ int xm_pileup_call_snps(xm_pileup* p, const xm_mutation_filter* filter, xm_snp_c
 
 void xm_snp_calls_free(xm_snp_calls* calls) {
   if (calls) freeSnpBox((SnpBox*)calls);  // pub is the first member
+}
+
+int xm_pileup_call_indels(xm_pileup* p, const xm_mutation_filter* filter, xm_indel_calls** out) {
+  if (!p || !p->hs || !out) return fail("xm_pileup_call_indels: null argument");
+  *out = nullptr;
+  if (!p->groupEvents) return fail("xm_pileup_call_indels: the pile-up does not group its events on the device (xm_pileup_group_events)");
+  try {
+    const HostIndex& host = p->hs->host;
+    HIP_CHECK(hipSetDevice(p->device));
+    HIP_CHECK(hipDeviceSynchronize());
+    xm::MutationFilter f;
+    if (filter) f = mutationsFilter(filter);
+    const MutationsCounts c = mutationsCountsOf(p);
+    IndelBox* box = igroupsCall(p->groups, p->mutations, c.mid ? c.mid : c.depth, host.contigStart.data(), host.contigLen.data(), host.numContigs(), filter ? &f : nullptr, nullptr);
+    box->pub.events = p->eventsSeen;
+    box->pub.left_over = (int64_t)(p->events.size() / 8);
+    box->pub.table_bytes = (int64_t)(p->groups.cap * 16 + p->groups.dGroups.n * sizeof(xm::IndelGroup) + p->groups.dArena.n);
+    *out = &box->pub;
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_pileup_call_indels: ") + e.what()); }
+}
+
+void xm_indel_calls_free(xm_indel_calls* calls) {
+  if (calls) freeIndelBox((IndelBox*)calls);  // pub is the first member
 }
 
 int xm_pileup_judge_indels(xm_pileup* p, const xm_mutation_filter* filter, const xm_indel_candidate* candidates, int64_t n, xm_indel_verdict* verdicts) {

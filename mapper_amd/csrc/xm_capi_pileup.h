@@ -2,6 +2,7 @@
 #pragma once
 #include "xm_pileup_text.h"
 #include "xm_mutations.h"
+#include "xm_indel_groups.h"
 
 namespace {
 
@@ -114,6 +115,9 @@ struct xm_pileup {
   std::vector<char> text;         // ... into the letters of the insertions, parallel to events
   long long absorbedAt = -1;      // queriesAdded when xm_pileup_absorb last moved these counts away (-1: never, or counts came in since): nothing to move again
   MutationsStage mutations;       // (device) what xm_pileup_absorb, xm_pileup_call_snps and xm_pileup_judge_indels work with: empty until one of them is called
+  bool groupEvents = false;       // xm_pileup_group_events: the events are grouped on the device; events, textOff and text above then hold the left-overs only
+  IGroupsStage groups;            // (device) the table of the groups and what a fold works with: empty until the first add with grouping on
+  long long eventsSeen = 0;       // with grouping: the events of all calls so far, grouped or not
 };
 
 extern "C" {
@@ -167,6 +171,20 @@ int xm_pileup_keep_insert_text(xm_pileup* p, int32_t on) {
   } catch (std::exception& e) { return fail(std::string("xm_pileup_keep_insert_text: ") + e.what()); }
 }
 
+int xm_pileup_group_events(xm_pileup* p, int32_t on) {
+  if (!p) return fail("xm_pileup_group_events: null argument");
+  if (p->queriesAdded > 0) return fail("xm_pileup_group_events: alignments were already added");
+  try {
+    HIP_CHECK(hipSetDevice(p->device));
+    p->groupEvents = on != 0;
+    if (p->groupEvents) {  // (grouping needs the letters: the text stage runs, and its counter is summed)
+      p->keepText = true;
+      p->dEventCount.ensure(2);
+    }
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_pileup_group_events: ") + e.what()); }
+}
+
 int xm_pileup_read_middle(xm_pileup* p, int32_t contig, int64_t first, int64_t n, uint64_t* depth) {
   if (!p || !p->hs || !depth) return fail("xm_pileup_read_middle: null argument");
   try {
@@ -207,6 +225,24 @@ int xm_pileup_add_last(xm_pileup* p, int64_t* num_events) {
       HIP_CHECK(hipStreamSynchronize(s));
       const unsigned long long n = counts[0], textBytes = counts[1];
       if (n > cap) throw std::runtime_error("internal error: more indel events than blocks");
+      if (p->groupEvents) {
+        // The events are grouped where they lie (xm_indel_groups.h): the table grows first, the text stage runs without a copy or a wait of its own, and the
+        // fold waits once for its small record.  Only left-overs - true fingerprint collisions - come down, in a second wait that a call without them skips.
+        p->eventsSeen += (long long)n;
+        if (n) {
+          p->groups.reserve((long long)n, (long long)textBytes, s);
+          const BatchView batch = idx->resident.view();
+          const PileupTextJob job{p->dEvents.p, (long long)n, p->queriesAdded, batch.nq, batch.mateOffset, batch.mateLength, batch.codes};
+          p->textStage.offsets(job, s);
+          p->textStage.dText.ensure((size_t)textBytes + 1);
+          if (textBytes) p->textStage.gather(job, (long long)textBytes, s);
+          const IGroupsItems items{p->dEvents.p, p->textStage.dOff.p, p->textStage.dText.p, nullptr, nullptr, (long long)n};
+          p->groups.fold(items, s, IGroupsLeft{&p->events, &p->textOff, &p->text});
+        }
+        p->queriesAdded += nq;
+        if (num_events) *num_events = (int64_t)(p->events.size() / 8);
+        return 0;
+      }
       std::vector<long long> got((size_t)n * 8);
       std::vector<int64_t> off;
       std::vector<char> text;

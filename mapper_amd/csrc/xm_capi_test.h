@@ -385,6 +385,83 @@ int xm_test_pileup_text(int32_t device, const xm_test_pileup_job* t, int64_t* te
   } catch (std::exception& e) { return fail(std::string("xm_test_pileup_text: ") + e.what()); }
 }
 
+// Test-only entry (tests/test_gpu_indel_groups.py): the fold of xm_pileup_add_last with grouping on, the absorb of xm_pileup_absorb and the unjudged end of
+// xm_pileup_call_indels over host-given events and text - no index, no alignment and no pile-up.  The events may hold anything; the host checks the offsets.
+int xm_test_pileup_group(int32_t device, xm_test_group_job* t, xm_indel_calls** out) {
+  if (!t || !out) return fail("xm_test_pileup_group: null argument");
+  *out = nullptr;
+  try {
+    if (t->fingerprint_bits < 1) throw std::runtime_error("fingerprint_bits must be >= 1");
+    if (t->initial_capacity < 0 || t->left_cap < 0 || t->left_text_cap < 0) throw std::runtime_error("negative size");
+    if (t->num_calls[0] < 0 || t->num_calls[1] < 0 || (t->num_calls[0] && !t->calls[0]) || (t->num_calls[1] && !t->calls[1])) throw std::runtime_error("calls without arrays");
+    for (int set = 0; set < 2; set++)
+      for (int k = 0; k < t->num_calls[set]; k++) {
+        const xm_test_group_call& c = t->calls[set][k];
+        if (c.num_events < 0) throw std::runtime_error("negative size");
+        if (c.num_events == 0) continue;
+        if (!c.events || !c.text_off) throw std::runtime_error("null array");
+        if (c.text_off[0] != 0) throw std::runtime_error("text offsets must start at 0");
+        for (int64_t i = 0; i < c.num_events; i++) if (c.text_off[i + 1] < c.text_off[i]) throw std::runtime_error("text offsets fall");
+        if (c.text_off[c.num_events] > 0 && !c.text) throw std::runtime_error("null array");
+      }
+    if (device >= 0) HIP_CHECK(hipSetDevice(device));
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    IGroupsStage stage[2];
+    std::vector<long long> events;
+    std::vector<int64_t> textOff;
+    std::vector<char> text;
+    std::vector<int32_t> callOf;
+    const IGroupsLeft left{&events, &textOff, &text};
+    int ordinal = 0;
+    for (int set = 0; set < 2; set++) {
+      stage[set].bits = t->fingerprint_bits > 64 ? 64 : t->fingerprint_bits;
+      stage[set].leastCap = (unsigned long long)t->initial_capacity;
+      for (int k = 0; k < t->num_calls[set]; k++, ordinal++) {
+        const xm_test_group_call& c = t->calls[set][k];
+        const int64_t n = c.num_events;
+        if (n == 0) continue;
+        const int64_t bytes = c.text_off[n];
+        DevBuf<long long> dEvents;
+        DevBuf<int64_t> dOff;
+        DevBuf<char> dText;
+        dEvents.ensure((size_t)n * 8); dOff.ensure((size_t)n + 1); dText.ensure((size_t)bytes + 1);
+        HIP_CHECK(hipMemcpy(dEvents.p, c.events, sizeof(int64_t) * (size_t)n * 8, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dOff.p, c.text_off, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice));
+        if (bytes) HIP_CHECK(hipMemcpy(dText.p, c.text, (size_t)bytes, hipMemcpyHostToDevice));
+        stage[set].reserve(n, bytes, nullptr);
+        const long long nLeft = stage[set].fold(IGroupsItems{dEvents.p, dOff.p, dText.p, nullptr, nullptr, n}, nullptr, left);
+        callOf.insert(callOf.end(), (size_t)nLeft, (int32_t)ordinal);
+        HIP_CHECK(hipDeviceSynchronize());
+      }
+    }
+    if (t->num_calls[1] > 0) {
+      const size_t before = events.size() / 8;
+      igroupsAbsorb(stage[0], current, stage[1], current, left);
+      callOf.insert(callOf.end(), events.size() / 8 - before, (int32_t)ordinal);
+      if (stage[1].groups != 0) throw std::runtime_error("internal error: the absorbed table is not empty");
+    }
+    const int64_t nLeft = (int64_t)(events.size() / 8), leftBytes = (int64_t)text.size();
+    if (nLeft > t->left_cap || leftBytes > t->left_text_cap) throw std::runtime_error("the left-overs take " + std::to_string(nLeft) + " events and " + std::to_string(leftBytes) + " bytes");
+    if (nLeft && (!t->left_events || !t->left_call || !t->left_text_off || (leftBytes && !t->left_text))) throw std::runtime_error("null array");
+    t->num_left = nLeft;
+    if (nLeft) {
+      memcpy(t->left_events, events.data(), sizeof(long long) * events.size());
+      memcpy(t->left_call, callOf.data(), sizeof(int32_t) * callOf.size());
+      memcpy(t->left_text_off, textOff.data(), sizeof(int64_t) * ((size_t)nLeft + 1));
+      if (leftBytes) memcpy(t->left_text, text.data(), (size_t)leftBytes);
+    } else if (t->left_text_off) {
+      t->left_text_off[0] = 0;
+    }
+    t->grows[0] = stage[0].tableGrows; t->grows[1] = stage[0].recordGrows; t->grows[2] = stage[0].arenaGrows;
+    MutationsStage m;
+    IndelBox* box = igroupsCall(stage[0], m, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+    box->pub.left_over = nLeft;
+    *out = &box->pub;
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_test_pileup_group: ") + e.what()); }
+}
+
 // Test-only entry (tests/test_gpu_sam.py): Double.toString of xm_sam_rules.h run by the device on n values; out24 gets 24 bytes a value, len the lengths.
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len) {
   if (n < 0 || (n > 0 && (!x || !out24 || !len))) return fail("xm_test_format_doubles: bad arguments");

@@ -67,12 +67,17 @@ def _number(x):
 class MatchDatabase:
     """MatchDatabase(queryEndFraction) + groupByPosition() for one ReferenceDatabase (or the replicas of a MultiGpuDatabase: one device pile-up
     each, summed on the host in replica order).  keep_insert_text: the device pile-ups keep the bases of every insertion with its event
-    (xm_pileup_keep_insert_text), so add_last needs no queries for the text of insertions and nothing of a batch has to outlive it."""
+    (xm_pileup_keep_insert_text), so add_last needs no queries for the text of insertions and nothing of a batch has to outlive it.  group_on_gpu: the
+    device pile-ups group the insertion / deletion events themselves as the batches come in (xm_pileup_group_events): no event and no letter is
+    copied to the host but the left-overs of fingerprint collisions, _indels() reads the groups, and mutations(on_gpu=True) has them judged where they lie."""
 
-    def __init__(self, databases, query_end_fraction=0.0, keep_insert_text=False):
+    group_on_gpu = False   # (subclasses that hold handed-in counts never group on a device)
+
+    def __init__(self, databases, query_end_fraction=0.0, keep_insert_text=False, group_on_gpu=False):
         self.dbs = list(databases) if isinstance(databases, (list, tuple)) else [databases]
         self.query_end_fraction = float(query_end_fraction)
-        self.keep_insert_text = bool(keep_insert_text)
+        self.group_on_gpu = bool(group_on_gpu)
+        self.keep_insert_text = bool(keep_insert_text) or self.group_on_gpu   # (grouping needs the letters: the device keeps them)
         self._L = _capi.lib()
         self._h = []
         for db in self.dbs:
@@ -84,6 +89,8 @@ class MatchDatabase:
                 raise RuntimeError(self._L.xm_last_error().decode())
             if self.keep_insert_text and self._L.xm_pileup_keep_insert_text(h, 1):
                 raise RuntimeError(self._L.xm_last_error().decode())
+            if self.group_on_gpu and self._L.xm_pileup_group_events(h, 1):
+                raise RuntimeError(self._L.xm_last_error().decode())
         self.contigs = self.dbs[0].contigs
         self._reads = {}   # query ordinal (per replica) -> mates, kept only for queries with an insertion
         self._batches = [[] for _ in self.dbs]
@@ -92,6 +99,8 @@ class MatchDatabase:
         """addAlignments(List<QueryAlignments>) for the batch replica `replica` aligned last (its streams are still in HBM).  `queries`: the
         batch's Query objects or mate arrays, needed for the text of insertions (None: the text the device kept, with keep_insert_text; without it
         insertions are reported by length only)."""
+        if self.group_on_gpu and queries is not None:
+            raise RuntimeError("add_last(queries) with group_on_gpu: the text of insertions is the device's, the events are grouped where they lie")
         n = C.c_int64(0)
         if self._L.xm_pileup_add_last(self._h[replica], C.byref(n)):
             raise RuntimeError(self._L.xm_last_error().decode())
@@ -171,9 +180,45 @@ class MatchDatabase:
             at += len(qs)
         return None
 
+    def _device_groups(self, h, filt=None):
+        """xm_pileup_call_indels of one device pile-up -> (xm_indel_call records, their letters, the call's figures); filt None: every group, unjudged."""
+        calls = C.POINTER(_capi.XmIndelCalls)()
+        if self._L.xm_pileup_call_indels(h, C.byref(filt) if filt is not None else None, C.byref(calls)):
+            raise RuntimeError(self._L.xm_last_error().decode())
+        try:
+            return _capi.indel_calls(calls)
+        finally:
+            self._L.xm_indel_calls_free(calls)
+
+    def _group_keys(self, rows, letters):
+        """The keys of _indels() for xm_indel_call records: one Python object per record that came down, none per event."""
+        keys = []
+        for c, kind, pos1, length, at, n in zip(rows["contig"].tolist(), rows["kind"].tolist(), rows["pos1"].tolist(), rows["length"].tolist(), rows["letters_at"].tolist(),
+                                                rows["num_letters"].tolist()):
+            if kind == 1:
+                keys.append((c, pos1, 1, "-" * length, letters[at:at + n].decode("ascii")))
+            else:
+                keys.append((c, pos1, 2, decode(self.contigs[c][1][pos1 - 1:pos1 - 1 + length]), "-" * length))
+        return keys
+
     def _indels(self):
         """The insertion / deletion events away from the query ends, grouped: (contig, 1-based position, kind 1 insertion / 2 deletion, reference allele, query
-        allele) -> summed weight in units, in the order the events first name them."""
+        allele) -> summed weight in units, in the order the events first name them.  group_on_gpu: the groups of the device pile-ups in key order, and the
+        groups of the left-over events behind them."""
+        if self.group_on_gpu:
+            indels = {}
+            for h in self._h:
+                rows, letters, _ = self._device_groups(h)
+                for key, w in zip(self._group_keys(rows, letters), rows["support_units"].tolist()):
+                    indels[key] = indels.get(key, 0) + w
+            indels = dict(sorted(indels.items()))
+            for key, w in self._host_indels().items():
+                indels[key] = indels.get(key, 0) + w
+            return indels
+        return self._host_indels()
+
+    def _host_indels(self):
+        """_indels() over the events the host holds."""
         indels = {}
         events = self._events()
         kept = getattr(self, "_texts", {})
@@ -241,7 +286,9 @@ class MatchDatabase:
         """mutations(f) without reading the pile-up back: every replica's counts are moved into the first pile-up (xm_pileup_absorb: the sums over
         the replicas stay what they were, so the host path still gives the same rows afterwards), the SNP rows come from the device in contig, position and
         letter order (xm_pileup_call_snps), and the indel candidates of all contigs - the events are host memory already and are grouped as ever - are judged
-        in one call (xm_pileup_judge_indels).  What crosses to the host is the rows and a verdict per candidate.  self.last_on_gpu: the figures of the call."""
+        in one call (xm_pileup_judge_indels).  What crosses to the host is the rows and a verdict per candidate.  self.last_on_gpu: the figures of the call.
+        group_on_gpu: the absorb also moves the replicas' groups into the first pile-up's table, the groups are judged where they lie and only the
+        kept ones come down (xm_pileup_call_indels); candidates are then the groups of the left-over events alone."""
         if not self._h:
             raise RuntimeError("mutations(on_gpu=True) needs a device pile-up")
         L, first = self._L, self._h[0]
@@ -260,13 +307,28 @@ class MatchDatabase:
             snps = np.frombuffer((_capi.XmSnpRow * n).from_address(C.addressof(got.rows.contents)), dtype=_capi.SNP_ROW).copy() if n else np.zeros(0, _capi.SNP_ROW)
         finally:
             L.xm_snp_calls_free(calls)
-        indels = list(self._indels().items())
+        kept, kept_verdicts = [], np.zeros(0, _capi.INDEL_VERDICT)
+        left = {}
+        if self.group_on_gpu:
+            left = self._host_indels()
+        if self.group_on_gpu and not (left and len(self._h) > 1):
+            # the groups are judged where they lie and only the kept ones come down; the left-overs' groups - disjoint from the table's - go the old way
+            rows, letters, figures = self._device_groups(first, filt)
+            kept = list(zip(self._group_keys(rows, letters), rows["support_units"].tolist()))
+            kept_verdicts = np.zeros(len(rows), _capi.INDEL_VERDICT)
+            kept_verdicts["total_units"], kept_verdicts["keep"] = rows["total_units"], rows["keep"]
+            self.last_on_gpu.update(groups=figures["groups"], kept=len(rows), left_over=figures["left_over"], group_bytes_to_host=figures["bytes_to_host"],
+                                    table_bytes=figures["table_bytes"], bytes_to_host=self.last_on_gpu["bytes_to_host"] + figures["bytes_to_host"])
+            indels = list(left.items())
+        else:
+            # (left-overs of several pile-ups: a key may be left over in one and in the table of another, so the sums are made on the host before the judge)
+            indels = list(self._indels().items())
         candidates = indel_candidates(indels)
         verdicts = np.zeros(len(indels), _capi.INDEL_VERDICT)
         if L.xm_pileup_judge_indels(first, C.byref(filt), candidates.ctypes.data, len(indels), verdicts.ctypes.data):
             raise RuntimeError(L.xm_last_error().decode())
         self.last_on_gpu.update(candidates=len(indels), bytes_to_host=self.last_on_gpu["bytes_to_host"] + verdicts.nbytes)
-        return merged_rows(snps, indels, verdicts, lambda contig, position, code: decode((code,)))
+        return merged_rows(snps, kept + indels, np.concatenate([kept_verdicts, verdicts]), lambda contig, position, code: decode((code,)))
 
     def write_mutations(self, out, parameters=None, on_gpu=False):
         """MutationsWriter.write: one line per mutation.  The two header lines are [unpinned] (the reference's test drops '#' and 'CHR' lines)."""
