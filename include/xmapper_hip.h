@@ -633,6 +633,10 @@ typedef struct xm_test_group_job {
   int64_t grows[3];
 } xm_test_group_job;
 int xm_test_pileup_group(int32_t device, xm_test_group_job* job, xm_indel_calls** out);
+/* Test-only (tests/test_gpu_scan.py): the exclusive prefix sums every on-GPU output stage takes (mapper_amd/csrc/xm_scan.h), alone, on `device`; no index and
+ * no context.  lens: `channels` (1, 2 or 3) arrays of n lengths one behind the other; offsets: channels arrays of n + 1 sums the same way, the last of each
+ * its total.  keep (may be NULL): n bytes, 0 or 1 - then kept[0 .. *num_kept) are the indices of the kept items in ascending order (kept holds n entries). */
+int xm_test_scan(int32_t device, int32_t channels, int64_t n, const int64_t* lens, const uint8_t* keep, int64_t* offsets, int64_t* kept, int64_t* num_kept);
 /* Test-only: Double.toString as the SAM tags print it, run by the device on n values: out24[24 * i ...] the string of x[i] (padded with NUL), len[i] its length. */
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len);
 

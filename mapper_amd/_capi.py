@@ -189,7 +189,7 @@ class XmIndexInfo(C.Structure):
 EXPORTS = ["xm_last_error", "xm_build_stamp", "xm_abi_version", "xm_pinned_host_bytes", "xm_device_count", "xm_index_build", "xm_index_replicate", "xm_context_new", "xm_context_set_scratch", "xm_context_set_collapse", "xm_context_set_memo", "xm_context_memo_info", "xm_memory_new", "xm_context_attach_memory", "xm_memory_info", "xm_memory_free", "xm_device_memory", "xm_index_save", "xm_index_load", "xm_index_ensure_length", "xm_index_free", "xm_index_get_info",
            "xm_index_table_info", "xm_index_table_shape", "xm_index_table_dump", "xm_index_bucket_stats", "xm_index_dup_keys", "xm_align_batch", "xm_result_free", "xm_batch_upload", "xm_batch_stage", "xm_batch_commit", "xm_batch_unstage", "xm_batch_stage_fastq", "xm_batch_stage_fasta", "xm_fastq_batch_free", "xm_fastq_tile_bytes", "xm_sam_set_contigs", "xm_sam_format_last", "xm_sam_text_free", "xm_sam_tile_bytes", "xm_test_sam_format", "xm_test_format_doubles", "xm_align_resident", "xm_seed_probe_packed", "xm_measure_random_gather", "xm_test_local_align", "xm_test_bound_counters", "xm_test_bound", "xm_pileup_new", "xm_pileup_set_query_ends", "xm_pileup_read_middle", "xm_pileup_add_last", "xm_pileup_read", "xm_pileup_events", "xm_pileup_keep_insert_text", "xm_pileup_event_text", "xm_test_pileup_text", "xm_pileup_free", "xm_context_set_result_copy", "xm_summary_last", "xm_summary_free", "xm_test_summary", "xm_refs_count_last", "xm_refs_count_free", "xm_test_refs_count", "xm_unaligned_format_last", "xm_context_set_batch_copy", "xm_test_unaligned_format",
            "xm_pileup_absorb", "xm_pileup_call_snps", "xm_snp_calls_free", "xm_pileup_judge_indels", "xm_mutations_block_positions", "xm_test_pileup_call",
-           "xm_pileup_group_events", "xm_pileup_call_indels", "xm_indel_calls_free", "xm_test_pileup_group"]
+           "xm_pileup_group_events", "xm_pileup_call_indels", "xm_indel_calls_free", "xm_test_pileup_group", "xm_test_scan"]
 
 
 def build_library(force=False):
@@ -327,6 +327,7 @@ def lib():
         L.xm_indel_calls_free.argtypes = [C.POINTER(XmIndelCalls)]
         L.xm_indel_calls_free.restype = None
         L.xm_test_pileup_group.argtypes = [C.c_int32, C.POINTER(XmTestGroupJob), C.POINTER(C.POINTER(XmIndelCalls))]
+        L.xm_test_scan.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]  # (test-only: no new ABI version)
         _lib = L
     return _lib
 

@@ -6,8 +6,9 @@
 // CollapseBuffers, MemoCallBuffers - and the context (xm_index) that holds one of each beside its stream and its ResultStage; the steps of an align call
 // (AlignCall ... finishStreams), which launch what xm_pass_plan.h plans - reads a pass could not finish are run again by a later pass on the GPU, never
 // on the CPU; the C entries for indexes, contexts, batches and alignment (a first context is opened by openFirstContext, whichever entry asks).
-// Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_result_stage.h (ResultStage: the result arenas,
-// the scan and gather kernels, the canonical streams; throwFailedQuery), xm_conf_table.h (the host's confidence table), xm_capi_probe.h (seed-probe and
+// Beside it, included once each: xm_device_rt.h (error checking, DevBuf, the pinned result pool), xm_scan.h (the exclusive prefix sums in item order that
+// every output stage below takes: three kernels over a stage's Items, and the block-level sum and scan), xm_result_stage.h (ResultStage: the result arenas,
+// the gather kernel, the canonical streams; throwFailedQuery), xm_conf_table.h (the host's confidence table), xm_capi_probe.h (seed-probe and
 // random-gather measurements), xm_capi_pileup.h (the pile-up), xm_capi_test.h (test-only entries), xm_capi_fastq.h (a batch staged from FASTQ text: the kernels of xm_fastq.h),
 // xm_capi_fasta.h (the same from FASTA text of any number of lines a record: the kernels of xm_fasta.h),
 // xm_capi_sam.h (SAM records formatted from the resident results: the kernels of xm_sam.h), xm_capi_summary.h (the statistics, the penalties and the unaligned
@@ -36,6 +37,7 @@
 #include "xm_memo.h"
 #include "xm_conf_table.h"
 #include "xm_device_rt.h"
+#include "xm_scan.h"
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
@@ -297,7 +299,7 @@ struct SamStage {
 // the control word and the three counters; the penalties and the list of unaligned queries, which only grow; the call's events on the context's stream.
 struct SummaryStage {
   DevBuf<int32_t> dAlignments, dUnalignedFlag;
-  DevBuf<long long> dBlockA, dBlockU;
+  DevBuf<long long> dBlockSums;
   DevBuf<int64_t> dOff, dUoff, dUnaligned;
   DevBuf<unsigned long long> dCtl;
   DevBuf<double> dPenalties;
@@ -310,7 +312,7 @@ struct SummaryStage {
 // allocated before the first call.
 struct UnalignedStage {
   DevBuf<int32_t> dBytes, dFlag;
-  DevBuf<long long> dBlockB, dBlockU;
+  DevBuf<long long> dBlockSums;
   DevBuf<int64_t> dOff, dUoff, dList;
   DevBuf<unsigned long long> dCtl;
   DevBuf<char> dText;
@@ -320,13 +322,13 @@ struct UnalignedStage {
 
 // What xm_refs_count_last works with (xm_refs.h; xm_capi_refs.h): the table of the sets' fingerprints (keys, the lowest query and the count per slot); per query
 // its slot, whether it is its slot's representative, and what it leaves to the host (a flag and its sequence alignments); the scan's block sums and the three
-// offset arrays (dSpare: the scan's second output of the flags); the control words; the records and the left-over contigs with their starts, which only
+// offset arrays; the control words; the records and the left-over contigs with their starts, which only
 // grow; the call's events on the context's stream.  Nothing is allocated before the first call.
 struct RefsStage {
   DevBuf<unsigned long long> dKeys, dReps, dCounts, dCtl;
   DevBuf<int32_t> dSlotOf, dIsRep, dLeftLen, dLeftFlag, dLeft;
-  DevBuf<long long> dBlockA, dBlockB;
-  DevBuf<int64_t> dOff, dLoff, dLqoff, dSpare, dLeftStart;
+  DevBuf<long long> dBlockSums;
+  DevBuf<int64_t> dOff, dLoff, dLqoff, dLeftStart;
   DevBuf<RefsRecord> dRecords;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // claim, verify and offsets | (host sizes the arrays) | gather | arrays down
   ~RefsStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
@@ -672,6 +674,12 @@ static void prepareCall(AlignCall& c) {
   c.nTodo = nq;
 }
 
+// the queries of the batch that xmListed lists (hit: null, or the memory's look-up of the representatives) in ascending order -> list, their number ->
+// dCollapseTotal; three launches enqueued on s (collapseBuildList has sized the block sums for the batch)
+static void collapseList(CollapseBuffers& b, int64_t nq, const int64_t* hit, int64_t* list, hipStream_t s) {
+  xmScan(CollapseListed{nq, b.dRepOf.p, hit, list, b.dCollapseTotal.p}, nq, b.dCollapseBlocks, s);
+}
+
 // identical queries (xm_context_set_collapse): the first pass gets the representatives, the lowest query index of each group of byte-identical queries,
 // in ascending order (xm_collapse.h).  Every later list is built by the passes from the reads they ran: representatives only.
 static void collapseBuildList(AlignCall& c) {
@@ -680,9 +688,8 @@ static void collapseBuildList(AlignCall& c) {
   hipStream_t s = c.s;
   size_t cap = 64;
   while (cap < (size_t)nq * 2) cap <<= 1;
-  const long long nBlocks = (nq + XM_COLLAPSE_PER_BLOCK - 1) / XM_COLLAPSE_PER_BLOCK;
   idx->collapseBufs.dCollapseKeys.ensure(cap); idx->collapseBufs.dCollapseReps.ensure(cap); idx->collapseBufs.dCollapseTotal.ensure(1);
-  idx->collapseBufs.dRepOf.ensure((size_t)nq); idx->collapseBufs.dRepList.ensure((size_t)nq); idx->collapseBufs.dCollapseBlocks.ensure((size_t)nBlocks);
+  idx->collapseBufs.dRepOf.ensure((size_t)nq); idx->collapseBufs.dRepList.ensure((size_t)nq); idx->collapseBufs.dCollapseBlocks.ensure(xmScanSums(nq, 1));
   HIP_CHECK(hipMemsetAsync(idx->collapseBufs.dCollapseKeys.p, 0, sizeof(unsigned long long) * cap, s));
   HIP_CHECK(hipMemsetAsync(idx->collapseBufs.dCollapseReps.p, 0xFF, sizeof(unsigned long long) * cap, s));
   const unsigned waveGrid = (unsigned)((nq + 3) / 4);  // one wave per query, four per block
@@ -690,9 +697,7 @@ static void collapseBuildList(AlignCall& c) {
   timedLaunch(c, 5, -1, [&] {
     hipLaunchKernelGGL(xm_collapse_fingerprint_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, idx->collapseBufs.dCollapseKeys.p, idx->collapseBufs.dCollapseReps.p, (unsigned long long)(cap - 1), idx->collapseBufs.dRepOf.p);
     hipLaunchKernelGGL(xm_collapse_verify_kernel, dim3(waveGrid), dim3(256), 0, s, c.bv, (const unsigned long long*)idx->collapseBufs.dCollapseReps.p, idx->collapseBufs.dRepOf.p);
-    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)nullptr, idx->collapseBufs.dCollapseBlocks.p);
-    hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dCollapseTotal.p);
-    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)nullptr, (const long long*)idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dRepList.p);
+    collapseList(idx->collapseBufs, nq, nullptr, idx->collapseBufs.dRepList.p, s);
   }, [&] { HIP_CHECK(hipMemcpyAsync(&nReps, idx->collapseBufs.dCollapseTotal.p, sizeof(nReps), hipMemcpyDeviceToHost, s)); });
   if (nReps < 1 || (long long)nReps > nq) throw std::runtime_error("internal error: collapsing found " + std::to_string(nReps) + " distinct queries in a batch of " + std::to_string(nq));
   c.copies = nq - (int64_t)nReps;
@@ -726,16 +731,12 @@ static void memoLookup(AlignCall& c) {
   hipStream_t s = c.s;
   if (memoMustEmpty(m.filled, &m.filledUnder, &c.cParams, sizeof(xm_params))) { m.clear(s); m.timesEmptied++; }
   const long long nReps = c.nTodo;
-  const long long nBlocks = (nq + XM_COLLAPSE_PER_BLOCK - 1) / XM_COLLAPSE_PER_BLOCK;
   mc.dHit.ensure((size_t)nq); mc.dFp.ensure((size_t)nq); mc.dMissList.ensure((size_t)nq); mc.dTotals.ensure(8);
   HIP_CHECK(hipMemsetAsync(mc.dTotals.p, 0, sizeof(unsigned long long) * 8, s));
   unsigned long long totals[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nMisses = 0;
   timedLaunch(c, 4, -1, [&] {
     hipLaunchKernelGGL(xm_memo_lookup_kernel, dim3((unsigned)((nReps + 3) / 4)), dim3(256), 0, s, c.bv, (const int64_t*)idx->collapseBufs.dRepList.p, nReps, m.view(), mc.dHit.p, mc.dFp.p, mc.dTotals.p);
-    hipLaunchKernelGGL(xm_collapse_count_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)mc.dHit.p, idx->collapseBufs.dCollapseBlocks.p);
-    hipLaunchKernelGGL(xm_collapse_scan_kernel, dim3(1), dim3(64), 0, s, nBlocks, idx->collapseBufs.dCollapseBlocks.p, idx->collapseBufs.dCollapseTotal.p);
-    hipLaunchKernelGGL(xm_collapse_compact_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int64_t*)idx->collapseBufs.dRepOf.p, (const int64_t*)mc.dHit.p,
-                       (const long long*)idx->collapseBufs.dCollapseBlocks.p, mc.dMissList.p);
+    collapseList(idx->collapseBufs, nq, mc.dHit.p, mc.dMissList.p, s);
   }, [&] {
     HIP_CHECK(hipMemcpyAsync(totals, mc.dTotals.p, sizeof(totals), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&nMisses, idx->collapseBufs.dCollapseTotal.p, sizeof(nMisses), hipMemcpyDeviceToHost, s));

@@ -10,11 +10,8 @@ void fastaLines(FastqStage& f, const xm_fastq_text* up, const FastqText texts[2]
   fastqLines(f, up, texts, paired, s);
   for (int k = 0; k < (paired ? 2 : 1); k++) {
     const long long n = lines[k].lines;
-    const long long nBlocks = (n + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
     hipLaunchKernelGGL(xm_fasta_lines_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, texts[k], lines[k], k, f.dCtl.p);
-    hipLaunchKernelGGL(xm_fasta_line_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, lines[k], k, (const FastqCtl*)f.dCtl.p);
-    hipLaunchKernelGGL(xm_fasta_line_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, texts[k], lines[k], k, f.dCtl.p);
-    hipLaunchKernelGGL(xm_fasta_line_offsets_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, texts[k], lines[k], k, (const FastqCtl*)f.dCtl.p);
+    xmScan(FastaLineOffsets{lines[k], texts[k].records, k, f.dCtl.p}, n, f.dLineBlockSums[k], s);  // (n announced: the grid; the kernels stop at the lines kept)
   }
 }
 
@@ -88,9 +85,9 @@ int xm_batch_stage_fasta(xm_index* idx, const xm_fasta_text* t, xm_fastq_batch**
       f.dTileCount[k].ensure((size_t)((bytes + XM_FASTQ_TILE_BYTES - 1) / XM_FASTQ_TILE_BYTES));
       f.dLineStart[k].ensure((size_t)n); f.dLineBases[k].ensure((size_t)n); f.dLineHeader[k].ensure((size_t)n);
       f.dBaseBefore[k].ensure((size_t)n + 1); f.dRecLine[k].ensure((size_t)records + 1);
-      f.dLineBlockSums[k].ensure((size_t)(2 * ((n + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK)));
+      f.dLineBlockSums[k].ensure(xmScanSums(n, 2));
       texts[k] = FastqText{f.dText[k].p, bytes, records, f.dLineEnd[k].p, f.dTileCount[k].p, n + 1};
-      lines[k] = FastaLines{n, f.dLineStart[k].p, f.dLineBases[k].p, f.dLineHeader[k].p, f.dBaseBefore[k].p, f.dRecLine[k].p, f.dLineBlockSums[k].p};
+      lines[k] = FastaLines{n, f.dLineStart[k].p, f.dLineBases[k].p, f.dLineHeader[k].p, f.dBaseBefore[k].p, f.dRecLine[k].p};
       gather[k] = FastaGatherText{f.dText[k].p, bytes, f.dLineStart[k].p, f.dBaseBefore[k].p, n};
     }
     f.dCtl.ensure(1);
@@ -106,16 +103,11 @@ int xm_batch_stage_fasta(xm_index* idx, const xm_fasta_text* t, xm_fastq_batch**
       // it, exactly as xm_batch_stage_fastq does (three waits in the call)
       const long long records = t->records1;
       f.dRecs.ensure((size_t)records); f.dRecCount.ensure((size_t)records); f.dRecFirst.ensure((size_t)records + 1);
-      const long long nBlocks = (records + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
-      f.dRecBlockSums.ensure((size_t)nBlocks);
+      f.dRecBlockSums.ensure(xmScanSums(records, 1));
       idx->dt->onStagingStream([&](hipStream_t s) {
         fastaLines(f, &up, texts, lines, false, s);
         hipLaunchKernelGGL(xm_fasta_split_records_kernel, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, s, texts[0], lines[0], (long long)split, f.dRecs.p, f.dRecCount.p, f.dCtl.p);
-        hipLaunchKernelGGL(xm_fastq_split_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, records, (const int32_t*)f.dRecCount.p, f.dRecBlockSums.p);
-        hipLaunchKernelGGL(xm_fastq_split_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, records, f.dRecBlockSums.p, f.dRecFirst.p, f.dCtl.p);
-        hipLaunchKernelGGL(xm_fastq_split_first_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, records, (const int32_t*)f.dRecCount.p, (const long long*)f.dRecBlockSums.p, f.dRecFirst.p);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(f.ev[6], s));
+        fastqSplitFirst(f, records, s);
         HIP_CHECK(hipMemcpyAsync(&ctl, f.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
       });
@@ -127,7 +119,7 @@ int xm_batch_stage_fasta(xm_index* idx, const xm_fasta_text* t, xm_fastq_batch**
     if (nq > (1ll << 28)) throw std::runtime_error(fastqWhere(0, 0) + "too many records for one text");
     const long long slots = 2 * nq;
     f.dMates.ensure((size_t)slots); d.hasQual.ensure((size_t)slots);
-    f.dBlockSums.ensure((size_t)(3 * ((slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK)));
+    f.dBlockSums.ensure(xmScanSums(slots, 3));
     d.nameOff.ensure((size_t)slots + 1);
     if (keepQual) d.qualOff.ensure((size_t)slots + 1);
     d.mateCount.ensure((size_t)nq); d.mateOffset.ensure((size_t)slots); d.mateLength.ensure((size_t)slots);

@@ -41,13 +41,7 @@ void fastqLines(FastqStage& f, const xm_fastq_text* t, const FastqText texts[2],
 
 // stage 3 (the offsets of the mate slots, the totals) on stream s (queued; the caller waits for ev[2])
 void fastqOffsets(FastqStage& f, DeviceBatch& d, long long slots, bool keepQual, hipStream_t s) {
-  const long long nBlocks = (slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
-  int64_t* qualOff = keepQual ? d.qualOff.p : nullptr;
-  hipLaunchKernelGGL(xm_fastq_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, f.dBlockSums.p);
-  hipLaunchKernelGGL(xm_fastq_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, slots, f.dBlockSums.p, d.nameOff.p, qualOff, f.dCtl.p);
-  hipLaunchKernelGGL(xm_fastq_offsets_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, slots, (const FastqMate*)f.dMates.p, keepQual ? 1 : 0, (const long long*)f.dBlockSums.p, d.mateOffset.p,
-                     d.nameOff.p, qualOff);
-  HIP_CHECK(hipGetLastError());
+  xmScan(FastqMateOffsets{slots, f.dMates.p, keepQual ? 1 : 0, d.mateOffset.p, d.nameOff.p, keepQual ? d.qualOff.p : nullptr, f.dCtl.p}, slots, f.dBlockSums, s);
   HIP_CHECK(hipEventRecord(f.ev[2], s));
 }
 
@@ -60,17 +54,18 @@ void fastqParse(FastqStage& f, DeviceBatch& d, const xm_fastq_text* t, const Fas
   fastqOffsets(f, d, slots, keepQual, s);
 }
 
-// the split form: the text up, stage 1, stages 2a and 2b (the records and their first queries) on stream s; the caller reads FastqCtl::sections behind ev[6]
+// the split form's stage 2b (the records' first queries) behind whatever made the section counts, on stream s; the caller reads FastqCtl::sections behind ev[6]
+void fastqSplitFirst(FastqStage& f, long long records, hipStream_t s) {
+  xmScan(FastqSplitFirst{records, f.dRecCount.p, f.dRecFirst.p, f.dCtl.p}, records, f.dRecBlockSums, s);
+  HIP_CHECK(hipEventRecord(f.ev[6], s));
+}
+
+// the split form: the text up, stage 1, stages 2a and 2b on stream s
 void fastqSplitRecords(FastqStage& f, const xm_fastq_text* t, const FastqText texts[2], hipStream_t s) {
   const long long records = texts[0].records;
   fastqLines(f, t, texts, false, s);
   hipLaunchKernelGGL(xm_fastq_split_records_kernel, dim3((unsigned)((records + 255) / 256)), dim3(256), 0, s, texts[0], (long long)t->split_past_size, f.dRecs.p, f.dRecCount.p, f.dCtl.p);
-  const long long nBlocks = (records + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK;
-  hipLaunchKernelGGL(xm_fastq_split_sums_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, records, (const int32_t*)f.dRecCount.p, f.dRecBlockSums.p);
-  hipLaunchKernelGGL(xm_fastq_split_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, records, f.dRecBlockSums.p, f.dRecFirst.p, f.dCtl.p);
-  hipLaunchKernelGGL(xm_fastq_split_first_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, records, (const int32_t*)f.dRecCount.p, (const long long*)f.dRecBlockSums.p, f.dRecFirst.p);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(f.ev[6], s));
+  fastqSplitFirst(f, records, s);
 }
 
 // the split form: stage 2c (a lane per section) and stage 3 over the section slots, which the caller has sized for nq queries
@@ -220,7 +215,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
       // (one wait more than without a split: three in the call)
       const long long records = t->records1;
       f.dRecs.ensure((size_t)records); f.dRecCount.ensure((size_t)records); f.dRecFirst.ensure((size_t)records + 1);
-      f.dRecBlockSums.ensure((size_t)((records + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK));
+      f.dRecBlockSums.ensure(xmScanSums(records, 1));
       idx->dt->onStagingStream([&](hipStream_t s) {
         fastqSplitRecords(f, t, texts, s);
         HIP_CHECK(hipMemcpyAsync(&ctl, f.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
@@ -233,7 +228,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     }
     const long long slots = 2 * nq;
     f.dMates.ensure((size_t)slots); d.hasQual.ensure((size_t)slots);
-    f.dBlockSums.ensure((size_t)(3 * ((slots + XM_FASTQ_SCAN_PER_BLOCK - 1) / XM_FASTQ_SCAN_PER_BLOCK)));
+    f.dBlockSums.ensure(xmScanSums(slots, 3));
     d.nameOff.ensure((size_t)slots + 1);
     if (keepQual) d.qualOff.ensure((size_t)slots + 1);
     d.mateCount.ensure((size_t)nq); d.mateOffset.ensure((size_t)slots); d.mateLength.ensure((size_t)slots);

@@ -195,16 +195,15 @@ IndelBox* igroupsCall(IGroupsStage& g, MutationsStage& m, const unsigned long lo
   const long long n = g.groups;
   if (n <= 0) return box;  // (nothing is launched)
   try {
-    const long long nBlocks = (n + XM_PTEXT_SCAN_PER_BLOCK - 1) / XM_PTEXT_SCAN_PER_BLOCK;
-    g.dKeep.ensure((size_t)n); g.dTotal.ensure((size_t)n); g.dFlag.ensure((size_t)n); g.dLen.ensure((size_t)n); g.dBlocks.ensure((size_t)nBlocks);
+    g.dKeep.ensure((size_t)n); g.dTotal.ensure((size_t)n); g.dFlag.ensure((size_t)n); g.dLen.ensure((size_t)n); g.dBlocks.ensure(xmScanSums(n, 1));
     g.dOffA.ensure((size_t)n + 1); g.dOffB.ensure((size_t)n + 1);
     if (middle) mutationsContigs(m, contigStart, contigLen, numContigs, s);
     const unsigned grid = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(xm_igroups_judge_kernel, dim3(grid), dim3(256), 0, s, (const xm::IndelGroup*)g.dGroups.p, n, middle, (const int64_t*)m.dContigStart.p, (const int32_t*)m.dContigLen.p,
                        middle ? numContigs : 0, f ? *f : xm::MutationFilter{0, 0, 0, 0, 0, 0, 0}, f ? 1 : 0, g.dKeep.p, g.dTotal.p, g.dFlag.p, g.dLen.p);
     HIP_CHECK(hipGetLastError());
-    igroupsScan(n, g.dFlag.p, g.dBlocks, g.dOffA.p, s);
-    igroupsScan(n, g.dLen.p, g.dBlocks, g.dOffB.p, s);
+    xmScan(XmOffsets<long long, 1>{n, {g.dFlag.p}, {g.dOffA.p}}, n, g.dBlocks, s);
+    xmScan(XmOffsets<long long, 1>{n, {g.dLen.p}, {g.dOffB.p}}, n, g.dBlocks, s);
     int64_t totals[2] = {0, 0};
     HIP_CHECK(hipMemcpyAsync(&totals[0], g.dOffA.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&totals[1], g.dOffB.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));

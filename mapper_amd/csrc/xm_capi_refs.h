@@ -34,11 +34,10 @@ RefsBox* refsRun(RefsStage& g, const xm::SummaryStreams& st, int64_t nq, int bit
     // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
     size_t cap = 2;
     while (cap < 2 * (size_t)nq) cap <<= 1;
-    const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
     g.dKeys.ensure(cap); g.dReps.ensure(cap); g.dCounts.ensure(cap);
     g.dSlotOf.ensure((size_t)nq); g.dLeftLen.ensure((size_t)nq); g.dLeftFlag.ensure((size_t)nq); g.dIsRep.ensure((size_t)nq);
-    g.dOff.ensure((size_t)nq + 1); g.dLoff.ensure((size_t)nq + 1); g.dLqoff.ensure((size_t)nq + 1); g.dSpare.ensure((size_t)nq + 1);
-    g.dBlockA.ensure((size_t)nBlocks); g.dBlockB.ensure((size_t)nBlocks); g.dCtl.ensure(XM_REFS_CTL_WORDS);
+    g.dOff.ensure((size_t)nq + 1); g.dLoff.ensure((size_t)nq + 1); g.dLqoff.ensure((size_t)nq + 1);
+    g.dBlockSums.ensure(xmScanSums(nq, 3)); g.dCtl.ensure(XM_REFS_CTL_WORDS);
     const RefsTable table{g.dKeys.p, g.dReps.p, g.dCounts.p, (unsigned long long)cap - 1};
     const unsigned grid = (unsigned)((nq + 255) / 256);
     HIP_CHECK(hipEventRecord(g.ev[0], s));
@@ -49,16 +48,7 @@ RefsBox* refsRun(RefsStage& g, const xm::SummaryStreams& st, int64_t nq, int bit
     HIP_CHECK(hipMemsetAsync(g.dReps.p, 0xFF, sizeof(unsigned long long) * cap, s));  // XM_REFS_NO_REP
     hipLaunchKernelGGL(xm_refs_claim_kernel, dim3(grid), dim3(256), 0, s, st, (long long)nq, bits, table, g.dSlotOf.p, g.dLeftLen.p, g.dLeftFlag.p, g.dCtl.p);
     hipLaunchKernelGGL(xm_refs_verify_kernel, dim3(grid), dim3(256), 0, s, st, (long long)nq, table, g.dSlotOf.p, g.dLeftLen.p, g.dLeftFlag.p, g.dIsRep.p);
-    // offsets of (isRep, leftLen), then of leftFlag (its second copy of the sums goes to a spare array)
-    hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dIsRep.p, (const int32_t*)g.dLeftLen.p, g.dBlockA.p, g.dBlockB.p);
-    hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, g.dBlockA.p, g.dBlockB.p, g.dOff.p, g.dLoff.p);
-    hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dIsRep.p, (const int32_t*)g.dLeftLen.p,
-                       (const long long*)g.dBlockA.p, (const long long*)g.dBlockB.p, g.dOff.p, g.dLoff.p);
-    hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dLeftFlag.p, (const int32_t*)g.dLeftFlag.p, g.dBlockA.p, g.dBlockB.p);
-    hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, g.dBlockA.p, g.dBlockB.p, g.dLqoff.p, g.dSpare.p);
-    hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dLeftFlag.p, (const int32_t*)g.dLeftFlag.p,
-                       (const long long*)g.dBlockA.p, (const long long*)g.dBlockB.p, g.dLqoff.p, g.dSpare.p);
-    HIP_CHECK(hipGetLastError());
+    xmScan(XmOffsets<int32_t, 3>{nq, {g.dIsRep.p, g.dLeftLen.p, g.dLeftFlag.p}, {g.dOff.p, g.dLoff.p, g.dLqoff.p}}, nq, g.dBlockSums, s);
     HIP_CHECK(hipEventRecord(g.ev[1], s));
     unsigned long long ctl[XM_REFS_CTL_WORDS] = {0, 0};
     int64_t totals[3] = {0, 0, 0};

@@ -50,8 +50,7 @@ SamBox* samFormat(SamStage& g, SamJob job, const xm_sam_names* hostNames, hipStr
     nameBytes = samCheckNameOffsets(hostNames->name_off, nq);
   }
   // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
-  const long long nBlocks = (nq + XM_SAM_SCAN_PER_BLOCK - 1) / XM_SAM_SCAN_PER_BLOCK;
-  g.dBytes.ensure((size_t)nq); g.dRecords.ensure((size_t)nq); g.dOffset.ensure((size_t)nq + 1); g.dBlockSums.ensure((size_t)(2 * nBlocks)); g.dCtl.ensure(4);
+  g.dBytes.ensure((size_t)nq); g.dRecords.ensure((size_t)nq); g.dOffset.ensure((size_t)nq + 1); g.dBlockSums.ensure(xmScanSums(nq, 2)); g.dCtl.ensure(4);
   if (hostNames) {
     g.dNames.ensure((size_t)nameBytes); g.dNameOff.ensure((size_t)(2 * nq + 1));
     job.batch.names = g.dNames.p; job.batch.nameOff = g.dNameOff.p;
@@ -67,14 +66,9 @@ SamBox* samFormat(SamStage& g, SamJob job, const xm_sam_names* hostNames, hipStr
       HIP_CHECK(hipMemcpyAsync(g.dNameOff.p, hostNames->name_off, sizeof(int64_t) * (size_t)(2 * nq + 1), hipMemcpyHostToDevice, s));
     }
     HIP_CHECK(hipEventRecord(g.ev[1], s));
-    if (nq > 0) {
-      hipLaunchKernelGGL(xm_sam_measure_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, job, g.dBytes.p, g.dRecords.p, g.dCtl.p);
-      hipLaunchKernelGGL(xm_sam_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const long long*)g.dBytes.p, (const long long*)g.dRecords.p, g.dBlockSums.p);
-    }
-    hipLaunchKernelGGL(xm_sam_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, g.dBlockSums.p, g.dOffset.p, g.dCtl.p);
-    if (nq > 0)
-      hipLaunchKernelGGL(xm_sam_offsets_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const long long*)g.dBytes.p, (const long long*)g.dBlockSums.p, g.dOffset.p);
-    HIP_CHECK(hipGetLastError());
+    if (nq > 0) hipLaunchKernelGGL(xm_sam_measure_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, job, g.dBytes.p, g.dRecords.p, g.dCtl.p);
+    xmScanTotals(SamSums{nq, g.dBytes.p, g.dRecords.p, g.dOffset.p, g.dCtl.p}, nq, g.dBlockSums, s);  // (a batch of 0 queries: the totals are still written)
+    xmScanPlace(SamByteOffsets{nq, g.dBytes.p, g.dOffset.p}, nq, g.dBlockSums, s, SamSums::N);
     HIP_CHECK(hipEventRecord(g.ev[2], s));
     HIP_CHECK(hipMemcpyAsync(ctl, g.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));

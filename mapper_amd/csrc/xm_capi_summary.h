@@ -31,19 +31,14 @@ SummaryBox* summaryRun(SummaryStage& g, const xm::SummaryStreams& st, int64_t nq
   try {
     for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
     // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
-    const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
     g.dAlignments.ensure((size_t)nq); g.dUnalignedFlag.ensure((size_t)nq); g.dOff.ensure((size_t)nq + 1); g.dUoff.ensure((size_t)nq + 1);
-    g.dBlockA.ensure((size_t)nBlocks); g.dBlockU.ensure((size_t)nBlocks); g.dCtl.ensure(XM_SUMMARY_CTL_WORDS);
+    g.dBlockSums.ensure(xmScanSums(nq, 2)); g.dCtl.ensure(XM_SUMMARY_CTL_WORDS);
     const unsigned grid = (unsigned)((nq + 255) / 256);
     HIP_CHECK(hipEventRecord(g.ev[0], s));
     HIP_CHECK(hipMemsetAsync(g.dCtl.p, 0xFF, sizeof(unsigned long long), s));                                               // XM_SUMMARY_NO_ERROR
     HIP_CHECK(hipMemsetAsync(g.dCtl.p + 1, 0, sizeof(unsigned long long) * (XM_SUMMARY_CTL_WORDS - 1), s));                 // the three counters
     hipLaunchKernelGGL(xm_summary_measure_kernel, dim3(grid), dim3(256), 0, s, st, (long long)nq, g.dAlignments.p, g.dUnalignedFlag.p, g.dCtl.p);
-    hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dAlignments.p, (const int32_t*)g.dUnalignedFlag.p, g.dBlockA.p, g.dBlockU.p);
-    hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, g.dBlockA.p, g.dBlockU.p, g.dOff.p, g.dUoff.p);
-    hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dAlignments.p, (const int32_t*)g.dUnalignedFlag.p,
-                       (const long long*)g.dBlockA.p, (const long long*)g.dBlockU.p, g.dOff.p, g.dUoff.p);
-    HIP_CHECK(hipGetLastError());
+    xmScan(XmOffsets<int32_t, 2>{nq, {g.dAlignments.p, g.dUnalignedFlag.p}, {g.dOff.p, g.dUoff.p}}, nq, g.dBlockSums, s);
     HIP_CHECK(hipEventRecord(g.ev[1], s));
     unsigned long long ctl[XM_SUMMARY_CTL_WORDS] = {0, 0, 0, 0};
     int64_t totals[2] = {0, 0};

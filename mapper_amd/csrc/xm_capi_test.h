@@ -462,6 +462,85 @@ int xm_test_pileup_group(int32_t device, xm_test_group_job* t, xm_indel_calls** 
   } catch (std::exception& e) { return fail(std::string("xm_test_pileup_group: ") + e.what()); }
 }
 
+}  // extern "C"
+
+namespace {
+
+// xm_test_scan's compaction: the kept items in ascending order, as a scan of the mask
+struct ScanTestKept {
+  static constexpr int N = 1;
+  long long n;
+  const uint8_t* keep;
+  int64_t* list; long long* total;
+  __device__ long long count() const { return n; }
+  __device__ void lens(long long i, long long v[1]) const { v[0] = keep[i] ? 1 : 0; }
+  __device__ void put(long long i, const long long at[1]) const { if (keep[i]) list[at[0]] = i; }
+  __device__ void totals(const long long t[1]) const { total[0] = t[0]; }
+};
+
+// the buffers of xm_test_scan, kept from call to call (a scan's block sums outlive the call that sized them everywhere else, too); never destroyed, as g_pinned
+struct ScanTestStage {
+  std::mutex mu;
+  int device = -1;
+  DevBuf<long long> dLens, dBlockSums, dTotal;
+  DevBuf<int64_t> dOff, dKept;
+  DevBuf<uint8_t> dKeep;
+};
+ScanTestStage* g_scanTest = new ScanTestStage();
+
+template <int CH>
+void scanTestOffsets(ScanTestStage& g, long long n) {
+  XmOffsets<long long, CH> items;
+  items.n = n;
+  for (int j = 0; j < CH; j++) { items.len[j] = g.dLens.p + (size_t)j * (size_t)n; items.off[j] = g.dOff.p + (size_t)j * ((size_t)n + 1); }
+  xmScan(items, n, g.dBlockSums, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+// Test-only entry (tests/test_gpu_scan.py): the scan of xm_scan.h alone.  lens: `channels` (1, 2 or 3) arrays of n lengths one behind the other; offsets gets
+// the n + 1 exclusive sums of each the same way.  keep (may be NULL): n bytes, 0 or 1 - kept[0 .. *num_kept) then gets the indices of the kept items in
+// ascending order, by a second scan over the mask with the same block sums.
+int xm_test_scan(int32_t device, int32_t channels, int64_t n, const int64_t* lens, const uint8_t* keep, int64_t* offsets, int64_t* kept, int64_t* num_kept) {
+  if (channels < 1 || channels > 3 || n < 0 || !offsets || (n > 0 && !lens) || (keep && (!kept || !num_kept))) return fail("xm_test_scan: bad arguments");
+  try {
+    ScanTestStage& g = *g_scanTest;
+    std::lock_guard<std::mutex> lock(g.mu);
+    if (device >= 0) HIP_CHECK(hipSetDevice(device));
+    int current = 0;
+    HIP_CHECK(hipGetDevice(&current));
+    if (g.device != current) {  // (buffers of another GPU are of no use)
+      g.dLens.release(); g.dBlockSums.release(); g.dTotal.release(); g.dOff.release(); g.dKept.release(); g.dKeep.release();
+      g.device = current;
+    }
+    const size_t nLens = (size_t)channels * (size_t)n, nOff = (size_t)channels * ((size_t)n + 1);
+    g.dLens.ensure(nLens); g.dOff.ensure(nOff);
+    if (nLens) HIP_CHECK(hipMemcpy(g.dLens.p, lens, sizeof(int64_t) * nLens, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemset(g.dOff.p, 0xFF, sizeof(int64_t) * nOff));  // (an offset the scan does not write shows)
+    if (channels == 1) scanTestOffsets<1>(g, n);
+    else if (channels == 2) scanTestOffsets<2>(g, n);
+    else scanTestOffsets<3>(g, n);
+    if (keep) {
+      g.dKeep.ensure((size_t)n); g.dKept.ensure((size_t)n); g.dTotal.ensure(1);
+      if (n) HIP_CHECK(hipMemcpy(g.dKeep.p, keep, (size_t)n, hipMemcpyHostToDevice));
+      if (n) HIP_CHECK(hipMemset(g.dKept.p, 0xFF, sizeof(int64_t) * (size_t)n));
+      xmScan(ScanTestKept{n, g.dKeep.p, g.dKept.p, g.dTotal.p}, n, g.dBlockSums, nullptr);
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemcpy(offsets, g.dOff.p, sizeof(int64_t) * nOff, hipMemcpyDeviceToHost));
+    if (keep) {
+      long long total = 0;
+      HIP_CHECK(hipMemcpy(&total, g.dTotal.p, sizeof(total), hipMemcpyDeviceToHost));
+      if (total < 0 || total > n) throw std::runtime_error("the scan kept " + std::to_string(total) + " of " + std::to_string(n) + " items");
+      if (total) HIP_CHECK(hipMemcpy(kept, g.dKept.p, sizeof(int64_t) * (size_t)total, hipMemcpyDeviceToHost));
+      *num_kept = total;
+    }
+    return 0;
+  } catch (std::exception& e) { return fail(std::string("xm_test_scan: ") + e.what()); }
+}
+
 // Test-only entry (tests/test_gpu_sam.py): Double.toString of xm_sam_rules.h run by the device on n values; out24 gets 24 bytes a value, len the lengths.
 int xm_test_format_doubles(int32_t device, int64_t n, const double* x, char* out24, int32_t* len) {
   if (n < 0 || (n > 0 && (!x || !out24 || !len))) return fail("xm_test_format_doubles: bad arguments");

@@ -20,20 +20,15 @@ SamBox* unalignedFormat(UnalignedStage& g, const xm::UnalignedBatch& b, const xm
     }
     for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
     // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
-    const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
     g.dBytes.ensure((size_t)nq); g.dFlag.ensure((size_t)nq); g.dOff.ensure((size_t)nq + 1); g.dUoff.ensure((size_t)nq + 1);
-    g.dBlockB.ensure((size_t)nBlocks); g.dBlockU.ensure((size_t)nBlocks); g.dCtl.ensure(XM_UNALIGNED_CTL_WORDS);
+    g.dBlockSums.ensure(xmScanSums(nq, 2)); g.dCtl.ensure(XM_UNALIGNED_CTL_WORDS);
     const unsigned grid = (unsigned)((nq + 255) / 256);
     unsigned long long ctl[XM_UNALIGNED_CTL_WORDS] = {XM_UNALIGNED_NO_ERROR, 0, XM_UNALIGNED_NO_ERROR, 0};
     int64_t totals[2] = {0, 0};
     HIP_CHECK(hipEventRecord(g.ev[0], s));
     HIP_CHECK(hipMemcpyAsync(g.dCtl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(xm_unaligned_measure_kernel, dim3(grid), dim3(256), 0, s, b, st, g.dBytes.p, g.dFlag.p, g.dCtl.p);
-    hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dBytes.p, (const int32_t*)g.dFlag.p, g.dBlockB.p, g.dBlockU.p);
-    hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, g.dBlockB.p, g.dBlockU.p, g.dOff.p, g.dUoff.p);
-    hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, (const int32_t*)g.dBytes.p, (const int32_t*)g.dFlag.p,
-                       (const long long*)g.dBlockB.p, (const long long*)g.dBlockU.p, g.dOff.p, g.dUoff.p);
-    HIP_CHECK(hipGetLastError());
+    xmScan(XmOffsets<int32_t, 2>{nq, {g.dBytes.p, g.dFlag.p}, {g.dOff.p, g.dUoff.p}}, nq, g.dBlockSums, s);
     HIP_CHECK(hipEventRecord(g.ev[1], s));
     HIP_CHECK(hipMemcpyAsync(ctl, g.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&totals[0], g.dOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));

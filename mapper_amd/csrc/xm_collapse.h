@@ -7,7 +7,7 @@
 //                                     open-addressing table (device-scope CAS claims the key, atomicMin keeps the lowest query index)
 //   2 xm_collapse_verify_kernel       one wave per query: a query whose slot holds a lower index is compared with that query byte for byte; any
 //                                     difference (a fingerprint collision) makes it its own representative.  repOf[q] = the query q is served from.
-//   3 xm_collapse_count_kernel, xm_collapse_scan_kernel, xm_collapse_compact_kernel
+//   3 the scan of xm_scan.h over CollapseListed
 //                                     the representatives in ascending query order: the first pass's work list (with the run-wide memory, xm_memo.h, a
 //                                     second time over the representatives it did not hold: the predicate is an argument)
 //   4 xm_collapse_fanout_kernel       after the last pass: every copy's slice (offsets and lengths in the result arena) is its representative's
@@ -18,9 +18,6 @@
 #include <cstdint>
 
 namespace xm {
-
-constexpr int XM_COLLAPSE_PER_THREAD = 16;
-constexpr int XM_COLLAPSE_PER_BLOCK = 256 * XM_COLLAPSE_PER_THREAD;  // queries per block of the count / compact kernels
 
 __device__ __forceinline__ unsigned long long xmCollapseMix(unsigned long long z) {  // SplitMix64's finaliser
   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
@@ -89,56 +86,21 @@ __global__ void __launch_bounds__(256) xm_collapse_verify_kernel(BatchView batch
   if (lane == 0) repOf[q] = same ? (int64_t)r : (int64_t)q;
 }
 
-__device__ __forceinline__ long long xmBlockSum(long long a, long long* sh) {
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 // The work list's predicate: q is a representative and, where the run-wide memory looked the representatives up (xm_memo.h: hit[q] = the record's offset, -1 =
 // a miss; null without the memory), it missed.
 __device__ __forceinline__ bool xmListed(const int64_t* repOf, const int64_t* hit, long long q) { return repOf[q] == q && (hit == nullptr || hit[q] < 0); }
 
-// listed queries per block of XM_COLLAPSE_PER_BLOCK queries
-__global__ void __launch_bounds__(256) xm_collapse_count_kernel(long long nq, const int64_t* repOf, const int64_t* hit, long long* blockCount) {
-  __shared__ long long sh[256];
-  const long long base = (long long)blockIdx.x * XM_COLLAPSE_PER_BLOCK + (long long)threadIdx.x * XM_COLLAPSE_PER_THREAD;
-  long long a = 0;
-  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && xmListed(repOf, hit, base + k)) a++;
-  a = xmBlockSum(a, sh);
-  if (threadIdx.x == 0) blockCount[blockIdx.x] = a;
-}
-
-// exclusive prefix of the block counts; total[0] = number of listed queries
-__global__ void xm_collapse_scan_kernel(long long nBlocks, long long* blockCount, unsigned long long* total) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long a = 0;
-  for (long long i = 0; i < nBlocks; i++) { const long long x = blockCount[i]; blockCount[i] = a; a += x; }
-  total[0] = (unsigned long long)a;
-}
-
-// list[0 .. total) = the listed queries in ascending query order
-__global__ void __launch_bounds__(256) xm_collapse_compact_kernel(long long nq, const int64_t* repOf, const int64_t* hit, const long long* blockCount, int64_t* list) {
-  __shared__ long long sh[256];
-  const long long base = (long long)blockIdx.x * XM_COLLAPSE_PER_BLOCK + (long long)threadIdx.x * XM_COLLAPSE_PER_THREAD;
-  long long a = 0;
-  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && xmListed(repOf, hit, base + k)) a++;
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the 256 thread counts
-    long long x = 0;
-    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
-    __syncthreads();
-    sh[threadIdx.x] += x;
-    __syncthreads();
-  }
-  long long at = blockCount[blockIdx.x] + sh[threadIdx.x] - a;
-  for (int k = 0; k < XM_COLLAPSE_PER_THREAD; k++) if (base + k < nq && xmListed(repOf, hit, base + k)) list[at++] = base + k;
-}
+// The work list as a scan (xm_scan.h) of the predicate: list[0 .. total[0]) = the listed queries in ascending query order, total[0] = how many
+struct CollapseListed {
+  static constexpr int N = 1;
+  long long nq;
+  const int64_t* repOf; const int64_t* hit;
+  int64_t* list; unsigned long long* total;
+  __device__ long long count() const { return nq; }
+  __device__ void lens(long long q, long long v[1]) const { v[0] = xmListed(repOf, hit, q) ? 1 : 0; }
+  __device__ void put(long long q, const long long at[1]) const { if (xmListed(repOf, hit, q)) list[at[0]] = q; }
+  __device__ void totals(const long long t[1]) const { total[0] = (unsigned long long)t[0]; }
+};
 
 // every copy's slice is its representative's (the representatives were written by the passes, in earlier launches; no copy is a representative)
 __global__ void __launch_bounds__(256) xm_collapse_fanout_kernel(long long nq, const int64_t* repOf, int64_t* intOff, int64_t* dblOff, int32_t* intLen, int32_t* dblLen) {

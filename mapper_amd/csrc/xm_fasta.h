@@ -4,8 +4,8 @@
 // another workgroup of the same launch wrote (the per-XCD L2s are not coherent):
 //   1 line ends   xm_fastq_count / tiles / ends_kernel (xm_fastq.h, unchanged), with FastqText::lineCap = the lines announced + 1
 //   2 lines       xm_fasta_lines_kernel          a lane per line: header or body, where its name or its trimmed bases start, how many bases it adds
-//   3 line scans  xm_fasta_line_sums_kernel, xm_fasta_line_blocks_kernel, xm_fasta_line_offsets_kernel
-//                                                exclusive scans of the header flags and of the trimmed lengths, XM_FASTQ_SCAN_PER_BLOCK lines a block: header r
+//   3 line scans  the scan of xm_scan.h over FastaLineOffsets
+//                                                exclusive sums of the header flags and of the trimmed lengths: header r
 //                                                scatters recLine[r], every line gets baseBefore[line]; recLine[records] = lines, baseBefore[lines] = the bases;
 //                                                the headers found go to FastqCtl::headers for the host's check of the strict form
 //   4 records     xm_fasta_records_kernel        a lane per mate slot: the name from the header line, first = baseBefore[recLine[r]], length from recLine[r + 1]
@@ -29,7 +29,6 @@ struct FastaLines {
   uint8_t* lineHeader;
   int32_t* baseBefore;   // a text holds at most 2^30 bytes: int32 suffices
   int32_t* recLine;
-  long long* blockSums;  // [2 * blocks of the line scan]
 };
 
 // the lines stages 2 to 6 look at: those found (FastqCtl::lines, a launch earlier) and kept (no more than announced)
@@ -57,58 +56,26 @@ __global__ void __launch_bounds__(256) xm_fasta_lines_kernel(FastqText t, FastaL
   L.lineHeader[line] = header ? 1 : 0;
 }
 
-__global__ void __launch_bounds__(256) xm_fasta_line_sums_kernel(FastaLines L, int file, const FastqCtl* ctl) {
-  __shared__ long long sh[2][256];
-  const long long n = fastaLinesKept(ctl, file, L);
-  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
-  long long a[2] = {0, 0};
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < n) { a[0] += L.lineHeader[base + k]; a[1] += L.lineBases[base + k]; }
-  sh[0][threadIdx.x] = a[0]; sh[1][threadIdx.x] = a[1];
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) { sh[0][threadIdx.x] += sh[0][threadIdx.x + d]; sh[1][threadIdx.x] += sh[1][threadIdx.x + d]; }
-    __syncthreads();
+// stage 3's Items (xm_scan.h) over the lines kept: (header flag, bases) per line
+struct FastaLineOffsets {
+  static constexpr int N = 2;
+  FastaLines L;
+  long long records;  // announced: recLine holds records + 1 entries
+  int file;
+  FastqCtl* ctl;
+  __device__ long long count() const { return fastaLinesKept(ctl, file, L); }
+  __device__ void lens(long long line, long long v[2]) const { v[0] = L.lineHeader[line]; v[1] = L.lineBases[line]; }
+  __device__ void put(long long line, const long long off[2]) const {
+    L.baseBefore[line] = (int32_t)off[1];
+    if (L.lineHeader[line] && off[0] < records) L.recLine[off[0]] = (int32_t)line;  // (more headers than announced: the host sees it in FastqCtl::headers)
   }
-  if (threadIdx.x < 2) L.blockSums[2 * (long long)blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
-}
-
-__global__ void xm_fasta_line_blocks_kernel(long long nBlocks, FastqText t, FastaLines L, int file, FastqCtl* ctl) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long run[2] = {0, 0};
-  for (long long i = 0; i < nBlocks; i++)
-    for (int j = 0; j < 2; j++) { const long long x = L.blockSums[2 * i + j]; L.blockSums[2 * i + j] = run[j]; run[j] += x; }
-  const long long n = fastaLinesKept(ctl, file, L);
-  ctl->headers[file] = run[0];
-  L.baseBefore[n] = (int32_t)run[1];
-  L.recLine[t.records] = (int32_t)n;
-}
-
-__global__ void __launch_bounds__(256) xm_fasta_line_offsets_kernel(FastqText t, FastaLines L, int file, const FastqCtl* ctl) {
-  __shared__ long long sh[2][256];
-  const long long n = fastaLinesKept(ctl, file, L);
-  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
-  long long a[2] = {0, 0};
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < n) { a[0] += L.lineHeader[base + k]; a[1] += L.lineBases[base + k]; }
-  sh[0][threadIdx.x] = a[0]; sh[1][threadIdx.x] = a[1];
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    long long x[2] = {0, 0};
-    if ((int)threadIdx.x >= d) { x[0] = sh[0][threadIdx.x - d]; x[1] = sh[1][threadIdx.x - d]; }
-    __syncthreads();
-    sh[0][threadIdx.x] += x[0]; sh[1][threadIdx.x] += x[1];
-    __syncthreads();
+  __device__ void totals(const long long t[2]) const {
+    const long long n = count();
+    ctl->headers[file] = t[0];
+    L.baseBefore[n] = (int32_t)t[1];
+    L.recLine[records] = (int32_t)n;
   }
-  long long rec = L.blockSums[2 * (long long)blockIdx.x] + sh[0][threadIdx.x] - a[0];
-  long long bases = L.blockSums[2 * (long long)blockIdx.x + 1] + sh[1][threadIdx.x] - a[1];
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < n) {
-    L.baseBefore[base + k] = (int32_t)bases;
-    if (L.lineHeader[base + k]) {
-      if (rec < t.records) L.recLine[rec] = (int32_t)(base + k);  // (more headers than announced: the host sees it in FastqCtl::headers)
-      rec++;
-    }
-    bases += L.lineBases[base + k];
-  }
-}
+};
 
 // record r of a text whose counts hold -> its name and its ordinals; false: nothing to read (the host refuses the text by its counts)
 __device__ __forceinline__ bool fastaRecordOf(const FastqText& t, const FastaLines& L, int file, const FastqCtl* ctl, long long r, FastqMate& m) {

@@ -9,14 +9,15 @@
 //   2 fields      xm_fastq_fields_kernel   a lane per mate slot: the four line bounds of its record -> name, sequence, quality (fastqRecord); the first
 //                                          record that is not of the strict form is kept with atomicMin on (file, record)
 //                 (with a split size: 2a-2c below - records, the scan of their section counts, a lane per section; stages 3 and 4 then see section slots)
-//   3 offsets     xm_fastq_sums_kernel, xm_fastq_blocks_kernel, xm_fastq_offsets_kernel
-//                                          exclusive scans of the sequence, name and quality lengths in batch order (the three-kernel scan of
-//                                          xm_result_stage.h with three values); the host reads the totals to size codes, names, quals
+//   3 offsets     the scan of xm_scan.h over FastqMateOffsets
+//                                          exclusive sums of the sequence, name and quality lengths in batch order; the host reads the totals to size
+//                                          codes, names, quals
 //   4 gather      xm_fastq_gather_kernel   a wave per mate, the code table in LDS: bases translated into codes, name and quality bytes copied, 64 bytes a round
 // Plain HIP.  Everything is sized by the host from `records` and `bytes`: lineEnd holds 4 * records + 1 entries (FastqText::lineCap), stage 1 writes no entry behind them and
 // stage 2 reads none that was not written, whatever the text holds; a text whose line count is not 4 * records is an error the host sees in FastqCtl.
 #pragma once
 #include "xm_fastq_rules.h"
+#include "xm_scan.h"
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -24,8 +25,6 @@ namespace xm {
 
 constexpr int XM_FASTQ_LANE_BYTES = 16;
 constexpr int XM_FASTQ_TILE_BYTES = 256 * XM_FASTQ_LANE_BYTES;  // (xm_fastq_tile_bytes(): tests/test_gpu_fastq.py walks the edges this gives)
-constexpr int XM_FASTQ_SCAN_PER_THREAD = 16;
-constexpr int XM_FASTQ_SCAN_PER_BLOCK = 256 * XM_FASTQ_SCAN_PER_THREAD;  // mate slots per block of the offset scan
 constexpr unsigned long long XM_FASTQ_NO_ERROR = ~0ull;
 
 // what the host reads back after stage 3
@@ -78,38 +77,27 @@ __device__ __forceinline__ int fastqLaneNewlines(const FastqText& t, long long a
 }
 
 __global__ void __launch_bounds__(256) xm_fastq_count_kernel(FastqText t) {
-  __shared__ int sh[256];
+  __shared__ int sh[1][256];
   uint32_t bits[4];
   const long long at = (long long)blockIdx.x * XM_FASTQ_TILE_BYTES + (long long)threadIdx.x * XM_FASTQ_LANE_BYTES;
-  sh[threadIdx.x] = fastqLaneNewlines(t, at, bits);
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) t.tileCount[blockIdx.x] = sh[0];
+  int count[1] = {fastqLaneNewlines(t, at, bits)};
+  xmBlockSum(count, sh);
+  if (threadIdx.x == 0) t.tileCount[blockIdx.x] = count[0];
 }
 
 // one block: tileCount[] becomes its exclusive scan; lines found (with the virtual one) -> ctl->lines[file]
 __global__ void __launch_bounds__(256) xm_fastq_tiles_kernel(FastqText t, long long nTiles, int file, FastqCtl* ctl) {
-  __shared__ long long sh[256];
+  __shared__ long long sh[1][256];
   const long long per = (nTiles + 255) / 256;
   const long long a = (long long)threadIdx.x * per, b = a + per < nTiles ? a + per : nTiles;
   long long mine = 0;
   for (long long i = a; i < b; i++) mine += t.tileCount[i];
-  sh[threadIdx.x] = mine;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the 256 thread totals
-    long long x = 0;
-    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
-    __syncthreads();
-    sh[threadIdx.x] += x;
-    __syncthreads();
-  }
-  long long run = sh[threadIdx.x] - mine;
+  long long upTo[1] = {mine};
+  xmBlockScan(upTo, sh);
+  long long run = upTo[0] - mine;
   for (long long i = a; i < b; i++) { const int c = t.tileCount[i]; t.tileCount[i] = (int32_t)run; run += c; }  // (a text holds less than 2^31 bytes)
   if (threadIdx.x == 0) {
-    long long lines = sh[255];
+    long long lines = sh[0][255];
     if (t.bytes > 0 && t.text[t.bytes - 1] != '\n') {  // the last block of a file may lack the final newline
       if (lines < t.lineCap) t.lineEnd[lines] = (int32_t)t.bytes;
       lines++;
@@ -119,20 +107,13 @@ __global__ void __launch_bounds__(256) xm_fastq_tiles_kernel(FastqText t, long l
 }
 
 __global__ void __launch_bounds__(256) xm_fastq_ends_kernel(FastqText t) {
-  __shared__ int sh[256];
+  __shared__ int sh[1][256];
   uint32_t bits[4];
   const long long at = (long long)blockIdx.x * XM_FASTQ_TILE_BYTES + (long long)threadIdx.x * XM_FASTQ_LANE_BYTES;
   const int mine = fastqLaneNewlines(t, at, bits);
-  sh[threadIdx.x] = mine;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    int x = 0;
-    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
-    __syncthreads();
-    sh[threadIdx.x] += x;
-    __syncthreads();
-  }
-  long long line = (long long)t.tileCount[blockIdx.x] + sh[threadIdx.x] - mine;
+  int upTo[1] = {mine};
+  xmBlockScan(upTo, sh);
+  long long line = (long long)t.tileCount[blockIdx.x] + upTo[0] - mine;
   const long long cap = t.lineCap;
   for (int k = 0; k < 4; k++) {
     uint32_t b = bits[k];
@@ -195,8 +176,8 @@ __global__ void __launch_bounds__(256) xm_fastq_fields_kernel(FastqText t0, Fast
 // ---- the split form of stage 2 (split_past_size > 0, single reads): a record becomes its SequenceSplitter sections, each a query.  Three steps
 // in the place of xm_fastq_fields_kernel, each its own launch(es); the host reads the query count between the second and the third to size the slot arrays.
 //   2a records    xm_fastq_split_records_kernel   a lane per record: fastqRecordSplit -> the record's fields and how many sections it gives
-//   2b first      xm_fastq_split_sums_kernel, xm_fastq_split_blocks_kernel, xm_fastq_split_first_kernel
-//                                                 exclusive scan of the section counts: first[r] = the first query of record r, first[records] = ctl->sections
+//   2b first      the scan of xm_scan.h over FastqSplitFirst
+//                                                 exclusive sums of the section counts: first[r] = the first query of record r, first[records] = ctl->sections
 //   2c sections   xm_fastq_split_sections_kernel  a lane per query: its record by binary search over first[], its section by fastqSectionMate -> both mate slots
 __global__ void __launch_bounds__(256) xm_fastq_split_records_kernel(FastqText t, long long split, FastqMate* recs, int32_t* counts, FastqCtl* ctl) {
   const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -224,45 +205,17 @@ __global__ void __launch_bounds__(256) xm_fastq_split_records_kernel(FastqText t
   counts[r] = count;
 }
 
-__global__ void __launch_bounds__(256) xm_fastq_split_sums_kernel(long long records, const int32_t* counts, long long* blockSums) {
-  __shared__ long long sh[256];
-  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
-  long long a = 0;
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < records) a += counts[base + k];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) blockSums[blockIdx.x] = sh[0];
-}
-
-__global__ void xm_fastq_split_blocks_kernel(long long nBlocks, long long records, long long* blockSums, int64_t* first, FastqCtl* ctl) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long run = 0;
-  for (long long i = 0; i < nBlocks; i++) { const long long x = blockSums[i]; blockSums[i] = run; run += x; }
-  first[records] = run;
-  ctl->sections = run;
-}
-
-__global__ void __launch_bounds__(256) xm_fastq_split_first_kernel(long long records, const int32_t* counts, const long long* blockSums, int64_t* first) {
-  __shared__ long long sh[256];
-  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
-  long long a = 0;
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < records) a += counts[base + k];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    long long x = 0;
-    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
-    __syncthreads();
-    sh[threadIdx.x] += x;
-    __syncthreads();
-  }
-  long long at = blockSums[blockIdx.x] + sh[threadIdx.x] - a;
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < records) { first[base + k] = at; at += counts[base + k]; }
-}
+// stage 2b's Items (xm_scan.h): first[r] = the sections in front of record r, first[records] = ctl->sections = all of them
+struct FastqSplitFirst {
+  static constexpr int N = 1;
+  long long records;
+  const int32_t* counts;
+  int64_t* first; FastqCtl* ctl;
+  __device__ long long count() const { return records; }
+  __device__ void lens(long long r, long long v[1]) const { v[0] = counts[r]; }
+  __device__ void put(long long r, const long long at[1]) const { first[r] = at[0]; }
+  __device__ void totals(const long long t[1]) const { first[records] = t[0]; ctl->sections = t[0]; }
+};
 
 // nq = first[records] as the host read it, which sized out's arrays: no lane writes behind them
 __global__ void __launch_bounds__(256) xm_fastq_split_sections_kernel(long long nq, long long records, const FastqMate* recs, const int64_t* first, FastqFieldsOut out) {
@@ -297,67 +250,25 @@ __global__ void __launch_bounds__(256) xm_fastq_split_sections_kernel(long long 
   out.hasQual[2 * q + 1] = 0;
 }
 
-// ---- stage 3: the scans (xm_result_stage.h's, over three values; without qualities the third is 0)
-__device__ __forceinline__ void fastqLens(const FastqMate& m, int keepQual, long long v[3]) { v[0] = m.seqLen; v[1] = m.nameLen; v[2] = keepQual ? m.qualLen : 0; }
-
-__global__ void __launch_bounds__(256) xm_fastq_sums_kernel(long long slots, const FastqMate* mates, int keepQual, long long* blockSums) {
-  __shared__ long long sh[3][256];
-  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
-  long long a[3] = {0, 0, 0};
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < slots) {
-    long long v[3];
-    fastqLens(mates[base + k], keepQual, v);
-    a[0] += v[0]; a[1] += v[1]; a[2] += v[2];
+// ---- stage 3: the scan (xm_scan.h) of the sequence, name and quality lengths of the mate slots; without qualities the third is 0 and qualOff is null
+struct FastqMateOffsets {
+  static constexpr int N = 3;
+  long long slots;
+  const FastqMate* mates; int keepQual;
+  int64_t* mateOffset; int64_t* nameOff; int64_t* qualOff; FastqCtl* ctl;
+  __device__ long long count() const { return slots; }
+  __device__ void lens(long long i, long long v[3]) const { const FastqMate& m = mates[i]; v[0] = m.seqLen; v[1] = m.nameLen; v[2] = keepQual ? m.qualLen : 0; }
+  __device__ void put(long long i, const long long off[3]) const {
+    mateOffset[i] = mates[i].seqLen > 0 ? off[0] : 0;  // (the padding mate of a single query: offset 0)
+    nameOff[i] = off[1];
+    if (qualOff) qualOff[i] = off[2];
   }
-  for (int j = 0; j < 3; j++) sh[j][threadIdx.x] = a[j];
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) for (int j = 0; j < 3; j++) sh[j][threadIdx.x] += sh[j][threadIdx.x + d];
-    __syncthreads();
+  __device__ void totals(const long long t[3]) const {
+    for (int j = 0; j < 3; j++) ctl->totals[j] = t[j];
+    nameOff[slots] = t[1];
+    if (qualOff) qualOff[slots] = t[2];
   }
-  if (threadIdx.x < 3) blockSums[3 * (long long)blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
-}
-
-__global__ void xm_fastq_blocks_kernel(long long nBlocks, long long slots, long long* blockSums, int64_t* nameOff, int64_t* qualOff, FastqCtl* ctl) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long run[3] = {0, 0, 0};
-  for (long long i = 0; i < nBlocks; i++)
-    for (int j = 0; j < 3; j++) { const long long x = blockSums[3 * i + j]; blockSums[3 * i + j] = run[j]; run[j] += x; }
-  for (int j = 0; j < 3; j++) ctl->totals[j] = run[j];
-  nameOff[slots] = run[1];
-  if (qualOff) qualOff[slots] = run[2];
-}
-
-__global__ void __launch_bounds__(256) xm_fastq_offsets_kernel(long long slots, const FastqMate* mates, int keepQual, const long long* blockSums, int64_t* mateOffset, int64_t* nameOff,
-                                                               int64_t* qualOff) {
-  __shared__ long long sh[3][256];
-  const long long base = (long long)blockIdx.x * XM_FASTQ_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_FASTQ_SCAN_PER_THREAD;
-  long long a[3] = {0, 0, 0};
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < slots) {
-    long long v[3];
-    fastqLens(mates[base + k], keepQual, v);
-    a[0] += v[0]; a[1] += v[1]; a[2] += v[2];
-  }
-  for (int j = 0; j < 3; j++) sh[j][threadIdx.x] = a[j];
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    long long x[3] = {0, 0, 0};
-    if ((int)threadIdx.x >= d) for (int j = 0; j < 3; j++) x[j] = sh[j][threadIdx.x - d];
-    __syncthreads();
-    for (int j = 0; j < 3; j++) sh[j][threadIdx.x] += x[j];
-    __syncthreads();
-  }
-  long long off[3];
-  for (int j = 0; j < 3; j++) off[j] = blockSums[3 * (long long)blockIdx.x + j] + sh[j][threadIdx.x] - a[j];
-  for (int k = 0; k < XM_FASTQ_SCAN_PER_THREAD; k++) if (base + k < slots) {
-    long long v[3];
-    fastqLens(mates[base + k], keepQual, v);
-    mateOffset[base + k] = v[0] > 0 ? off[0] : 0;  // (the padding mate of a single query: offset 0)
-    nameOff[base + k] = off[1];
-    if (qualOff) qualOff[base + k] = off[2];
-    off[0] += v[0]; off[1] += v[1]; off[2] += v[2];
-  }
-}
+};
 
 // ---- stage 4: a wave per mate slot, four to a block
 __global__ void __launch_bounds__(256) xm_fastq_gather_kernel(long long slots, const FastqMate* mates, const char* text0, const char* text1, const int64_t* mateOffset, const int64_t* nameOff,

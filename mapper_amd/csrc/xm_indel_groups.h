@@ -230,15 +230,6 @@ __global__ void __launch_bounds__(256) xm_igroups_gather_kernel(const xm::IndelG
 }
 
 // ---------------------------------------------------------------- the host's side
-// the exclusive sums of len[0 .. n) and their total in off[0 .. n], enqueued on s (the three kernels of xm_pileup_text.h); n > 0
-void igroupsScan(long long n, const long long* len, DevBuf<long long>& blocks, int64_t* off, hipStream_t s) {
-  const long long nBlocks = (n + XM_PTEXT_SCAN_PER_BLOCK - 1) / XM_PTEXT_SCAN_PER_BLOCK;
-  hipLaunchKernelGGL(xm_ptext_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, n, len, blocks.p);
-  hipLaunchKernelGGL(xm_ptext_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, n, blocks.p, off);
-  hipLaunchKernelGGL(xm_ptext_offsets_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, n, len, (const long long*)blocks.p, off);
-  HIP_CHECK(hipGetLastError());
-}
-
 // A buffer grows and keeps its first `keep` entries: the copy is enqueued on s in front of the call's launches, and the old buffer goes to `old`, which the
 // fold frees behind its own wait - growth adds no wait to a call.
 template <class T>
@@ -314,16 +305,15 @@ struct IGroupsStage {
   long long fold(const IGroupsItems& v, hipStream_t s, const IGroupsLeft& left) {
     const long long n = v.n;
     const unsigned grid = (unsigned)((n + 255) / 256);
-    const long long nBlocks = (n + XM_PTEXT_SCAN_PER_BLOCK - 1) / XM_PTEXT_SCAN_PER_BLOCK;
-    dSlot.ensure((size_t)n); dFlag.ensure((size_t)n); dLen.ensure((size_t)n); dFlag2.ensure((size_t)n); dLen2.ensure((size_t)n); dBlocks.ensure((size_t)nBlocks);
+    dSlot.ensure((size_t)n); dFlag.ensure((size_t)n); dLen.ensure((size_t)n); dFlag2.ensure((size_t)n); dLen2.ensure((size_t)n); dBlocks.ensure(xmScanSums(n, 1));
     dOffA.ensure((size_t)n + 1); dOffB.ensure((size_t)n + 1);
     const IGroupsTable t = view();
     HIP_CHECK(hipMemsetAsync(dCtl.p, 0, sizeof(unsigned long long) * XM_IGROUPS_CTL_WORDS, s));
     hipLaunchKernelGGL(xm_igroups_claim_kernel, dim3(grid), dim3(256), 0, s, v, bits, t, dSlot.p);
     hipLaunchKernelGGL(xm_igroups_mark_kernel, dim3(grid), dim3(256), 0, s, v, t, (const long long*)dSlot.p, dFlag.p, dLen.p);
     HIP_CHECK(hipGetLastError());
-    igroupsScan(n, dFlag.p, dBlocks, dOffA.p, s);
-    igroupsScan(n, dLen.p, dBlocks, dOffB.p, s);
+    xmScan(XmOffsets<long long, 1>{n, {dFlag.p}, {dOffA.p}}, n, dBlocks, s);
+    xmScan(XmOffsets<long long, 1>{n, {dLen.p}, {dOffB.p}}, n, dBlocks, s);
     hipLaunchKernelGGL(xm_igroups_place_kernel, dim3(grid), dim3(256), 0, s, v, t, (const long long*)dSlot.p, (const long long*)dFlag.p, (const int64_t*)dOffA.p, (const int64_t*)dOffB.p, groups,
                        arenaUsed, (long long)dGroups.n, (long long)dArena.n, dCtl.p);
     hipLaunchKernelGGL(xm_igroups_add_kernel, dim3(grid), dim3(256), 0, s, v, t, (const long long*)dSlot.p, (long long)std::min<size_t>(dGroups.n, (size_t)(groups + n)), dFlag2.p, dLen2.p, dCtl.p);
@@ -340,8 +330,8 @@ struct IGroupsStage {
     const long long nLeft = (long long)ctl[0];
     if (nLeft == 0) return 0;
     // left-overs: true fingerprint collisions (with whole fingerprints none in any run that has been seen)
-    igroupsScan(n, dFlag2.p, dBlocks, dOffA.p, s);
-    igroupsScan(n, dLen2.p, dBlocks, dOffB.p, s);
+    xmScan(XmOffsets<long long, 1>{n, {dFlag2.p}, {dOffA.p}}, n, dBlocks, s);
+    xmScan(XmOffsets<long long, 1>{n, {dLen2.p}, {dOffB.p}}, n, dBlocks, s);
     long long textBytes = 0;
     HIP_CHECK(hipMemcpyAsync(&textBytes, dOffB.p + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));

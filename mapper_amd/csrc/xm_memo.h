@@ -6,7 +6,7 @@
 //   1 xm_memo_lookup_kernel   one wave per representative: the collapse's fingerprint, a linear probe, and on a key match the record's header and bytes
 //                             compared with the query across the lanes - in the young generation first, then in the old one.  hit[q] = the record's
 //                             offset in the whole arena (which says where it is), -1 = a miss.
-//   2 xm_collapse_count / scan / compact_kernel with hit[] as their predicate: the representatives that missed, ascending - the first pass's work list
+//   2 the scan over CollapseListed (xm_collapse.h) with hit[] in its predicate: the representatives that missed, ascending - the first pass's work list
 //   3 xm_memo_replay_kernel   before the passes, one wave per representative (a miss leaves at once): room in the call's result arenas from the call's own
 //                             cursors, the two slices copied, offsets, lengths and status set to what a read a pass finished has
 //   3b xm_memo_promote_kernel the hits of the old generation copied into the young one, when it takes them all (second chance)

@@ -2,8 +2,7 @@
 // over the plain rules of xm_pileup_text_rules.h.  Three stages, separate launches on the context's stream, no launch reads what another workgroup of the
 // same launch wrote:
 //   measure   a lane per event of the call, in the order the atomic counter appended them: the bytes of text the event keeps (0 for a deletion)
-//   offsets   the exclusive sums of those lengths and their total (three kernels, the twin of xm_result_stage.h's scan over one 64-bit array: 16 events a
-//             thread, 4096 a block)
+//   offsets   the exclusive sums of those lengths and their total (the scan of xm_scan.h over one 64-bit array)
 //   gather    a lane per byte of the text: it finds its event by a binary search over the offsets and writes one letter.  Insertions are a few bases each
 //             and a rare one is a thousand: a lane per byte keeps the stores of a wavefront side by side and the long event costs no lane more than a
 //             short one, for log2(events) reads of offsets that sit in the cache.  A lane stores byte b only, and only with off[e] <= b < off[e + 1].
@@ -12,9 +11,6 @@
 #include <hip/hip_runtime.h>
 
 namespace {
-
-constexpr int XM_PTEXT_SCAN_PER_THREAD = 16;
-constexpr int XM_PTEXT_SCAN_PER_BLOCK = 256 * XM_PTEXT_SCAN_PER_THREAD;
 
 // what the stages read: the n events of the call where the pile-up kernel appended them, and the batch they came from (event[4] - queryBase is the query)
 struct PileupTextJob {
@@ -43,45 +39,6 @@ __global__ void __launch_bounds__(256) xm_ptext_measure_kernel(PileupTextJob j, 
   len[e] = xm::pileupTextKept(ev[2], ev[3], ev[6], readLen);
 }
 
-__global__ void __launch_bounds__(256) xm_ptext_totals_kernel(long long n, const long long* len, long long* blockSums) {
-  __shared__ long long sh[256];
-  const long long base = (long long)blockIdx.x * XM_PTEXT_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_PTEXT_SCAN_PER_THREAD;
-  long long a = 0;
-  for (int k = 0; k < XM_PTEXT_SCAN_PER_THREAD; k++) if (base + k < n) a += len[base + k];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) blockSums[blockIdx.x] = sh[0];
-}
-
-__global__ void xm_ptext_blocks_kernel(long long nBlocks, long long n, long long* blockSums, int64_t* off) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long a = 0;
-  for (long long i = 0; i < nBlocks; i++) { const long long x = blockSums[i]; blockSums[i] = a; a += x; }
-  off[n] = a;
-}
-
-__global__ void __launch_bounds__(256) xm_ptext_offsets_kernel(long long n, const long long* len, const long long* blockSums, int64_t* off) {
-  __shared__ long long sh[256];
-  const long long base = (long long)blockIdx.x * XM_PTEXT_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_PTEXT_SCAN_PER_THREAD;
-  long long a = 0;
-  for (int k = 0; k < XM_PTEXT_SCAN_PER_THREAD; k++) if (base + k < n) a += len[base + k];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the 256 thread totals
-    long long x = 0;
-    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
-    __syncthreads();
-    sh[threadIdx.x] += x;
-    __syncthreads();
-  }
-  long long at = blockSums[blockIdx.x] + sh[threadIdx.x] - a;
-  for (int k = 0; k < XM_PTEXT_SCAN_PER_THREAD; k++) if (base + k < n) { off[base + k] = at; at += len[base + k]; }
-}
-
 // textCap: the bytes the text buffer holds (the host sized it for the total; no lane stores behind it whatever the offsets say)
 __global__ void __launch_bounds__(256) xm_ptext_gather_kernel(PileupTextJob j, const int64_t* off, char* text, long long textCap) {
   const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -106,13 +63,9 @@ struct PileupTextStage {
   DevBuf<char> dText;
   // measure and offsets of the j.n > 0 events, enqueued on s: afterwards dOff[0 .. n] are the offsets and dOff[n] the bytes of the whole text
   void offsets(const PileupTextJob& j, hipStream_t s) {
-    const long long nBlocks = (j.n + XM_PTEXT_SCAN_PER_BLOCK - 1) / XM_PTEXT_SCAN_PER_BLOCK;
-    dLen.ensure((size_t)j.n); dBlocks.ensure((size_t)nBlocks); dOff.ensure((size_t)j.n + 1);
+    dLen.ensure((size_t)j.n); dBlocks.ensure(xmScanSums(j.n, 1)); dOff.ensure((size_t)j.n + 1);
     hipLaunchKernelGGL(xm_ptext_measure_kernel, dim3((unsigned)((j.n + 255) / 256)), dim3(256), 0, s, j, dLen.p);
-    hipLaunchKernelGGL(xm_ptext_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, j.n, (const long long*)dLen.p, dBlocks.p);
-    hipLaunchKernelGGL(xm_ptext_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, j.n, dBlocks.p, dOff.p);
-    hipLaunchKernelGGL(xm_ptext_offsets_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, j.n, (const long long*)dLen.p, (const long long*)dBlocks.p, dOff.p);
-    HIP_CHECK(hipGetLastError());
+    xmScan(XmOffsets<long long, 1>{j.n, {dLen.p}, {dOff.p}}, j.n, dBlocks, s);
   }
   // the letters of a text of total > 0 bytes, enqueued on s behind offsets()
   void gather(const PileupTextJob& j, long long total, hipStream_t s) {

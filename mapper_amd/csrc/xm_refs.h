@@ -8,7 +8,7 @@
 //   verify    a lane with a slot compares its set with that of the slot's representative (the representative's slice walked again): equal - it is counted
 //             on the slot; different - a fingerprint collision: slotOf[q] = -2, leftLen[q] = nSeq, the host counts it.  The count is one atomic add per
 //             distinct slot per wavefront, not per lane: a reference of one contig sends every aligned query of a batch to one address.
-//   offsets   exclusive sums in query order of isRep and leftLen, and of leftFlag: the scan of xm_result_stage.h (xm_scan_*_kernel) run twice, not a third one
+//   offsets   exclusive sums in query order of isRep, leftLen and leftFlag: one scan of xm_scan.h over the three int32 arrays
 //   gather    a representative walks again and writes its record {count, n, ids} at records[off[q]]; a left-over query writes its nSeq contigs, repeats and
 //             stream order kept, at left[loff[q] .. loff[q + 1]) and where they start at leftStart[lqoff[q]].  No lane stores outside its own range or behind
 //             a buffer's end, whatever the second walk yields.

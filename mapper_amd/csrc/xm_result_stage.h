@@ -1,65 +1,12 @@
-// The result stage of a context (included once, by xm_capi.hip, behind xm_device_rt.h, xm_pass_plan.h and its `using namespace xm`): where the passes
+// The result stage of a context (included once, by xm_capi.hip, behind xm_scan.h, xm_pass_plan.h and its `using namespace xm`): where the passes
 // of an align call leave their results and how those become the streams the caller gets.  Every kernel that publishes a read writes its slice into one of two arenas through the call's
-// cursors and notes offset, length and status per query (OutView, xm_kernel_args.h); after the last pass the lengths are prefix-summed in query order, the
+// cursors and notes offset, length and status per query (OutView, xm_kernel_args.h); after the last pass the lengths are prefix-summed in query order (xm_scan.h), the
 // slices gathered into canonical streams on the device, and the streams copied to pinned host memory.  The arenas are per context and only ever grow: how
 // large they start and what an overflow grows them to is xm_pass_plan.h (firstArenaSize, grownArenaSize).  The canonical streams stay in HBM until the
 // next call (xm_pileup_add_last reads them there: lastStreams).
 #pragma once
 
 namespace {
-
-// Exclusive prefix sums of the per-query stream lengths (query order), three small kernels: block totals, scan of the totals,
-// final offsets.  4096 queries per block.
-constexpr int XM_SCAN_PER_THREAD = 16;  // (the edges this gives - 16 per thread, 256 per gather block, 4096 per scan block - are walked by tests/test_gpu_result_stage.py)
-constexpr int XM_SCAN_PER_BLOCK = 256 * XM_SCAN_PER_THREAD;
-
-__device__ __forceinline__ void blockReduce2(long long& a, long long& b, long long* shA, long long* shB) {
-  shA[threadIdx.x] = a; shB[threadIdx.x] = b;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) { shA[threadIdx.x] += shA[threadIdx.x + d]; shB[threadIdx.x] += shB[threadIdx.x + d]; }
-    __syncthreads();
-  }
-  a = shA[0]; b = shB[0];
-}
-
-__global__ void __launch_bounds__(256) xm_scan_totals_kernel(long long nq, const int32_t* intLen, const int32_t* dblLen, long long* blockI, long long* blockD) {
-  __shared__ long long shA[256], shB[256];
-  long long base = (long long)blockIdx.x * XM_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_SCAN_PER_THREAD;
-  long long a = 0, b = 0;
-  for (int k = 0; k < XM_SCAN_PER_THREAD; k++) if (base + k < nq) { a += intLen[base + k]; b += dblLen[base + k]; }
-  blockReduce2(a, b, shA, shB);
-  if (threadIdx.x == 0) { blockI[blockIdx.x] = a; blockD[blockIdx.x] = b; }
-}
-
-__global__ void xm_scan_blocks_kernel(long long nBlocks, long long nq, long long* blockI, long long* blockD, int64_t* finalIntOff, int64_t* finalDblOff) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long a = 0, b = 0;
-  for (long long i = 0; i < nBlocks; i++) { long long x = blockI[i], y = blockD[i]; blockI[i] = a; blockD[i] = b; a += x; b += y; }
-  finalIntOff[nq] = a; finalDblOff[nq] = b;
-}
-
-__global__ void __launch_bounds__(256) xm_scan_final_kernel(long long nq, const int32_t* intLen, const int32_t* dblLen, const long long* blockI, const long long* blockD,
-                                                            int64_t* finalIntOff, int64_t* finalDblOff) {
-  __shared__ long long shA[256], shB[256];
-  long long base = (long long)blockIdx.x * XM_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_SCAN_PER_THREAD;
-  long long a = 0, b = 0;
-  for (int k = 0; k < XM_SCAN_PER_THREAD; k++) if (base + k < nq) { a += intLen[base + k]; b += dblLen[base + k]; }
-  shA[threadIdx.x] = a; shB[threadIdx.x] = b;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the 256 thread totals
-    long long x = 0, y = 0;
-    if ((int)threadIdx.x >= d) { x = shA[threadIdx.x - d]; y = shB[threadIdx.x - d]; }
-    __syncthreads();
-    shA[threadIdx.x] += x; shB[threadIdx.x] += y;
-    __syncthreads();
-  }
-  long long offA = blockI[blockIdx.x] + shA[threadIdx.x] - a, offB = blockD[blockIdx.x] + shB[threadIdx.x] - b;
-  for (int k = 0; k < XM_SCAN_PER_THREAD; k++) if (base + k < nq) {
-    finalIntOff[base + k] = offA; finalDblOff[base + k] = offB;
-    offA += intLen[base + k]; offB += dblLen[base + k];
-  }
-}
 
 // canonical streams: every query's slice copied from where its pass left it to its place in query order
 __global__ void __launch_bounds__(256) xm_gather_kernel(long long nq, const int64_t* srcIntOff, const int64_t* srcDblOff, const int32_t* intLen, const int32_t* dblLen,
@@ -80,7 +27,7 @@ struct ResultStage {
   DevBuf<unsigned long long> dCursors;            // [0],[1] what is used of them; [2] the next item of a launch's work list, [3] the next unused hand-over region
   DevBuf<int32_t> dStatus, dIntLen, dDblLen;      // per query: status, and where its slices are
   DevBuf<int64_t> dIntOff, dDblOff;
-  DevBuf<long long> dBlockI, dBlockD;             // the scan's block totals
+  DevBuf<long long> dBlockSums;                   // the scan's block sums
   DevBuf<int64_t> dFinalIntOff, dFinalDblOff;     // [nq + 1] the canonical streams: offsets ...
   DevBuf<int32_t> dFinalInts;                     // ... and slices in query order
   DevBuf<double> dFinalDbls;
@@ -117,13 +64,12 @@ struct ResultStage {
   // caller waits for it).  copies: queries that share their representative's slice (collapseFanOut); gen: the resident batch these streams belong to.
   // copy = false (xm_context_set_result_copy(0)): the same launches, the streams stay where they lie, and only the scan's two totals are read, into res->num_ints / num_dbls.
   void toHost(int64_t nq, int64_t copies, int64_t gen, xm_result* res, ResultBox* box, hipStream_t s, bool copy = true) {
-    const long long nBlocks = (nq + XM_SCAN_PER_BLOCK - 1) / XM_SCAN_PER_BLOCK;
-    dBlockI.ensure((size_t)nBlocks); dBlockD.ensure((size_t)nBlocks);
+    dBlockSums.ensure(xmScanSums(nq, 2));
     dFinalIntOff.ensure((size_t)nq + 1); dFinalDblOff.ensure((size_t)nq + 1);
     size_t usedI = (size_t)std::min<unsigned long long>(cursors[0], dOutInts.n), usedD = (size_t)std::min<unsigned long long>(cursors[1], dOutDbls.n);  // upper bounds of the totals
     if (copies == 0) { dFinalInts.ensure(usedI); dFinalDbls.ensure(usedD); }
-    hipLaunchKernelGGL(xm_scan_totals_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, dIntLen.p, dDblLen.p, dBlockI.p, dBlockD.p);
-    hipLaunchKernelGGL(xm_scan_blocks_kernel, dim3(1), dim3(64), 0, s, nBlocks, (long long)nq, dBlockI.p, dBlockD.p, dFinalIntOff.p, dFinalDblOff.p);
+    const XmOffsets<int32_t, 2> lengths{nq, {dIntLen.p, dDblLen.p}, {dFinalIntOff.p, dFinalDblOff.p}};
+    xmScanTotals(lengths, nq, dBlockSums, s);
     if (copies > 0) {  // (a copy's slice is in the result arena once and in the streams once per copy: the totals are the scan's)
       int64_t totals[2] = {0, 0};
       HIP_CHECK(hipMemcpyAsync(&totals[0], dFinalIntOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -132,7 +78,7 @@ struct ResultStage {
       usedI = (size_t)totals[0]; usedD = (size_t)totals[1];
       dFinalInts.ensure(usedI); dFinalDbls.ensure(usedD);
     }
-    hipLaunchKernelGGL(xm_scan_final_kernel, dim3((unsigned)nBlocks), dim3(256), 0, s, (long long)nq, dIntLen.p, dDblLen.p, dBlockI.p, dBlockD.p, dFinalIntOff.p, dFinalDblOff.p);
+    xmScanPlace(lengths, nq, dBlockSums, s);
     hipLaunchKernelGGL(xm_gather_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (long long)nq, dIntOff.p, dDblOff.p, dIntLen.p, dDblLen.p,
                        dFinalIntOff.p, dFinalDblOff.p, dOutInts.p, dOutDbls.p, dFinalInts.p, dFinalDbls.p);
     HIP_CHECK(hipGetLastError());

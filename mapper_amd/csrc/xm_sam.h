@@ -2,7 +2,7 @@
 // plain rules of xm_sam_rules.h.  Three stages, separate launches, no launch reads what another workgroup of the same launch wrote:
 //   measure   a lane per query walks the query's slice with the sink that only counts: bytes and records per query (0 for an unaligned one); a malformed
 //             slice leaves the lowest such query in the control words
-//   offsets   exclusive sums of the bytes in query order and both totals (three kernels, as xm_result_stage.h's scan: 4096 queries a block)
+//   offsets   exclusive sums of the bytes in query order and both totals (the scan of xm_scan.h over SamSums, placed over SamByteOffsets)
 //   write     a wavefront per query walks the slice again with the sink that composes the text in LDS, a tile of XM_SAM_TILE_BYTES bytes that lies where the
 //             text buffer's own tiles lie: names, contig names and SEQ go into the tile 64 bytes a round (a byte a lane), the short fields are composed there
 //             by lane 0, and a tile leaves for HBM as 16-byte pieces, 64 a round, with single bytes only in front of the first and behind the last whole piece
@@ -14,8 +14,6 @@
 namespace {
 
 constexpr int XM_SAM_TILE_BYTES = 1024;  // one round of 16-byte stores of a wavefront (xm_sam_tile_bytes(): tests put record ends on both sides of the multiples)
-constexpr int XM_SAM_SCAN_PER_THREAD = 16;
-constexpr int XM_SAM_SCAN_PER_BLOCK = 256 * XM_SAM_SCAN_PER_THREAD;
 constexpr unsigned long long XM_SAM_NO_ERROR = ~0ull;
 
 // what a format call reads; the control words: [0] the lowest query with a malformed slice (XM_SAM_NO_ERROR: none), [1] queries whose text did not end where
@@ -37,45 +35,26 @@ __global__ void __launch_bounds__(256) xm_sam_measure_kernel(SamJob j, long long
   bytes[q] = count.bytes; records[q] = count.records;
 }
 
-__global__ void __launch_bounds__(256) xm_sam_totals_kernel(long long nq, const long long* bytes, const long long* records, long long* blockSums) {
-  __shared__ long long shA[256], shB[256];
-  const long long base = (long long)blockIdx.x * XM_SAM_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_SAM_SCAN_PER_THREAD;
-  long long a = 0, b = 0;
-  for (int k = 0; k < XM_SAM_SCAN_PER_THREAD; k++) if (base + k < nq) { a += bytes[base + k]; b += records[base + k]; }
-  shA[threadIdx.x] = a; shB[threadIdx.x] = b;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) { shA[threadIdx.x] += shA[threadIdx.x + d]; shB[threadIdx.x] += shB[threadIdx.x + d]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { blockSums[2 * blockIdx.x] = shA[0]; blockSums[2 * blockIdx.x + 1] = shB[0]; }
-}
-
-__global__ void xm_sam_blocks_kernel(long long nBlocks, long long nq, long long* blockSums, long long* offset, unsigned long long* ctl) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  long long a = 0, b = 0;
-  for (long long i = 0; i < nBlocks; i++) { const long long x = blockSums[2 * i], y = blockSums[2 * i + 1]; blockSums[2 * i] = a; blockSums[2 * i + 1] = b; a += x; b += y; }
-  offset[nq] = a;
-  ctl[2] = (unsigned long long)a; ctl[3] = (unsigned long long)b;
-}
-
-__global__ void __launch_bounds__(256) xm_sam_offsets_kernel(long long nq, const long long* bytes, const long long* blockSums, long long* offset) {
-  __shared__ long long sh[256];
-  const long long base = (long long)blockIdx.x * XM_SAM_SCAN_PER_BLOCK + (long long)threadIdx.x * XM_SAM_SCAN_PER_THREAD;
-  long long a = 0;
-  for (int k = 0; k < XM_SAM_SCAN_PER_THREAD; k++) if (base + k < nq) a += bytes[base + k];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {  // inclusive Hillis-Steele scan of the 256 thread totals
-    long long x = 0;
-    if ((int)threadIdx.x >= d) x = sh[threadIdx.x - d];
-    __syncthreads();
-    sh[threadIdx.x] += x;
-    __syncthreads();
-  }
-  long long off = blockSums[2 * blockIdx.x] + sh[threadIdx.x] - a;
-  for (int k = 0; k < XM_SAM_SCAN_PER_THREAD; k++) if (base + k < nq) { offset[base + k] = off; off += bytes[base + k]; }
-}
+// The offsets stage's two Items (xm_scan.h): the sums pass takes bytes and records per query and leaves the totals; the place pass needs the offsets of the
+// bytes only, so it runs over that one array (the records are not read a second time).
+struct SamSums {
+  static constexpr int N = 2;
+  long long nq;
+  const long long* bytes; const long long* records;
+  long long* offset; unsigned long long* ctl;
+  __device__ long long count() const { return nq; }
+  __device__ void lens(long long q, long long v[2]) const { v[0] = bytes[q]; v[1] = records[q]; }
+  __device__ void totals(const long long t[2]) const { offset[nq] = t[0]; ctl[2] = (unsigned long long)t[0]; ctl[3] = (unsigned long long)t[1]; }
+};
+struct SamByteOffsets {
+  static constexpr int N = 1;
+  long long nq;
+  const long long* bytes;
+  long long* offset;
+  __device__ long long count() const { return nq; }
+  __device__ void lens(long long q, long long v[1]) const { v[0] = bytes[q]; }
+  __device__ void put(long long q, const long long off[1]) const { offset[q] = off[0]; }
+};
 
 // The sink of the write kernel: one wavefront (a workgroup of 64 lanes, so __syncthreads() is the wavefront's barrier), every call made by all of its lanes
 // with the same arguments.  tile[0] is byte `base` of the text, base a multiple of XM_SAM_TILE_BYTES; tile[lo, fill) is text of this query that has not left yet.

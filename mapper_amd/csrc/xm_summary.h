@@ -3,7 +3,7 @@
 //   measure   a lane per query walks the query's slice: alignments[q] and unalignedFlag[q] (both 0 for a malformed slice); aligned queries, aligned length
 //             and indels are summed over the wavefront by shuffles and added by its lane 0 to three 64-bit counters (integers: exact in any order); a
 //             malformed slice leaves the lowest such query in the control word
-//   offsets   exclusive sums of the two arrays in query order and both totals: the scan of xm_result_stage.h (xm_scan_*_kernel), not a third one
+//   offsets   exclusive sums of the two arrays in query order and both totals: the scan of xm_scan.h over the two int32 arrays
 //   gather    a lane per query walks again and stores its alignments' penalties at penalties[off[q] + a] and, when it is unaligned and the list is wanted,
 //             its index at unaligned[uoff[q]].  No lane stores outside its own [off[q], off[q + 1]) or behind the buffer's end, whatever the second walk yields.
 // The double sum of the penalties is the host's: Mapper.run adds them in query order and the order is part of the result.

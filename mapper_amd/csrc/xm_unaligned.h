@@ -4,7 +4,7 @@
 //   measure   a lane per query walks the query's slice with the summary's walk (xm_summary_rules.h): unalignedFlag[q], and bytes[q] - the closed form of
 //             the record's size, 0 for an aligned query; the mates of the unaligned queries are summed over the wavefront and added by its lane 0 to a
 //             64-bit counter; a malformed slice leaves the lowest such query in the control word, a record beyond an int32 the lowest such query in another
-//   offsets   exclusive sums of the two int32 arrays in query order and both totals: the scan of xm_result_stage.h (xm_scan_*_kernel), not a third one
+//   offsets   exclusive sums of the two int32 arrays in query order and both totals: the scan of xm_scan.h
 //   compact   a lane per query: an unaligned one stores its index at list[uoff[q]] - the ascending list, so that no wavefront is spent on an aligned query
 //   write     a wavefront per list entry composes the record in LDS through xm_sam.h's SamTileSink - names, bases and qualities enter the tile 64 bytes a
 //             round, a byte a lane, the bases through the 16-entry table; a tile leaves for HBM as 16-byte pieces with single bytes only in front of the
