@@ -279,8 +279,7 @@ struct FastqStage {
   DevBuf<uint8_t> dLineHeader[2];                                             // the line scans' block sums
   DevBuf<long long> dLineBlockSums[2];
   // on the GPU's staging stream: text up | stages 1-3 | (host sizes the arrays) | stage 4 | arrays down; the split form also [6] behind stage 2b and [7] in front of 2c (the host sizes the slots between them)
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  ~FastqStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  StageEvents<8> ev;
 };
 
 // What xm_sam_format_last works with (xm_sam.h; xm_capi_sam.h): the contig names, uploaded once per context; names the host handed in for a call; bytes and
@@ -291,8 +290,7 @@ struct SamStage {
   DevBuf<int64_t> dContigOff, dNameOff;
   DevBuf<long long> dBytes, dRecords, dBlockSums, dOffset;
   DevBuf<unsigned long long> dCtl;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // names up | measure and offsets | (host sizes the text) | write | text down
-  ~SamStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  StageEvents<6> ev;  // names up | measure and offsets | (host sizes the text) | write | text down
 };
 
 // What xm_summary_last works with (xm_summary.h; xm_capi_summary.h): alignments and the unaligned flag per query, the scan's block sums and both offset arrays;
@@ -303,8 +301,7 @@ struct SummaryStage {
   DevBuf<int64_t> dOff, dUoff, dUnaligned;
   DevBuf<unsigned long long> dCtl;
   DevBuf<double> dPenalties;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // measure and offsets | (host sizes the arrays) | gather | arrays down
-  ~SummaryStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  StageEvents<5> ev;  // measure and offsets | (host sizes the arrays) | gather | arrays down
 };
 
 // What xm_unaligned_format_last works with (xm_unaligned.h; xm_capi_unaligned.h): the record bytes and the unaligned flag per query, the scan's block sums and
@@ -316,8 +313,7 @@ struct UnalignedStage {
   DevBuf<int64_t> dOff, dUoff, dList;
   DevBuf<unsigned long long> dCtl;
   DevBuf<char> dText;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // measure and offsets | (host sizes the list and the text) | compact and write | text down
-  ~UnalignedStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  StageEvents<5> ev;  // measure and offsets | (host sizes the list and the text) | compact and write | text down
 };
 
 // What xm_refs_count_last works with (xm_refs.h; xm_capi_refs.h): the table of the sets' fingerprints (keys, the lowest query and the count per slot); per query
@@ -330,8 +326,7 @@ struct RefsStage {
   DevBuf<long long> dBlockSums;
   DevBuf<int64_t> dOff, dLoff, dLqoff, dLeftStart;
   DevBuf<RefsRecord> dRecords;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // claim, verify and offsets | (host sizes the arrays) | gather | arrays down
-  ~RefsStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  StageEvents<5> ev;  // claim, verify and offsets | (host sizes the arrays) | gather | arrays down
 };
 
 // What the lane-per-read passes of a call work with besides the batch and the result stage: the work lists the lanes file unfinished reads into and the
@@ -603,6 +598,29 @@ struct xm_index {
     if (stream) (void)hipStreamDestroy(stream);
   }  // (every DevBuf member releases its memory itself; the shared tables go with their last context)
 };
+
+// What every C entry that reads the last align call's result streams where they lie in HBM begins with (caller holds idx->mu): the streams, or the error of a
+// context whose resident batch is no longer the one they belong to; behind it the context's device is current.
+static ResultStage::LastStreams lastCall(xm_index* idx, const char* entry) {
+  const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
+  if (last.nq < 0)
+    throw std::runtime_error(std::string("the batch of the last align call is no longer resident (call ") + entry +
+                             " after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
+  HIP_CHECK(hipSetDevice(idx->device));
+  return last;
+}
+// ... and the frame around it for the entries that hand back one object: *out = body(), run under the context's mutex; what body throws is the entry's error.
+template <class Out, class Body>
+static int lastCallEntry(xm_index* idx, Out** out, const char* entry, Body&& body) {
+  if (!idx || !out) return fail(std::string(entry) + ": null argument");
+  *out = nullptr;
+  if (idx->hostOnly) return fail(std::string(entry) + ": index was built with host_only=1");
+  try {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    *out = body();
+    return 0;
+  } catch (std::exception& e) { return fail(std::string(entry) + ": " + e.what()); }
+}
 
 // ---------------------------------------------------------------- the align call: its state and its steps, in the order alignResidentLocked runs them
 // (what the passes are sized by and how they follow each other is xm_pass_plan.h; here are the buffers, the launches and the copies)

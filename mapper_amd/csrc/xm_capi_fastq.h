@@ -193,7 +193,7 @@ int xm_batch_stage_fastq(xm_index* idx, const xm_fastq_text* t, xm_fastq_batch**
     d.hasNames = false;
     d.hasQuals = false;
     HIP_CHECK(hipSetDevice(idx->device));
-    for (hipEvent_t& e : f.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+    f.ev.ready();
     box = (FastqBox*)calloc(1, sizeof(FastqBox));
     if (!box) throw std::runtime_error("out of host memory");
     xm_fastq_batch& b = box->pub;

@@ -83,7 +83,7 @@ SnpBox* mutationsSelect(MutationsStage& g, const MutationsCounts& c, const int64
   box->pub.positions = c.total;
   if (c.total <= 0) return box;  // (nothing is launched)
   try {
-    for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+    g.ev.ready();
     // the levels of the scan: the block counts, then the sums of every XM_MUTATIONS_SCAN_BLOCK entries of the level below, up to a level one block covers
     std::vector<long long> levelN, levelAt;
     long long words = 0;

@@ -204,10 +204,7 @@ int xm_pileup_add_last(xm_pileup* p, int64_t* num_events) {
   xm_index* idx = p->index;
   try {
     std::lock_guard<std::mutex> lock(idx->mu);
-    const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
-    if (last.nq < 0)
-      throw std::runtime_error("the batch of the last align call is no longer resident (call xm_pileup_add_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
-    HIP_CHECK(hipSetDevice(idx->device));
+    const ResultStage::LastStreams last = lastCall(idx, "xm_pileup_add_last");
     hipStream_t s = idx->stream;
     const int64_t nq = last.nq;
     if (nq > 0) {

@@ -22,7 +22,7 @@ void freeRefsBox(RefsBox* box) {
 
 // The four stages on stream s over streams in HBM; bits: what refsFingerprint keeps (64 outside of tests).  Returns the count, its arrays in pinned buffers
 // (NULL where there is nothing to hold), or throws: a malformed slice gives no count.
-RefsBox* refsRun(RefsStage& g, const xm::SummaryStreams& st, int64_t nq, int bits, hipStream_t s) {
+RefsBox* refsRun(RefsStage& g, const xm::ResultStreams& st, int64_t nq, int bits, hipStream_t s) {
   RefsBox* box = (RefsBox*)calloc(1, sizeof(RefsBox));
   if (!box) throw std::runtime_error("out of host memory");
   box->pub.store = box;
@@ -30,7 +30,7 @@ RefsBox* refsRun(RefsStage& g, const xm::SummaryStreams& st, int64_t nq, int bit
   if (nq == 0) return box;  // (nothing is launched)
   try {
     if (nq > (1ll << 30)) throw std::runtime_error("more than 2^30 queries");  // (a slot is an int32)
-    for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+    g.ev.ready();
     // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
     size_t cap = 2;
     while (cap < 2 * (size_t)nq) cap <<= 1;
@@ -41,7 +41,7 @@ RefsBox* refsRun(RefsStage& g, const xm::SummaryStreams& st, int64_t nq, int bit
     const RefsTable table{g.dKeys.p, g.dReps.p, g.dCounts.p, (unsigned long long)cap - 1};
     const unsigned grid = (unsigned)((nq + 255) / 256);
     HIP_CHECK(hipEventRecord(g.ev[0], s));
-    HIP_CHECK(hipMemsetAsync(g.dCtl.p, 0xFF, sizeof(unsigned long long), s));      // XM_REFS_NO_ERROR
+    HIP_CHECK(hipMemsetAsync(g.dCtl.p, 0xFF, sizeof(unsigned long long), s));      // XM_NO_QUERY
     HIP_CHECK(hipMemsetAsync(g.dCtl.p + 1, 0, sizeof(unsigned long long), s));     // aligned queries
     HIP_CHECK(hipMemsetAsync(g.dKeys.p, 0, sizeof(unsigned long long) * cap, s));
     HIP_CHECK(hipMemsetAsync(g.dCounts.p, 0, sizeof(unsigned long long) * cap, s));
@@ -57,7 +57,7 @@ RefsBox* refsRun(RefsStage& g, const xm::SummaryStreams& st, int64_t nq, int bit
     HIP_CHECK(hipMemcpyAsync(&totals[1], g.dLoff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&totals[2], g.dLqoff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));  // (the one wait for the control word and the totals)
-    if (ctl[0] != XM_REFS_NO_ERROR) throw std::runtime_error("malformed result streams: query " + std::to_string(ctl[0]));
+    throwIfMalformed(ctl[0]);
     const size_t nRec = (size_t)totals[0], nLeft = (size_t)totals[1], nLeftQ = (size_t)totals[2];
     box->pub.num_aligned = (int64_t)ctl[1];
     box->pub.num_combinations = (int64_t)nRec; box->pub.num_leftover_queries = (int64_t)nLeftQ;
@@ -107,20 +107,10 @@ void xm_refs_count_free(xm_refs_count* count) {
 }
 
 int xm_refs_count_last(xm_index* idx, xm_refs_count** out) {
-  if (!idx || !out) return fail("xm_refs_count_last: null argument");
-  *out = nullptr;
-  if (idx->hostOnly) return fail("xm_refs_count_last: index was built with host_only=1");
-  try {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
-    if (last.nq < 0)
-      throw std::runtime_error("the batch of the last align call is no longer resident (call xm_refs_count_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
-    HIP_CHECK(hipSetDevice(idx->device));
-    const xm::SummaryStreams st{last.ints, last.dbls, last.intOff, last.dblOff, (int32_t)idx->host().numContigs()};
-    RefsBox* box = refsRun(idx->refs, st, last.nq, 64, idx->stream);
-    *out = &box->pub;
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_refs_count_last: ") + e.what()); }
+  return lastCallEntry(idx, out, "xm_refs_count_last", [&] {
+    const ResultStage::LastStreams last = lastCall(idx, "xm_refs_count_last");
+    return &refsRun(idx->refs, last.streams(idx->host().numContigs()), last.nq, 64, idx->stream)->pub;
+  });
 }
 
 }  // extern "C"

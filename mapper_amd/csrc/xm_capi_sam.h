@@ -43,7 +43,7 @@ int64_t samCheckNameOffsets(const int64_t* off, int64_t nq) {
 // are copied up first, from memory that may be pageable).  Returns the text in a pinned buffer, or throws: a malformed slice gives no text.
 SamBox* samFormat(SamStage& g, SamJob job, const xm_sam_names* hostNames, hipStream_t s) {
   const int64_t nq = job.batch.nq;
-  for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+  g.ev.ready();
   int64_t nameBytes = 0;
   if (hostNames) {
     if (!hostNames->names || !hostNames->name_off) throw std::runtime_error("names and name_off must both be given");
@@ -58,7 +58,7 @@ SamBox* samFormat(SamStage& g, SamJob job, const xm_sam_names* hostNames, hipStr
   SamBox* box = (SamBox*)calloc(1, sizeof(SamBox));
   if (!box) throw std::runtime_error("out of host memory");
   try {
-    unsigned long long ctl[4] = {XM_SAM_NO_ERROR, 0, 0, 0};
+    unsigned long long ctl[4] = {XM_NO_QUERY, 0, 0, 0};
     HIP_CHECK(hipEventRecord(g.ev[0], s));
     HIP_CHECK(hipMemcpyAsync(g.dCtl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
     if (hostNames) {
@@ -72,7 +72,7 @@ SamBox* samFormat(SamStage& g, SamJob job, const xm_sam_names* hostNames, hipStr
     HIP_CHECK(hipEventRecord(g.ev[2], s));
     HIP_CHECK(hipMemcpyAsync(ctl, g.dCtl.p, sizeof(ctl), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    if (ctl[0] != XM_SAM_NO_ERROR) throw std::runtime_error("malformed result streams: query " + std::to_string(ctl[0]));
+    throwIfMalformed(ctl[0]);
     const size_t total = (size_t)ctl[2];
     g.dText.ensure(total);
     box->pub.text = (char*)g_pinned->get(total ? total : 1, &box->bytesText);
@@ -130,27 +130,18 @@ int xm_sam_set_contigs(xm_index* idx, int32_t num_contigs, const char* const* na
 }
 
 int xm_sam_format_last(xm_index* idx, const xm_sam_names* names, xm_sam_text** out) {
-  if (!idx || !out) return fail("xm_sam_format_last: null argument");
-  *out = nullptr;
-  if (idx->hostOnly) return fail("xm_sam_format_last: index was built with host_only=1");
-  try {
-    std::lock_guard<std::mutex> lock(idx->mu);
+  return lastCallEntry(idx, out, "xm_sam_format_last", [&] {
     if (idx->sam.numContigs < 0) throw std::runtime_error("the contig names are not set (call xm_sam_set_contigs first)");
-    const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
-    if (last.nq < 0)
-      throw std::runtime_error("the batch of the last align call is no longer resident (call xm_sam_format_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
+    const ResultStage::LastStreams last = lastCall(idx, "xm_sam_format_last");
     const DeviceBatch& d = idx->resident;
     if (!names && !d.hasNames)
       throw std::runtime_error("the resident batch has no names in HBM (it was staged from arrays, not by xm_batch_stage_fastq): hand the names in");
-    HIP_CHECK(hipSetDevice(idx->device));
     SamJob job;
     job.batch = xm::SamBatch{last.nq, d.mateCount.p, d.mateOffset.p, d.mateLength.p, d.codes.p, names ? nullptr : d.names.p, names ? nullptr : d.nameOff.p};
-    job.streams = xm::SamStreams{last.ints, last.dbls, last.intOff, last.dblOff};
+    job.streams = last.streams(idx->sam.numContigs);  // (xm_sam_set_contigs takes as many names as the index has contigs, no other number)
     job.contigs = xm::SamContigs{idx->sam.numContigs, idx->sam.dContigNames.p, idx->sam.dContigOff.p};
-    SamBox* box = samFormat(idx->sam, job, names, idx->stream);
-    *out = &box->pub;
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_sam_format_last: ") + e.what()); }
+    return &samFormat(idx->sam, job, names, idx->stream)->pub;
+  });
 }
 
 }  // extern "C"

@@ -22,20 +22,20 @@ void freeSummaryBox(SummaryBox* box) {
 
 // The three stages on stream s over streams in HBM.  Returns the summary, its two arrays in pinned buffers (NULL where there is nothing to hold), or throws:
 // a malformed slice gives no summary.
-SummaryBox* summaryRun(SummaryStage& g, const xm::SummaryStreams& st, int64_t nq, bool wantUnaligned, hipStream_t s) {
+SummaryBox* summaryRun(SummaryStage& g, const xm::ResultStreams& st, int64_t nq, bool wantUnaligned, hipStream_t s) {
   SummaryBox* box = (SummaryBox*)calloc(1, sizeof(SummaryBox));
   if (!box) throw std::runtime_error("out of host memory");
   box->pub.store = box;
   box->pub.num_queries = nq;
   if (nq == 0) return box;  // (nothing is launched)
   try {
-    for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+    g.ev.ready();
     // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
     g.dAlignments.ensure((size_t)nq); g.dUnalignedFlag.ensure((size_t)nq); g.dOff.ensure((size_t)nq + 1); g.dUoff.ensure((size_t)nq + 1);
     g.dBlockSums.ensure(xmScanSums(nq, 2)); g.dCtl.ensure(XM_SUMMARY_CTL_WORDS);
     const unsigned grid = (unsigned)((nq + 255) / 256);
     HIP_CHECK(hipEventRecord(g.ev[0], s));
-    HIP_CHECK(hipMemsetAsync(g.dCtl.p, 0xFF, sizeof(unsigned long long), s));                                               // XM_SUMMARY_NO_ERROR
+    HIP_CHECK(hipMemsetAsync(g.dCtl.p, 0xFF, sizeof(unsigned long long), s));                                               // XM_NO_QUERY
     HIP_CHECK(hipMemsetAsync(g.dCtl.p + 1, 0, sizeof(unsigned long long) * (XM_SUMMARY_CTL_WORDS - 1), s));                 // the three counters
     hipLaunchKernelGGL(xm_summary_measure_kernel, dim3(grid), dim3(256), 0, s, st, (long long)nq, g.dAlignments.p, g.dUnalignedFlag.p, g.dCtl.p);
     xmScan(XmOffsets<int32_t, 2>{nq, {g.dAlignments.p, g.dUnalignedFlag.p}, {g.dOff.p, g.dUoff.p}}, nq, g.dBlockSums, s);
@@ -46,7 +46,7 @@ SummaryBox* summaryRun(SummaryStage& g, const xm::SummaryStreams& st, int64_t nq
     HIP_CHECK(hipMemcpyAsync(&totals[0], g.dOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&totals[1], g.dUoff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));  // (the one wait for the totals and the counters)
-    if (ctl[0] != XM_SUMMARY_NO_ERROR) throw std::runtime_error("malformed result streams: query " + std::to_string(ctl[0]));
+    throwIfMalformed(ctl[0]);
     const size_t nAl = (size_t)totals[0], nUn = wantUnaligned ? (size_t)totals[1] : 0;
     box->pub.num_aligned = (int64_t)ctl[1]; box->pub.total_aligned_length = (int64_t)ctl[2]; box->pub.num_indels = (int64_t)ctl[3];
     box->pub.num_alignments = (int64_t)nAl; box->pub.num_unaligned = (int64_t)nUn;
@@ -85,20 +85,10 @@ void xm_summary_free(xm_batch_summary* summary) {
 }
 
 int xm_summary_last(xm_index* idx, int32_t want_unaligned, xm_batch_summary** out) {
-  if (!idx || !out) return fail("xm_summary_last: null argument");
-  *out = nullptr;
-  if (idx->hostOnly) return fail("xm_summary_last: index was built with host_only=1");
-  try {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
-    if (last.nq < 0)
-      throw std::runtime_error("the batch of the last align call is no longer resident (call xm_summary_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
-    HIP_CHECK(hipSetDevice(idx->device));
-    const xm::SummaryStreams st{last.ints, last.dbls, last.intOff, last.dblOff, (int32_t)idx->host().numContigs()};
-    SummaryBox* box = summaryRun(idx->summary, st, last.nq, want_unaligned != 0, idx->stream);
-    *out = &box->pub;
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_summary_last: ") + e.what()); }
+  return lastCallEntry(idx, out, "xm_summary_last", [&] {
+    const ResultStage::LastStreams last = lastCall(idx, "xm_summary_last");
+    return &summaryRun(idx->summary, last.streams(idx->host().numContigs()), last.nq, want_unaligned != 0, idx->stream)->pub;
+  });
 }
 
 }  // extern "C"

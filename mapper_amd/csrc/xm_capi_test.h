@@ -2,6 +2,27 @@
 // error contract are here; the kernels stand behind the align kernel in xm_align_kernel.hip (TestLocalLaunch, TestBoundLaunch: xm_kernel_common.h).
 #pragma once
 
+namespace {
+
+// Host-given result streams copied to HBM, to be walked like ResultStage::lastStreams' (the entries below check the offsets first)
+struct TestStreams {
+  DevBuf<int32_t> dInts;
+  DevBuf<double> dDbls;
+  DevBuf<int64_t> dIntOff, dDblOff;
+  TestStreams(int64_t nq, const int32_t* ints, const double* dbls, const int64_t* intOff, const int64_t* dblOff) {
+    const size_t nInts = (size_t)intOff[nq], nDbls = (size_t)dblOff[nq];
+    dInts.ensure(nInts); dDbls.ensure(nDbls); dIntOff.ensure((size_t)nq + 1); dDblOff.ensure((size_t)nq + 1);
+    if (nInts) HIP_CHECK(hipMemcpy(dInts.p, ints, sizeof(int32_t) * nInts, hipMemcpyHostToDevice));
+    if (nDbls) HIP_CHECK(hipMemcpy(dDbls.p, dbls, sizeof(double) * nDbls, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dIntOff.p, intOff, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dDblOff.p, dblOff, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+  }
+  xm::ResultStreams streams(int32_t numContigs) const { return xm::ResultStreams{dInts.p, dDbls.p, dIntOff.p, dDblOff.p, numContigs}; }
+};
+const xm::ResultStreams kNoStreams{nullptr, nullptr, nullptr, nullptr, 0};  // of a batch of 0 queries: nothing is read
+
+}  // namespace
+
 extern "C" {
 
 // Test-only, not declared in the header (tests/test_launch_const_layout.py binds it by name): the layout of the launch block as the host side, which writes
@@ -130,25 +151,20 @@ int xm_test_sam_format(int32_t device, const xm_test_sam_job* t, xm_sam_text** o
     if (device >= 0) HIP_CHECK(hipSetDevice(device));
     SamStage g;
     samUploadContigs(g, t->num_contigs, t->contig_names);
-    DevBuf<int32_t> dCount, dLength, dInts;
-    DevBuf<int64_t> dMateOff, dIntOff, dDblOff;
+    DevBuf<int32_t> dCount, dLength;
+    DevBuf<int64_t> dMateOff;
     DevBuf<uint8_t> dCodes;
-    DevBuf<double> dDbls;
     dCount.ensure((size_t)nq); dLength.ensure((size_t)nq * 2); dMateOff.ensure((size_t)nq * 2); dCodes.ensure((size_t)t->codes_length);
-    dInts.ensure(nInts); dDbls.ensure(nDbls); dIntOff.ensure((size_t)nq + 1); dDblOff.ensure((size_t)nq + 1);
     if (nq) {
       HIP_CHECK(hipMemcpy(dCount.p, t->mate_count, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice));
       HIP_CHECK(hipMemcpy(dLength.p, t->mate_length, sizeof(int32_t) * (size_t)nq * 2, hipMemcpyHostToDevice));
       HIP_CHECK(hipMemcpy(dMateOff.p, t->mate_offset, sizeof(int64_t) * (size_t)nq * 2, hipMemcpyHostToDevice));
     }
     if (t->codes_length) HIP_CHECK(hipMemcpy(dCodes.p, t->codes, (size_t)t->codes_length, hipMemcpyHostToDevice));
-    if (nInts) HIP_CHECK(hipMemcpy(dInts.p, t->ints, sizeof(int32_t) * nInts, hipMemcpyHostToDevice));
-    if (nDbls) HIP_CHECK(hipMemcpy(dDbls.p, t->dbls, sizeof(double) * nDbls, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dIntOff.p, t->int_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dDblOff.p, t->dbl_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    const TestStreams up(nq, t->ints, t->dbls, t->int_off, t->dbl_off);
     SamJob job;
     job.batch = xm::SamBatch{nq, dCount.p, dMateOff.p, dLength.p, dCodes.p, nullptr, nullptr};
-    job.streams = xm::SamStreams{dInts.p, dDbls.p, dIntOff.p, dDblOff.p};
+    job.streams = up.streams(g.numContigs);
     job.contigs = xm::SamContigs{g.numContigs, g.dContigNames.p, g.dContigOff.p};
     const xm_sam_names names{t->names, t->name_off};
     SamBox* box = samFormat(g, job, &names, nullptr);
@@ -172,17 +188,10 @@ int xm_test_summary(int32_t device, int64_t num_queries, int32_t num_contigs, co
     const size_t nInts = nq ? (size_t)int_off[nq] : 0, nDbls = nq ? (size_t)dbl_off[nq] : 0;
     if ((nInts && !ints) || (nDbls && !dbls)) throw std::runtime_error("null array");
     SummaryStage g;
-    if (nq == 0) { *out = &summaryRun(g, xm::SummaryStreams{nullptr, nullptr, nullptr, nullptr, num_contigs}, 0, want_unaligned != 0, nullptr)->pub; return 0; }
+    if (nq == 0) { *out = &summaryRun(g, kNoStreams, 0, want_unaligned != 0, nullptr)->pub; return 0; }
     if (device >= 0) HIP_CHECK(hipSetDevice(device));
-    DevBuf<int32_t> dInts;
-    DevBuf<double> dDbls;
-    DevBuf<int64_t> dIntOff, dDblOff;
-    dInts.ensure(nInts); dDbls.ensure(nDbls); dIntOff.ensure((size_t)nq + 1); dDblOff.ensure((size_t)nq + 1);
-    if (nInts) HIP_CHECK(hipMemcpy(dInts.p, ints, sizeof(int32_t) * nInts, hipMemcpyHostToDevice));
-    if (nDbls) HIP_CHECK(hipMemcpy(dDbls.p, dbls, sizeof(double) * nDbls, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dIntOff.p, int_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dDblOff.p, dbl_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
-    SummaryBox* box = summaryRun(g, xm::SummaryStreams{dInts.p, dDbls.p, dIntOff.p, dDblOff.p, num_contigs}, nq, want_unaligned != 0, nullptr);
+    const TestStreams up(nq, ints, dbls, int_off, dbl_off);
+    SummaryBox* box = summaryRun(g, up.streams(num_contigs), nq, want_unaligned != 0, nullptr);
     *out = &box->pub;
     return 0;
   } catch (std::exception& e) { return fail(std::string("xm_test_summary: ") + e.what()); }
@@ -201,7 +210,7 @@ int xm_test_unaligned_format(int32_t device, const xm_test_unaligned_job* t, xm_
     if (nq == 0) {
       xm::UnalignedBatch none;
       memset(&none, 0, sizeof(none));
-      *out = &unalignedFormat(g, none, xm::SummaryStreams{nullptr, nullptr, nullptr, nullptr, t->num_contigs}, nullptr)->pub;
+      *out = &unalignedFormat(g, none, kNoStreams, nullptr)->pub;
       return 0;
     }
     if (!t->mate_count || !t->mate_offset || !t->mate_length || !t->names || !t->name_off || !t->int_off || !t->dbl_off) throw std::runtime_error("null array");
@@ -220,14 +229,12 @@ int xm_test_unaligned_format(int32_t device, const xm_test_unaligned_job* t, xm_
     const size_t nInts = (size_t)t->int_off[nq], nDbls = (size_t)t->dbl_off[nq];
     if ((nInts && !t->ints) || (nDbls && !t->dbls) || (t->codes_length && !t->codes)) throw std::runtime_error("null array");
     if (device >= 0) HIP_CHECK(hipSetDevice(device));
-    DevBuf<int32_t> dCount, dLength, dInts;
-    DevBuf<int64_t> dMateOff, dIntOff, dDblOff, dNameOff, dQualOff;
+    DevBuf<int32_t> dCount, dLength;
+    DevBuf<int64_t> dMateOff, dNameOff, dQualOff;
     DevBuf<uint8_t> dCodes, dHasQual;
     DevBuf<char> dNames, dQuals;
-    DevBuf<double> dDbls;
     const size_t slots = (size_t)nq * 2;
     dCount.ensure((size_t)nq); dLength.ensure(slots); dMateOff.ensure(slots); dCodes.ensure((size_t)t->codes_length); dNames.ensure((size_t)nameBytes); dNameOff.ensure(slots + 1);
-    dInts.ensure(nInts); dDbls.ensure(nDbls); dIntOff.ensure((size_t)nq + 1); dDblOff.ensure((size_t)nq + 1);
     HIP_CHECK(hipMemcpy(dCount.p, t->mate_count, sizeof(int32_t) * (size_t)nq, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dLength.p, t->mate_length, sizeof(int32_t) * slots, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(dMateOff.p, t->mate_offset, sizeof(int64_t) * slots, hipMemcpyHostToDevice));
@@ -240,13 +247,10 @@ int xm_test_unaligned_format(int32_t device, const xm_test_unaligned_job* t, xm_
       HIP_CHECK(hipMemcpy(dHasQual.p, t->has_qual, slots, hipMemcpyHostToDevice));
       if (qualBytes) HIP_CHECK(hipMemcpy(dQuals.p, t->quals, (size_t)qualBytes, hipMemcpyHostToDevice));
     }
-    if (nInts) HIP_CHECK(hipMemcpy(dInts.p, t->ints, sizeof(int32_t) * nInts, hipMemcpyHostToDevice));
-    if (nDbls) HIP_CHECK(hipMemcpy(dDbls.p, t->dbls, sizeof(double) * nDbls, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dIntOff.p, t->int_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dDblOff.p, t->dbl_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
+    const TestStreams up(nq, t->ints, t->dbls, t->int_off, t->dbl_off);
     const xm::UnalignedBatch b{nq, dCount.p, dMateOff.p, dLength.p, dCodes.p, t->codes_length, dNames.p, dNameOff.p, nameBytes,
                                withQual ? dQuals.p : nullptr, withQual ? dQualOff.p : nullptr, withQual ? dHasQual.p : nullptr, qualBytes};
-    SamBox* box = unalignedFormat(g, b, xm::SummaryStreams{dInts.p, dDbls.p, dIntOff.p, dDblOff.p, t->num_contigs}, nullptr);
+    SamBox* box = unalignedFormat(g, b, up.streams(t->num_contigs), nullptr);
     *out = &box->pub;
     return 0;
   } catch (std::exception& e) { return fail(std::string("xm_test_unaligned_format: ") + e.what()); }
@@ -269,17 +273,10 @@ int xm_test_refs_count(int32_t device, int64_t num_queries, int32_t num_contigs,
     if ((nInts && !ints) || (nDbls && !dbls)) throw std::runtime_error("null array");
     const int bits = fingerprint_bits > 64 ? 64 : fingerprint_bits;
     RefsStage g;
-    if (nq == 0) { *out = &refsRun(g, xm::SummaryStreams{nullptr, nullptr, nullptr, nullptr, num_contigs}, 0, bits, nullptr)->pub; return 0; }
+    if (nq == 0) { *out = &refsRun(g, kNoStreams, 0, bits, nullptr)->pub; return 0; }
     if (device >= 0) HIP_CHECK(hipSetDevice(device));
-    DevBuf<int32_t> dInts;
-    DevBuf<double> dDbls;
-    DevBuf<int64_t> dIntOff, dDblOff;
-    dInts.ensure(nInts); dDbls.ensure(nDbls); dIntOff.ensure((size_t)nq + 1); dDblOff.ensure((size_t)nq + 1);
-    if (nInts) HIP_CHECK(hipMemcpy(dInts.p, ints, sizeof(int32_t) * nInts, hipMemcpyHostToDevice));
-    if (nDbls) HIP_CHECK(hipMemcpy(dDbls.p, dbls, sizeof(double) * nDbls, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dIntOff.p, int_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dDblOff.p, dbl_off, sizeof(int64_t) * ((size_t)nq + 1), hipMemcpyHostToDevice));
-    RefsBox* box = refsRun(g, xm::SummaryStreams{dInts.p, dDbls.p, dIntOff.p, dDblOff.p, num_contigs}, nq, bits, nullptr);
+    const TestStreams up(nq, ints, dbls, int_off, dbl_off);
+    RefsBox* box = refsRun(g, up.streams(num_contigs), nq, bits, nullptr);
     *out = &box->pub;
     return 0;
   } catch (std::exception& e) { return fail(std::string("xm_test_refs_count: ") + e.what()); }

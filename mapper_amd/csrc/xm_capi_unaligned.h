@@ -8,7 +8,7 @@ namespace {
 
 // The four stages on stream s over a batch and streams in HBM.  Returns the text in a pinned buffer (an xm_sam_text: records = the mates written, h2d_ms = 0), or
 // throws: a malformed slice gives no text.  Nothing is launched for a batch of 0 queries, and nothing behind the totals for one without an unaligned query.
-SamBox* unalignedFormat(UnalignedStage& g, const xm::UnalignedBatch& b, const xm::SummaryStreams& st, hipStream_t s) {
+SamBox* unalignedFormat(UnalignedStage& g, const xm::UnalignedBatch& b, const xm::ResultStreams& st, hipStream_t s) {
   const int64_t nq = b.nq;
   SamBox* box = (SamBox*)calloc(1, sizeof(SamBox));
   if (!box) throw std::runtime_error("out of host memory");
@@ -18,12 +18,12 @@ SamBox* unalignedFormat(UnalignedStage& g, const xm::UnalignedBatch& b, const xm
       box->pub.text = (char*)g_pinned->get(1, &box->bytesText);
       return box;
     }
-    for (hipEvent_t& e : g.ev) if (!e) HIP_CHECK(hipEventCreate(&e));
+    g.ev.ready();
     // everything that is sized by the queries (a buffer that grows frees the old one, which waits for the device: before anything is queued)
     g.dBytes.ensure((size_t)nq); g.dFlag.ensure((size_t)nq); g.dOff.ensure((size_t)nq + 1); g.dUoff.ensure((size_t)nq + 1);
     g.dBlockSums.ensure(xmScanSums(nq, 2)); g.dCtl.ensure(XM_UNALIGNED_CTL_WORDS);
     const unsigned grid = (unsigned)((nq + 255) / 256);
-    unsigned long long ctl[XM_UNALIGNED_CTL_WORDS] = {XM_UNALIGNED_NO_ERROR, 0, XM_UNALIGNED_NO_ERROR, 0};
+    unsigned long long ctl[XM_UNALIGNED_CTL_WORDS] = {XM_NO_QUERY, 0, XM_NO_QUERY, 0};
     int64_t totals[2] = {0, 0};
     HIP_CHECK(hipEventRecord(g.ev[0], s));
     HIP_CHECK(hipMemcpyAsync(g.dCtl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, s));
@@ -34,8 +34,8 @@ SamBox* unalignedFormat(UnalignedStage& g, const xm::UnalignedBatch& b, const xm
     HIP_CHECK(hipMemcpyAsync(&totals[0], g.dOff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemcpyAsync(&totals[1], g.dUoff.p + nq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));  // (the one wait for the totals and the control words)
-    if (ctl[0] != XM_UNALIGNED_NO_ERROR) throw std::runtime_error("malformed result streams: query " + std::to_string(ctl[0]));
-    if (ctl[2] != XM_UNALIGNED_NO_ERROR) throw std::runtime_error("the record of query " + std::to_string(ctl[2]) + " is longer than 2^31 - 1 bytes");
+    throwIfMalformed(ctl[0]);
+    if (ctl[2] != XM_NO_QUERY) throw std::runtime_error("the record of query " + std::to_string(ctl[2]) + " is longer than 2^31 - 1 bytes");
     const size_t total = (size_t)totals[0], nUn = (size_t)totals[1];
     float measure = 0, write = 0, down = 0;
     HIP_CHECK(hipEventElapsedTime(&measure, g.ev[0], g.ev[1]));
@@ -72,26 +72,16 @@ SamBox* unalignedFormat(UnalignedStage& g, const xm::UnalignedBatch& b, const xm
 extern "C" {
 
 int xm_unaligned_format_last(xm_index* idx, xm_sam_text** out) {
-  if (!idx || !out) return fail("xm_unaligned_format_last: null argument");
-  *out = nullptr;
-  if (idx->hostOnly) return fail("xm_unaligned_format_last: index was built with host_only=1");
-  try {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    const ResultStage::LastStreams last = idx->results.lastStreams(idx->residentGen, idx->resident.nq);
-    if (last.nq < 0)
-      throw std::runtime_error("the batch of the last align call is no longer resident (call xm_unaligned_format_last after xm_align_batch / xm_align_resident, before the next batch is uploaded or committed)");
+  return lastCallEntry(idx, out, "xm_unaligned_format_last", [&] {
+    const ResultStage::LastStreams last = lastCall(idx, "xm_unaligned_format_last");
     const DeviceBatch& d = idx->resident;
     if (!d.hasNames)
       throw std::runtime_error("the resident batch has no names in HBM (it was staged from arrays, not by xm_batch_stage_fastq or xm_batch_stage_fasta)");
-    HIP_CHECK(hipSetDevice(idx->device));
     const bool q = d.hasQuals;
     const xm::UnalignedBatch b{last.nq, d.mateCount.p, d.mateOffset.p, d.mateLength.p, d.codes.p, d.codesLength, d.names.p, d.nameOff.p, d.namesLength,
                                q ? d.quals.p : nullptr, q ? d.qualOff.p : nullptr, q ? d.hasQual.p : nullptr, q ? d.qualsLength : 0};
-    const xm::SummaryStreams st{last.ints, last.dbls, last.intOff, last.dblOff, (int32_t)idx->host().numContigs()};
-    SamBox* box = unalignedFormat(idx->unaligned, b, st, idx->stream);
-    *out = &box->pub;
-    return 0;
-  } catch (std::exception& e) { return fail(std::string("xm_unaligned_format_last: ") + e.what()); }
+    return &unalignedFormat(idx->unaligned, b, last.streams(idx->host().numContigs()), idx->stream)->pub;
+  });
 }
 
 int xm_context_set_batch_copy(xm_index* idx, int32_t on) {

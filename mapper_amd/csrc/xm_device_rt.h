@@ -67,6 +67,18 @@ struct DevBuf {
   ~DevBuf() { release(); }
 };
 
+// The N timing events of a stage: created by the first call that records them (ready()), destroyed with their owner
+template <int N>
+struct StageEvents {
+  hipEvent_t e[N] = {};
+  StageEvents() = default;
+  StageEvents(const StageEvents&) = delete;
+  StageEvents& operator=(const StageEvents&) = delete;
+  void ready() { for (hipEvent_t& x : e) if (!x) HIP_CHECK(hipEventCreate(&x)); }
+  hipEvent_t operator[](int i) const { return e[i]; }
+  ~StageEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
 // Result streams live in pinned host memory (the final device-to-host copy is then one DMA per stream); the buffers are recycled
 // through a process-wide pool because pinning is far more expensive than the copy itself.
 struct PinnedPool {

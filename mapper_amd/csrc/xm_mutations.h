@@ -219,8 +219,7 @@ struct MutationsStage {
   DevBuf<MutationsSnpRow> dRows;
   DevBuf<MutationsCandidate> dCandidates;
   DevBuf<MutationsVerdict> dVerdicts;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // count and scan | (host sizes the rows) | place | rows down
-  ~MutationsStage() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  StageEvents<5> ev;  // count and scan | (host sizes the rows) | place | rows down
 };
 
 }  // namespace

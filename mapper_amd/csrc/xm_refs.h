@@ -20,17 +20,16 @@
 
 namespace {
 
-constexpr unsigned long long XM_REFS_NO_ERROR = ~0ull;
 constexpr unsigned long long XM_REFS_NO_REP = ~0ull;
 constexpr int32_t XM_REFS_UNALIGNED = -1, XM_REFS_LEFT = -2;  // slotOf[q] of a query that has no slot
 
-// ctl[0]: the lowest query with a malformed slice (XM_REFS_NO_ERROR: none); ctl[1]: aligned queries
+// ctl[0]: the lowest query with a malformed slice (xm::XM_NO_QUERY: none); ctl[1]: aligned queries
 constexpr int XM_REFS_CTL_WORDS = 2;
 
 // keys[cap] (0 = empty), reps[cap] (the lowest query of the slot; XM_REFS_NO_REP = none), counts[cap]; cap a power of two >= 2 nq, mask = cap - 1
 struct RefsTable { unsigned long long* keys; unsigned long long* reps; unsigned long long* counts; unsigned long long mask; };
 
-__global__ void __launch_bounds__(256) xm_refs_claim_kernel(xm::SummaryStreams st, long long nq, int bits, RefsTable table, int32_t* slotOf, int32_t* leftLen, int32_t* leftFlag,
+__global__ void __launch_bounds__(256) xm_refs_claim_kernel(xm::ResultStreams st, long long nq, int bits, RefsTable table, int32_t* slotOf, int32_t* leftLen, int32_t* leftFlag,
                                                             unsigned long long* ctl) {
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63u);
@@ -70,7 +69,7 @@ __global__ void __launch_bounds__(256) xm_refs_claim_kernel(xm::SummaryStreams s
   if (lane == 0 && all) atomicAdd(&ctl[1], (unsigned long long)__popcll(all));
 }
 
-__global__ void __launch_bounds__(256) xm_refs_verify_kernel(xm::SummaryStreams st, long long nq, RefsTable table, int32_t* slotOf, int32_t* leftLen, int32_t* leftFlag, int32_t* isRep) {
+__global__ void __launch_bounds__(256) xm_refs_verify_kernel(xm::ResultStreams st, long long nq, RefsTable table, int32_t* slotOf, int32_t* leftLen, int32_t* leftFlag, int32_t* isRep) {
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = (int)(threadIdx.x & 63u);
   bool counted = false;
@@ -120,7 +119,7 @@ struct RefsContigStore {
   }
 };
 
-__global__ void __launch_bounds__(256) xm_refs_gather_kernel(xm::SummaryStreams st, long long nq, RefsTable table, const int32_t* slotOf, const int64_t* off, const int64_t* loff,
+__global__ void __launch_bounds__(256) xm_refs_gather_kernel(xm::ResultStreams st, long long nq, RefsTable table, const int32_t* slotOf, const int64_t* off, const int64_t* loff,
                                                              const int64_t* lqoff, RefsRecord* records, long long recordCap, int32_t* left, long long leftCap, int64_t* leftStart,
                                                              long long leftStartCap) {
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;

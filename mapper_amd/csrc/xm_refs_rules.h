@@ -4,12 +4,15 @@
 // tests/refs_rules_main.cpp calls them on the host, so tests/test_refs_rules.py checks without a GPU the very code the GPU runs.  No HIP, no threads, no
 // allocation, no library call.  Contig names and their order are the host's business: here a contig is its index.
 //
-// The walk is summaryWalkQuery's (xm_summary_rules.h): the same slice layout, the same malformed conditions (nseq outside 1 .. 2, nb < 1, a contig outside
-// [0, numContigs), the cursor past the slice's end, a slice that ends early), and it reads the same SummaryStreams.  It looks at no block and at no double.
+// The walk of a slice and what makes one malformed is xm_result_walk.h's; the visitor here looks at no block and at no double.
 #pragma once
-#include "xm_summary_rules.h"
+#include "xm_result_walk.h"
 
-#define XM_REFS_FN XM_SUMMARY_FN
+#if defined(__HIPCC__)
+#define XM_REFS_FN __host__ __device__ inline
+#else
+#define XM_REFS_FN inline
+#endif
 
 namespace xm {
 
@@ -44,49 +47,35 @@ struct RefsNoContigs {
   XM_REFS_FN void contig(long long, int32_t) {}
 };
 
-// Query q's slice -> out; sink.contig(k, contig) for every sequence alignment in stream order, repeats included.  false: the slice is malformed, exactly
-// where summaryWalkQuery says so, and out is untouched (the sink may have seen the contigs in front of the fault).  No int is read at or behind the end
-// of q's slice of the int stream; of the doubles only the slice's length is looked at.
+// The visitor that collects: every sequence's contig to the sink and into the set.
 template <class Sink>
-XM_REFS_FN bool refsWalkQuery(const SummaryStreams& st, long long q, RefSet& out, Sink& sink) {
-  const int32_t* ints = st.ints;
-  long long at = st.intOff[q];
-  const long long end = st.intOff[q + 1];
-  long long dat = st.dblOff[q];
-  const long long dend = st.dblOff[q + 1];
+struct RefsCollect {
   RefSet s;
-  long long alignments = 0;
-  if (at >= end) return false;
-  const int ncomp = ints[at++];
-  for (int c = 0; c < ncomp; c++) {
-    if (at >= end) return false;
-    const int nal = ints[at++];
-    for (int a = 0; a < nal; a++) {
-      if (at + 2 > end || dat + 4 > dend) return false;
-      const int nseq = ints[at + 1];  // ([at]: innerDistance)
-      at += 2;
-      dat += 4;
-      if (nseq < 1 || nseq > 2) return false;
-      for (int k = 0; k < nseq; k++) {
-        if (at + 3 > end || dat + 2 > dend) return false;
-        const int32_t contig = ints[at], nb = ints[at + 2];
-        if (nb < 1 || contig < 0 || contig >= st.numContigs) return false;
-        at += 3 + 4ll * nb;
-        dat += 2;
-        if (at > end) return false;
-        sink.contig(s.nSeq, contig);
-        refsInsert(s, contig);
-        s.nSeq++;  // (a slice's length is an int32, and a sequence alignment takes seven ints: no overflow)
-      }
-      alignments++;
-    }
+  Sink& sink;
+  XM_WALK_FN void take(int32_t contig) {
+    sink.contig(s.nSeq, contig);
+    refsInsert(s, contig);
+    s.nSeq++;  // (a slice's length is an int32, and a sequence alignment takes seven ints: no overflow)
   }
-  s.aligned = alignments > 0;
-  out = s;
+  XM_WALK_FN bool operator()(const ResultAlignment& al) {
+    take(al.first.contig);
+    if (al.nseq == 2) take(al.second.contig);
+    s.aligned = true;
+    return true;
+  }
+};
+
+// Query q's slice -> out; sink.contig(k, contig) for every sequence alignment in stream order, repeats included.  false: the slice is malformed
+// (xm_result_walk.h), and out is untouched (the sink may have seen the contigs of the alignments in front of the fault).
+template <class Sink>
+XM_REFS_FN bool refsWalkQuery(const ResultStreams& st, long long q, RefSet& out, Sink& sink) {
+  RefsCollect<Sink> collect{RefSet(), sink};
+  if (!resultWalkQuery(st, q, collect)) return false;
+  out = collect.s;
   return true;
 }
 
-XM_REFS_FN bool refsWalkQuery(const SummaryStreams& st, long long q, RefSet& out) {
+XM_REFS_FN bool refsWalkQuery(const ResultStreams& st, long long q, RefSet& out) {
   RefsNoContigs none;
   return refsWalkQuery(st, q, out, none);
 }

@@ -101,7 +101,11 @@ struct ResultStage {
   // an align call begins: until it has succeeded (toHost) there are no streams of a last call - a call that fails leaves none behind
   void forgetLast() { lastAlignedNq = -1; lastAlignedGen = -1; }
   // the streams of the last call where they lie in HBM, if they belong to the resident batch of generation gen with nq queries (else: nq = -1)
-  struct LastStreams { int64_t nq; const int32_t* ints; const int64_t* intOff; size_t intsHeld; const double* dbls; const int64_t* dblOff; };
+  struct LastStreams {
+    int64_t nq; const int32_t* ints; const int64_t* intOff; size_t intsHeld; const double* dbls; const int64_t* dblOff;
+    // as the walk of a slice takes them (xm_result_walk.h), for an index of numContigs contigs
+    ResultStreams streams(int64_t numContigs) const { return ResultStreams{ints, dbls, intOff, dblOff, (int32_t)numContigs}; }
+  };
   LastStreams lastStreams(int64_t gen, int64_t nq) const {
     if (lastAlignedNq < 0 || lastAlignedNq != nq || lastAlignedGen != gen) return LastStreams{-1, nullptr, nullptr, 0, nullptr, nullptr};
     return LastStreams{lastAlignedNq, dFinalInts.p, dFinalIntOff.p, dFinalInts.n, dFinalDbls.p, dFinalDblOff.p};
@@ -115,6 +119,11 @@ struct ResultStage {
   code &= 0xFF;
   if (code == XM_ST_NEED_GROW) throw std::runtime_error("Failed to align query " + std::to_string(query) + ": gapmer longer than the hashed lengths");
   throw std::runtime_error("Failed to align query " + std::to_string(query) + ": the reference implementation would have thrown here (status " + std::to_string(code) + ")");
+}
+
+// The error of a stage whose walk (xm_result_walk.h) left `query` as the lowest one with a malformed slice; nothing to do while there is none.
+void throwIfMalformed(unsigned long long query) {
+  if (query != XM_NO_QUERY) throw std::runtime_error("malformed result streams: query " + std::to_string(query));
 }
 
 }  // namespace

@@ -14,13 +14,12 @@
 namespace {
 
 constexpr int XM_SAM_TILE_BYTES = 1024;  // one round of 16-byte stores of a wavefront (xm_sam_tile_bytes(): tests put record ends on both sides of the multiples)
-constexpr unsigned long long XM_SAM_NO_ERROR = ~0ull;
 
-// what a format call reads; the control words: [0] the lowest query with a malformed slice (XM_SAM_NO_ERROR: none), [1] queries whose text did not end where
+// what a format call reads; the control words: [0] the lowest query with a malformed slice (xm::XM_NO_QUERY: none), [1] queries whose text did not end where
 // it was measured to (an internal error), [2] bytes of the whole text, [3] its records
 struct SamJob {
   xm::SamBatch batch;
-  xm::SamStreams streams;
+  xm::ResultStreams streams;
   xm::SamContigs contigs;
 };
 

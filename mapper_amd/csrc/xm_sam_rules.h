@@ -1,5 +1,5 @@
 // The rules of a SAM record, once, as plain C++: what libxm_hostio.so's formatter (xm_hostio.cpp, formatRange / appendCigar / appendSeq /
-// javaDouble: the definition) writes for the result streams of a batch - the walk of a query's slice with the checks that make a slice malformed, the
+// javaDouble: the definition) writes for the result streams of a batch - the visitor of the walk of a query's slice (xm_result_walk.h) that makes the records, the
 // fields of a record, Double.toString, and the byte length of a record and of a query.  The kernels of xm_sam.h call these functions on the device (they
 // are host+device there, and plain inline functions everywhere else); tests/sam_rules_main.cpp calls them on the host, so tests/test_sam_rules.py checks
 // without a GPU the very code the GPU runs.  No HIP, no threads, no allocation, no library call.
@@ -11,7 +11,7 @@
 //   endRecord()
 // SamCount is the sink that only measures; xm_sam.h has the one that writes a wavefront's tile, the test program one that appends to a string.
 #pragma once
-#include <cstdint>
+#include "xm_result_walk.h"
 
 #if defined(__HIPCC__)
 #define XM_SAM_FN __host__ __device__ __forceinline__
@@ -237,14 +237,13 @@ XM_SAM_FN int samComplement(int b) { return ((b & 1) << 3) | ((b & 2) << 1) | ((
 // base i of the SEQ field of a mate of n codes
 XM_SAM_FN char samSeqBase(const uint8_t* codes, int n, bool rev, int i) { return rev ? samBase(samComplement(codes[n - 1 - i] & 15)) : samBase(codes[i]); }
 
-// the batch (xm_query_batch's arrays and xmio_batch's names: name_off has 2 * nq + 1 entries), the four result streams (include/xmapper_hip.h:73-82), and the
-// contig names one behind the other (off has num + 1 entries)
+// the batch (xm_query_batch's arrays and xmio_batch's names: name_off has 2 * nq + 1 entries) and the contig names one behind the other (off has num + 1
+// entries; a contig of a record is one of these names, so num is the walk's bound, whatever the streams' own count says)
 struct SamBatch {
   int64_t nq;
   const int32_t* mateCount; const int64_t* mateOffset; const int32_t* mateLength; const uint8_t* codes;
   const char* names; const int64_t* nameOff;
 };
-struct SamStreams { const int32_t* ints; const double* dbls; const int64_t* intOff; const int64_t* dblOff; };
 struct SamContigs { int32_t num; const char* names; const int64_t* off; };
 
 // one sequence of an alignment where it lies in the int stream: (contig, reversed, nb) at `at`, the blocks behind
@@ -282,85 +281,75 @@ XM_SAM_WALK void samCigar(const SamSeq& sa, int queryLen, Sink& sink) {
   if (tail > 0) sink.compose([&](char* p) { int n = samPutInt(p, tail); p[n++] = 'S'; return n; });
 }
 
-// The records of query q to the sink, in formatRange's order.  false: the slice is malformed - exactly where formatRange returns false (nseq outside 1 .. 2,
-// nb < 1, a contig outside [0, num), the cursor past the slice's end, mate >= nMates, a paired single-component alignment with nseq != 2) - and nothing
-// the sink got counts.  No int is read at or behind the end of q's slice of the int stream, no double at or behind the end of its slice of the other.
+// The visitor that turns an alignment of query q into its records (one per sequence), in formatRange's order.  What only a SAM record cannot express
+// is refused here, where formatRange returns false when it writes SAM: mate >= nMates (with that, the third component of a pair) and a paired
+// single-component alignment with nseq != 2.
 template <class Sink>
-XM_SAM_WALK bool samWalkQuery(const SamBatch& b, const SamStreams& st, const SamContigs& contigs, long long q, Sink& sink) {
-  const int32_t* ints = st.ints;
-  long long at = st.intOff[q];
-  const long long end = st.intOff[q + 1];
-  long long dat = st.dblOff[q];
-  const long long dend = st.dblOff[q + 1];
-  const int nMates = b.mateCount[q];
-  const bool paired = nMates > 1;
-  if (at >= end) return false;
-  const int ncomp = ints[at++];
-  for (int c = 0; c < ncomp; c++) {
-    if (at >= end) return false;
-    const int nal = ints[at++];
-    for (int a = 0; a < nal; a++) {
-      if (at + 2 > end || dat + 4 > dend) return false;
-      const int nseq = ints[at + 1];  // ([at]: innerDistance)
-      at += 2;
-      const double spacingPenalty = st.dbls[dat], penalty = st.dbls[dat + 3];
-      dat += 4;
-      if (nseq < 1 || nseq > 2) return false;
-      SamSeq sas[2];
-      for (int k = 0; k < nseq; k++) {
-        if (at + 3 > end || dat + 2 > dend) return false;
-        sas[k].contig = ints[at]; sas[k].rev = ints[at + 1]; sas[k].nb = ints[at + 2]; sas[k].blocks = ints + at + 3;
-        if (sas[k].nb < 1 || sas[k].contig < 0 || sas[k].contig >= contigs.num) return false;
-        at += 3 + 4ll * sas[k].nb;
-        dat += 2;
-        if (at > end) return false;
-      }
-      for (int k = 0; k < nseq; k++) {
-        const SamSeq& sa = sas[k];
-        const int mate = ncomp == 1 ? k : c;  // (a pair that fell back to unpaired alignments: one component per mate)
-        if (mate >= nMates) return false;
-        const long long m = 2 * q + mate;
-        int flag;
-        const SamSeq* other = nullptr;
-        if (ncomp == 1) {
-          if (paired) {
-            if (nseq != 2) return false;
-            other = &sas[1 - k];
-            flag = 1 | 2 | (sa.rev ? 0x10 : 0) | (other->rev ? 0x20 : 0) | (k == 0 ? 0x40 : 0x80);
-          } else {
-            flag = sa.rev ? 0x10 : 0;
-          }
+struct SamRecords {
+  const SamBatch& b;
+  const SamContigs& contigs;
+  long long q;
+  Sink& sink;
+  XM_SAM_FN bool operator()(const ResultAlignment& al) {
+    const int nMates = b.mateCount[q];
+    const bool paired = nMates > 1;
+    const int ncomp = al.ncomp, nseq = al.nseq;
+    const double* dbls = al.dbls;  // (spacingPenalty, .., .., totalPenalty: loaded where they are written)
+    SamSeq sas[2];
+    sas[0] = SamSeq{al.first.contig, al.first.at[1], al.first.nb, al.first.blocks()};
+    if (nseq == 2) sas[1] = SamSeq{al.second.contig, al.second.at[1], al.second.nb, al.second.blocks()};
+    for (int k = 0; k < nseq; k++) {
+      const SamSeq& sa = sas[k];
+      const int mate = ncomp == 1 ? k : al.comp;  // (a pair that fell back to unpaired alignments: one component per mate)
+      if (mate >= nMates) return false;
+      const long long m = 2 * q + mate;
+      int flag;
+      const SamSeq* other = nullptr;
+      if (ncomp == 1) {
+        if (paired) {
+          if (nseq != 2) return false;
+          other = &sas[1 - k];
+          flag = 1 | 2 | (sa.rev ? 0x10 : 0) | (other->rev ? 0x20 : 0) | (k == 0 ? 0x40 : 0x80);
         } else {
-          flag = 1 | 8 | (sa.rev ? 0x10 : 0) | (mate == 0 ? 0x40 : 0x80);
+          flag = sa.rev ? 0x10 : 0;
         }
-        const int len = b.mateLength[m];
-        sink.bytesAt(b.names + b.nameOff[m], b.nameOff[m + 1] - b.nameOff[m]);
-        sink.compose([&](char* p) { int n = 0; p[n++] = '\t'; n += samPutInt(p + n, flag); p[n++] = '\t'; return n; });
-        sink.bytesAt(contigs.names + contigs.off[sa.contig], contigs.off[sa.contig + 1] - contigs.off[sa.contig]);
-        sink.compose([&](char* p) { int n = 0; p[n++] = '\t'; n += samPutInt(p + n, (long long)sa.blocks[1] + 1); n += samPutText(p + n, "\t255\t"); return n; });
-        samCigar(sa, len, sink);
-        if (other) {
-          sink.compose([&](char* p) { p[0] = '\t'; return 1; });
-          sink.bytesAt(contigs.names + contigs.off[other->contig], contigs.off[other->contig + 1] - contigs.off[other->contig]);
-          sink.compose([&](char* p) { int n = 0; p[n++] = '\t'; n += samPutInt(p + n, (long long)other->blocks[1] + 1); p[n++] = '\t'; n += samPutInt(p + n, len); p[n++] = '\t'; return n; });
-        } else {
-          sink.compose([&](char* p) { int n = samPutText(p, "\t*\t0\t"); n += samPutInt(p + n, len); p[n++] = '\t'; return n; });
-        }
-        sink.seq(b.codes + b.mateOffset[m], len, sa.rev != 0);
-        sink.compose([&](char* p) {
-          int n = samPutText(p, "\t*");
-          if (ncomp != 1) n += samPutText(p + n, "\tcs:f:0.0");
-          else if (paired) { n += samPutText(p + n, "\tcs:f:"); n += samPutDouble(p + n, spacingPenalty); }
-          n += samPutText(p + n, "\tAS:f:");
-          n += samPutDouble(p + n, penalty);
-          p[n++] = '\n';
-          return n;
-        });
-        sink.endRecord();
+      } else {
+        flag = 1 | 8 | (sa.rev ? 0x10 : 0) | (mate == 0 ? 0x40 : 0x80);
       }
+      const int len = b.mateLength[m];
+      sink.bytesAt(b.names + b.nameOff[m], b.nameOff[m + 1] - b.nameOff[m]);
+      sink.compose([&](char* p) { int n = 0; p[n++] = '\t'; n += samPutInt(p + n, flag); p[n++] = '\t'; return n; });
+      sink.bytesAt(contigs.names + contigs.off[sa.contig], contigs.off[sa.contig + 1] - contigs.off[sa.contig]);
+      sink.compose([&](char* p) { int n = 0; p[n++] = '\t'; n += samPutInt(p + n, (long long)sa.blocks[1] + 1); n += samPutText(p + n, "\t255\t"); return n; });
+      samCigar(sa, len, sink);
+      if (other) {
+        sink.compose([&](char* p) { p[0] = '\t'; return 1; });
+        sink.bytesAt(contigs.names + contigs.off[other->contig], contigs.off[other->contig + 1] - contigs.off[other->contig]);
+        sink.compose([&](char* p) { int n = 0; p[n++] = '\t'; n += samPutInt(p + n, (long long)other->blocks[1] + 1); p[n++] = '\t'; n += samPutInt(p + n, len); p[n++] = '\t'; return n; });
+      } else {
+        sink.compose([&](char* p) { int n = samPutText(p, "\t*\t0\t"); n += samPutInt(p + n, len); p[n++] = '\t'; return n; });
+      }
+      sink.seq(b.codes + b.mateOffset[m], len, sa.rev != 0);
+      sink.compose([&](char* p) {
+        int n = samPutText(p, "\t*");
+        if (ncomp != 1) n += samPutText(p + n, "\tcs:f:0.0");
+        else if (paired) { n += samPutText(p + n, "\tcs:f:"); n += samPutDouble(p + n, dbls[0]); }
+        n += samPutText(p + n, "\tAS:f:");
+        n += samPutDouble(p + n, dbls[3]);
+        p[n++] = '\n';
+        return n;
+      });
+      sink.endRecord();
     }
+    return true;
   }
-  return true;
+};
+
+// The records of query q to the sink.  false: the slice is malformed (xm_result_walk.h, or what SamRecords refuses), and nothing the sink got counts.
+template <class Sink>
+XM_SAM_WALK bool samWalkQuery(const SamBatch& b, const ResultStreams& st, const SamContigs& contigs, long long q, Sink& sink) {
+  SamRecords<Sink> records{b, contigs, q, sink};
+  return resultWalkQuery(ResultStreams{st.ints, st.dbls, st.intOff, st.dblOff, contigs.num}, q, records);
 }
 
 }  // namespace xm

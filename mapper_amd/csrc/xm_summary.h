@@ -13,9 +13,7 @@
 
 namespace {
 
-constexpr unsigned long long XM_SUMMARY_NO_ERROR = ~0ull;
-
-// ctl[0]: the lowest query with a malformed slice (XM_SUMMARY_NO_ERROR: none); ctl[1..3]: aligned queries, aligned length, indels
+// ctl[0]: the lowest query with a malformed slice (xm::XM_NO_QUERY: none); ctl[1..3]: aligned queries, aligned length, indels
 constexpr int XM_SUMMARY_CTL_WORDS = 4;
 
 __device__ __forceinline__ long long summaryWaveSum(long long v) {
@@ -23,7 +21,7 @@ __device__ __forceinline__ long long summaryWaveSum(long long v) {
   return v;  // (lane 0 holds the sum)
 }
 
-__global__ void __launch_bounds__(256) xm_summary_measure_kernel(xm::SummaryStreams st, long long nq, int32_t* alignments, int32_t* unalignedFlag, unsigned long long* ctl) {
+__global__ void __launch_bounds__(256) xm_summary_measure_kernel(xm::ResultStreams st, long long nq, int32_t* alignments, int32_t* unalignedFlag, unsigned long long* ctl) {
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   xm::QuerySummary s;
   if (q < nq) {  // (lanes behind the last query stay for the shuffles and add nothing)
@@ -52,7 +50,7 @@ struct SummaryPenaltyStore {
   }
 };
 
-__global__ void __launch_bounds__(256) xm_summary_gather_kernel(xm::SummaryStreams st, long long nq, const int64_t* off, const int64_t* uoff, double* penalties, long long penaltyCap,
+__global__ void __launch_bounds__(256) xm_summary_gather_kernel(xm::ResultStreams st, long long nq, const int64_t* off, const int64_t* uoff, double* penalties, long long penaltyCap,
                                                                 int64_t* unaligned, long long unalignedCap) {
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nq) return;

@@ -16,13 +16,11 @@
 
 namespace {
 
-constexpr unsigned long long XM_UNALIGNED_NO_ERROR = ~0ull;
-
-// ctl[0]: the lowest query with a malformed slice, ctl[2]: the lowest query whose record does not fit an int32 (XM_UNALIGNED_NO_ERROR: none);
+// ctl[0]: the lowest query with a malformed slice, ctl[2]: the lowest query whose record does not fit an int32 (xm::XM_NO_QUERY: none);
 // ctl[1]: mates of the unaligned queries; ctl[3]: records that did not end where they were measured to (an internal error)
 constexpr int XM_UNALIGNED_CTL_WORDS = 4;
 
-__global__ void __launch_bounds__(256) xm_unaligned_measure_kernel(xm::UnalignedBatch b, xm::SummaryStreams st, int32_t* bytes, int32_t* unalignedFlag, unsigned long long* ctl) {
+__global__ void __launch_bounds__(256) xm_unaligned_measure_kernel(xm::UnalignedBatch b, xm::ResultStreams st, int32_t* bytes, int32_t* unalignedFlag, unsigned long long* ctl) {
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   long long mates = 0;
   if (q < b.nq) {  // (lanes behind the last query stay for the shuffles and add nothing)
